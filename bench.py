@@ -21,10 +21,16 @@ In ``--shard frames`` mode the per-rank depth maps are gathered to rank 0 over x
 GPU call -- starts ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py ...`` as a child process, relays rank 0's
 JSON line and exits with the child's code (the reference's launcher contract: docs/user_infer.md:124-129, tools/dist_test.sh).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with ``roofline`` (dominant kernel,
-HIP-event timed on its launch stream) and ``cpu_baseline`` (the oracle restatement on host cores,
-bounded sample).  ``operating_point``: shader clock / board power sampled while the timed frames run (the frame is power-limited:
-its throughput depends on how much the operands toggle -- ``--data zeros|rand`` fixes the two ends of that range).
+Rank 0 prints ONE JSON line: ``value`` (maps/s), ``ms_per_step`` (one timed step), ``dtype``.  A plain run does only that: set up,
+warm up, time the K steps, write ``--dump-outputs`` if asked, print.  ``--full`` adds the rest, each after the timed region:
+``roofline`` (dominant kernel, HIP-event timed on its launch stream), ``cpu_baseline`` (the oracle restatement on host cores,
+bounded sample), ``alt`` (``--prec f16f6``: the bf16x3 run beside it) and ``operating_point``: shader clock / board power sampled
+while the timed frames run (the frame is power-limited: its throughput depends on how much the operands toggle -- ``--data
+zeros|rand`` fixes the two ends of that range).
+
+``--dump-outputs DIR``: after the timed steps, rank 0 writes what its last timed step returned -- ``depth.npy`` (the depth map) and
+``coarse_prediction.npy`` (the coarse branch's map from the returned log), float32 -- so that two builds can be compared output for
+output: frames and weights are seeded, so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -73,9 +79,12 @@ def parse():
     ap.add_argument("--no-prefetch-coarse", dest="prefetch_coarse", action="store_false",
                     help="do not enqueue the next frame's coarse forward beside the current frame's tile batches")
     ap.add_argument("--hip-graph", action="store_true", help="capture the device side of a frame into a hipGraph and replay it per frame")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="--prec f16f6: skip the bf16x3 run reported beside it")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline, CPU baseline, the "
+                    "bf16x3 run beside --prec f16f6, operating point (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="--full --prec f16f6: skip the bf16x3 run reported beside it")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline's instrumented frames")
     ap.add_argument("--layer-report", default=None, help="write a per-layer-shape timing table (extra instrumented frame)")
     ap.add_argument("--data", default="rand", choices=["rand", "zeros"],
                     help="synthetic frames: uniform random pixels (default) or all-zero frames -- the frame is power-limited, so its "
@@ -241,6 +250,21 @@ def pmc_traffic(kernel_tag, workload, prec):
     return b, os.path.relpath(path, ROOT)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """``--dump-outputs``: each tensor as float32 ``DIR/<name>.npy`` (None entries skipped), 64 MB in all at most"""
+    import numpy as np
+    arrays = {k: v.detach().to("cpu", torch.float32).numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -304,8 +328,8 @@ def main():
         random.seed(621)
         sh = None if solo else shard
         fg = frame_gather and not solo
-        depth, _ = model(mode="infer", cai_mode=w["mode"], process_num=4, tile_cfg=tile_cfg, image_lr=lr, image_hr=hr,
-                         shard=sh, gather_dst=gather_dst if sh is not None else None, return_device=fg, next_image_lr=nxt)
+        depth, log = model(mode="infer", cai_mode=w["mode"], process_num=4, tile_cfg=tile_cfg, image_lr=lr, image_hr=hr,
+                           shard=sh, gather_dst=gather_dst if sh is not None else None, return_device=fg, next_image_lr=nxt)
         if fg:
             # cfg-5 "full xGMI gather": the N per-rank maps (33 MB each at 4K) to rank 0, which hands them to the host
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -323,7 +347,7 @@ def main():
                     coll["n"] += 1
             else:
                 torch.cuda.current_stream().synchronize()
-        return depth
+        return depth, log
 
     def barrier():
         if world > 1:
@@ -333,15 +357,17 @@ def main():
     for i in range(args.warmup):
         step(i, last=i == args.warmup - 1)  # (no prefetch across t0: the timed region does exactly K coarse forwards)
     barrier()
-    op = OperatingPoint(local) if rank == 0 else None
+    op = OperatingPoint(local) if (rank == 0 and args.full) else None
     if op is not None:
         op.start()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        out = step(args.warmup + i, timed=True, last=i == args.steps - 1)
+        out, out_log = step(args.warmup + i, timed=True, last=i == args.steps - 1)
     barrier()
     elapsed = time.perf_counter() - t0
     operating_point = op.finish() if op is not None else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(depth=out, coarse_prediction=out_log["coarse_prediction"]))
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -362,7 +388,8 @@ def main():
                     frames=("torch.rand, seeded" if args.data == "rand" else "zeros"), weights="synthetic (numpy PCG64 keyed by parameter name)",
                     parity_note=("refiner encoder MobileNetV4-S: parity unpinned (timm absent; two independent transcriptions agree)"
                                  if w["kind"] == "PatchRefinerPlus" and not w.get("refiner_encoder") else None)))
-    result["operating_point"] = operating_point
+    if args.full:
+        result["operating_point"] = operating_point
     if f6_on:
         # the mode's fp16 range guard (ops.F6Range, models.forward): frames recomputed in the timed region because a layer's input left fp16's range (0 on this data)
         result["f16f6_guard"] = dict(recomputed_frames=int(getattr(model, "f6_recalibrations", 0)),
@@ -371,7 +398,7 @@ def main():
                                 "GatedConvUnit.conv and the unit's fusion_conv.0 inside the fused tail kernel (its LayerNorm, gate GEMM and final stage stay "
                                 "bf16x3 / fp32) -- which run fp16 + two block-scaled fp6 (e2m3) corrections per product (csrc/conv3x3_f6.hip): fp32-grade, rms "
                                 "1.2e-5 per dot product; kernels tagged <..,f16f6> are priced against 2.5 PF x 2/3")
-        if world == 1 and not args.no_alt:
+        if world == 1 and args.full and not args.no_alt:
             # the same timed loop in the default arithmetic, beside it
             f6_model = model
             mc2 = model_config(name, prec="bf16x3", max_batch=args.max_batch, n_streams=args.streams)
@@ -416,7 +443,7 @@ def main():
         torch.distributed.destroy_process_group()
         if rank != 0:
             return
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # extra, instrumented frames: HIP events on the launch stream around every matrix-kernel launch
         # rank 0 alone runs these frames: UNSHARDED (a sharded forward would wait in a collective nobody else joins)
         model.n_streams = 1  # per-launch durations must not include kernels of other streams
@@ -475,7 +502,7 @@ def main():
             f.write("ms,pct,launches,TFLOP/s,kernel shape\n")
             for k, v in rows:
                 f.write(f"{v['ms']:.3f},{100 * v['ms'] / tot:.1f},{v['launches']},{v['flops'] / max(v['ms'], 1e-9) / 1e9:.1f},{k}\n")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(name, sd, 0)
     if rank == 0:
         print(json.dumps(result))

@@ -1,4 +1,4 @@
-"""Print the headline numbers of a bench.py JSON line (file argument): value, ms/step, per-kernel ms and TFLOP/s."""
+"""Print the headline numbers of a `bench.py --full` JSON line (file argument): value, ms/step, per-kernel ms and TFLOP/s."""
 import json
 import sys
 
