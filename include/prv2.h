@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define PRV2_ABI_VERSION 19
+#define PRV2_ABI_VERSION 20
 
 enum prv2_act { PRV2_ACT_NONE = 0, PRV2_ACT_RELU = 1, PRV2_ACT_GELU = 2, PRV2_ACT_SIGMOID = 3, PRV2_ACT_SOFTPLUS = 4,
                 PRV2_ACT_SILU = 5 /* x * sigmoid(x): EfficientNet refiner encoder (timm 'swish') */ };
@@ -508,6 +508,40 @@ int prv2_blend_update(float* avg, float* cnt, int32_t map_h, int32_t map_w, cons
 /* RunningAverageMap.resize: avg -> nearest, cnt -> bilinear(align_corners=True) (utils.py:38-43) */
 int prv2_blend_resize(const float* avg, const float* cnt, int32_t h, int32_t w, float* avg_out, float* cnt_out,
                       int32_t oh, int32_t ow, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Frames (ABI 20): B frames per call.  Each entry point below is the B-frame form of the entry point of the same name without
+ * ``_frames`` -- the same kernel, same arithmetic per tile, bit-identical to calling the single-frame form on each frame.
+ * n_frames = B >= 1.  Per-frame inputs are dense and frame-major: images [B, 3, H, W], feature maps / tap tables [B, h, w, ld].
+ * A tile names its frame in its first column: tiles int32 [k][3] = (frame, h_start, w_start), boxes fp32 [k][5] =
+ * (frame, x1, y1, x2, y2) (torchvision's roi_align format).  Frame indices live on the device and are clamped to [0, B) there.
+ * ------------------------------------------------------------------------------------------ */
+int prv2_crop_resize_frames(const float* img_bchw, int32_t n_frames, int32_t img_h, int32_t img_w, const int32_t* tiles, int32_t k,
+                            int32_t ch, int32_t cw, int32_t oh, int32_t ow, const float* mean3_host, const float* std3_host, float* out,
+                            int32_t ldo, void* stream);
+int prv2_roi_align_frames(const float* feat, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes, int32_t k,
+                          float spatial_scale, int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream);
+int prv2_roi_align_x2_frames(const float* feat, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes, int32_t k,
+                             float spatial_scale, int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream);
+/* g [B, h, w, ldg] -> v [B, 3h, 3w, ldv] in one launch; the gather reads each box's own frame of v and g */
+int prv2_coarse_tap_knots_frames(const float* g, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldg, float knot_bh, float knot_bw,
+                                 float* v, int32_t ldv, void* stream);
+int prv2_coarse_tap_gather_frames(const float* v, const float* g, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldv, int32_t ldg,
+                                  float knot_bh, float knot_bw, const float* boxes, int32_t k, float spatial_scale, int32_t oh, int32_t ow,
+                                  float* out, int32_t ldo, void* stream);
+/* One pass step of the overlap blend for B maps avg / cnt [B, map_h, map_w] in one launch.  Frame f's k tiles are
+ * tiles[f * tile_fstride .. + k) (rows of 2: (h_start, w_start)) and its predictions start at pred + f * pred_fstride
+ * ([k, ph, pw] each; tile_fstride >= k, pred_fstride >= k * ph * pw: frames do not overlap).  Within a frame the tiles are
+ * applied in order, as prv2_blend_paste / prv2_blend_update. */
+int prv2_blend_paste_frames(float* avg, float* cnt, int32_t n_frames, int32_t map_h, int32_t map_w, const float* pred, int32_t ph, int32_t pw,
+                            int64_t pred_fstride, const float* mask, const int32_t* tiles, int32_t tile_fstride, int32_t k, int32_t th,
+                            int32_t tw, void* stream);
+int prv2_blend_update_frames(float* avg, float* cnt, int32_t n_frames, int32_t map_h, int32_t map_w, const float* pred, int32_t ph, int32_t pw,
+                             int64_t pred_fstride, const float* mask, const int32_t* tiles, int32_t tile_fstride, int32_t k, int32_t th,
+                             int32_t tw, void* stream);
+/* RunningAverageMap.resize of B maps [B, h, w] -> [B, oh, ow] in one launch */
+int prv2_blend_resize_frames(const float* avg, const float* cnt, int32_t n_frames, int32_t h, int32_t w, float* avg_out, float* cnt_out,
+                             int32_t oh, int32_t ow, void* stream);
 
 #ifdef __cplusplus
 }

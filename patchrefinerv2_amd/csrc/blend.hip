@@ -4,18 +4,28 @@
 // order-exact AND parallel, each thread owns one map pixel and walks the tile list in order
 // (gather form): K is small (<= a few dozen), the maps are HBM-resident, one read + one write
 // of the touched pixels per call.
+// Frames (the *_frames entry points): B maps [B, MH, MW], grid.y = frame; frame f's tiles / predictions start at f * tile_fs /
+// f * pred_fs (a frame-major tile list: the pass's tiles of every frame in one launch, no copies).  The single-frame entry
+// points are the FR = false instances of the same kernels.
 #include "common.h"
 
 PRV2_NO_PACKED_FP32_BEGIN  // (common.h)
 
 namespace prv2 {
 
-template <bool PASTE>
+template <bool PASTE, bool FR = false>
 __global__ void __launch_bounds__(256) blend_kernel(float* __restrict__ avg, float* __restrict__ cnt, int MH, int MW,
                                                     const float* __restrict__ pred, int ph, int pw,
                                                     const float* __restrict__ mask, const int* __restrict__ tiles, int K,
                                                     int th, int tw, float sy, float sx, int y_lo, int x_lo, int bh,
-                                                    int bw) {
+                                                    int bw, int64_t pred_fs = 0, int tile_fs = 0) {
+  if constexpr (FR) {  // this block's frame: its map, its tiles, its predictions
+    const int f = blockIdx.y;
+    avg += (int64_t)f * MH * MW;
+    cnt += (int64_t)f * MH * MW;
+    pred += (int64_t)f * pred_fs;
+    tiles += (int64_t)f * 2 * tile_fs;
+  }
   // threads cover the bounding box [y_lo, y_lo+bh) x [x_lo, x_lo+bw) of all tiles
   int64_t total = (int64_t)bh * bw;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
@@ -53,10 +63,18 @@ __global__ void __launch_bounds__(256) blend_kernel(float* __restrict__ avg, flo
   }
 }
 
+template <bool FR = false>
 __global__ void __launch_bounds__(256) blend_resize_kernel(const float* __restrict__ avg, const float* __restrict__ cnt,
                                                            int H, int W, float* __restrict__ avg_o,
                                                            float* __restrict__ cnt_o, int oh, int ow, float ny, float nx,
                                                            float by, float bx) {
+  if constexpr (FR) {
+    const int f = blockIdx.y;
+    avg += (int64_t)f * H * W;
+    cnt += (int64_t)f * H * W;
+    avg_o += (int64_t)f * oh * ow;
+    cnt_o += (int64_t)f * oh * ow;
+  }
   int64_t total = (int64_t)oh * ow;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     int ox = (int)(idx % ow), oy = (int)(idx / ow);
@@ -70,13 +88,23 @@ __global__ void __launch_bounds__(256) blend_resize_kernel(const float* __restri
 
 template <bool PASTE>
 static int blend_launch(const char* name, float* avg, float* cnt, int MH, int MW, const float* pred, int ph, int pw,
-                        const float* mask, const int* tiles, int K, int th, int tw, void* stream) {
+                        const float* mask, const int* tiles, int K, int th, int tw, void* stream, int B = 0, int64_t pred_fs = 0,
+                        int tile_fs = 0) {
   PRV2_REQUIRE(avg && cnt && pred && mask && tiles, "%s: null pointer", name);
   PRV2_REQUIRE(K > 0 && th > 0 && tw > 0 && ph > 0 && pw > 0 && th <= MH && tw <= MW, "%s: bad geometry", name);
   // tile coordinates live on the device; cover the whole map (cheap: one pass over <= 33 MB maps)
   int64_t total = (int64_t)MH * MW;
-  hipLaunchKernelGGL(blend_kernel<PASTE>, dim3(flat_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, avg, cnt, MH, MW,
-                     pred, ph, pw, mask, tiles, K, th, tw, (float)ph / (float)th, (float)pw / (float)tw, 0, 0, MH, MW);
+  if (B == 0) {  // (the single-frame entry points)
+    hipLaunchKernelGGL(blend_kernel<PASTE>, dim3(flat_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, avg, cnt, MH, MW,
+                       pred, ph, pw, mask, tiles, K, th, tw, (float)ph / (float)th, (float)pw / (float)tw, 0, 0, MH, MW, 0, 0);
+  } else {
+    PRV2_REQUIRE(B >= 1 && B <= 65535, "%s: frame count %d out of range [1, 65535]", name, B);
+    // frames must not overlap: frame f's K predictions / tiles lie in [f * stride, f * stride + K)
+    PRV2_REQUIRE(tile_fs >= K && pred_fs >= (int64_t)K * ph * pw, "%s: frame strides (tiles %d, predictions %lld) smaller than the pass (%d tiles)",
+                 name, tile_fs, (long long)pred_fs, K);
+    hipLaunchKernelGGL((blend_kernel<PASTE, true>), dim3(flat_grid(total, 256), B), dim3(256), 0, (hipStream_t)stream, avg, cnt, MH, MW,
+                       pred, ph, pw, mask, tiles, K, th, tw, (float)ph / (float)th, (float)pw / (float)tw, 0, 0, MH, MW, pred_fs, tile_fs);
+  }
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }
@@ -97,15 +125,47 @@ extern "C" int prv2_blend_update(float* avg, float* cnt, int32_t map_h, int32_t 
   return blend_launch<false>("blend_update", avg, cnt, map_h, map_w, pred, ph, pw, mask, tiles, k, th, tw, stream);
 }
 
+extern "C" int prv2_blend_paste_frames(float* avg, float* cnt, int32_t n_frames, int32_t map_h, int32_t map_w, const float* pred, int32_t ph,
+                                       int32_t pw, int64_t pred_fstride, const float* mask, const int32_t* tiles, int32_t tile_fstride, int32_t k,
+                                       int32_t th, int32_t tw, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "blend_paste_frames: n_frames %d < 1", n_frames);
+  return blend_launch<true>("blend_paste_frames", avg, cnt, map_h, map_w, pred, ph, pw, mask, tiles, k, th, tw, stream, n_frames, pred_fstride,
+                            tile_fstride);
+}
+
+extern "C" int prv2_blend_update_frames(float* avg, float* cnt, int32_t n_frames, int32_t map_h, int32_t map_w, const float* pred, int32_t ph,
+                                        int32_t pw, int64_t pred_fstride, const float* mask, const int32_t* tiles, int32_t tile_fstride, int32_t k,
+                                        int32_t th, int32_t tw, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "blend_update_frames: n_frames %d < 1", n_frames);
+  return blend_launch<false>("blend_update_frames", avg, cnt, map_h, map_w, pred, ph, pw, mask, tiles, k, th, tw, stream, n_frames, pred_fstride,
+                             tile_fstride);
+}
+
+static int blend_resize_launch(const char* name, const float* avg, const float* cnt, int B, int h, int w, float* avg_out, float* cnt_out, int oh,
+                               int ow, void* stream) {
+  PRV2_REQUIRE(avg && cnt && avg_out && cnt_out && h > 0 && w > 0 && oh > 0 && ow > 0, "%s: bad arguments", name);
+  int64_t total = (int64_t)oh * ow;
+  if (B == 0)
+    hipLaunchKernelGGL(blend_resize_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, avg, cnt, h, w,
+                       avg_out, cnt_out, oh, ow, (float)h / (float)oh, (float)w / (float)ow, ac_scale(h, oh),
+                       ac_scale(w, ow));
+  else
+    hipLaunchKernelGGL(blend_resize_kernel<true>, dim3(flat_grid(total, 256), B), dim3(256), 0, (hipStream_t)stream, avg, cnt, h, w,
+                       avg_out, cnt_out, oh, ow, (float)h / (float)oh, (float)w / (float)ow, ac_scale(h, oh),
+                       ac_scale(w, ow));
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
 extern "C" int prv2_blend_resize(const float* avg, const float* cnt, int32_t h, int32_t w, float* avg_out,
                                  float* cnt_out, int32_t oh, int32_t ow, void* stream) {
-  PRV2_REQUIRE(avg && cnt && avg_out && cnt_out && h > 0 && w > 0 && oh > 0 && ow > 0, "blend_resize: bad arguments");
-  int64_t total = (int64_t)oh * ow;
-  hipLaunchKernelGGL(blend_resize_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, avg, cnt, h, w,
-                     avg_out, cnt_out, oh, ow, (float)h / (float)oh, (float)w / (float)ow, ac_scale(h, oh),
-                     ac_scale(w, ow));
-  PRV2_LAUNCH_CHECK("blend_resize");
-  return 0;
+  return blend_resize_launch("blend_resize", avg, cnt, 0, h, w, avg_out, cnt_out, oh, ow, stream);
+}
+
+extern "C" int prv2_blend_resize_frames(const float* avg, const float* cnt, int32_t n_frames, int32_t h, int32_t w, float* avg_out,
+                                        float* cnt_out, int32_t oh, int32_t ow, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1 && n_frames <= 65535, "blend_resize_frames: frame count %d out of range [1, 65535]", n_frames);
+  return blend_resize_launch("blend_resize_frames", avg, cnt, n_frames, h, w, avg_out, cnt_out, oh, ow, stream);
 }
 
 PRV2_NO_PACKED_FP32_END

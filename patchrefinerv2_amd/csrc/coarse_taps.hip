@@ -22,6 +22,10 @@
 // term -- but only inside a frame with two tile streams and a third stream busy; never in isolation, and independent of every
 // s_waitcnt / s_nop added around the loads and the store (tools/probes/taps_stage_checksums.py, profiles/r04_experiments.txt).
 // Scalar v_fma_f32 code is bit-stable under the same load; the kernels are HBM-bound, the flag costs nothing measurable.
+//
+// Frames (FR = true, the *_frames entry points): G [B, H, W, ldg] -> V [B, 3H, 3W, ldv] with grid.z = frame, and the gather takes
+// boxes (frame, x1, y1, x2, y2) and reads each tile's own frame's tables (frame index clamped to [0, B)).  The single-frame entry
+// points are the FR = false instances of the same kernels.
 #include <cstdlib>
 
 #include "common.h"
@@ -49,8 +53,13 @@ __device__ __forceinline__ void offset_weights(int o, float b, float (&w)[3]) {
 // V[3k + a][3m + c][ch] = sum_tap Bil(G_tap; k + (a - 1 + dy) b_h, m + (c - 1 + dx) b_w).
 // G: [H, W, ldg], channel = tap * C + ch at ``g_off``; thread = (coarse pixel, 4 channels): per tap the 3 x 3 neighbourhood is
 // loaded once (9 loads) and serves the 9 knots of the pixel.
+template <bool FR = false>
 __global__ void __launch_bounds__(256) tap_knots_kernel(const float* __restrict__ G, int H, int W, int C, int ldg, float bh, float bw,
                                                         float* __restrict__ V, int ldv) {
+  if constexpr (FR) {
+    G += (int64_t)blockIdx.z * H * W * ldg;
+    V += (int64_t)blockIdx.z * 9 * H * W * ldv;
+  }
   const unsigned cg = C / 4;
   const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (unsigned)W * cg) return;
@@ -136,16 +145,25 @@ __device__ __forceinline__ void roi_axis(float v, int n, int& lo, int& hi, float
 
 // B[k, i, j, ch] = U(ys(i), xs(j)) - (taps hidden by the zero padding at the tile border).  Thread = (column j, 4 channels) x R
 // output rows; the x-interpolated knot rows of the previous output row are kept (consecutive rows share one knot row).
-template <int R, bool NT = false>
+template <int R, bool NT = false, bool FR = false>
 __global__ void __launch_bounds__(256) tap_gather_kernel(const float* __restrict__ V, const float* __restrict__ G, int H, int W, int C, int ldv,
                                                          int ldg, float kbh, float kbw, const float* __restrict__ boxes, float scale, int oh,
-                                                         int ow, float* __restrict__ out, int ldo) {
+                                                         int ow, float* __restrict__ out, int ldo, int B = 1) {
   const unsigned cg = C / 4;
   const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (unsigned)ow * cg) return;
   const int px = (int)(t / cg), ch = (int)(t - (unsigned)px * cg) * 4;
   const int py0 = blockIdx.y * R, k = blockIdx.z;
-  const float* b = boxes + 4 * k;
+  const float* b;
+  if constexpr (FR) {
+    b = boxes + 5 * k;
+    const int64_t f = min(max((int)b[0], 0), B - 1);
+    G += f * H * W * ldg;
+    V += f * 9 * H * W * ldv;
+    ++b;
+  } else {
+    b = boxes + 4 * k;
+  }
   // torchvision roi_align_forward_kernel_impl, aligned=True (as gather.hip::roi_align_kernel)
   const float rsw = b[0] * scale - 0.5f, rsh = b[1] * scale - 0.5f;
   const float rew = b[2] * scale - 0.5f, reh = b[3] * scale - 0.5f;
@@ -225,40 +243,75 @@ static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t
 
 using namespace prv2;
 
+static int tap_knots_impl(const char* name, const float* g, int32_t B, int32_t h, int32_t w, int32_t c, int32_t ldg, float knot_bh, float knot_bw,
+                          float* v, int32_t ldv, void* stream) {
+  PRV2_REQUIRE(g && v, "%s: null pointer", name);
+  PRV2_REQUIRE(h > 0 && w > 0 && c > 0 && c % 4 == 0 && ldg >= 9 * c && ldg % 4 == 0 && ldv >= c && ldv % 4 == 0 && aligned16(g) && aligned16(v),
+               "%s: c %% 4 == 0, ldg >= 9 c, 16-byte aligned rows (c=%d ldg=%d ldv=%d)", name, c, ldg, ldv);
+  PRV2_REQUIRE(knot_bh > 0.f && knot_bh <= 0.5f && knot_bw > 0.f && knot_bw <= 0.5f,
+               "%s: the knot offsets (tile size / frame size per axis) must be in (0, 1/2] (got %g, %g)", name, (double)knot_bh, (double)knot_bw);
+  PRV2_REQUIRE(h <= 65535 && B <= 65535, "%s: grid too large", name);
+  if (B == 0) {
+    const dim3 grid((unsigned)cdiv((int64_t)w * (c / 4), 256), (unsigned)h);
+    hipLaunchKernelGGL(tap_knots_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, h, w, c, ldg, knot_bh, knot_bw, v, ldv);
+  } else {
+    const dim3 grid((unsigned)cdiv((int64_t)w * (c / 4), 256), (unsigned)h, (unsigned)B);
+    hipLaunchKernelGGL(tap_knots_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, g, h, w, c, ldg, knot_bh, knot_bw, v, ldv);
+  }
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
 extern "C" int prv2_coarse_tap_knots(const float* g, int32_t h, int32_t w, int32_t c, int32_t ldg, float knot_bh, float knot_bw, float* v,
                                      int32_t ldv, void* stream) {
-  PRV2_REQUIRE(g && v, "coarse_tap_knots: null pointer");
-  PRV2_REQUIRE(h > 0 && w > 0 && c > 0 && c % 4 == 0 && ldg >= 9 * c && ldg % 4 == 0 && ldv >= c && ldv % 4 == 0 && aligned16(g) && aligned16(v),
-               "coarse_tap_knots: c %% 4 == 0, ldg >= 9 c, 16-byte aligned rows (c=%d ldg=%d ldv=%d)", c, ldg, ldv);
+  return tap_knots_impl("coarse_tap_knots", g, 0, h, w, c, ldg, knot_bh, knot_bw, v, ldv, stream);
+}
+
+extern "C" int prv2_coarse_tap_knots_frames(const float* g, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldg, float knot_bh, float knot_bw,
+                                            float* v, int32_t ldv, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "coarse_tap_knots_frames: n_frames %d < 1", n_frames);
+  return tap_knots_impl("coarse_tap_knots_frames", g, n_frames, h, w, c, ldg, knot_bh, knot_bw, v, ldv, stream);
+}
+
+static int tap_gather_impl(const char* name, const float* v, const float* g, int32_t B, int32_t h, int32_t w, int32_t c, int32_t ldv, int32_t ldg,
+                           float knot_bh, float knot_bw, const float* boxes, int32_t k, float spatial_scale, int32_t oh, int32_t ow, float* out,
+                           int32_t ldo, void* stream) {
+  PRV2_REQUIRE(v && g && boxes && out, "%s: null pointer", name);
+  PRV2_REQUIRE(h > 0 && w > 0 && k > 0 && oh > 0 && ow > 0 && c > 0 && c % 4 == 0 && ldg >= 9 * c && ldg % 4 == 0 && ldv >= c && ldv % 4 == 0 &&
+                   ldo >= c && ldo % 4 == 0 && aligned16(g) && aligned16(v) && aligned16(out),
+               "%s: c %% 4 == 0, ldg >= 9 c, 16-byte aligned rows (c=%d ldg=%d ldv=%d ldo=%d)", name, c, ldg, ldv, ldo);
   PRV2_REQUIRE(knot_bh > 0.f && knot_bh <= 0.5f && knot_bw > 0.f && knot_bw <= 0.5f,
-               "coarse_tap_knots: the knot offsets (tile size / frame size per axis) must be in (0, 1/2] (got %g, %g)", (double)knot_bh, (double)knot_bw);
-  PRV2_REQUIRE(h <= 65535, "coarse_tap_knots: grid too large");
-  const dim3 grid((unsigned)cdiv((int64_t)w * (c / 4), 256), (unsigned)h);
-  hipLaunchKernelGGL(tap_knots_kernel, grid, dim3(256), 0, (hipStream_t)stream, g, h, w, c, ldg, knot_bh, knot_bw, v, ldv);
-  PRV2_LAUNCH_CHECK("coarse_tap_knots");
+               "%s: the knot offsets must be in (0, 1/2] (got %g, %g)", name, (double)knot_bh, (double)knot_bw);
+  static const int variant = getenv("PRV2_TAPG") ? atoi(getenv("PRV2_TAPG")) : 0;  // A/B switch: bit 0 = 8 rows per thread, bit 1 = nontemporal stores
+  const int R = (variant & 1) && oh >= 32 ? 8 : 4;
+  PRV2_REQUIRE(cdiv(oh, 4) <= 65535 && k <= 65535, "%s: grid too large", name);
+  const dim3 grid((unsigned)cdiv((int64_t)ow * (c / 4), 256), (unsigned)cdiv(oh, R), (unsigned)k);
+#define PRV2_TG(R_, NT_, FR_) hipLaunchKernelGGL((tap_gather_kernel<R_, NT_, FR_>), grid, dim3(256), 0, (hipStream_t)stream, v, g, h, w, c, ldv, ldg, knot_bh, \
+                                                 knot_bw, boxes, spatial_scale, oh, ow, out, ldo, B > 0 ? B : 1)
+  if (B == 0) {
+    if (R == 8) { if (variant & 2) PRV2_TG(8, true, false); else PRV2_TG(8, false, false); }
+    else { if (variant & 2) PRV2_TG(4, true, false); else PRV2_TG(4, false, false); }
+  } else {
+    if (R == 8) { if (variant & 2) PRV2_TG(8, true, true); else PRV2_TG(8, false, true); }
+    else { if (variant & 2) PRV2_TG(4, true, true); else PRV2_TG(4, false, true); }
+  }
+#undef PRV2_TG
+  PRV2_LAUNCH_CHECK(name);
   return 0;
 }
 
 extern "C" int prv2_coarse_tap_gather(const float* v, const float* g, int32_t h, int32_t w, int32_t c, int32_t ldv, int32_t ldg, float knot_bh,
                                       float knot_bw, const float* boxes, int32_t k, float spatial_scale, int32_t oh, int32_t ow, float* out,
                                       int32_t ldo, void* stream) {
-  PRV2_REQUIRE(v && g && boxes && out, "coarse_tap_gather: null pointer");
-  PRV2_REQUIRE(h > 0 && w > 0 && k > 0 && oh > 0 && ow > 0 && c > 0 && c % 4 == 0 && ldg >= 9 * c && ldg % 4 == 0 && ldv >= c && ldv % 4 == 0 &&
-                   ldo >= c && ldo % 4 == 0 && aligned16(g) && aligned16(v) && aligned16(out),
-               "coarse_tap_gather: c %% 4 == 0, ldg >= 9 c, 16-byte aligned rows (c=%d ldg=%d ldv=%d ldo=%d)", c, ldg, ldv, ldo);
-  PRV2_REQUIRE(knot_bh > 0.f && knot_bh <= 0.5f && knot_bw > 0.f && knot_bw <= 0.5f,
-               "coarse_tap_gather: the knot offsets must be in (0, 1/2] (got %g, %g)", (double)knot_bh, (double)knot_bw);
-  static const int variant = getenv("PRV2_TAPG") ? atoi(getenv("PRV2_TAPG")) : 0;  // A/B switch: bit 0 = 8 rows per thread, bit 1 = nontemporal stores
-  const int R = (variant & 1) && oh >= 32 ? 8 : 4;
-  PRV2_REQUIRE(cdiv(oh, 4) <= 65535 && k <= 65535, "coarse_tap_gather: grid too large");
-  const dim3 grid((unsigned)cdiv((int64_t)ow * (c / 4), 256), (unsigned)cdiv(oh, R), (unsigned)k);
-#define PRV2_TG(R_, NT_) hipLaunchKernelGGL((tap_gather_kernel<R_, NT_>), grid, dim3(256), 0, (hipStream_t)stream, v, g, h, w, c, ldv, ldg, knot_bh, knot_bw, boxes, \
-                                            spatial_scale, oh, ow, out, ldo)
-  if (R == 8) { if (variant & 2) PRV2_TG(8, true); else PRV2_TG(8, false); }
-  else { if (variant & 2) PRV2_TG(4, true); else PRV2_TG(4, false); }
-#undef PRV2_TG
-  PRV2_LAUNCH_CHECK("coarse_tap_gather");
-  return 0;
+  return tap_gather_impl("coarse_tap_gather", v, g, 0, h, w, c, ldv, ldg, knot_bh, knot_bw, boxes, k, spatial_scale, oh, ow, out, ldo, stream);
+}
+
+extern "C" int prv2_coarse_tap_gather_frames(const float* v, const float* g, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldv, int32_t ldg,
+                                             float knot_bh, float knot_bw, const float* boxes, int32_t k, float spatial_scale, int32_t oh, int32_t ow,
+                                             float* out, int32_t ldo, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "coarse_tap_gather_frames: n_frames %d < 1", n_frames);
+  return tap_gather_impl("coarse_tap_gather_frames", v, g, n_frames, h, w, c, ldv, ldg, knot_bh, knot_bw, boxes, k, spatial_scale, oh, ow, out, ldo,
+                         stream);
 }
 
 PRV2_NO_PACKED_FP32_END

@@ -4,6 +4,10 @@
 // Grid = (chunks of one output row, output row, image): the row / image coordinates are scalar
 // (blockIdx) and the only per-thread index arithmetic is one 32-bit divide -- the flat 64-bit
 // index decomposition these kernels started with cost more ALU time than the memory traffic.
+// Frames (FR = true, the *_frames entry points): B images / feature maps, each tile names its own frame in its
+// first column -- tiles (frame, h, w), boxes (frame, x1, y1, x2, y2) as torchvision's roi_align takes them.  The
+// frame index is clamped to [0, B) (a bad index reads a wrong frame, never outside the buffer).  The single-frame
+// entry points are the FR = false instances of the same kernels.
 #include "common.h"
 
 PRV2_NO_PACKED_FP32_BEGIN  // (common.h)
@@ -18,15 +22,25 @@ struct Norm3 {
   float std[3];
 };
 
+template <bool FR = false>
 __global__ void __launch_bounds__(256) crop_resize_kernel(const float* __restrict__ img, int H, int W,
                                                           const int* __restrict__ tiles, int K, int ch, int cw, int oh,
                                                           int ow, float sy, float sx, Norm3 nrm, float* __restrict__ out,
-                                                          int ldo) {
+                                                          int ldo, int B = 1) {
   const int ox = blockIdx.x * blockDim.x + threadIdx.x;
   const int oy = blockIdx.y, k = blockIdx.z;
   if (ox >= ow) return;
   const int64_t idx = ((int64_t)k * oh + oy) * ow + ox;
-  int h0 = tiles[2 * k], w0 = tiles[2 * k + 1];
+  int h0, w0;
+  if constexpr (FR) {
+    const int f = min(max(tiles[3 * k], 0), B - 1);
+    img += (int64_t)f * 3 * H * W;
+    h0 = tiles[3 * k + 1];
+    w0 = tiles[3 * k + 2];
+  } else {
+    h0 = tiles[2 * k];
+    w0 = tiles[2 * k + 1];
+  }
   AxisTap ty = ac_tap(oy, sy, ch), tx = ac_tap(ox, sx, cw);
   const float* base = img + (int64_t)(h0)*W + w0;
   float* o = out + idx * ldo;
@@ -137,10 +151,23 @@ __device__ __forceinline__ void store4_fmt(float* pix_base, int c, const float4 
   }
 }
 
-template <int VEC, bool X2 = false>
+// box k of a (frame, x1, y1, x2, y2) list: its (x1, y1, x2, y2) and (``foff``) the offset of its frame's map
+template <bool FR>
+__device__ __forceinline__ const float* frame_box(const float* boxes, int k, int64_t frame_size, int B, int64_t& foff) {
+  if constexpr (FR) {
+    const float* b = boxes + 5 * k;
+    foff = (int64_t)min(max((int)b[0], 0), B - 1) * frame_size;
+    return b + 1;
+  } else {
+    foff = 0;
+    return boxes + 4 * k;
+  }
+}
+
+template <int VEC, bool X2 = false, bool FR = false>
 __global__ void __launch_bounds__(256) roi_align_kernel(const float* __restrict__ feat, int H, int W, int C, int ldf,
                                                         const float* __restrict__ boxes, int K, float scale, int oh,
-                                                        int ow, float* __restrict__ out, int ldo) {
+                                                        int ow, float* __restrict__ out, int ldo, int B = 1) {
   using V = typename VecT<VEC>::type;
   const unsigned cg = C / VEC;
   const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -149,7 +176,9 @@ __global__ void __launch_bounds__(256) roi_align_kernel(const float* __restrict_
   const int py = blockIdx.y, k = blockIdx.z;
   const int64_t pix = ((int64_t)k * oh + py) * ow + px;
   {
-    const float* b = boxes + 4 * k;
+    int64_t foff;
+    const float* b = frame_box<FR>(boxes, k, (int64_t)H * W * ldf, B, foff);
+    feat += foff;
     // torchvision roi_align_forward_kernel_impl, aligned=True
     float rsw = b[0] * scale - 0.5f, rsh = b[1] * scale - 0.5f;
     float rew = b[2] * scale - 0.5f, reh = b[3] * scale - 0.5f;
@@ -195,16 +224,18 @@ __global__ void __launch_bounds__(256) roi_align_kernel(const float* __restrict_
 // rows per source row), so the four taps stay in registers while (y_low, y_high) does not change -- ~1.3 instead of 4 tap loads
 // per output, the SAME arithmetic per output as roi_align_kernel (w1 v1 + w2 v2 + w3 v3 + w4 v4, left to right).  Boxes whose
 // sampling grid is larger than 1 x 1 (down-sampling ROIs) take the general per-pixel loop.
-template <int R, bool X2 = false>
+template <int R, bool X2 = false, bool FR = false>
 __global__ void __launch_bounds__(256) roi_align_rows_kernel(const float* __restrict__ feat, int H, int W, int C, int ldf,
                                                              const float* __restrict__ boxes, int K, float scale, int oh, int ow,
-                                                             float* __restrict__ out, int ldo) {
+                                                             float* __restrict__ out, int ldo, int B = 1) {
   const unsigned cg = C / 4;
   const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (unsigned)ow * cg) return;
   const int px = (int)(t / cg), c = (int)(t - (unsigned)px * cg) * 4;
   const int py0 = blockIdx.y * R, k = blockIdx.z;
-  const float* b = boxes + 4 * k;
+  int64_t foff;
+  const float* b = frame_box<FR>(boxes, k, (int64_t)H * W * ldf, B, foff);
+  feat += foff;
   const float rsw = b[0] * scale - 0.5f, rsh = b[1] * scale - 0.5f;
   const float rew = b[2] * scale - 0.5f, reh = b[3] * scale - 0.5f;
   const float roi_w = rew - rsw, roi_h = reh - rsh;
@@ -448,9 +479,9 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 
 using namespace prv2;
 
-extern "C" int prv2_crop_resize(const float* img, int32_t H, int32_t W, const int32_t* tiles, int32_t K, int32_t ch,
-                                int32_t cw, int32_t oh, int32_t ow, const float* mean3, const float* std3, float* out,
-                                int32_t ldo, void* stream) {
+static int crop_resize_impl(const float* img, int32_t B, int32_t H, int32_t W, const int32_t* tiles, int32_t K, int32_t ch,
+                            int32_t cw, int32_t oh, int32_t ow, const float* mean3, const float* std3, float* out,
+                            int32_t ldo, void* stream) {
   PRV2_REQUIRE(img && tiles && out, "crop_resize: null pointer");
   PRV2_REQUIRE(K > 0 && ch > 0 && cw > 0 && oh > 0 && ow > 0 && ch <= H && cw <= W && ldo >= 3,
                "crop_resize: bad geometry K=%d crop=%dx%d out=%dx%d img=%dx%d ldo=%d", K, ch, cw, oh, ow, H, W, ldo);
@@ -460,10 +491,27 @@ extern "C" int prv2_crop_resize(const float* img, int32_t H, int32_t W, const in
     n.std[i] = std3 ? std3[i] : 1.f;
   }
   PRV2_REQUIRE(oh <= 65535 && K <= 65535, "crop_resize: grid too large");
-  hipLaunchKernelGGL(crop_resize_kernel, dim3((unsigned)cdiv(ow, 256), oh, K), dim3(256), 0, (hipStream_t)stream, img, H, W, tiles,
-                     K, ch, cw, oh, ow, ac_scale(ch, oh), ac_scale(cw, ow), n, out, ldo);
+  if (B == 0)
+    hipLaunchKernelGGL(crop_resize_kernel, dim3((unsigned)cdiv(ow, 256), oh, K), dim3(256), 0, (hipStream_t)stream, img, H, W, tiles,
+                       K, ch, cw, oh, ow, ac_scale(ch, oh), ac_scale(cw, ow), n, out, ldo, 1);
+  else
+    hipLaunchKernelGGL(crop_resize_kernel<true>, dim3((unsigned)cdiv(ow, 256), oh, K), dim3(256), 0, (hipStream_t)stream, img, H, W, tiles,
+                       K, ch, cw, oh, ow, ac_scale(ch, oh), ac_scale(cw, ow), n, out, ldo, B);
   PRV2_LAUNCH_CHECK("crop_resize");
   return 0;
+}
+
+extern "C" int prv2_crop_resize(const float* img, int32_t H, int32_t W, const int32_t* tiles, int32_t K, int32_t ch,
+                                int32_t cw, int32_t oh, int32_t ow, const float* mean3, const float* std3, float* out,
+                                int32_t ldo, void* stream) {
+  return crop_resize_impl(img, 0, H, W, tiles, K, ch, cw, oh, ow, mean3, std3, out, ldo, stream);
+}
+
+extern "C" int prv2_crop_resize_frames(const float* img, int32_t n_frames, int32_t H, int32_t W, const int32_t* tiles, int32_t K, int32_t ch,
+                                       int32_t cw, int32_t oh, int32_t ow, const float* mean3, const float* std3, float* out, int32_t ldo,
+                                       void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "crop_resize_frames: n_frames %d < 1", n_frames);
+  return crop_resize_impl(img, n_frames, H, W, tiles, K, ch, cw, oh, ow, mean3, std3, out, ldo, stream);
 }
 
 extern "C" int prv2_bicubic_resize(const void* src_hwc, int32_t src_is_u8, int32_t h, int32_t w, float* dst_chw, int32_t H,
@@ -482,7 +530,7 @@ extern "C" int prv2_bicubic_resize(const void* src_hwc, int32_t src_is_u8, int32
 }
 
 static int roi_align_impl(const float* feat, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes, int32_t k, float spatial_scale,
-                          int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream, bool x2);
+                          int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream, bool x2, int32_t B = 0);
 
 extern "C" int prv2_roi_align(const float* feat, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes,
                               int32_t k, float spatial_scale, int32_t oh, int32_t ow, float* out, int32_t ldo,
@@ -498,35 +546,50 @@ extern "C" int prv2_roi_align_x2(const float* feat, int32_t h, int32_t w, int32_
   return roi_align_impl(feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow, out, ldo, stream, true);
 }
 
+extern "C" int prv2_roi_align_frames(const float* feat, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes,
+                                     int32_t k, float spatial_scale, int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "roi_align_frames: n_frames %d < 1", n_frames);
+  return roi_align_impl(feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow, out, ldo, stream, false, n_frames);
+}
+
+extern "C" int prv2_roi_align_x2_frames(const float* feat, int32_t n_frames, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes,
+                                        int32_t k, float spatial_scale, int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream) {
+  PRV2_REQUIRE(n_frames >= 1, "roi_align_x2_frames: n_frames %d < 1", n_frames);
+  PRV2_REQUIRE(feat && out && c > 0 && c % 8 == 0 && ldf % 4 == 0 && ldo % 8 == 0 && aligned16(feat) && (reinterpret_cast<uintptr_t>(out) & 31) == 0,
+               "roi_align_x2_frames: c %% 8 == 0, ldo %% 8 == 0, 32-byte aligned output (c=%d ldo=%d)", c, ldo);
+  return roi_align_impl(feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow, out, ldo, stream, true, n_frames);
+}
+
 static int roi_align_impl(const float* feat, int32_t h, int32_t w, int32_t c, int32_t ldf, const float* boxes, int32_t k, float spatial_scale,
-                          int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream, bool x2) {
+                          int32_t oh, int32_t ow, float* out, int32_t ldo, void* stream, bool x2, int32_t B) {
   PRV2_REQUIRE(feat && boxes && out, "roi_align: null pointer");
   PRV2_REQUIRE(h > 0 && w > 0 && c > 0 && k > 0 && oh > 0 && ow > 0 && ldf >= c && ldo >= c, "roi_align: bad geometry");
   bool vec = (c % 4 == 0) && (ldf % 4 == 0) && (ldo % 4 == 0) && aligned16(feat) && aligned16(out);
   PRV2_REQUIRE(oh <= 65535 && k <= 65535, "roi_align: grid too large");
   const dim3 grid((unsigned)cdiv((int64_t)ow * (vec ? c / 4 : c), 256), oh, k);
+  constexpr int R = 4;
+  const dim3 grid_r((unsigned)cdiv((int64_t)ow * (c / 4), 256), (unsigned)cdiv(oh, R), k);
+  const int nb = B > 0 ? B : 1;
+  // B > 0: the *_frames entry points (the FR = true instances); the frame count argument is 1 otherwise
+#define PRV2_ROI(KERNEL, G) hipLaunchKernelGGL((KERNEL), G, dim3(256), 0, (hipStream_t)stream, feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow, \
+                                                    out, ldo, nb)
   if (x2) {  // (vec holds: checked by the caller)
     if (oh >= 16) {
-      constexpr int R = 4;
-      const dim3 grid_r((unsigned)cdiv((int64_t)ow * (c / 4), 256), (unsigned)cdiv(oh, R), k);
-      hipLaunchKernelGGL((roi_align_rows_kernel<R, true>), grid_r, dim3(256), 0, (hipStream_t)stream, feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow,
-                         out, ldo);
-    } else
-      hipLaunchKernelGGL((roi_align_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow, out, ldo);
+      if (B > 0) PRV2_ROI((roi_align_rows_kernel<R, true, true>), grid_r); else PRV2_ROI((roi_align_rows_kernel<R, true>), grid_r);
+    } else {
+      if (B > 0) PRV2_ROI((roi_align_kernel<4, true, true>), grid); else PRV2_ROI((roi_align_kernel<4, true>), grid);
+    }
     PRV2_LAUNCH_CHECK("roi_align_x2");
     return 0;
   }
   if (vec && oh >= 16) {
-    constexpr int R = 4;
-    const dim3 grid_r((unsigned)cdiv((int64_t)ow * (c / 4), 256), (unsigned)cdiv(oh, R), k);
-    hipLaunchKernelGGL(roi_align_rows_kernel<R>, grid_r, dim3(256), 0, (hipStream_t)stream, feat, h, w, c, ldf, boxes, k, spatial_scale, oh, ow,
-                       out, ldo);
-  } else if (vec)
-    hipLaunchKernelGGL(roi_align_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, feat, h, w,
-                       c, ldf, boxes, k, spatial_scale, oh, ow, out, ldo);
-  else
-    hipLaunchKernelGGL(roi_align_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, feat, h, w,
-                       c, ldf, boxes, k, spatial_scale, oh, ow, out, ldo);
+    if (B > 0) PRV2_ROI((roi_align_rows_kernel<R, false, true>), grid_r); else PRV2_ROI(roi_align_rows_kernel<R>, grid_r);
+  } else if (vec) {
+    if (B > 0) PRV2_ROI((roi_align_kernel<4, false, true>), grid); else PRV2_ROI(roi_align_kernel<4>, grid);
+  } else {
+    if (B > 0) PRV2_ROI((roi_align_kernel<1, false, true>), grid); else PRV2_ROI(roi_align_kernel<1>, grid);
+  }
+#undef PRV2_ROI
   PRV2_LAUNCH_CHECK("roi_align");
   return 0;
 }

@@ -794,6 +794,105 @@ std::tuple<Tensor, Tensor> blend_resize(const Tensor& avg, const Tensor& cnt, in
   return {a, c};
 }
 
+// ---- B frames per call (include/prv2.h, ABI 20): tiles (frame, h, w), boxes (frame, x1, y1, x2, y2), B maps / images ----------
+void frame_tiles(const Tensor& t, int64_t cols, at::ScalarType type, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == type && t.dim() == 2 && t.size(1) == cols && t.is_contiguous(), "prv2::", what, ": ",
+              cols == 3 ? "tiles must be an int32 GPU tensor [k, 3] = (frame, h_start, w_start)" : "boxes must be a float32 GPU tensor [k, 5] = (frame, x1, y1, x2, y2)");
+}
+
+Tensor crop_resize_frames(const Tensor& img, const Tensor& tiles, int64_t ch, int64_t cw, int64_t oh, int64_t ow, optional<at::ArrayRef<double>> mean,
+                          optional<at::ArrayRef<double>> std_, const optional<Tensor>& out) {
+  dev_f32(img, "img");
+  TORCH_CHECK(img.dim() == 4 && img.size(1) == 3 && img.is_contiguous(), "prv2::crop_resize_frames: img must be contiguous [B, 3, H, W]");
+  frame_tiles(tiles, 3, at::kInt, "crop_resize_frames");
+  TORCH_CHECK(mean.has_value() == std_.has_value() && (!mean.has_value() || (mean->size() == 3 && std_->size() == 3)), "prv2::crop_resize_frames: mean / std are 3 + 3 floats");
+  const int64_t k = tiles.size(0);
+  Tensor y = out_or_alloc(out, img, k, oh, ow, 3, "crop_resize_frames");
+  float m[3], s[3];
+  if (mean.has_value()) for (int i = 0; i < 3; ++i) { m[i] = (float)(*mean)[i]; s[i] = (float)(*std_)[i]; }
+  Launch L(img);
+  ok(prv2_crop_resize_frames(img.data_ptr<float>(), (int)img.size(0), (int)img.size(2), (int)img.size(3), tiles.data_ptr<int32_t>(), (int)k, (int)ch, (int)cw,
+                             (int)oh, (int)ow, mean.has_value() ? m : nullptr, mean.has_value() ? s : nullptr, y.data_ptr<float>(), (int)nhwc_ld(y, "out"), L.stream),
+     "crop_resize_frames");
+  return y;
+}
+
+Tensor roi_align_frames(const Tensor& feat, const Tensor& boxes, double spatial_scale, int64_t oh, int64_t ow, const optional<Tensor>& out, bool x2) {
+  frame_tiles(boxes, 5, at::kFloat, "roi_align_frames");
+  const int64_t ld = nhwc_ld(feat, "feat");
+  Tensor y = out_or_alloc(out, feat, boxes.size(0), oh, ow, feat.size(3), "roi_align_frames");
+  Launch L(feat);
+  ok((x2 ? prv2_roi_align_x2_frames : prv2_roi_align_frames)(feat.data_ptr<float>(), (int)feat.size(0), (int)feat.size(1), (int)feat.size(2), (int)feat.size(3),
+                                                              (int)ld, boxes.data_ptr<float>(), (int)boxes.size(0), (float)spatial_scale, (int)oh, (int)ow,
+                                                              y.data_ptr<float>(), (int)nhwc_ld(y, "out"), L.stream),
+     "roi_align_frames");
+  return y;
+}
+
+Tensor coarse_tap_knots_frames(const Tensor& g, int64_t cout, double knot_bh, double knot_bw) {
+  const int64_t ldg = nhwc_ld(g, "g");
+  TORCH_CHECK(g.size(3) == 9 * cout, "prv2::coarse_tap_knots_frames: g is [B, h, w, 9 * cout] (tap-major)");
+  Tensor v = at::empty({g.size(0), 3 * g.size(1), 3 * g.size(2), cout}, g.options());
+  Launch L(g);
+  ok(prv2_coarse_tap_knots_frames(g.data_ptr<float>(), (int)g.size(0), (int)g.size(1), (int)g.size(2), (int)cout, (int)ldg, (float)knot_bh, (float)knot_bw,
+                                  v.data_ptr<float>(), (int)cout, L.stream), "coarse_tap_knots_frames");
+  return v;
+}
+
+Tensor coarse_tap_gather_frames(const Tensor& v, const Tensor& g, double knot_bh, double knot_bw, const Tensor& boxes, double spatial_scale, int64_t oh,
+                                int64_t ow, const optional<Tensor>& out) {
+  const int64_t ldv = nhwc_ld(v, "v"), ldg = nhwc_ld(g, "g"), cout = v.size(3);
+  frame_tiles(boxes, 5, at::kFloat, "coarse_tap_gather_frames");
+  TORCH_CHECK(g.size(3) == 9 * cout && v.size(0) == g.size(0) && v.size(1) == 3 * g.size(1) && v.size(2) == 3 * g.size(2),
+              "prv2::coarse_tap_gather_frames: v [B, 3h, 3w, cout], g [B, h, w, 9 cout], boxes [k, 5]");
+  Tensor y = out_or_alloc(out, v, boxes.size(0), oh, ow, cout, "coarse_tap_gather_frames");
+  Launch L(v);
+  ok(prv2_coarse_tap_gather_frames(v.data_ptr<float>(), g.data_ptr<float>(), (int)g.size(0), (int)g.size(1), (int)g.size(2), (int)cout, (int)ldv, (int)ldg,
+                                   (float)knot_bh, (float)knot_bw, boxes.data_ptr<float>(), (int)boxes.size(0), (float)spatial_scale, (int)oh, (int)ow,
+                                   y.data_ptr<float>(), (int)nhwc_ld(y, "out"), L.stream),
+     "coarse_tap_gather_frames");
+  return y;
+}
+
+// pred [B, k, ph, pw] and tiles [B, k, 2]: frame f's slice of a frame-major list (any frame stride, dense inside a frame -- e.g.
+// preds.view(B, n, ph, pw)[:, o:o + k]); avg / cnt: B contiguous maps [B, H, W]
+void blend_frames_args(const Tensor& avg, const Tensor& cnt, const Tensor& pred, const Tensor& mask, const Tensor& tiles, int64_t th, int64_t tw) {
+  dev_f32(avg, "avg"); dev_f32(cnt, "cnt"); dev_f32(pred, "pred"); dev_f32(mask, "mask");
+  TORCH_CHECK(avg.dim() == 3 && avg.is_contiguous() && cnt.sizes() == avg.sizes() && cnt.is_contiguous(), "prv2::blend_frames: avg / cnt must be contiguous [B, H, W] maps");
+  TORCH_CHECK(pred.dim() == 4 && pred.size(0) == avg.size(0) && pred.stride(3) == 1 && pred.stride(2) == pred.size(3) && pred.stride(1) == pred.size(2) * pred.size(3),
+              "prv2::blend_frames: pred must be [B, k, ph, pw], dense within a frame");
+  TORCH_CHECK(tiles.is_cuda() && tiles.scalar_type() == at::kInt && tiles.dim() == 3 && tiles.size(0) == avg.size(0) && tiles.size(1) == pred.size(1) &&
+                  tiles.size(2) == 2 && tiles.stride(2) == 1 && tiles.stride(1) == 2,
+              "prv2::blend_frames: tiles must be an int32 GPU tensor [B, k, 2], one row per prediction, dense within a frame");
+  TORCH_CHECK(mask.is_contiguous() && mask.dim() == 2 && mask.size(0) == th && mask.size(1) == tw, "prv2::blend_frames: mask must be [th, tw]");
+  TORCH_CHECK(tiles.stride(0) % 2 == 0, "prv2::blend_frames: the tiles' frame stride must be whole rows");
+}
+void blend_init_frames(Tensor avg, Tensor cnt, const Tensor& pred, const Tensor& mask, const Tensor& tiles, int64_t th, int64_t tw) {
+  blend_frames_args(avg, cnt, pred, mask, tiles, th, tw);
+  Launch L(avg);
+  ok(prv2_blend_paste_frames(avg.data_ptr<float>(), cnt.data_ptr<float>(), (int)avg.size(0), (int)avg.size(1), (int)avg.size(2), pred.data_ptr<float>(),
+                             (int)pred.size(2), (int)pred.size(3), pred.size(0) > 1 ? pred.stride(0) : pred.size(1) * pred.size(2) * pred.size(3),
+                             mask.data_ptr<float>(), tiles.data_ptr<int32_t>(), (int)(tiles.size(0) > 1 ? tiles.stride(0) / 2 : tiles.size(1)),
+                             (int)tiles.size(1), (int)th, (int)tw, L.stream), "blend_init_frames");
+}
+void blend_update_frames(Tensor avg, Tensor cnt, const Tensor& pred, const Tensor& mask, const Tensor& tiles, int64_t th, int64_t tw) {
+  blend_frames_args(avg, cnt, pred, mask, tiles, th, tw);
+  Launch L(avg);
+  ok(prv2_blend_update_frames(avg.data_ptr<float>(), cnt.data_ptr<float>(), (int)avg.size(0), (int)avg.size(1), (int)avg.size(2), pred.data_ptr<float>(),
+                              (int)pred.size(2), (int)pred.size(3), pred.size(0) > 1 ? pred.stride(0) : pred.size(1) * pred.size(2) * pred.size(3),
+                              mask.data_ptr<float>(), tiles.data_ptr<int32_t>(), (int)(tiles.size(0) > 1 ? tiles.stride(0) / 2 : tiles.size(1)),
+                              (int)tiles.size(1), (int)th, (int)tw, L.stream), "blend_update_frames");
+}
+std::tuple<Tensor, Tensor> blend_resize_frames(const Tensor& avg, const Tensor& cnt, int64_t oh, int64_t ow) {
+  dev_f32(avg, "avg"); dev_f32(cnt, "cnt");
+  TORCH_CHECK(avg.dim() == 3 && avg.is_contiguous() && cnt.sizes() == avg.sizes() && cnt.is_contiguous(), "prv2::blend_resize_frames: avg / cnt must be contiguous [B, H, W] maps");
+  Tensor a = at::empty({avg.size(0), oh, ow}, avg.options()), c = at::empty({avg.size(0), oh, ow}, avg.options());
+  Launch L(avg);
+  ok(prv2_blend_resize_frames(avg.data_ptr<float>(), cnt.data_ptr<float>(), (int)avg.size(0), (int)avg.size(1), (int)avg.size(2), a.data_ptr<float>(),
+                              c.data_ptr<float>(), (int)oh, (int)ow, L.stream), "blend_resize_frames");
+  return {a, c};
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -903,6 +1002,16 @@ TORCH_LIBRARY(prv2, m) {
   m.def("zoe_bins_head(Tensor pt, Tensor centers, float min_temp, float max_temp) -> Tensor");
   m.def("nchw_to_nhwc(Tensor x) -> Tensor");
   m.def("nhwc_to_nchw(Tensor x) -> Tensor");
+  // ABI 20: B frames per call
+  m.def("crop_resize_frames(Tensor img, Tensor tiles, int ch, int cw, int oh, int ow, float[]? mean=None, float[]? std=None, "
+        "Tensor(a!)? out=None) -> Tensor");
+  m.def("roi_align_frames(Tensor feat, Tensor boxes, float spatial_scale, int oh, int ow, Tensor(a!)? out=None, bool x2=False) -> Tensor");
+  m.def("coarse_tap_knots_frames(Tensor g, int cout, float knot_bh, float knot_bw) -> Tensor");
+  m.def("coarse_tap_gather_frames(Tensor v, Tensor g, float knot_bh, float knot_bw, Tensor boxes, float spatial_scale, int oh, int ow, "
+        "Tensor(a!)? out=None) -> Tensor");
+  m.def("blend_init_frames(Tensor(a!) avg, Tensor(b!) cnt, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
+  m.def("blend_update_frames(Tensor(a!) avg, Tensor(b!) cnt, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
+  m.def("blend_resize_frames(Tensor avg, Tensor cnt, int oh, int ow) -> (Tensor, Tensor)");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -959,4 +1068,11 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("zoe_bins_head", &zoe_bins_head);
   m.impl("nchw_to_nhwc", &nchw_to_nhwc);
   m.impl("nhwc_to_nchw", &nhwc_to_nchw);
+  m.impl("crop_resize_frames", &crop_resize_frames);
+  m.impl("roi_align_frames", &roi_align_frames);
+  m.impl("coarse_tap_knots_frames", &coarse_tap_knots_frames);
+  m.impl("coarse_tap_gather_frames", &coarse_tap_gather_frames);
+  m.impl("blend_init_frames", &blend_init_frames);
+  m.impl("blend_update_frames", &blend_update_frames);
+  m.impl("blend_resize_frames", &blend_resize_frames);
 }

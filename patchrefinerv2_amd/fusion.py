@@ -163,7 +163,7 @@ class _EncDec(StateDictModule):
         kb = (float(knot_b[0]), float(knot_b[1]))
         for l, (tw, cons) in P["taps"].items():
             f = c_feat[l]
-            if f.c != tw.cin or f.n != 1 or (f.aux is not None and f.aux.get("kb") == kb):
+            if f.c != tw.cin or (f.aux is not None and f.aux.get("kb") == kb):  # (B frames: one GEMM and one knot launch for all)
                 continue
             g = ops.conv2d(f, tw, algo=0.0)  # [1, H, W, sum 9 * cout]
             taps, o = {}, 0

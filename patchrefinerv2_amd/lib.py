@@ -21,7 +21,7 @@ PREC_LABEL = {PREC_F32: "f32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", PREC_F1
 # (stage 1: GatedConvUnit.conv, csrc/conv3x3_f6.hip) -- the modules map the name to PREC_BF16X3 and fusion.py looks at the name itself
 PREC_NAMES = {"f32": PREC_F32, "bf16x3": PREC_BF16X3, "bf16": PREC_BF16, "f16f6": PREC_BF16X3}
 FMT_X_X2, FMT_MUL_X2, FMT_Y_X2 = 1, 2, 4  # prv2_conv_desc.fmt: operands in the pre-split "X2" activation format
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 class ConvDesc(C.Structure):
@@ -124,6 +124,15 @@ SIGNATURES = {
     "prv2_blend_paste": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     "prv2_blend_update": (_I, [_P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     "prv2_blend_resize": (_I, [_P, _P, _I, _I, _P, _P, _I, _I, _P]),
+    # ABI 20: B frames per call (n_frames after the first pointer(s))
+    "prv2_crop_resize_frames": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P, _I, _P]),
+    "prv2_roi_align_frames": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _F, _I, _I, _P, _I, _P]),
+    "prv2_roi_align_x2_frames": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _F, _I, _I, _P, _I, _P]),
+    "prv2_coarse_tap_knots_frames": (_I, [_P, _I, _I, _I, _I, _I, _F, _F, _P, _I, _P]),
+    "prv2_coarse_tap_gather_frames": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _I, _F, _I, _I, _P, _I, _P]),
+    "prv2_blend_paste_frames": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
+    "prv2_blend_update_frames": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
+    "prv2_blend_resize_frames": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -7,6 +7,8 @@ Host-side mirrors, registered under the reference ``type`` names:
 Call contract (tester.py:69, patchrefinerplus.py:367-380,526-530):
   depth, log = model(mode='infer', cai_mode, process_num, tile_cfg, image_lr, image_hr)
   depth: [1,1,H',W'] fp32 CPU tensor; log['coarse_prediction']: [1,1,ph,pw] device tensor.
+  B frames per call: image_lr [B,3,h,w], image_hr [B,3,H,W] -> depth [B,1,H',W'], coarse_prediction [B,1,ph,pw]; frame f is
+  bit-identical to a call on frame f alone (the B tile plans are drawn in frame order, ``frame_seeds`` reseeds per frame).
 
 What differs from the reference on purpose (results identical):
   * the complete tile list is drawn up-front (consuming Python's ``random`` in the reference's
@@ -117,16 +119,22 @@ class Resizer:
 
 
 class DeviceRunningAverageMap:
-    """RunningAverageMap (estimator/models/utils.py:22-49) resident in HBM."""
+    """RunningAverageMap (estimator/models/utils.py:22-49) resident in HBM.  ``frames``: B maps [B, h, w], each pass step one launch
+    for all of them (preds [B, k, ph, pw] / tiles [B, k, 2]: the pass's slice of every frame)."""
 
-    def __init__(self, h, w, device):
-        self.avg = torch.zeros((h, w), device=device)
-        self.cnt = torch.zeros((h, w), device=device)
+    def __init__(self, h, w, device, frames=None):
+        shape = (h, w) if frames is None else (frames, h, w)
+        self.avg = torch.zeros(shape, device=device)
+        self.cnt = torch.zeros(shape, device=device)
 
     def paste(self, preds, mask, tiles, th, tw):
+        if self.avg.dim() == 3:
+            return ops.blend_paste_frames(self.avg, self.cnt, preds, mask, tiles, th, tw)
         ops.blend_paste(self.avg, self.cnt, preds, mask, tiles, th, tw)
 
     def update(self, preds, mask, tiles, th, tw):
+        if self.avg.dim() == 3:
+            return ops.blend_update_frames(self.avg, self.cnt, preds, mask, tiles, th, tw)
         ops.blend_update(self.avg, self.cnt, preds, mask, tiles, th, tw)
 
     def resize(self, resolution):
@@ -211,6 +219,19 @@ class _PatchModel(StateDictModule):
             passes.append(dict(kind="random", raw=tiles, proc=tiles))
         return passes
 
+    def plan_frames(self, tile_cfg, cai_mode: str, process_num: int, n_frames: int, frame_seeds=None):
+        """The tile plans of ``n_frames`` frames, in frame order: Python's ``random`` is consumed exactly as by ``n_frames``
+        sequential ``plan_tiles`` calls, and with ``frame_seeds`` it is reseeded with ``frame_seeds[f]`` right before frame f's
+        plan (what a per-frame ``random.seed`` of the caller's loop does).  Host only."""
+        if frame_seeds is not None and len(frame_seeds) != n_frames:
+            raise ValueError(f"frame_seeds has {len(frame_seeds)} entries for {n_frames} frames")
+        plans = []
+        for f in range(n_frames):
+            if frame_seeds is not None:
+                random.seed(frame_seeds[f])
+            plans.append(self.plan_tiles(tile_cfg, cai_mode, process_num))
+        return plans
+
     # -- coarse pyramid ROI + crops for a set of tiles ---------------------------------------------
     def _boxes(self, tiles, tile_cfg) -> np.ndarray:
         """bboxs * bboxs_feat_factor in float32 (baseline_pretrain.py:289-296)."""
@@ -222,7 +243,8 @@ class _PatchModel(StateDictModule):
         return (bb * fac[None]).astype(np.float32)
 
     def _prepare_batch(self, image_hr_chw, t_dev, boxes_dev, tile_cfg, coarse_feats: List[Feat], coarse_depth: Feat):
-        """t_dev: int32 [k, 2] (h_start, w_start) of the batch's tiles, boxes_dev: fp32 [k, 4] lr-frame ROI boxes, on the device"""
+        """t_dev: int32 [k, 2] (h_start, w_start) of the batch's tiles, boxes_dev: fp32 [k, 4] lr-frame ROI boxes, on the device.
+        B frames: image [B, 3, H, W], t_dev [k, 3] = (frame, h, w), boxes_dev [k, 5] = (frame, x1, y1, x2, y2), pyramid of B maps."""
         dev = image_hr_chw.device
         ph, pw = self.patch_process_shape
         rh, rw = tile_cfg["patch_raw_shape"]
@@ -242,7 +264,7 @@ class _PatchModel(StateDictModule):
     @torch.no_grad()
     def forward(self, mode=None, image_lr=None, image_hr=None, crops_image_hr=None, depth_gt=None, crop_depths=None,
                 bboxs=None, tile_cfg=None, cai_mode="m1", process_num=4, select_patch=-1, shard=None,
-                return_device=False, gather_dst=None, next_image_lr=None, frame_index=None, **kwargs):
+                return_device=False, gather_dst=None, next_image_lr=None, frame_index=None, frame_seeds=None, **kwargs):
         """``shard=(rank, world)``: this process computes its share of the frame's tiles (``shard_layout``) and the predictions
         are exchanged (RCCL): all-gather when ``gather_dst`` is None (every rank blends and returns the map), gather to rank
         ``gather_dst`` otherwise (only that rank blends; the others return ``depth=None``).
@@ -251,17 +273,28 @@ class _PatchModel(StateDictModule):
         enqueued on a stream of its own beside this frame's tile batches and picked up by the next call (same tensor object);
         results are bit-identical with and without.  In the patch-sharded mode ONE rank computes it (the owner rotates with the frame) and
         broadcasts pyramid + tap tables (``_prefetch_coarse_sharded``); ``frame_index``: the frame's number when the caller's loop is not the
-        only one driving this model (tools that emulate several ranks with one object) -- by default the sharded frames are counted."""
+        only one driving this model (tools that emulate several ranks with one object) -- by default the sharded frames are counted.
+        B frames per call (image_lr [B,3,h,w], image_hr [B,3,H,W]): depth [B,1,H,W], coarse_prediction [B,1,ph,pw], frame f bit-identical
+        to a call on frame f alone; ``frame_seeds`` (B ints): ``random.seed(frame_seeds[f])`` right before frame f's tile plan;
+        ``next_image_lr`` may be the next batch.  Not combined with the patch-sharded mode."""
         if mode != "infer":
             raise NotImplementedError("only mode='infer' is built (training is out of scope, SURVEY.md 2 #12-13)")
         if select_patch != -1:
             raise NotImplementedError("select_patch (feature visualisation hook) is not on the inference path")
         if not (image_lr.is_cuda and image_hr.is_cuda):
             raise RuntimeError("image_lr / image_hr must be on the GPU (tester.py:43-49 moves them); no CPU path")
+        n_frames = image_hr.shape[0]
+        if image_lr.shape[0] != n_frames:
+            raise ValueError(f"image_lr holds {image_lr.shape[0]} frames, image_hr {n_frames}: one low-resolution image per frame")
+        if n_frames > 1 and shard is not None and shard[1] > 1:
+            raise ValueError(f"{n_frames} frames per call with shard={tuple(shard)}: the patch-sharded mode takes one frame per call")
+        if frame_seeds is not None and len(frame_seeds) != n_frames:
+            raise ValueError(f"frame_seeds has {len(frame_seeds)} entries for {n_frames} frames")
         # every kernel is enqueued on the current device's stream: make the inputs' device current for the whole frame
         with torch.cuda.device(image_hr.device):
             self._next_lr = next_image_lr
             self._frame_index = frame_index
+            self._frame_seeds = frame_seeds
             try:
                 # (the guard follows the fusion model's own flag: PRV2_F16F6=1 switches the layers on under arith 'bf16x3' as well)
                 f16f6 = getattr(self, "arith", None) == "f16f6" or bool(getattr(getattr(self, "refiner_fusion_model", None), "f16f6", False))
@@ -294,15 +327,20 @@ class _PatchModel(StateDictModule):
             finally:
                 self._next_lr = None
                 self._frame_index = None
+                self._frame_seeds = None
 
     __call__ = forward
 
     def _infer(self, image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst):
         tile_cfg = self.tile_cfg if tile_cfg is None else self.prepare_tile_cfg(tile_cfg["image_raw_shape"],
                                                                               tile_cfg["patch_split_num"])
-        assert image_hr.shape[0] == 1
+        if image_hr.shape[0] > 1:
+            return self._infer_frames(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, return_device)
         dev = image_hr.device
         # ---- host: the frame's tile plan (consumes Python's ``random`` in the reference's order) ----------------------
+        seeds = self.__dict__.get("_frame_seeds")
+        if seeds is not None:
+            random.seed(seeds[0])
         passes = self.plan_tiles(tile_cfg, cai_mode, process_num)
         self.last_plan = passes
         if shard is not None and shard[1] > 1:
@@ -332,6 +370,39 @@ class _PatchModel(StateDictModule):
             depth = self._to_host(depth)
         elif use_graph:
             depth = depth.clone()  # the graph's own output buffer is rewritten by the next replay
+        return depth, dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
+
+    def _infer_frames(self, image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, return_device):
+        """B frames in one call: the B tile plans drawn in frame order, ONE frame-major tile list (frame f's tiles are rows
+        [f n, (f + 1) n), in the reference's order) whose launch batches may span frames, the coarse forward on the B images, and the
+        blend pass by pass for all frames (``_device_frame``).  The plan's coordinates: int32 [(frame, h, w) of every tile | (h, w)
+        blend origins], flat; boxes fp32 [B n, 5] = (frame, x1, y1, x2, y2)."""
+        B, dev = image_hr.shape[0], image_hr.device
+        plans = self.plan_frames(tile_cfg, cai_mode, process_num, B, self.__dict__.get("_frame_seeds"))
+        self.last_plans = plans
+        self.last_plan = plans[-1]
+        kinds, counts = [p["kind"] for p in plans[0]], [len(p["raw"]) for p in plans[0]]
+        n = sum(counts)
+        raw = [[t for p in ps for t in p["raw"]] for ps in plans]
+        crop = [(f, h, w) for f in range(B) for h, w in raw[f]]
+        proc = [t for ps in plans for p in ps for t in p["proc"]]
+        tiles_i = torch.cat([torch.tensor(crop, dtype=torch.int32).view(-1), torch.tensor(proc, dtype=torch.int32).view(-1)])
+        if self.needs_coarse:
+            boxes_f = torch.from_numpy(np.concatenate([np.concatenate([np.full((n, 1), f, dtype=np.float32), self._boxes(raw[f], tile_cfg)], 1)
+                                                       for f in range(B)]))
+        else:
+            boxes_f = torch.zeros((B * n, 5))
+        plan = dict(kinds=kinds, counts=counts, n_mine=B * n, n_all=n, frames=B)
+        use_graph = bool(getattr(self, "hip_graph", False)) and not ops.PROFILER.enabled
+        if use_graph:
+            depth, coarse_prediction = self._graph_frame(image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode)
+        else:
+            depth, coarse_prediction = self._device_frame(image_lr, image_hr, tiles_i.to(dev, non_blocking=True), boxes_f.to(dev, non_blocking=True),
+                                                          plan, tile_cfg, process_num)
+        if not return_device:
+            depth = self._to_host(depth)
+        elif use_graph:
+            depth = depth.clone()
         return depth, dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
 
     @staticmethod
@@ -682,20 +753,24 @@ class _PatchModel(StateDictModule):
         """Everything of a frame that runs on the device, given the plan's coordinates in device memory: coarse forward, the
         per-patch networks over this rank's tiles (batches round-robin over the HIP streams), the exchange (sharded mode), the
         overlap blend.  No host synchronisation inside (captured into a hipGraph by ``_graph_frame``).
-        tiles_dev: int32 [n_mine + n_all, 2]: this rank's tile origins, then every tile's blend coordinates."""
+        tiles_dev: int32 [n_mine + n_all, 2]: this rank's tile origins, then every tile's blend coordinates.
+        B frames (plan["frames"]): tiles_dev flat int32 [(frame, h, w) x B n | (h, w) x B n] frame-major, boxes_dev [B n, 5]; n_all = n."""
         dev = image_hr.device
         ph, pw = self.patch_process_shape
         rh, rw = tile_cfg["patch_raw_shape"]
         RH, RW = tile_cfg["patch_reensemble_shape"]
         n_mine, n_all = plan["n_mine"], plan["n_all"]
+        B = plan.get("frames", 1)
         if self.needs_coarse:
             coarse_feats, coarse_prediction = self._coarse_of(image_lr, tile_cfg)
-            coarse_depth = Feat(coarse_prediction.view(1, coarse_prediction.shape[-2], coarse_prediction.shape[-1], 1))
+            coarse_depth = Feat(coarse_prediction.view(B, coarse_prediction.shape[-2], coarse_prediction.shape[-1], 1))
         else:
             coarse_feats = coarse_prediction = coarse_depth = None
+        if B > 1:  # (frame-major: tile batches may span frames)
+            tiles_dev, proc_dev = tiles_dev[:3 * n_mine].view(n_mine, 3), tiles_dev[3 * n_mine:].view(B, n_all, 2)
 
         # ---- per-patch networks over the tile list (any batching; optional rank sharding) ----
-        image_chw = image_hr[0].contiguous().float()
+        image_chw = image_hr[0].contiguous().float() if B == 1 else image_hr.contiguous().float()
         bs = max(1, int(getattr(self, "max_batch", None) or process_num))
         preds = torch.empty((n_mine, 1, ph, pw), device=dev)  # this rank's predictions, in tile order
         # Tile batches are independent: they are issued round-robin on ``n_streams`` HIP streams so that the
@@ -719,6 +794,8 @@ class _PatchModel(StateDictModule):
         if n_streams > 1:
             for st in streams:
                 main.wait_stream(st)
+        if B > 1:
+            return self._blend_frames(preds.view(B, n_all, ph, pw), proc_dev, plan, tile_cfg), coarse_prediction
         preds = preds.view(n_all, ph, pw)
 
         # ---- overlap blend, in the reference's order ----------------------------------------------
@@ -740,6 +817,30 @@ class _PatchModel(StateDictModule):
                 if k:
                     ram.update(pr, mask_r, tdev, rh, rw)
         return ram.avg[None, None], coarse_prediction
+
+    def _blend_frames(self, preds, proc, plan, tile_cfg):
+        """the overlap blend of B frames, pass by pass, one launch per pass step for all frames: preds [B, n, ph, pw], proc int32
+        [B, n, 2] (frame-major; within a frame the reference's order) -> depth [B, 1, H, W]"""
+        B, dev = preds.shape[0], preds.device
+        ph, pw = self.patch_process_shape
+        rh, rw = tile_cfg["patch_raw_shape"]
+        RH, RW = tile_cfg["patch_reensemble_shape"]
+        mask = blend_mask((ph, pw), self.blend_border, 0.0, dev)
+        ram = DeviceRunningAverageMap(RH, RW, dev, frames=B)
+        o = 0
+        for kind, k in zip(plan["kinds"], plan["counts"]):
+            pr, tdev = preds[:, o:o + k], proc[:, o:o + k]
+            o += k
+            if kind == "init":
+                ram.paste(pr, mask, tdev, ph, pw)
+            elif kind == "grid":
+                ram.update(pr, mask, tdev, ph, pw)
+            else:
+                mask_r = blend_mask((rh, rw), self.blend_border, 1e-3, dev)
+                ram.resize(tile_cfg["image_raw_shape"])
+                if k:
+                    ram.update(pr, mask_r, tdev, rh, rw)
+        return ram.avg[:, None]
 
     def _graph_frame(self, image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode):
         """``hip_graph=True``: the device side of a frame (``_device_frame``: a few thousand launches on up to ``n_streams``
@@ -1222,7 +1323,7 @@ class PatchRefinerSemi(StateDictModule):
             raise NotImplementedError("PatchRefinerSemi: only inference is built (training is out of scope, SURVEY.md 2 #12-14)")
         # (:208-210 forwards cai_mode but neither tile_cfg nor process_num: the student runs with its configured tiling -- unless the
         #  caller passes them, which the reference's wrapper would have dropped)
-        extra = {k: v for k, v in kw.items() if k in ("tile_cfg", "process_num", "next_image_lr", "return_device") and v is not None}
+        extra = {k: v for k, v in kw.items() if k in ("tile_cfg", "process_num", "next_image_lr", "return_device", "frame_seeds") and v is not None}
         return self.student_model(mode=mode, image_lr=image_lr, image_hr=image_hr, depth_gt=depth_gt, cai_mode=cai_mode, **extra)
 
     __call__ = forward

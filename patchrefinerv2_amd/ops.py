@@ -1114,10 +1114,22 @@ def attention(qkv: torch.Tensor, b: int, ntok: int, heads: int, prec: int = PREC
 
 def crop_resize(img_chw: torch.Tensor, tiles: torch.Tensor, ch: int, cw: int, oh: int, ow: int,
                 mean: Optional[Sequence[float]], std: Optional[Sequence[float]], out: Feat):
-    """img_chw [3,H,W] device; tiles int32 [k,2] device; writes channels 0..2 of ``out`` [k,oh,ow,*]."""
+    """img_chw [3,H,W] device; tiles int32 [k,2] device; writes channels 0..2 of ``out`` [k,oh,ow,*].
+    B frames: img [B,3,H,W] and tiles int32 [k,3] = (frame, h, w) (prv2_crop_resize_frames)."""
     _require_dev(img_chw)
     assert tiles.dtype == torch.int32 and tiles.is_cuda and img_chw.is_contiguous()
     k = tiles.shape[0]
+    if img_chw.dim() == 4:
+        assert tiles.shape[1] == 3, "crop_resize of B frames takes tiles (frame, h, w)"
+        if DISPATCH == "torch":
+            _tops().crop_resize_frames(img_chw, tiles.contiguous(), ch, cw, oh, ow, list(mean) if mean is not None else None,
+                                       list(std) if std is not None else None, out.slice(0, 3).view())
+            return
+        m = (C.c_float * 3)(*mean) if mean is not None else None
+        s = (C.c_float * 3)(*std) if std is not None else None
+        L.check(L.load().prv2_crop_resize_frames(img_chw.data_ptr(), img_chw.shape[0], img_chw.shape[2], img_chw.shape[3], tiles.data_ptr(), k,
+                                                 ch, cw, oh, ow, m, s, out.ptr, out.ld, _stream()), "crop_resize_frames")
+        return
     if DISPATCH == "torch":
         _tops().crop_resize_bilinear(img_chw, tiles.contiguous(), ch, cw, oh, ow, list(mean) if mean is not None else None,
                                      list(std) if std is not None else None, out.slice(0, 3).view())
@@ -1144,10 +1156,25 @@ def bicubic_resize(img_hwc: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
 
 
 def roi_align(feat: Feat, boxes: torch.Tensor, spatial_scale: float, oh: int, ow: int, out: Optional[Feat] = None) -> Feat:
-    assert feat.n == 1 and boxes.dtype == torch.float32 and boxes.is_cuda and boxes.shape[1] == 4
+    """boxes [k, 4] = (x1, y1, x2, y2) on ONE map (feat.n == 1), or [k, 5] = (frame, x1, y1, x2, y2) on B maps (torchvision's
+    format; prv2_roi_align_frames)"""
+    frames = boxes.shape[1] == 5
+    assert (feat.n == 1 or frames) and boxes.dtype == torch.float32 and boxes.is_cuda and boxes.shape[1] in (4, 5)
     k = boxes.shape[0]
     if out is None:
         out = Feat.alloc(k, oh, ow, feat.c, feat.device)
+    if frames:
+        if DISPATCH == "torch":
+            PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.n * feat.h * feat.w + k * oh * ow),
+                                lambda: _tops().roi_align_frames(feat.view(), boxes.contiguous(), float(spatial_scale), oh, ow, out.raw(), out.x2),
+                                f"{feat.c}ch {feat.n}x{feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
+            return out
+        fn = L.load().prv2_roi_align_x2_frames if out.x2 else L.load().prv2_roi_align_frames
+        PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.n * feat.h * feat.w + k * oh * ow),
+                            lambda: L.check(fn(feat.ptr, feat.n, feat.h, feat.w, feat.c, feat.ld, boxes.data_ptr(), k,
+                                               spatial_scale, oh, ow, out.ptr, out.ld, _stream()), "roi_align_frames"),
+                            f"{feat.c}ch {feat.n}x{feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
+        return out
     if DISPATCH == "torch":
         PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.h * feat.w + k * oh * ow),
                             lambda: _tops().roi_align(feat.view(), boxes.contiguous(), float(spatial_scale), oh, ow, out.raw(), out.x2),
@@ -1305,11 +1332,24 @@ COARSE_TAPS = os.environ.get("PRV2_COARSE_TAPS", "1") != "0"  # A/B and test swi
 class CoarseTaps:
     """The coarse half of one ``cat([fine, coarse_roi])`` 3x3 conv, tabulated once per frame (include/prv2.h::prv2_coarse_tap_knots):
     ``g`` [1, H, W, 9 * cout] = the level's map through the conv's coarse weights, tap-major (a 1x1 GEMM at coarse resolution),
-    ``v`` [1, 3H, 3W, cout] = the unmasked tap sum on the knot grid, ``kb`` = (tile height / frame height, tile width / frame width)."""
+    ``v`` [1, 3H, 3W, cout] = the unmasked tap sum on the knot grid, ``kb`` = (tile height / frame height, tile width / frame width).
+    B frames: ``g`` [B, H, W, 9 * cout] -> ``v`` [B, 3H, 3W, cout] in one launch, and ``gather`` takes boxes (frame, x1, y1, x2, y2)."""
 
     def __init__(self, g: Feat, cout: int, kb):
-        assert g.n == 1 and g.c == 9 * cout and 0 < kb[0] <= 0.5 and 0 < kb[1] <= 0.5
+        assert g.c == 9 * cout and 0 < kb[0] <= 0.5 and 0 < kb[1] <= 0.5
         self.g, self.cout, self.kb = g, cout, (float(kb[0]), float(kb[1]))
+        if g.n > 1:
+            if DISPATCH == "torch":
+                box = []
+                PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.n * g.h * g.w * 18 * cout,
+                                    lambda: box.append(_tops().coarse_tap_knots_frames(g.view(), cout, self.kb[0], self.kb[1])), f"{cout}ch {g.n}x{g.h}x{g.w}")
+                self.v = Feat(box[0])
+                return
+            self.v = Feat(torch.empty((g.n, 3 * g.h, 3 * g.w, cout), device=g.device, dtype=torch.float32))
+            PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.n * g.h * g.w * 18 * cout,
+                                lambda: L.check(L.load().prv2_coarse_tap_knots_frames(g.ptr, g.n, g.h, g.w, cout, g.ld, self.kb[0], self.kb[1], self.v.ptr,
+                                                                                      self.v.ld, _stream()), "coarse_tap_knots_frames"), f"{cout}ch {g.n}x{g.h}x{g.w}")
+            return
         if DISPATCH == "torch":
             box = []
             PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.h * g.w * 18 * cout, lambda: box.append(_tops().coarse_tap_knots(g.view(), cout, self.kb[0], self.kb[1])),
@@ -1323,15 +1363,16 @@ class CoarseTaps:
 
     def gather(self, boxes: torch.Tensor, spatial_scale: float, oh: int, ow: int, out: Optional[Feat] = None) -> Feat:
         """the conv's coarse half for the tiles ``boxes`` (as roi_align takes them): [k, oh, ow, cout], zero padding at the tile border
-        included (prv2_coarse_tap_gather)"""
-        assert boxes.dtype == torch.float32 and boxes.is_cuda and boxes.shape[1] == 4
+        included (prv2_coarse_tap_gather).  Tables of B frames: boxes (frame, x1, y1, x2, y2) (prv2_coarse_tap_gather_frames)."""
+        frames = self.g.n > 1
+        assert boxes.dtype == torch.float32 and boxes.is_cuda and boxes.shape[1] == (5 if frames else 4)
         k = boxes.shape[0]
         # The knot-grid algebra holds when consecutive output pixels are exactly ``kb`` coarse pixels apart (ROI bin == knot spacing): every
         # box must span kb * (g.h, g.w) * (oh, ow) / spatial_scale frame pixels.  The boxes live on the device (no host sync on the frame
         # path): PRV2_CHECK_TAPS=1 verifies them here; the library checks what it can see (knot spacing in (0, 1/2]), fusion.py compares the
         # ROI's output size with its consumer's map before taking this path.
         if os.environ.get("PRV2_CHECK_TAPS"):
-            b = boxes.detach().cpu()
+            b = boxes.detach().cpu()[:, -4:]
             bin_w = (b[:, 2] - b[:, 0]) * spatial_scale / ow
             bin_h = (b[:, 3] - b[:, 1]) * spatial_scale / oh
             assert float((bin_h - self.kb[0]).abs().max()) < 1e-4 and float((bin_w - self.kb[1]).abs().max()) < 1e-4, \
@@ -1340,6 +1381,18 @@ class CoarseTaps:
             out = Feat(torch.empty((k, oh, ow, self.cout), device=self.g.device, dtype=torch.float32))
         assert (out.n, out.h, out.w, out.c) == (k, oh, ow, self.cout) and not out.x2
         g, v = self.g, self.v
+        if frames:
+            if DISPATCH == "torch":
+                PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.n * g.h * g.w + k * oh * ow),
+                                    lambda: _tops().coarse_tap_gather_frames(v.view(), g.view(), self.kb[0], self.kb[1], boxes.contiguous(), float(spatial_scale),
+                                                                             oh, ow, out.view()),
+                                    f"{self.cout}ch {g.n}x{g.h}x{g.w}->{k}x{oh}x{ow}")
+                return out
+            PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.n * g.h * g.w + k * oh * ow),
+                                lambda: L.check(L.load().prv2_coarse_tap_gather_frames(v.ptr, g.ptr, g.n, g.h, g.w, self.cout, v.ld, g.ld, self.kb[0], self.kb[1],
+                                                                                       boxes.data_ptr(), k, spatial_scale, oh, ow, out.ptr, out.ld, _stream()),
+                                                "coarse_tap_gather_frames"), f"{self.cout}ch {g.n}x{g.h}x{g.w}->{k}x{oh}x{ow}")
+            return out
         if DISPATCH == "torch":
             PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.h * g.w + k * oh * ow),
                                 lambda: _tops().coarse_tap_gather(v.view(), g.view(), self.kb[0], self.kb[1], boxes.contiguous(), float(spatial_scale), oh, ow, out.view()),
@@ -1428,7 +1481,37 @@ def blend_update(avg, cnt, pred, mask, tiles, th, tw):
                                        th, tw, _stream()), "blend_update")
 
 
+def _blend_frames(paste, avg, cnt, pred, mask, tiles, th, tw):
+    """one pass step of the blend for B maps avg / cnt [B, H, W]: pred [B, k, ph, pw] and tiles int32 [B, k, 2] are frame f's slice of
+    frame-major lists (any frame stride: ``preds.view(B, n, ph, pw)[:, o:o + k]``, no copies)"""
+    B, k = pred.shape[0], pred.shape[1]
+    assert avg.dim() == 3 and tiles.shape[:2] == (B, k) and pred.stride(1) == pred.shape[2] * pred.shape[3] and tiles.stride(1) == 2
+    if DISPATCH == "torch":
+        return (_tops().blend_init_frames if paste else _tops().blend_update_frames)(avg, cnt, pred, mask, tiles, th, tw)
+    fn = L.load().prv2_blend_paste_frames if paste else L.load().prv2_blend_update_frames
+    L.check(fn(avg.data_ptr(), cnt.data_ptr(), B, avg.shape[1], avg.shape[2], pred.data_ptr(), pred.shape[-2], pred.shape[-1],
+               pred.stride(0) if B > 1 else k * pred.shape[2] * pred.shape[3], mask.data_ptr(), tiles.data_ptr(),
+               tiles.stride(0) // 2 if B > 1 else k, k, th, tw, _stream()), "blend_paste_frames" if paste else "blend_update_frames")
+
+
+def blend_paste_frames(avg, cnt, pred, mask, tiles, th, tw):
+    _blend_frames(True, avg, cnt, pred, mask, tiles, th, tw)
+
+
+def blend_update_frames(avg, cnt, pred, mask, tiles, th, tw):
+    _blend_frames(False, avg, cnt, pred, mask, tiles, th, tw)
+
+
 def blend_resize(avg, cnt, oh, ow):
+    """[H, W] maps, or B maps [B, H, W] in one launch (prv2_blend_resize_frames)"""
+    if avg.dim() == 3:
+        if DISPATCH == "torch":
+            return _tops().blend_resize_frames(avg, cnt, oh, ow)
+        a = torch.empty((avg.shape[0], oh, ow), device=avg.device, dtype=torch.float32)
+        c = torch.empty((avg.shape[0], oh, ow), device=avg.device, dtype=torch.float32)
+        L.check(L.load().prv2_blend_resize_frames(avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], avg.shape[2], a.data_ptr(),
+                                                  c.data_ptr(), oh, ow, _stream()), "blend_resize_frames")
+        return a, c
     if DISPATCH == "torch":
         return _tops().blend_resize(avg, cnt, oh, ow)
     a = torch.empty((oh, ow), device=avg.device, dtype=torch.float32)

@@ -162,32 +162,44 @@ class Tester:
         self.config, self.runner_info, self.dataloader, self.model = config, runner_info, dataloader, model
 
     @torch.no_grad()
-    def run(self, cai_mode="m1", process_num=4, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), seed=None, shard="frames"):
+    def run(self, cai_mode="m1", process_num=4, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), seed=None, shard="frames",
+            frame_batch=1):
         """``shard='frames'`` (the reference's data parallelism, tester.py:58: frame f on rank f mod world) or ``'patches'`` (every
         rank works on EVERY frame: its tiles are sharded over the ranks and gathered to rank 0, which blends, saves and scores --
         models._PatchModel.forward(shard=...)).  The loop knows its next frame: its low-resolution image is announced to the
-        model, which runs that coarse forward beside the current frame's tiles (``next_image_lr``)."""
+        model, which runs that coarse forward beside the current frame's tiles (``next_image_lr``).
+        ``frame_batch``: N frames per model call (the last group may be shorter; a frame-sharded run groups each rank's frames); the
+        results are split per frame -- names, order, PNGs and metrics as with one frame per call, and bit-identical to it."""
         import random
         results = []
         rank, world = self.runner_info.rank, getattr(self.runner_info, "world_size", 1)
         patches = shard == "patches" and world > 1
+        fb = max(1, int(frame_batch))
+        if fb > 1 and patches:
+            raise ValueError("frame_batch > 1 with shard='patches': the patch-sharded mode takes one frame per call")
         prefetch = bool(getattr(self.model, "needs_coarse", False))
         todo = list(range(len(self.dataloader))) if patches else list(range(rank, len(self.dataloader), world))
+        groups = [todo[i:i + fb] for i in range(0, len(todo), fb)]
 
-        def load(idx):
-            item = self.dataloader[idx]
-            hr = item["image_hr"].unsqueeze(0).cuda()
-            return item, hr, self.model.resizer(hr)
+        def load(idxs):
+            items = [self.dataloader[idx] for idx in idxs]
+            hr = torch.stack([item["image_hr"] for item in items]).cuda()
+            return items, hr, self.model.resizer(hr)
 
-        nxt = load(todo[0]) if todo else None
-        for n, idx in enumerate(todo):
-            item, hr, lr = nxt
-            nxt = load(todo[n + 1]) if n + 1 < len(todo) else None
+        nxt = load(groups[0]) if groups else None
+        for n, idxs in enumerate(groups):
+            items, hr, lr = nxt
+            nxt = load(groups[n + 1]) if n + 1 < len(groups) else None
+            kw = {}
             if seed is not None:
-                random.seed(seed)
+                if fb == 1:
+                    random.seed(seed)
+                else:  # (every frame's plan from the same seed, as one frame per call does)
+                    kw["frame_seeds"] = [seed] * len(idxs)
             tile_cfg = dict(image_raw_shape=list(image_raw_shape), patch_split_num=list(patch_split_num))
             # with ground truth the frame is scored on the device (metrics.compute_metrics_device): ask for the device map
-            kw = dict(return_device=True) if item.get("depth_gt") is not None and getattr(self.model, "supports_return_device", False) else {}
+            if any(item.get("depth_gt") is not None for item in items) and getattr(self.model, "supports_return_device", False):
+                kw.update(return_device=True)
             if patches:
                 kw.update(shard=(rank, world), gather_dst=0)
             if prefetch and nxt is not None:
@@ -196,30 +208,11 @@ class Tester:
                                      image_lr=lr, image_hr=hr, **kw)
             if result is None:  # patch-sharded: only rank 0 holds the map
                 continue
-            result_dev = result if result.is_cuda else None
-            result = result.cpu()  # BaselinePretrain(target='coarse') hands back the device tensor (baseline_pretrain.py:464)
-            if self.runner_info.save:
-                os.makedirs(self.runner_info.work_dir, exist_ok=True)
-                base = os.path.join(self.runner_info.work_dir, item["img_file_basename"])
-                # raw depth as 16-bit PNG, multiplier 256 (tester.py:89-91)
-                write_png16(base + "_uint16.png", (result.squeeze().numpy() * 256).astype("uint16"))
-                from .metrics import colorize
-                if getattr(self.runner_info, "gray_scale", False):
-                    color = colorize(result, cmap="gray_r")
-                else:  # every dataset branch of tester.py:76-84 but cityscapes maps to Spectral, 0..100 percentiles
-                    cmap = "magma_r" if getattr(self.dataloader, "dataset_name", "") == "cityscapes" else "Spectral"
-                    color = colorize(result, cmap=cmap, vminp=0, vmaxp=100)
-                write_png8(base + ".png", np.ascontiguousarray(color[:, :, :3]))
-                from .metrics import depth_edges
-                write_png8(base + "_edge.png", depth_edges(result).astype(np.uint8) * 255)  # tester.py:99-106
-                if log.get("coarse_prediction") is not None:  # absent for BaselinePretrain
-                    coarse = F.interpolate(log["coarse_prediction"].cpu(), tuple(image_raw_shape), mode="bilinear")
-                    write_png8(base + "_coarse.png", np.ascontiguousarray(colorize(coarse, cmap="Spectral", vminp=0, vmaxp=100)[:, :, :3]))
-            entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(result.mean()))
-            if item.get("depth_gt") is not None:
-                entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result if result_dev is None else result_dev,
-                                                               disp_gt_edges=item.get("boundary"))
-            results.append(entry)
+            coarse = log.get("coarse_prediction")
+            for f, item in enumerate(items):
+                one = len(items) == 1
+                self._emit(results, item, result if one else result[f:f + 1], coarse if one or coarse is None else coarse[f:f + 1],
+                           image_raw_shape)
         if not patches:
             # collect results from all ranks (tester.py:124-127: collect_results_gpu); rank 0 evaluates the whole dataset
             allr = collect_results(results, len(self.dataloader))
@@ -228,6 +221,33 @@ class Tester:
             from .metrics import evaluate
             self.last_eval = evaluate([r["metrics"] for r in results])
         return results
+
+    def _emit(self, results, item, result, coarse, image_raw_shape):
+        """one frame's outputs: PNGs (--save), its metrics and its result entry"""
+        result_dev = result if result.is_cuda else None
+        result = result.cpu()  # BaselinePretrain(target='coarse') hands back the device tensor (baseline_pretrain.py:464)
+        if self.runner_info.save:
+            os.makedirs(self.runner_info.work_dir, exist_ok=True)
+            base = os.path.join(self.runner_info.work_dir, item["img_file_basename"])
+            # raw depth as 16-bit PNG, multiplier 256 (tester.py:89-91)
+            write_png16(base + "_uint16.png", (result.squeeze().numpy() * 256).astype("uint16"))
+            from .metrics import colorize
+            if getattr(self.runner_info, "gray_scale", False):
+                color = colorize(result, cmap="gray_r")
+            else:  # every dataset branch of tester.py:76-84 but cityscapes maps to Spectral, 0..100 percentiles
+                cmap = "magma_r" if getattr(self.dataloader, "dataset_name", "") == "cityscapes" else "Spectral"
+                color = colorize(result, cmap=cmap, vminp=0, vmaxp=100)
+            write_png8(base + ".png", np.ascontiguousarray(color[:, :, :3]))
+            from .metrics import depth_edges
+            write_png8(base + "_edge.png", depth_edges(result).astype(np.uint8) * 255)  # tester.py:99-106
+            if coarse is not None:  # absent for BaselinePretrain
+                coarse_map = F.interpolate(coarse.cpu(), tuple(image_raw_shape), mode="bilinear")
+                write_png8(base + "_coarse.png", np.ascontiguousarray(colorize(coarse_map, cmap="Spectral", vminp=0, vmaxp=100)[:, :, :3]))
+        entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(result.mean()))
+        if item.get("depth_gt") is not None:
+            entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result if result_dev is None else result_dev,
+                                                           disp_gt_edges=item.get("boundary"))
+        results.append(entry)
 
     @torch.no_grad()
     def run_consistency(self, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), overlap=270):

@@ -6,6 +6,7 @@
 
 CONFIG is an MMEngine-style python config (``model=dict(type=..., config=dict(...))``, ``_base_`` supported).
 Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``--prec``, ``--process-num``, ``--max-batch``, ``--streams``.
+``--frame-batch N``: N frames per model call on one GPU (per rank in a frame-sharded run), outputs split per frame.
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
 """
@@ -53,6 +54,8 @@ def main():
     ap.add_argument("--streams", type=int, default=3, help="HIP streams the tile batches are spread over (config key n_streams wins)")
     ap.add_argument("--synthetic-weights", action="store_true")
     ap.add_argument("--seed", type=int, default=621)
+    ap.add_argument("--frame-batch", type=int, default=1, metavar="N", help="N frames per model call (one GPU; the last group may be "
+                    "shorter): outputs are split per frame and bit-identical to one frame per call")
     ap.add_argument("--launcher", default="none", choices=["none", "pytorch"],
                     help="pytorch: started by torch.distributed.run (tools/dist_test.sh): one process per GPU, RCCL process group")
     ap.add_argument("--shard", default="frames", choices=["frames", "patches"],
@@ -112,7 +115,7 @@ def main():
         print(f"Model Flops: {b['flops'] / 1e12:.3f} T  Model Parameters: {b['params'] / 1e6:.1f} M")
         return
     results = tester.run(cai_mode=args.cai_mode, process_num=args.process_num, image_raw_shape=args.image_raw_shape,
-                         patch_split_num=args.patch_split_num, seed=args.seed, shard=args.shard)
+                         patch_split_num=args.patch_split_num, seed=args.seed, shard=args.shard, frame_batch=args.frame_batch)
     if rank == 0 or world == 1:  # (frame-sharded runs: rank 0 holds every rank's results, collected like collect_results_gpu)
         for r in results:
             print(f"[rank {rank}] {r['name']}: depth {r['shape']} mean {r['mean']:.4f}")
