@@ -543,6 +543,28 @@ int prv2_blend_update_frames(float* avg, float* cnt, int32_t n_frames, int32_t m
 int prv2_blend_resize_frames(const float* avg, const float* cnt, int32_t n_frames, int32_t h, int32_t w, float* avg_out, float* cnt_out,
                              int32_t oh, int32_t ow, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Overlap statistics: the blend of B >= 1 frames (arguments, frame strides and checks as the *_frames entry points; B = 1 is
+ * n_frames = 1) with two more maps per frame, m2 / ntiles [B, map_h, map_w]:
+ *   m2     weighted sum of squared deviations of the covering tiles' predictions from the running mean;
+ *   ntiles number of tiles whose footprint covers the pixel (an exact integer, stored as float).
+ * paste: avg = p, cnt = ct, m2 = 0, ntiles = 1.  update, for every covering tile in order: ntiles += 1; when ct > 0,
+ * d = p - avg, avg and cnt as prv2_blend_update, m2 += ct * d * (p - avg_new) (computed as its exact equal
+ * (cnt ct / (cnt + ct)) d^2, free of cancellation).  avg / cnt are bit-identical to the entry points without statistics.
+ * m2 / ntiles are read and written only where a tile of the call lies.
+ * The weighted standard deviation of the overlapping predictions is sqrt(max(m2, 0) / cnt) where cnt > 0.
+ * ------------------------------------------------------------------------------------------ */
+int prv2_blend_paste_stats(float* avg, float* cnt, float* m2, float* ntiles, int32_t n_frames, int32_t map_h, int32_t map_w, const float* pred,
+                           int32_t ph, int32_t pw, int64_t pred_fstride, const float* mask, const int32_t* tiles, int32_t tile_fstride,
+                           int32_t k, int32_t th, int32_t tw, void* stream);
+int prv2_blend_update_stats(float* avg, float* cnt, float* m2, float* ntiles, int32_t n_frames, int32_t map_h, int32_t map_w, const float* pred,
+                            int32_t ph, int32_t pw, int64_t pred_fstride, const float* mask, const int32_t* tiles, int32_t tile_fstride,
+                            int32_t k, int32_t th, int32_t tw, void* stream);
+/* prv2_blend_resize_frames plus: ntiles -> nearest; m2_out = v[nearest] * cnt_out with v = m2 / cnt where cnt > 0 and 0 elsewhere
+ * (the variance is kept and rescaled to the resampled weight) */
+int prv2_blend_resize_stats(const float* avg, const float* cnt, const float* m2, const float* ntiles, int32_t n_frames, int32_t h, int32_t w,
+                            float* avg_out, float* cnt_out, float* m2_out, float* ntiles_out, int32_t oh, int32_t ow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

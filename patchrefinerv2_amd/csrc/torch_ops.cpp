@@ -893,6 +893,49 @@ std::tuple<Tensor, Tensor> blend_resize_frames(const Tensor& avg, const Tensor& 
   return {a, c};
 }
 
+// overlap statistics (include/prv2.h prv2_blend_*_stats): the B-frame blend plus m2 / ntiles maps [B, H, W]; B = 1 is a batch of one
+void blend_stats_args(const Tensor& avg, const Tensor& cnt, const Tensor& m2, const Tensor& ntiles, const Tensor& pred, const Tensor& mask,
+                      const Tensor& tiles, int64_t th, int64_t tw) {
+  blend_frames_args(avg, cnt, pred, mask, tiles, th, tw);
+  dev_f32(m2, "m2"); dev_f32(ntiles, "ntiles");
+  TORCH_CHECK(m2.sizes() == avg.sizes() && m2.is_contiguous() && ntiles.sizes() == avg.sizes() && ntiles.is_contiguous(),
+              "prv2::blend_stats: m2 / ntiles must be contiguous [B, H, W] maps of avg's shape");
+}
+void blend_init_stats(Tensor avg, Tensor cnt, Tensor m2, Tensor ntiles, const Tensor& pred, const Tensor& mask, const Tensor& tiles, int64_t th,
+                      int64_t tw) {
+  blend_stats_args(avg, cnt, m2, ntiles, pred, mask, tiles, th, tw);
+  Launch L(avg);
+  ok(prv2_blend_paste_stats(avg.data_ptr<float>(), cnt.data_ptr<float>(), m2.data_ptr<float>(), ntiles.data_ptr<float>(), (int)avg.size(0), (int)avg.size(1),
+                            (int)avg.size(2), pred.data_ptr<float>(), (int)pred.size(2), (int)pred.size(3),
+                            pred.size(0) > 1 ? pred.stride(0) : pred.size(1) * pred.size(2) * pred.size(3), mask.data_ptr<float>(),
+                            tiles.data_ptr<int32_t>(), (int)(tiles.size(0) > 1 ? tiles.stride(0) / 2 : tiles.size(1)), (int)tiles.size(1), (int)th,
+                            (int)tw, L.stream), "blend_init_stats");
+}
+void blend_update_stats(Tensor avg, Tensor cnt, Tensor m2, Tensor ntiles, const Tensor& pred, const Tensor& mask, const Tensor& tiles, int64_t th,
+                        int64_t tw) {
+  blend_stats_args(avg, cnt, m2, ntiles, pred, mask, tiles, th, tw);
+  Launch L(avg);
+  ok(prv2_blend_update_stats(avg.data_ptr<float>(), cnt.data_ptr<float>(), m2.data_ptr<float>(), ntiles.data_ptr<float>(), (int)avg.size(0), (int)avg.size(1),
+                             (int)avg.size(2), pred.data_ptr<float>(), (int)pred.size(2), (int)pred.size(3),
+                             pred.size(0) > 1 ? pred.stride(0) : pred.size(1) * pred.size(2) * pred.size(3), mask.data_ptr<float>(),
+                             tiles.data_ptr<int32_t>(), (int)(tiles.size(0) > 1 ? tiles.stride(0) / 2 : tiles.size(1)), (int)tiles.size(1), (int)th,
+                             (int)tw, L.stream), "blend_update_stats");
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> blend_resize_stats(const Tensor& avg, const Tensor& cnt, const Tensor& m2, const Tensor& ntiles, int64_t oh,
+                                                              int64_t ow) {
+  dev_f32(avg, "avg"); dev_f32(cnt, "cnt"); dev_f32(m2, "m2"); dev_f32(ntiles, "ntiles");
+  TORCH_CHECK(avg.dim() == 3 && avg.is_contiguous() && cnt.sizes() == avg.sizes() && cnt.is_contiguous() && m2.sizes() == avg.sizes() &&
+                  m2.is_contiguous() && ntiles.sizes() == avg.sizes() && ntiles.is_contiguous(),
+              "prv2::blend_resize_stats: avg / cnt / m2 / ntiles must be contiguous [B, H, W] maps");
+  auto mk = [&] { return at::empty({avg.size(0), oh, ow}, avg.options()); };
+  Tensor a = mk(), c = mk(), s = mk(), n = mk();
+  Launch L(avg);
+  ok(prv2_blend_resize_stats(avg.data_ptr<float>(), cnt.data_ptr<float>(), m2.data_ptr<float>(), ntiles.data_ptr<float>(), (int)avg.size(0), (int)avg.size(1),
+                             (int)avg.size(2), a.data_ptr<float>(), c.data_ptr<float>(), s.data_ptr<float>(), n.data_ptr<float>(), (int)oh, (int)ow, L.stream),
+     "blend_resize_stats");
+  return {a, c, s, n};
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1012,6 +1055,10 @@ TORCH_LIBRARY(prv2, m) {
   m.def("blend_init_frames(Tensor(a!) avg, Tensor(b!) cnt, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
   m.def("blend_update_frames(Tensor(a!) avg, Tensor(b!) cnt, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
   m.def("blend_resize_frames(Tensor avg, Tensor cnt, int oh, int ow) -> (Tensor, Tensor)");
+  // overlap statistics: m2 / ntiles beside avg / cnt (B-frame layout; B = 1 is a batch of one)
+  m.def("blend_init_stats(Tensor(a!) avg, Tensor(b!) cnt, Tensor(c!) m2, Tensor(d!) ntiles, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
+  m.def("blend_update_stats(Tensor(a!) avg, Tensor(b!) cnt, Tensor(c!) m2, Tensor(d!) ntiles, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
+  m.def("blend_resize_stats(Tensor avg, Tensor cnt, Tensor m2, Tensor ntiles, int oh, int ow) -> (Tensor, Tensor, Tensor, Tensor)");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1075,4 +1122,7 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("blend_init_frames", &blend_init_frames);
   m.impl("blend_update_frames", &blend_update_frames);
   m.impl("blend_resize_frames", &blend_resize_frames);
+  m.impl("blend_init_stats", &blend_init_stats);
+  m.impl("blend_update_stats", &blend_update_stats);
+  m.impl("blend_resize_stats", &blend_resize_stats);
 }

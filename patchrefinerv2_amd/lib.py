@@ -133,6 +133,10 @@ SIGNATURES = {
     "prv2_blend_paste_frames": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
     "prv2_blend_update_frames": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
     "prv2_blend_resize_frames": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _P]),
+    # overlap statistics (m2 / ntiles maps beside avg / cnt; frames as above)
+    "prv2_blend_paste_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
+    "prv2_blend_update_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
+    "prv2_blend_resize_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -120,25 +120,42 @@ class Resizer:
 
 class DeviceRunningAverageMap:
     """RunningAverageMap (estimator/models/utils.py:22-49) resident in HBM.  ``frames``: B maps [B, h, w], each pass step one launch
-    for all of them (preds [B, k, ph, pw] / tiles [B, k, 2]: the pass's slice of every frame)."""
+    for all of them (preds [B, k, ph, pw] / tiles [B, k, 2]: the pass's slice of every frame).  ``stats``: two more maps, ``m2`` (the
+    weighted sum of squared deviations of the overlapping predictions) and ``ntl`` (tiles covering the pixel), kept by the
+    prv2_blend_*_stats kernels; avg / cnt are bit-identical to the map without them."""
 
-    def __init__(self, h, w, device, frames=None):
+    def __init__(self, h, w, device, frames=None, stats=False):
         shape = (h, w) if frames is None else (frames, h, w)
         self.avg = torch.zeros(shape, device=device)
         self.cnt = torch.zeros(shape, device=device)
+        self.m2 = torch.zeros(shape, device=device) if stats else None
+        self.ntl = torch.zeros(shape, device=device) if stats else None
 
     def paste(self, preds, mask, tiles, th, tw):
+        if self.m2 is not None:
+            return ops.blend_paste_stats(self.avg, self.cnt, self.m2, self.ntl, preds, mask, tiles, th, tw)
         if self.avg.dim() == 3:
             return ops.blend_paste_frames(self.avg, self.cnt, preds, mask, tiles, th, tw)
         ops.blend_paste(self.avg, self.cnt, preds, mask, tiles, th, tw)
 
     def update(self, preds, mask, tiles, th, tw):
+        if self.m2 is not None:
+            return ops.blend_update_stats(self.avg, self.cnt, self.m2, self.ntl, preds, mask, tiles, th, tw)
         if self.avg.dim() == 3:
             return ops.blend_update_frames(self.avg, self.cnt, preds, mask, tiles, th, tw)
         ops.blend_update(self.avg, self.cnt, preds, mask, tiles, th, tw)
 
     def resize(self, resolution):
+        if self.m2 is not None:
+            self.avg, self.cnt, self.m2, self.ntl = ops.blend_resize_stats(self.avg, self.cnt, self.m2, self.ntl, int(resolution[0]),
+                                                                           int(resolution[1]))
+            return
         self.avg, self.cnt = ops.blend_resize(self.avg, self.cnt, int(resolution[0]), int(resolution[1]))
+
+    def stats_maps(self):
+        """(uncertainty, count_map) of the current state, shaped like ``avg``: the weighted standard deviation of the overlapping tile
+        predictions (sqrt(max(m2, 0) / cnt), 0 where cnt == 0) and the number of tiles covering the pixel"""
+        return ops.blend_uncertainty(self.cnt, self.m2), self.ntl
 
 
 def _cfg(config):
@@ -264,7 +281,8 @@ class _PatchModel(StateDictModule):
     @torch.no_grad()
     def forward(self, mode=None, image_lr=None, image_hr=None, crops_image_hr=None, depth_gt=None, crop_depths=None,
                 bboxs=None, tile_cfg=None, cai_mode="m1", process_num=4, select_patch=-1, shard=None,
-                return_device=False, gather_dst=None, next_image_lr=None, frame_index=None, frame_seeds=None, **kwargs):
+                return_device=False, gather_dst=None, next_image_lr=None, frame_index=None, frame_seeds=None, return_uncertainty=False,
+                **kwargs):
         """``shard=(rank, world)``: this process computes its share of the frame's tiles (``shard_layout``) and the predictions
         are exchanged (RCCL): all-gather when ``gather_dst`` is None (every rank blends and returns the map), gather to rank
         ``gather_dst`` otherwise (only that rank blends; the others return ``depth=None``).
@@ -276,7 +294,11 @@ class _PatchModel(StateDictModule):
         only one driving this model (tools that emulate several ranks with one object) -- by default the sharded frames are counted.
         B frames per call (image_lr [B,3,h,w], image_hr [B,3,H,W]): depth [B,1,H,W], coarse_prediction [B,1,ph,pw], frame f bit-identical
         to a call on frame f alone; ``frame_seeds`` (B ints): ``random.seed(frame_seeds[f])`` right before frame f's tile plan;
-        ``next_image_lr`` may be the next batch.  Not combined with the patch-sharded mode."""
+        ``next_image_lr`` may be the next batch.  Not combined with the patch-sharded mode.
+        ``return_uncertainty``: the log dict gains ``uncertainty`` -- per pixel, the weighted standard deviation (metres) of the overlapping
+        tile predictions around the blended depth -- and ``count_map`` -- the number of tiles covering the pixel (float32, an exact
+        integer), both [B,1,H,W] at the depth's resolution, on the host or the device as the depth.  The depth itself is bit-identical to a
+        call without it.  Not combined with the patch-sharded mode."""
         if mode != "infer":
             raise NotImplementedError("only mode='infer' is built (training is out of scope, SURVEY.md 2 #12-13)")
         if select_patch != -1:
@@ -290,6 +312,9 @@ class _PatchModel(StateDictModule):
             raise ValueError(f"{n_frames} frames per call with shard={tuple(shard)}: the patch-sharded mode takes one frame per call")
         if frame_seeds is not None and len(frame_seeds) != n_frames:
             raise ValueError(f"frame_seeds has {len(frame_seeds)} entries for {n_frames} frames")
+        stats = bool(return_uncertainty)
+        if stats and shard is not None and shard[1] > 1:
+            raise ValueError(f"return_uncertainty with shard={tuple(shard)}: the patch-sharded mode does not keep the overlap statistics")
         # every kernel is enqueued on the current device's stream: make the inputs' device current for the whole frame
         with torch.cuda.device(image_hr.device):
             self._next_lr = next_image_lr
@@ -300,7 +325,7 @@ class _PatchModel(StateDictModule):
                 f16f6 = getattr(self, "arith", None) == "f16f6" or bool(getattr(getattr(self, "refiner_fusion_model", None), "f16f6", False))
                 guard = f16f6 and ops.F6Range.active(image_hr.device)
                 rnd = random.getstate() if guard else None
-                out = self._infer(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst)
+                out = self._infer(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst, stats)
                 if guard:
                     # fp16 range guard of the fp16 + fp6 layers (ops.F6Range): a frame in which a layer's input left fp16's range is
                     # computed again with that layer's power-of-two input scale moved (the tile plan's random draws are replayed)
@@ -322,7 +347,7 @@ class _PatchModel(StateDictModule):
                         self.f6_recalibrations = getattr(self, "f6_recalibrations", 0) + 1
                         self.__dict__.pop("_graphs", None)  # (a captured frame carries the old scales)
                         random.setstate(rnd)
-                        out = self._infer(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst)
+                        out = self._infer(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst, stats)
                 return out
             finally:
                 self._next_lr = None
@@ -331,11 +356,11 @@ class _PatchModel(StateDictModule):
 
     __call__ = forward
 
-    def _infer(self, image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst):
+    def _infer(self, image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, shard, return_device, gather_dst, stats=False):
         tile_cfg = self.tile_cfg if tile_cfg is None else self.prepare_tile_cfg(tile_cfg["image_raw_shape"],
                                                                               tile_cfg["patch_split_num"])
         if image_hr.shape[0] > 1:
-            return self._infer_frames(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, return_device)
+            return self._infer_frames(image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, return_device, stats)
         dev = image_hr.device
         # ---- host: the frame's tile plan (consumes Python's ``random`` in the reference's order) ----------------------
         seeds = self.__dict__.get("_frame_seeds")
@@ -358,21 +383,25 @@ class _PatchModel(StateDictModule):
 
         use_graph = bool(getattr(self, "hip_graph", False)) and shard is None and not ops.PROFILER.enabled
         if use_graph:
-            depth, coarse_prediction = self._graph_frame(image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode)
+            depth, coarse_prediction, extra = self._graph_frame(image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode,
+                                                                stats)
         else:
             tiles_dev = tiles_i.to(dev, non_blocking=True)
             boxes_dev = boxes_f.to(dev, non_blocking=True)
-            depth, coarse_prediction = self._device_frame(image_lr, image_hr, tiles_dev, boxes_dev, plan, tile_cfg, process_num,
-                                                          shard, gather_dst)
+            depth, coarse_prediction, extra = self._device_frame(image_lr, image_hr, tiles_dev, boxes_dev, plan, tile_cfg, process_num,
+                                                                 shard, gather_dst, stats)
             if depth is None:  # gather-to-one: this rank's part of the frame is done
                 return None, dict(rgb=image_lr, depth_pred=None, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
         if not return_device:
             depth = self._to_host(depth)
         elif use_graph:
             depth = depth.clone()  # the graph's own output buffer is rewritten by the next replay
-        return depth, dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
+        log = dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
+        if extra is not None:
+            log.update(self._stats_out(extra, return_device, use_graph))
+        return depth, log
 
-    def _infer_frames(self, image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, return_device):
+    def _infer_frames(self, image_lr, image_hr, depth_gt, tile_cfg, cai_mode, process_num, return_device, stats=False):
         """B frames in one call: the B tile plans drawn in frame order, ONE frame-major tile list (frame f's tiles are rows
         [f n, (f + 1) n), in the reference's order) whose launch batches may span frames, the coarse forward on the B images, and the
         blend pass by pass for all frames (``_device_frame``).  The plan's coordinates: int32 [(frame, h, w) of every tile | (h, w)
@@ -395,15 +424,29 @@ class _PatchModel(StateDictModule):
         plan = dict(kinds=kinds, counts=counts, n_mine=B * n, n_all=n, frames=B)
         use_graph = bool(getattr(self, "hip_graph", False)) and not ops.PROFILER.enabled
         if use_graph:
-            depth, coarse_prediction = self._graph_frame(image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode)
+            depth, coarse_prediction, extra = self._graph_frame(image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode,
+                                                                stats)
         else:
-            depth, coarse_prediction = self._device_frame(image_lr, image_hr, tiles_i.to(dev, non_blocking=True), boxes_f.to(dev, non_blocking=True),
-                                                          plan, tile_cfg, process_num)
+            depth, coarse_prediction, extra = self._device_frame(image_lr, image_hr, tiles_i.to(dev, non_blocking=True),
+                                                                 boxes_f.to(dev, non_blocking=True), plan, tile_cfg, process_num, stats=stats)
         if not return_device:
             depth = self._to_host(depth)
         elif use_graph:
             depth = depth.clone()
-        return depth, dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
+        log = dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt, coarse_prediction=coarse_prediction)
+        if extra is not None:
+            log.update(self._stats_out(extra, return_device, use_graph))
+        return depth, log
+
+    def _stats_out(self, extra, return_device, use_graph):
+        """the overlap statistics (uncertainty, count_map) [B,1,H,W] where the depth goes: pinned host copies, or device tensors
+        (a captured graph's static outputs are cloned: the next replay rewrites them)"""
+        unc, count = extra
+        if not return_device:
+            unc, count = self._to_host(unc), self._to_host(count)
+        elif use_graph:
+            unc, count = unc.clone(), count.clone()
+        return dict(uncertainty=unc, count_map=count)
 
     @staticmethod
     def _to_host(depth):
@@ -749,12 +792,13 @@ class _PatchModel(StateDictModule):
             ops.F6Range.clear(dev)  # (no guarded frame here: what these launches saw must not be judged by the next frame's check)
         return preds
 
-    def _device_frame(self, image_lr, image_hr, tiles_dev, boxes_dev, plan, tile_cfg, process_num, shard=None, gather_dst=None):
+    def _device_frame(self, image_lr, image_hr, tiles_dev, boxes_dev, plan, tile_cfg, process_num, shard=None, gather_dst=None, stats=False):
         """Everything of a frame that runs on the device, given the plan's coordinates in device memory: coarse forward, the
         per-patch networks over this rank's tiles (batches round-robin over the HIP streams), the exchange (sharded mode), the
         overlap blend.  No host synchronisation inside (captured into a hipGraph by ``_graph_frame``).
         tiles_dev: int32 [n_mine + n_all, 2]: this rank's tile origins, then every tile's blend coordinates.
-        B frames (plan["frames"]): tiles_dev flat int32 [(frame, h, w) x B n | (h, w) x B n] frame-major, boxes_dev [B n, 5]; n_all = n."""
+        B frames (plan["frames"]): tiles_dev flat int32 [(frame, h, w) x B n | (h, w) x B n] frame-major, boxes_dev [B n, 5]; n_all = n.
+        -> (depth, coarse_prediction, (uncertainty, count_map) with ``stats``, else None)"""
         dev = image_hr.device
         ph, pw = self.patch_process_shape
         rh, rw = tile_cfg["patch_raw_shape"]
@@ -795,12 +839,13 @@ class _PatchModel(StateDictModule):
             for st in streams:
                 main.wait_stream(st)
         if B > 1:
-            return self._blend_frames(preds.view(B, n_all, ph, pw), proc_dev, plan, tile_cfg), coarse_prediction
+            depth, extra = self._blend_frames(preds.view(B, n_all, ph, pw), proc_dev, plan, tile_cfg, stats)
+            return depth, coarse_prediction, extra
         preds = preds.view(n_all, ph, pw)
 
         # ---- overlap blend, in the reference's order ----------------------------------------------
         mask = blend_mask((ph, pw), self.blend_border, 0.0, dev)
-        ram = DeviceRunningAverageMap(RH, RW, dev)
+        ram = DeviceRunningAverageMap(RH, RW, dev, stats=stats)
         all_proc = tiles_dev[n_mine:]
         o = 0
         for kind, k in zip(plan["kinds"], plan["counts"]):
@@ -816,17 +861,18 @@ class _PatchModel(StateDictModule):
                 ram.resize(tile_cfg["image_raw_shape"])
                 if k:
                     ram.update(pr, mask_r, tdev, rh, rw)
-        return ram.avg[None, None], coarse_prediction
+        extra = tuple(t[None, None] for t in ram.stats_maps()) if stats else None
+        return ram.avg[None, None], coarse_prediction, extra
 
-    def _blend_frames(self, preds, proc, plan, tile_cfg):
+    def _blend_frames(self, preds, proc, plan, tile_cfg, stats=False):
         """the overlap blend of B frames, pass by pass, one launch per pass step for all frames: preds [B, n, ph, pw], proc int32
-        [B, n, 2] (frame-major; within a frame the reference's order) -> depth [B, 1, H, W]"""
+        [B, n, 2] (frame-major; within a frame the reference's order) -> (depth [B, 1, H, W], (uncertainty, count_map) or None)"""
         B, dev = preds.shape[0], preds.device
         ph, pw = self.patch_process_shape
         rh, rw = tile_cfg["patch_raw_shape"]
         RH, RW = tile_cfg["patch_reensemble_shape"]
         mask = blend_mask((ph, pw), self.blend_border, 0.0, dev)
-        ram = DeviceRunningAverageMap(RH, RW, dev, frames=B)
+        ram = DeviceRunningAverageMap(RH, RW, dev, frames=B, stats=stats)
         o = 0
         for kind, k in zip(plan["kinds"], plan["counts"]):
             pr, tdev = preds[:, o:o + k], proc[:, o:o + k]
@@ -840,9 +886,9 @@ class _PatchModel(StateDictModule):
                 ram.resize(tile_cfg["image_raw_shape"])
                 if k:
                     ram.update(pr, mask_r, tdev, rh, rw)
-        return ram.avg[:, None]
+        return ram.avg[:, None], (tuple(t[:, None] for t in ram.stats_maps()) if stats else None)
 
-    def _graph_frame(self, image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode):
+    def _graph_frame(self, image_lr, image_hr, tiles_i, boxes_f, plan, tile_cfg, process_num, cai_mode, stats=False):
         """``hip_graph=True``: the device side of a frame (``_device_frame``: a few thousand launches on up to ``n_streams``
         streams) is captured once per (mode, geometry, batching) into a hipGraph and replayed per frame; the per-frame inputs
         -- the two images and the plan's coordinates (random tiles change from frame to frame) -- are copied into the graph's
@@ -850,13 +896,13 @@ class _PatchModel(StateDictModule):
         embeddings / relative-position biases), the second is captured.  Results are bit-identical to the eager path."""
         dev = image_hr.device
         key = (cai_mode, process_num, tuple(tile_cfg["image_raw_shape"]), tuple(tile_cfg["patch_split_num"]), tuple(image_lr.shape),
-               getattr(self, "max_batch", None), getattr(self, "n_streams", 1), tuple(plan["counts"]), str(dev))
+               getattr(self, "max_batch", None), getattr(self, "n_streams", 1), tuple(plan["counts"]), str(dev), bool(stats))
         cache = self.__dict__.setdefault("_graphs", {})
         ent = cache.get(key)
         if ent is None:  # first frame: eager (warm-up of every constant cache)
             cache[key] = "warm"
             return self._device_frame(image_lr, image_hr, tiles_i.to(dev, non_blocking=True), boxes_f.to(dev, non_blocking=True), plan,
-                                      tile_cfg, process_num)
+                                      tile_cfg, process_num, stats=stats)
         if ent == "warm":
             st = dict(lr=torch.empty_like(image_lr), hr=torch.empty_like(image_hr), tiles=torch.empty(tiles_i.shape, dtype=torch.int32, device=dev),
                       boxes=torch.empty(boxes_f.shape, dtype=torch.float32, device=dev),
@@ -864,7 +910,8 @@ class _PatchModel(StateDictModule):
             torch.cuda.current_stream(dev).synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                st["depth"], st["coarse"] = self._device_frame(st["lr"], st["hr"], st["tiles"], st["boxes"], plan, tile_cfg, process_num)
+                st["depth"], st["coarse"], st["stats"] = self._device_frame(st["lr"], st["hr"], st["tiles"], st["boxes"], plan, tile_cfg,
+                                                                            process_num, stats=stats)
             st["graph"] = g
             cache[key] = ent = st
         if ent.get("staged") is not None:
@@ -878,7 +925,7 @@ class _PatchModel(StateDictModule):
         ent["staged"] = torch.cuda.Event()
         ent["staged"].record(torch.cuda.current_stream(dev))
         ent["graph"].replay()
-        return ent["depth"], (ent["coarse"].clone() if ent["coarse"] is not None else None)
+        return ent["depth"], (ent["coarse"].clone() if ent["coarse"] is not None else None), ent["stats"]
 
     def _exchange(self, mine, shard, dst, group=0):
         """blocking form of ``_exchange_begin`` (all-gather when dst is None, gather-to-dst otherwise) -> rank-major
@@ -1222,13 +1269,15 @@ class BaselinePretrain(_PatchModel):
         if mode == "train":
             raise NotImplementedError("only inference is built (training is out of scope, SURVEY.md 2 #12-13)")
         if self.target == "coarse":
+            if kw.get("return_uncertainty"):
+                raise ValueError("return_uncertainty: BaselinePretrain(target='coarse') predicts the whole frame at once -- no tiles overlap")
             if not image_lr.is_cuda:
                 raise RuntimeError("image_lr must be on the GPU (tester.py:43-49 moves it); no CPU path")
             with torch.cuda.device(image_lr.device):
                 depth = self.coarse_branch(image_lr)["metric_depth"]
             return depth, dict(rgb=image_lr, depth_pred=depth, depth_gt=depth_gt)
-        depth, _ = super().forward(mode="infer", image_lr=image_lr, image_hr=image_hr, depth_gt=depth_gt, **kw)
-        return depth, {}
+        depth, log = super().forward(mode="infer", image_lr=image_lr, image_hr=image_hr, depth_gt=depth_gt, **kw)
+        return depth, {k: log[k] for k in ("uncertainty", "count_map") if k in log}
 
     __call__ = forward
 
@@ -1323,7 +1372,7 @@ class PatchRefinerSemi(StateDictModule):
             raise NotImplementedError("PatchRefinerSemi: only inference is built (training is out of scope, SURVEY.md 2 #12-14)")
         # (:208-210 forwards cai_mode but neither tile_cfg nor process_num: the student runs with its configured tiling -- unless the
         #  caller passes them, which the reference's wrapper would have dropped)
-        extra = {k: v for k, v in kw.items() if k in ("tile_cfg", "process_num", "next_image_lr", "return_device", "frame_seeds") and v is not None}
+        extra = {k: v for k, v in kw.items() if k in ("tile_cfg", "process_num", "next_image_lr", "return_device", "frame_seeds", "return_uncertainty") and v is not None}
         return self.student_model(mode=mode, image_lr=image_lr, image_hr=image_hr, depth_gt=depth_gt, cai_mode=cai_mode, **extra)
 
     __call__ = forward

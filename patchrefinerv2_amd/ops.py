@@ -1521,6 +1521,61 @@ def blend_resize(avg, cnt, oh, ow):
     return a, c
 
 
+def _as_frames(avg, pred, tiles):
+    """B = 1 inputs of the statistics ops as a batch of one: maps [H, W] -> [1, H, W], pred [k, (1,) ph, pw] -> [1, k, ph, pw],
+    tiles [k, 2] -> [1, k, 2] (views)"""
+    if avg.dim() == 2:
+        avg = avg[None]
+        pred = pred.reshape(1, pred.shape[0], pred.shape[-2], pred.shape[-1])
+        tiles = tiles[None]
+    return avg, pred, tiles
+
+
+def _blend_stats(paste, avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
+    """one pass step of the blend with the overlap statistics m2 / ntl (prv2_blend_*_stats): maps [H, W] with pred [k, ph, pw] /
+    tiles [k, 2], or B maps [B, H, W] with frame-major slices pred [B, k, ph, pw] / tiles [B, k, 2] as ``blend_paste_frames``"""
+    a3, pred, tiles = _as_frames(avg, pred, tiles)
+    c3, s3, n3 = (t.view(a3.shape) for t in (cnt, m2, ntl))
+    B, k = pred.shape[0], pred.shape[1]
+    assert tiles.shape[:2] == (B, k) and pred.stride(1) == pred.shape[2] * pred.shape[3] and tiles.stride(1) == 2
+    if DISPATCH == "torch":
+        return (_tops().blend_init_stats if paste else _tops().blend_update_stats)(a3, c3, s3, n3, pred, mask, tiles, th, tw)
+    fn = L.load().prv2_blend_paste_stats if paste else L.load().prv2_blend_update_stats
+    L.check(fn(a3.data_ptr(), c3.data_ptr(), s3.data_ptr(), n3.data_ptr(), B, a3.shape[1], a3.shape[2], pred.data_ptr(), pred.shape[-2],
+               pred.shape[-1], pred.stride(0) if B > 1 else k * pred.shape[2] * pred.shape[3], mask.data_ptr(), tiles.data_ptr(),
+               tiles.stride(0) // 2 if B > 1 else k, k, th, tw, _stream()), "blend_paste_stats" if paste else "blend_update_stats")
+
+
+def blend_paste_stats(avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
+    """paste: avg = p, cnt = ct, m2 = 0, ntl = 1 under every tile"""
+    _blend_stats(True, avg, cnt, m2, ntl, pred, mask, tiles, th, tw)
+
+
+def blend_update_stats(avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
+    """update: avg / cnt as ``blend_update``; ntl += 1 under every tile, m2 += ct (p - avg_old)(p - avg_new) where ct > 0"""
+    _blend_stats(False, avg, cnt, m2, ntl, pred, mask, tiles, th, tw)
+
+
+def blend_resize_stats(avg, cnt, m2, ntl, oh, ow):
+    """``blend_resize`` of [H, W] or [B, H, W] maps plus ntl (nearest) and m2 (the nearest pixel's m2 / cnt times the resampled cnt)
+    -> (avg, cnt, m2, ntl) at [(B,) oh, ow]"""
+    one = avg.dim() == 2
+    a3, c3, s3, n3 = (t[None] if one else t for t in (avg, cnt, m2, ntl))
+    B = a3.shape[0]
+    if DISPATCH == "torch":
+        out = _tops().blend_resize_stats(a3, c3, s3, n3, oh, ow)
+    else:
+        out = tuple(torch.empty((B, oh, ow), device=avg.device, dtype=torch.float32) for _ in range(4))
+        L.check(L.load().prv2_blend_resize_stats(a3.data_ptr(), c3.data_ptr(), s3.data_ptr(), n3.data_ptr(), B, a3.shape[1], a3.shape[2],
+                                                 *(t.data_ptr() for t in out), oh, ow, _stream()), "blend_resize_stats")
+    return tuple(t[0] for t in out) if one else tuple(out)
+
+
+def blend_uncertainty(cnt, m2):
+    """the weighted standard deviation of the overlapping tile predictions: sqrt(max(m2, 0) / cnt) where cnt > 0, 0 elsewhere"""
+    return (m2.clamp(min=0) / cnt).sqrt_().masked_fill_(cnt <= 0, 0.0)
+
+
 def add(a: Feat, b: Feat, out: Optional[Feat] = None) -> Feat:
     assert (a.n, a.h, a.w, a.c) == (b.n, b.h, b.w, b.c)
     if out is None:

@@ -1,6 +1,7 @@
 """Inference driver + general image dataset (the callers on either side of the hot path).
 
 Tester.run          estimator/tester/tester.py:52-127 (frame loop, model call contract, uint16 PNG x256)
+Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, uncertainty and tile-count PNGs)
 ImageDataset        estimator/datasets/general_dataset.py:161-234 (folder of images -> image_hr / image_lr)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
@@ -132,6 +133,17 @@ class ImageDataset:
                                max_depth_eval=self.max_depth, garg_crop=False, eigen_crop=False, dataset=self.dataset_name)
 
 
+def pseudo_label_uncertainty(uncertainty: np.ndarray, count_map: np.ndarray, n_tiles: int, count_thr: float):
+    """-> (u, count) float64: ``uncertainty`` min-max normalised to [0, 1] (0 when it is flat), then 1 wherever fewer than
+    ``count_thr * n_tiles`` tiles cover the pixel (tester.py:164-166, whose hard-coded 177 is the tile count of an r128 plan at patch_split_num 4 x 4)"""
+    unc = uncertainty.astype(np.float64)
+    lo, hi = float(unc.min()), float(unc.max())
+    u = (unc - lo) / (hi - lo) if hi > lo else np.zeros_like(unc)
+    count = count_map.astype(np.float64)
+    u[count < count_thr * n_tiles] = 1.0
+    return u, count
+
+
 class RunnerInfo:
     def __init__(self, **kw):
         self.rank, self.save, self.gray_scale, self.work_dir = 0, False, False, "."
@@ -248,6 +260,73 @@ class Tester:
             entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result if result_dev is None else result_dev,
                                                            disp_gt_edges=item.get("boundary"))
         results.append(entry)
+
+    @torch.no_grad()
+    def generate_pl(self, cai_mode="r32", process_num=4, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), count_thr=0.05, seed=None,
+                    frame_batch=1):
+        """Pseudo labels for semi-supervised training (estimator/tester/tester.py:132-181): the model runs over the folder with
+        ``return_uncertainty=True`` and, with ``runner_info.save``, writes per image under ``work_dir`` what the pseudo-label loader of
+        the semi-supervised configs reads (estimator/datasets/cityscapes_dataset.py:115-123,202-214):
+          <name>.png                colour depth (magma_r, gray_r with gray_scale; percentiles 0..100)
+          <name>_uint16.png         depth x 256
+          <name>_uncert_uint16.png  floor(u x 256), u = the uncertainty min-max normalised to [0, 1] and set to 1 where fewer than
+                                    count_thr x (tiles of the frame's plan) tiles cover the pixel (0 everywhere when the map is flat)
+          <name>_uncert.png         u coloured with jet, percentiles 0..100
+          <name>_count_uint16.png   tile count x 256 (saturates at 65535: 256 tiles or more)
+        Frames are dealt to the ranks as in ``run`` (frame f on rank f mod world) and grouped ``frame_batch`` per model call.
+        Returns one dict per frame of this rank (name, shape, mean depth, tiles of the plan)."""
+        import random
+        results = []
+        rank, world = self.runner_info.rank, getattr(self.runner_info, "world_size", 1)
+        fb = max(1, int(frame_batch))
+        prefetch = bool(getattr(self.model, "needs_coarse", False))
+        todo = list(range(rank, len(self.dataloader), world))
+        groups = [todo[i:i + fb] for i in range(0, len(todo), fb)]
+        device = getattr(self.model, "device", "cuda")
+
+        def load(idxs):
+            items = [self.dataloader[idx] for idx in idxs]
+            hr = torch.stack([item["image_hr"] for item in items]).to(device)
+            return items, hr, self.model.resizer(hr)
+
+        nxt = load(groups[0]) if groups else None
+        for n, idxs in enumerate(groups):
+            items, hr, lr = nxt
+            nxt = load(groups[n + 1]) if n + 1 < len(groups) else None
+            kw = dict(return_uncertainty=True)
+            if seed is not None:
+                if len(idxs) == 1:
+                    random.seed(seed)
+                else:
+                    kw["frame_seeds"] = [seed] * len(idxs)
+            if prefetch and nxt is not None:
+                kw["next_image_lr"] = nxt[2]
+            tile_cfg = dict(image_raw_shape=list(image_raw_shape), patch_split_num=list(patch_split_num))
+            result, log = self.model(mode="infer", cai_mode=cai_mode, process_num=process_num, tile_cfg=tile_cfg, image_lr=lr, image_hr=hr,
+                                     **kw)
+            # the plan's tile count (every frame of a call has the same passes; only random positions differ)
+            n_tiles = sum(len(p["raw"]) for p in self.model.last_plan)
+            for f, item in enumerate(items):
+                depth = result[f:f + 1].cpu()
+                entry = dict(name=item["img_file_basename"], shape=tuple(depth.shape), mean=float(depth.mean()), n_tiles=n_tiles)
+                if self.runner_info.save:
+                    self._write_pl(item["img_file_basename"], depth, log["uncertainty"][f:f + 1].cpu(), log["count_map"][f:f + 1].cpu(),
+                                   n_tiles, count_thr)
+                results.append(entry)
+        return results
+
+    def _write_pl(self, name, depth, uncertainty, count_map, n_tiles, count_thr):
+        """one frame's pseudo-label files (``generate_pl``)"""
+        from .metrics import colorize
+        os.makedirs(self.runner_info.work_dir, exist_ok=True)
+        base = os.path.join(self.runner_info.work_dir, name)
+        cmap = "gray_r" if getattr(self.runner_info, "gray_scale", False) else "magma_r"
+        write_png8(base + ".png", np.ascontiguousarray(colorize(depth, cmap=cmap, vminp=0, vmaxp=100)[:, :, :3]))
+        write_png16(base + "_uint16.png", (depth.squeeze().numpy() * 256).astype("uint16"))
+        u, count = pseudo_label_uncertainty(uncertainty.squeeze().numpy(), count_map.squeeze().numpy(), n_tiles, count_thr)
+        write_png16(base + "_uncert_uint16.png", np.clip(np.floor(u * 256.0), 0, 65535).astype(np.uint16))
+        write_png8(base + "_uncert.png", np.ascontiguousarray(colorize(u, cmap="jet", vminp=0, vmaxp=100)[:, :, :3]))
+        write_png16(base + "_count_uint16.png", np.clip(count * 256.0, 0, 65535).astype(np.uint16))
 
     @torch.no_grad()
     def run_consistency(self, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), overlap=270):

@@ -30,7 +30,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "pack_chain32_weight", "chain32_c2f", "chain32_enc", "upconv5x5", "upconv5x5_lines", "upconv5x5_ring_", "pack_conv3x3_f6_weight", "conv3x3_f6", "conv3x3_ln_gate_f6",
        # ABI 20: B frames per call (tiles / boxes name their frame)
        "crop_resize_frames", "roi_align_frames", "coarse_tap_knots_frames", "coarse_tap_gather_frames", "blend_init_frames", "blend_update_frames",
-       "blend_resize_frames")
+       "blend_resize_frames",
+       # overlap statistics (m2 / ntiles beside the blend's avg / cnt)
+       "blend_init_stats", "blend_update_stats", "blend_resize_stats")
 _loaded = False
 
 

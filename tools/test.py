@@ -7,6 +7,7 @@
 CONFIG is an MMEngine-style python config (``model=dict(type=..., config=dict(...))``, ``_base_`` supported).
 Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``--prec``, ``--process-num``, ``--max-batch``, ``--streams``.
 ``--frame-batch N``: N frames per model call on one GPU (per rank in a frame-sharded run), outputs split per frame.
+``--generate-pl [--count-thr T]``: Tester.generate_pl instead of run -- pseudo labels with per-pixel uncertainty and tile counts.
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
 """
@@ -65,6 +66,11 @@ def main():
                     help="Tester.run_consistency (estimator/tester/tester.py:211): seam error over crops overlapping by OVERLAP pixels (reference: 270)")
     ap.add_argument("--benchmark", action="store_true", help="Tester.benchmark (estimator/tester/tester.py:325) instead of run")
     ap.add_argument("--repeat-times", type=int, default=10)
+    ap.add_argument("--generate-pl", action="store_true",
+                    help="Tester.generate_pl (estimator/tester/tester.py:132) instead of run: with --save, <name>.png, <name>_uint16.png, "
+                         "<name>_uncert_uint16.png, <name>_uncert.png and <name>_count_uint16.png per image (frame-sharded over the ranks)")
+    ap.add_argument("--count-thr", type=float, default=0.05,
+                    help="--generate-pl: pixels covered by fewer than COUNT_THR x (tiles of the plan) tiles get uncertainty 1")
     ap.add_argument("--benchmark-iters", nargs=2, type=int, default=[20, 50], metavar=("WARMUP", "TOTAL"))
     args = ap.parse_args()
     if args.test_type != "general":
@@ -113,6 +119,17 @@ def main():
         print(f"Average fps of {args.repeat_times} evaluations: {b['average_fps']}")
         print(f"The variance of {args.repeat_times} evaluations: {b['fps_variance']}")
         print(f"Model Flops: {b['flops'] / 1e12:.3f} T  Model Parameters: {b['params'] / 1e6:.1f} M")
+        return
+    if args.generate_pl:
+        if args.shard != "frames":
+            raise SystemExit("--generate-pl shards frames over the ranks (--shard frames)")
+        for r in tester.generate_pl(cai_mode=args.cai_mode, process_num=args.process_num, image_raw_shape=args.image_raw_shape,
+                                    patch_split_num=args.patch_split_num, count_thr=args.count_thr, seed=args.seed, frame_batch=args.frame_batch):
+            print(f"[rank {rank}] {r['name']}: pseudo label {r['shape']} mean {r['mean']:.4f} ({r['n_tiles']} tiles)")
+        if world > 1:
+            import torch.distributed as dist
+            dist.barrier()
+            dist.destroy_process_group()
         return
     results = tester.run(cai_mode=args.cai_mode, process_num=args.process_num, image_raw_shape=args.image_raw_shape,
                          patch_split_num=args.patch_split_num, seed=args.seed, shard=args.shard, frame_batch=args.frame_batch)
