@@ -565,6 +565,51 @@ int prv2_blend_update_stats(float* avg, float* cnt, float* m2, float* ntiles, in
 int prv2_blend_resize_stats(const float* avg, const float* cnt, const float* m2, const float* ntiles, int32_t n_frames, int32_t h, int32_t w,
                             float* avg_out, float* cnt_out, float* m2_out, float* ntiles_out, int32_t oh, int32_t ow, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Edge-aware evaluation (csrc/edges.hip): Canny edges of depth maps and the boundary metrics, B >= 1 frames [n, h, w] per call
+ * (frame-major, dense; h, w >= 3; n * h * w < 2^31).  Edge / mask maps are uint8 0/1 (a torch bool tensor is one).  Every entry
+ * point but prv2_binary_dilate takes a caller workspace of at least prv2_edges_workspace_bytes(n, h, w) bytes (device memory);
+ * the launch count of each call is fixed (no host loop, no readback: graph-capture safe).
+ * ------------------------------------------------------------------------------------------ */
+enum prv2_edge_pre { PRV2_EDGE_PRE_NONE = 0, PRV2_EDGE_PRE_LOG = 1, PRV2_EDGE_PRE_INV = 2 };
+
+/* bytes of workspace the edge entry points need for n frames of h x w (-1 for a bad shape) */
+int64_t prv2_edges_workspace_bytes(int32_t n, int32_t h, int32_t w);
+
+/* extract_edges' depth preprocessing (estimator/utils/metric.py:157-207; to_log :155-159, to_inv :161-165), fp32 -> fp32:
+ *   PRV2_EDGE_PRE_LOG   (d > 0) * log(max(d, eps_f32))
+ *   PRV2_EDGE_PRE_INV   (d > 0) / max(d, eps_f32), then -= min(frame), then /= max(frame) (deterministic device reductions)
+ *   PRV2_EDGE_PRE_NONE  log((d > 0) * max(d, eps_f32)) / log(1.5f)
+ * NaN propagates as in torch (clamp keeps it, min / max return it). */
+int prv2_depth_preprocess(const float* depth, int32_t n, int32_t h, int32_t w, int32_t mode, float* out, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
+/* skimage.feature.canny(image, sigma) as metrics.canny restates it (metric.py:203, tester.py:99-106): bit-identical to it on the
+ * same fp32 input.  gauss_w_host: HOST array of radius + 1 float64 Gaussian taps, centre first (scipy's _gaussian_kernel1d,
+ * radius = int(4 sigma + 0.5) <= 15); mode='constant' Gaussian with the bleed correction, reflect Sobel, 4-sector non-maximum
+ * suppression, hysteresis over 8-connected components.  edges: uint8 [n, h, w]. */
+int prv2_canny(const float* image, int32_t n, int32_t h, int32_t w, const double* gauss_w_host, int32_t radius, float low_threshold,
+               float high_threshold, uint8_t* edges, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* exact squared Euclidean distance of every pixel to the nearest set pixel of its frame (int32; INT32_MAX in a frame with no set
+ * pixel).  sqrt in float64 == scipy.ndimage.distance_transform_edt(~mask) (metric.py:225-229).  w <= 5120, h + w <= 32768. */
+int prv2_edt_sq(const uint8_t* mask, int32_t n, int32_t h, int32_t w, int32_t* d2, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* k x k binary dilation with zero padding, k in {3, 5, 7}: kornia.filters.gaussian_blur2d(m, (k, k), sigma, 'reflect') > 0
+ * (metric.py:252-263 k = 5; scannet_dataset.py:221-224 k = 7; tester.py:99-106 k = 3) */
+int prv2_binary_dilate(const uint8_t* mask, int32_t n, int32_t h, int32_t w, int32_t k, uint8_t* out, void* stream);
+
+/* the statistics of compute_boundary_metrics (metric.py:210-272) per frame, stats: DEVICE float64 [n, 8] =
+ *   TP, FP, FN, TN   of the dilated maps gt_ext / pred_ext at the valid pixels,
+ *   n_bde            #(pred & valid & sqrt(d2_target) < th_edges_acc),   n_gt    #(gt & valid),
+ *   sum_acc          sum of sqrt(d2_target) over the bde set,             sum_comp  sum of sqrt(d2_pred) over gt & valid.
+ * d2_* come from prv2_edt_sq of the unmasked maps (INT32_MAX -> scipy's distance to (-1, 0) for an empty frame).  Per-block
+ * partials and a fixed-order final sum: bit-identical run to run. */
+int prv2_boundary_stats(const uint8_t* gt_edges, const uint8_t* pred_edges, const uint8_t* valid, const int32_t* d2_target,
+                        const int32_t* d2_pred, const uint8_t* gt_ext, const uint8_t* pred_ext, int32_t n, int32_t h, int32_t w,
+                        double th_edges_acc, double* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -936,6 +936,75 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> blend_resize_stats(const Tensor& avg,
   return {a, c, s, n};
 }
 
+// edge-aware evaluation (include/prv2.h "Edge-aware evaluation"): frames [n, h, w]; masks are bool or uint8; the workspace comes
+// from the caching allocator
+void dev_frames(const Tensor& t, const char* name, at::ScalarType a, at::ScalarType b = at::ScalarType::Undefined) {
+  TORCH_CHECK(t.is_cuda(), "prv2: ", name, " must be a GPU tensor (there is no CPU path)");
+  TORCH_CHECK(t.scalar_type() == a || t.scalar_type() == b, "prv2: ", name, " has dtype ", t.scalar_type());
+  TORCH_CHECK(t.dim() == 3 && t.is_contiguous(), "prv2: ", name, " must be a contiguous [n, h, w] tensor");
+}
+Tensor edge_ws(const Tensor& like) {
+  const int64_t bytes = prv2_edges_workspace_bytes((int)like.size(0), (int)like.size(1), (int)like.size(2));
+  TORCH_CHECK(bytes > 0, "prv2: bad frame shape ", like.sizes());
+  return at::empty({bytes}, like.options().dtype(at::kByte));
+}
+void same_frames(const Tensor& a, const Tensor& b, const char* name) {
+  TORCH_CHECK(a.sizes() == b.sizes(), "prv2: ", name, " has shape ", b.sizes(), ", expected ", a.sizes());
+}
+Tensor depth_preprocess(const Tensor& depth, int64_t mode) {
+  dev_frames(depth, "depth", at::kFloat);
+  Tensor out = at::empty_like(depth), ws = edge_ws(depth);
+  Launch L(depth);
+  ok(prv2_depth_preprocess(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2), (int)mode, out.data_ptr<float>(),
+                           ws.data_ptr(), ws.numel(), L.stream), "depth_preprocess");
+  return out;
+}
+Tensor canny(const Tensor& image, at::ArrayRef<double> gauss_w, double low, double high) {
+  dev_frames(image, "image", at::kFloat);
+  TORCH_CHECK(!gauss_w.empty(), "prv2::canny: no Gaussian taps");
+  Tensor out = at::empty(image.sizes(), image.options().dtype(at::kBool)), ws = edge_ws(image);
+  Launch L(image);
+  ok(prv2_canny(image.data_ptr<float>(), (int)image.size(0), (int)image.size(1), (int)image.size(2), gauss_w.data(), (int)gauss_w.size() - 1,
+                (float)low, (float)high, (uint8_t*)out.data_ptr(), ws.data_ptr(), ws.numel(), L.stream), "canny");
+  return out;
+}
+Tensor edt_sq(const Tensor& mask) {
+  dev_frames(mask, "mask", at::kBool, at::kByte);
+  Tensor out = at::empty(mask.sizes(), mask.options().dtype(at::kInt)), ws = edge_ws(mask);
+  Launch L(mask);
+  ok(prv2_edt_sq((const uint8_t*)mask.data_ptr(), (int)mask.size(0), (int)mask.size(1), (int)mask.size(2), out.data_ptr<int32_t>(), ws.data_ptr(),
+                 ws.numel(), L.stream), "edt_sq");
+  return out;
+}
+Tensor binary_dilate(const Tensor& mask, int64_t k) {
+  dev_frames(mask, "mask", at::kBool, at::kByte);
+  Tensor out = at::empty(mask.sizes(), mask.options().dtype(at::kBool));
+  Launch L(mask);
+  ok(prv2_binary_dilate((const uint8_t*)mask.data_ptr(), (int)mask.size(0), (int)mask.size(1), (int)mask.size(2), (int)k, (uint8_t*)out.data_ptr(),
+                        L.stream), "binary_dilate");
+  return out;
+}
+Tensor boundary_stats(const Tensor& gt, const Tensor& pred, const Tensor& valid, const Tensor& d2_target, const Tensor& d2_pred, const Tensor& gt_ext,
+                      const Tensor& pred_ext, double th_edges_acc) {
+  const Tensor* masks[] = {&gt, &pred, &valid, &gt_ext, &pred_ext};
+  const char* names[] = {"gt_edges", "pred_edges", "valid", "gt_ext", "pred_ext"};
+  for (int i = 0; i < 5; ++i) {
+    dev_frames(*masks[i], names[i], at::kBool, at::kByte);
+    same_frames(gt, *masks[i], names[i]);
+  }
+  dev_frames(d2_target, "d2_target", at::kInt);
+  dev_frames(d2_pred, "d2_pred", at::kInt);
+  same_frames(gt, d2_target, "d2_target");
+  same_frames(gt, d2_pred, "d2_pred");
+  Tensor out = at::empty({gt.size(0), 8}, gt.options().dtype(at::kDouble)), ws = edge_ws(gt);
+  Launch L(gt);
+  ok(prv2_boundary_stats((const uint8_t*)gt.data_ptr(), (const uint8_t*)pred.data_ptr(), (const uint8_t*)valid.data_ptr(), d2_target.data_ptr<int32_t>(),
+                         d2_pred.data_ptr<int32_t>(), (const uint8_t*)gt_ext.data_ptr(), (const uint8_t*)pred_ext.data_ptr(), (int)gt.size(0), (int)gt.size(1),
+                         (int)gt.size(2), th_edges_acc, out.data_ptr<double>(), ws.data_ptr(), ws.numel(), L.stream),
+     "boundary_stats");
+  return out;
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1059,6 +1128,13 @@ TORCH_LIBRARY(prv2, m) {
   m.def("blend_init_stats(Tensor(a!) avg, Tensor(b!) cnt, Tensor(c!) m2, Tensor(d!) ntiles, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
   m.def("blend_update_stats(Tensor(a!) avg, Tensor(b!) cnt, Tensor(c!) m2, Tensor(d!) ntiles, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
   m.def("blend_resize_stats(Tensor avg, Tensor cnt, Tensor m2, Tensor ntiles, int oh, int ow) -> (Tensor, Tensor, Tensor, Tensor)");
+  // edge-aware evaluation: Canny, exact distance transform, dilation and the boundary statistics of B frames [n, h, w]
+  m.def("depth_preprocess(Tensor depth, int mode) -> Tensor");
+  m.def("canny(Tensor image, float[] gauss_w, float low, float high) -> Tensor");
+  m.def("edt_sq(Tensor mask) -> Tensor");
+  m.def("binary_dilate(Tensor mask, int k) -> Tensor");
+  m.def("boundary_stats(Tensor gt_edges, Tensor pred_edges, Tensor valid, Tensor d2_target, Tensor d2_pred, Tensor gt_ext, Tensor pred_ext, "
+        "float th_edges_acc) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1125,4 +1201,9 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("blend_init_stats", &blend_init_stats);
   m.impl("blend_update_stats", &blend_update_stats);
   m.impl("blend_resize_stats", &blend_resize_stats);
+  m.impl("depth_preprocess", &depth_preprocess);
+  m.impl("canny", &canny);
+  m.impl("edt_sq", &edt_sq);
+  m.impl("binary_dilate", &binary_dilate);
+  m.impl("boundary_stats", &boundary_stats);
 }

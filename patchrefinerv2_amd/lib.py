@@ -21,6 +21,7 @@ PREC_LABEL = {PREC_F32: "f32", PREC_BF16X3: "bf16x3", PREC_BF16: "bf16", PREC_F1
 # (stage 1: GatedConvUnit.conv, csrc/conv3x3_f6.hip) -- the modules map the name to PREC_BF16X3 and fusion.py looks at the name itself
 PREC_NAMES = {"f32": PREC_F32, "bf16x3": PREC_BF16X3, "bf16": PREC_BF16, "f16f6": PREC_BF16X3}
 FMT_X_X2, FMT_MUL_X2, FMT_Y_X2 = 1, 2, 4  # prv2_conv_desc.fmt: operands in the pre-split "X2" activation format
+EDGE_PRE_NONE, EDGE_PRE_LOG, EDGE_PRE_INV = 0, 1, 2  # prv2_depth_preprocess modes (extract_edges preprocess None / 'none', 'log', 'inv')
 ABI_VERSION = 20
 
 
@@ -49,7 +50,7 @@ class Chain32Desc(C.Structure):  # prv2_chain32_desc
                 ("ldx", C.c_int32), ("ldy", C.c_int32), ("ld_pre", C.c_int32), ("b3", C.c_float), ("ln_eps", C.c_float)]
 
 
-_P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_P, _I, _L, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol include/prv2.h declares
 SIGNATURES = {
@@ -137,6 +138,13 @@ SIGNATURES = {
     "prv2_blend_paste_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
     "prv2_blend_update_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _L, _P, _P, _I, _I, _I, _I, _P]),
     "prv2_blend_resize_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P]),
+    # edge-aware evaluation (csrc/edges.hip): B frames [n, h, w], caller workspace of prv2_edges_workspace_bytes
+    "prv2_edges_workspace_bytes": (_L, [_I, _I, _I]),
+    "prv2_depth_preprocess": (_I, [_P, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "prv2_canny": (_I, [_P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _L, _P]),
+    "prv2_edt_sq": (_I, [_P, _I, _I, _I, _P, _P, _L, _P]),
+    "prv2_binary_dilate": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "prv2_boundary_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _L, _P]),
 }
 
 _lib = None

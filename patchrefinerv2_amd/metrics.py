@@ -240,3 +240,144 @@ def depth_edges(depth) -> np.ndarray:
     d = torch.as_tensor(depth).detach().cpu().float().squeeze()
     d = (d > 0) * d.clamp(min=torch.finfo(torch.float32).eps).log()  # to_log, metric.py:157-161
     return ndi.binary_dilation(canny(d.numpy(), sigma=1.0), structure=np.ones((3, 3), bool))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Edge-aware evaluation (host restatements: the spec of csrc/edges.hip and its CPU oracle).
+#   extract_edges             estimator/utils/metric.py:169-207
+#   compute_boundary_metrics  estimator/utils/metric.py:210-272 (called by cityscapes_dataset.py:340-403)
+#   edge_split_masks          scannet_dataset.py:221-224 (the edge_* / noedge_* regions)
+# Pinned by tests/golden/edge_metrics.npz (tools/make_edge_golden.py runs the reference's own functions).
+# ------------------------------------------------------------------------------------------------------------------
+LOG_1_5_F32 = float(np.float32(np.log(1.5)))  # torch.log(torch.tensor(1.5)) (float32)
+
+
+def gaussian_weights(sigma: float = 1.0) -> np.ndarray:
+    """scipy.ndimage's Gaussian taps for gaussian_filter(sigma) (truncate 4): float64, centre first -> [radius + 1]
+    (the same expression as scipy's _gaussian_kernel1d, so the same float64 values)"""
+    sd = float(sigma)
+    radius = int(4.0 * sd + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sd * sd) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[radius:], dtype=np.float64)
+
+
+def preprocess_depth(depth, preprocess=None) -> np.ndarray:
+    """extract_edges' preprocessing (metric.py:184-198) on a float32 map -> float32 numpy"""
+    if preprocess not in {"log", "inv", "none", None}:
+        raise ValueError(f"Invalid depth preprocessing. ({preprocess})")
+    d = torch.as_tensor(np.asarray(depth.detach().cpu() if isinstance(depth, torch.Tensor) else depth)).float().squeeze()
+    eps = torch.finfo(torch.float32).eps
+    if preprocess == "log":  # to_log (metric.py:155-159)
+        d = (d > 0) * d.clamp(min=eps).log()
+    elif preprocess == "inv":  # to_inv (metric.py:161-165), then -= min, /= max
+        d = (d > 0) / d.clamp(min=eps)
+        d -= d.min()
+        d /= d.max()
+    else:  # 'none' / None: log base 1.5 of the clamped depth (log(0) = -inf where depth <= 0: the reference's quirk)
+        d = torch.log((d > 0) * d.clamp(min=eps)) / torch.log(torch.tensor(1.5))
+    return d.numpy()
+
+
+def extract_edges(depth, preprocess=None, sigma=1, mask=None) -> np.ndarray:
+    """metric.py:169-207 (use_canny=True): preprocess, then ``canny(., sigma)`` -> bool [H, W]"""
+    if mask is not None:
+        raise NotImplementedError("extract_edges(mask=...): no caller of the reference passes a mask")
+    return canny(preprocess_depth(depth, preprocess), sigma=sigma)
+
+
+def binary_dilate(edges, k: int) -> np.ndarray:
+    """k x k binary dilation, zero padding.  kornia.filters.gaussian_blur2d(e, (k, k), sigma, border_type='reflect') > 0 is
+    exactly this: every Gaussian weight is positive, and a reflected tap (pad (k-1)/2, 'reflect' excludes the edge pixel)
+    lands inside the same k x k window, so the blur is > 0 iff a set pixel lies in the in-bounds window."""
+    from scipy import ndimage as ndi
+    return ndi.binary_dilation(np.asarray(edges, bool), structure=np.ones((k, k), bool))
+
+
+def _np_bool(x) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x).squeeze().astype(bool)
+
+
+def binary_scores(tp, fp, fn, tn) -> dict:
+    """torchmetrics' BinaryPrecision / Recall / F1Score / HammingDistance / Accuracy from the confusion counts (the reference's
+    metric_dict, cityscapes_dataset.py:78-82; torchmetrics is absent): a zero denominator gives 0"""
+    tp, fp, fn, tn = (float(v) for v in (tp, fp, fn, tn))
+    n = tp + fp + fn + tn
+
+    def div(a, b):
+        return a / b if b else 0.0
+    return dict(precision=div(tp, tp + fp), recall=div(tp, tp + fn), f1_score=div(2 * tp, 2 * tp + fp + fn), hamming=div(fp + fn, n),
+                acc=div(tp + tn, n))
+
+
+def compute_boundary_metrics(gt_edges, pred_edges, valid_mask, th_edges_acc=10, th_edges_comp=10) -> dict:
+    """metric.py:210-272 with its quirks: both distance transforms on the UNMASKED edge maps (masks applied after); EdgeAcc =
+    mean D_target over pred & valid & (D_target < th_acc), th_acc when empty; EdgeComp = mean D_pred over ALL valid gt edges,
+    guarded by the pred BDE set being non-empty (:245); the F1 family on the 5 x 5-dilated unmasked maps at the valid pixels."""
+    from scipy import ndimage as ndi
+    gt, pred, valid = _np_bool(gt_edges), _np_bool(pred_edges), _np_bool(valid_mask)
+    d_target = ndi.distance_transform_edt(np.logical_not(gt))
+    d_pred = ndi.distance_transform_edt(np.logical_not(pred))
+    gt_m, pred_m = gt & valid, pred & valid
+    pred_bde = pred_m & (d_target < th_edges_acc)
+    out = dict(EdgeAcc=float(d_target[pred_bde].mean()) if pred_bde.sum() else float(th_edges_acc),
+               EdgeComp=float(d_pred[gt_m].mean()) if pred_bde.sum() else float(th_edges_comp))
+    ge, pe = binary_dilate(gt, 5)[valid], binary_dilate(pred, 5)[valid]
+    tp, fp, fn = int((pe & ge).sum()), int((pe & ~ge).sum()), int((~pe & ge).sum())
+    out.update(binary_scores(tp, fp, fn, int(ge.size) - tp - fp - fn))
+    return out
+
+
+def edge_split_masks(gt, k: int = 7) -> np.ndarray:
+    """scannet_dataset.py:221-224: Canny of the log ground truth, widened by gaussian_blur2d((7, 7), sigma 5, reflect) > 0, which
+    is the 7 x 7 binary dilation (binary_dilate) -> bool [H, W]; the noedge region is its complement"""
+    return binary_dilate(extract_edges(gt, "log"), k)
+
+
+# device route (csrc/edges.hip through ops.py): the same functions on GPU tensors, B frames per call
+def _frames_of(x: torch.Tensor):
+    """[H, W] / [1, 1, H, W] -> ([1, H, W], True); [B, H, W] / [B, 1, H, W] -> ([B, H, W], False)"""
+    single = x.dim() == 2 or (x.dim() == 4 and x.shape[0] == 1)
+    return x.reshape(-1, x.shape[-2], x.shape[-1]), single
+
+
+@torch.no_grad()
+def extract_edges_device(depth: torch.Tensor, preprocess="log", sigma=1) -> torch.Tensor:
+    """``extract_edges`` on the device: bool [H, W] for one map ([H, W] or [1, 1, H, W]), [B, H, W] for B maps"""
+    from . import ops
+    x, single = _frames_of(depth)
+    e = ops.canny(ops.depth_preprocess(x.float(), preprocess), sigma=sigma)
+    return e[0] if single else e
+
+
+def _boundary_dict(s, th_edges_acc, th_edges_comp) -> dict:
+    tp, fp, fn, tn, n_bde, n_gt, sum_acc, sum_comp = s
+    out = dict(EdgeAcc=sum_acc / n_bde if n_bde else float(th_edges_acc),
+               EdgeComp=(sum_comp / n_gt if n_gt else float("nan")) if n_bde else float(th_edges_comp))
+    out.update(binary_scores(tp, fp, fn, tn))
+    return out
+
+
+@torch.no_grad()
+def compute_boundary_metrics_device(gt_edges: torch.Tensor, pred_edges: torch.Tensor, valid_mask: torch.Tensor, th_edges_acc=10,
+                                    th_edges_comp=10):
+    """``compute_boundary_metrics`` on the device (two exact distance transforms, two 5 x 5 dilations, one statistics pass; one D2H
+    of the scalars): a dict for one map, a list of dicts for [B, H, W]"""
+    from . import ops
+    g, single = _frames_of(gt_edges.bool())
+    p, v = pred_edges.bool().reshape(g.shape), valid_mask.bool().reshape(g.shape)
+    stats = ops.boundary_stats(g, p, v, ops.edt_sq(g), ops.edt_sq(p), ops.binary_dilate(g, 5), ops.binary_dilate(p, 5), th_edges_acc)
+    rows = [_boundary_dict(r, th_edges_acc, th_edges_comp) for r in stats.cpu().tolist()]
+    return rows[0] if single else rows
+
+
+@torch.no_grad()
+def edge_split_masks_device(gt: torch.Tensor, k: int = 7) -> torch.Tensor:
+    """``edge_split_masks`` on the device"""
+    from . import ops
+    e = extract_edges_device(gt, "log")
+    d = ops.binary_dilate(e, k)
+    return d[0] if e.dim() == 2 else d

@@ -1606,3 +1606,80 @@ def zoe_logbinom_depth(pt: Feat, centers: Feat, min_temp: float, max_temp: float
     L.check(L.load().prv2_zoe_logbinom_depth(pt.ptr, pt.ld, centers.ptr, centers.ld, centers.c, min_temp, max_temp,
                                              pt.n * pt.h * pt.w, depth.data_ptr(), _stream()), "zoe_logbinom_depth")
     return depth
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Edge-aware evaluation (csrc/edges.hip): frames [B, H, W] on the device, both dispatch routes.  Masks are bool tensors.
+# ------------------------------------------------------------------------------------------------------------------
+EDGE_PRE = {None: L.EDGE_PRE_NONE, "none": L.EDGE_PRE_NONE, "log": L.EDGE_PRE_LOG, "inv": L.EDGE_PRE_INV}
+
+
+def _edge_frames(x, dtype=None):
+    """[H, W] or [B, H, W] -> contiguous [B, H, W] (of ``dtype`` when given)"""
+    if x.dim() == 2:
+        x = x[None]
+    assert x.dim() == 3 and x.is_cuda, x.shape
+    return (x if dtype is None else x.to(dtype)).contiguous()
+
+
+def _edge_ws(x):
+    n = L.load().prv2_edges_workspace_bytes(*x.shape)
+    return torch.empty((n,), dtype=torch.uint8, device=x.device)
+
+
+def depth_preprocess(depth, preprocess="log"):
+    """extract_edges' preprocessing (metric.py:184-198) of fp32 frames [B, H, W] -> fp32 [B, H, W]"""
+    if preprocess not in EDGE_PRE:
+        raise ValueError(f"Invalid depth preprocessing. ({preprocess})")
+    d = _edge_frames(depth, torch.float32)
+    if DISPATCH == "torch":
+        return _tops().depth_preprocess(d, EDGE_PRE[preprocess])
+    out, ws = torch.empty_like(d), _edge_ws(d)
+    L.check(L.load().prv2_depth_preprocess(d.data_ptr(), *d.shape, EDGE_PRE[preprocess], out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+            "depth_preprocess")
+    return out
+
+
+def canny(image, sigma=1.0, low_threshold=0.1, high_threshold=0.2):
+    """metrics.canny of fp32 frames [B, H, W] -> bool [B, H, W] (bit-identical to the host on the same input)"""
+    from .metrics import gaussian_weights
+    x, gw = _edge_frames(image, torch.float32), gaussian_weights(sigma)
+    if DISPATCH == "torch":
+        return _tops().canny(x, gw.tolist(), float(low_threshold), float(high_threshold))
+    out, ws = torch.empty(x.shape, dtype=torch.bool, device=x.device), _edge_ws(x)
+    L.check(L.load().prv2_canny(x.data_ptr(), *x.shape, gw.ctypes.data, len(gw) - 1, low_threshold, high_threshold, out.data_ptr(), ws.data_ptr(),
+                                ws.numel(), _stream()), "canny")
+    return out
+
+
+def edt_sq(mask):
+    """exact squared distance to the nearest set pixel of each frame: bool [B, H, W] -> int32 [B, H, W] (INT32_MAX: empty frame)"""
+    m = _edge_frames(mask, torch.bool)
+    if DISPATCH == "torch":
+        return _tops().edt_sq(m)
+    out, ws = torch.empty(m.shape, dtype=torch.int32, device=m.device), _edge_ws(m)
+    L.check(L.load().prv2_edt_sq(m.data_ptr(), *m.shape, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "edt_sq")
+    return out
+
+
+def binary_dilate(mask, k):
+    """k x k binary dilation (zero padding, k in 3 / 5 / 7) of bool [B, H, W]"""
+    m = _edge_frames(mask, torch.bool)
+    if DISPATCH == "torch":
+        return _tops().binary_dilate(m, k)
+    out = torch.empty_like(m)
+    L.check(L.load().prv2_binary_dilate(m.data_ptr(), *m.shape, k, out.data_ptr(), _stream()), "binary_dilate")
+    return out
+
+
+def boundary_stats(gt_edges, pred_edges, valid, d2_target, d2_pred, gt_ext, pred_ext, th_edges_acc=10.0):
+    """the per-frame statistics of compute_boundary_metrics -> float64 [B, 8]: TP, FP, FN, TN, n_bde, n_gt, sum_acc, sum_comp
+    (include/prv2.h prv2_boundary_stats)"""
+    g, p, v, ge, pe = (_edge_frames(t, torch.bool) for t in (gt_edges, pred_edges, valid, gt_ext, pred_ext))
+    dt, dp = _edge_frames(d2_target, torch.int32), _edge_frames(d2_pred, torch.int32)
+    if DISPATCH == "torch":
+        return _tops().boundary_stats(g, p, v, dt, dp, ge, pe, float(th_edges_acc))
+    out, ws = torch.empty((g.shape[0], 8), dtype=torch.float64, device=g.device), _edge_ws(g)
+    L.check(L.load().prv2_boundary_stats(g.data_ptr(), p.data_ptr(), v.data_ptr(), dt.data_ptr(), dp.data_ptr(), ge.data_ptr(), pe.data_ptr(),
+                                         *g.shape, float(th_edges_acc), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "boundary_stats")
+    return out

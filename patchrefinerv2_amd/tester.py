@@ -96,8 +96,10 @@ def read_image(path, dataset_name="", image_resolution=(2160, 3840)) -> np.ndarr
 @DATASETS.register_module()
 class ImageDataset:
     def __init__(self, rgb_image_dir, mode="", min_depth=1e-3, max_depth=80, gt_dir=None, image_resolution=(2160, 3840),
-                 dataset_name="", network_process_size=(384, 512), resize_mode="zoe"):
+                 dataset_name="", network_process_size=(384, 512), resize_mode="zoe", edge_metrics=False):
         self.rgb_image_dir = rgb_image_dir
+        # edge_metrics: get_metrics adds the boundary metrics and the edge_* / noedge_* splits (metrics.compute_boundary_metrics)
+        self.edge_metrics = bool(edge_metrics)
         self.files = sorted(os.listdir(rgb_image_dir))
         # ground truth: metric depth as <gt_dir>/<basename>.npy (the reference's per-dataset decoders -- u4k disparity +
         # factor files, gta exr, middlebury pfm ... general_dataset.py:74-150 -- are not built)
@@ -124,13 +126,41 @@ class ImageDataset:
         return item
 
     def get_metrics(self, depth_gt, result, disp_gt_edges=None, **kw):
-        """general_dataset.py:236-245 (a GPU ``result`` is scored where it is: metrics.compute_metrics_device)"""
+        """general_dataset.py:236-245 (a GPU ``result`` is scored where it is: metrics.compute_metrics_device).  With
+        ``edge_metrics`` also the boundary metrics (cityscapes_dataset.py:340-403; GT edges = extract_edges(gt, 'log'), no
+        segmentation map) and the edge_* / noedge_* splits of every metric (scannet_dataset.py:221-243)."""
         from .metrics import compute_metrics, compute_metrics_device
-        if isinstance(result, torch.Tensor) and result.is_cuda:
-            return compute_metrics_device(depth_gt, result, disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth,
-                                          max_depth_eval=self.max_depth, garg_crop=False, eigen_crop=False, dataset=self.dataset_name)
-        return compute_metrics(depth_gt, result, disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth,
-                               max_depth_eval=self.max_depth, garg_crop=False, eigen_crop=False, dataset=self.dataset_name)
+        dev = isinstance(result, torch.Tensor) and result.is_cuda
+        score = compute_metrics_device if dev else compute_metrics
+        common = dict(disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth, max_depth_eval=self.max_depth, garg_crop=False,
+                      eigen_crop=False, dataset=self.dataset_name)
+        out = score(depth_gt, result, **common)
+        if self.edge_metrics:
+            out.update(self._edge_metrics(depth_gt, result, dev, score, common))
+        return out
+
+    def _edge_metrics(self, depth_gt, result, dev, score, common):
+        """boundary metrics of the prediction (bilinearly resized to the GT's shape) against the GT's log-depth Canny edges at the
+        valid pixels, then every depth metric inside / outside the 7 x 7-widened GT edges; on the device when ``result`` is there"""
+        from . import metrics as M
+        gt = torch.as_tensor(depth_gt)
+        pred = result if result.dim() == 4 else result.reshape(1, 1, *result.shape[-2:])
+        if pred.shape[-2:] != gt.shape[-2:]:
+            pred = F.interpolate(pred, gt.shape[-2:], mode="bilinear", align_corners=False)
+        if dev:
+            g = gt.to(result.device).float().squeeze()
+            ge, pe = M.extract_edges_device(g, "log"), M.extract_edges_device(pred.float(), "log")
+            out = M.compute_boundary_metrics_device(ge, pe, (g > self.min_depth) & (g < self.max_depth))
+            from . import ops
+            region = ops.binary_dilate(ge, 7)[0]
+        else:
+            g = gt.float().squeeze().numpy()
+            ge, pe = M.extract_edges(g, "log"), M.extract_edges(pred, "log")
+            out = M.compute_boundary_metrics(ge, pe, (g > self.min_depth) & (g < self.max_depth))
+            region = torch.from_numpy(M.binary_dilate(ge, 7))
+        for name, mask in (("edge", region), ("noedge", ~region)):
+            out.update({f"{name}_{k}": v for k, v in score(depth_gt, result, additional_mask=mask, **common).items()})
+        return out
 
 
 def pseudo_label_uncertainty(uncertainty: np.ndarray, count_map: np.ndarray, n_tiles: int, count_thr: float):

@@ -32,7 +32,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "crop_resize_frames", "roi_align_frames", "coarse_tap_knots_frames", "coarse_tap_gather_frames", "blend_init_frames", "blend_update_frames",
        "blend_resize_frames",
        # overlap statistics (m2 / ntiles beside the blend's avg / cnt)
-       "blend_init_stats", "blend_update_stats", "blend_resize_stats")
+       "blend_init_stats", "blend_update_stats", "blend_resize_stats",
+       # edge-aware evaluation (Canny, distance transform, dilation, boundary statistics of B frames)
+       "depth_preprocess", "canny", "edt_sq", "binary_dilate", "boundary_stats")
 _loaded = False
 
 

@@ -8,6 +8,7 @@ CONFIG is an MMEngine-style python config (``model=dict(type=..., config=dict(..
 Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``--prec``, ``--process-num``, ``--max-batch``, ``--streams``.
 ``--frame-batch N``: N frames per model call on one GPU (per rank in a frame-sharded run), outputs split per frame.
 ``--generate-pl [--count-thr T]``: Tester.generate_pl instead of run -- pseudo labels with per-pixel uncertainty and tile counts.
+``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
 """
@@ -71,6 +72,9 @@ def main():
                          "<name>_uncert_uint16.png, <name>_uncert.png and <name>_count_uint16.png per image (frame-sharded over the ranks)")
     ap.add_argument("--count-thr", type=float, default=0.05,
                     help="--generate-pl: pixels covered by fewer than COUNT_THR x (tiles of the plan) tiles get uncertainty 1")
+    ap.add_argument("--edge-metrics", action="store_true",
+                    help="with ground truth (dataset gt_dir): add the boundary metrics (EdgeAcc, EdgeComp, precision, recall, f1_score, hamming, "
+                         "acc) and the edge_* / noedge_* split of every depth metric (metric.py:210-272, scannet_dataset.py:221-243)")
     ap.add_argument("--benchmark-iters", nargs=2, type=int, default=[20, 50], metavar=("WARMUP", "TOTAL"))
     args = ap.parse_args()
     if args.test_type != "general":
@@ -104,6 +108,8 @@ def main():
 
     ds_cfg = cfg.general_dataloader.dataset.to_dict()
     ds_cfg["image_resolution"] = args.image_raw_shape
+    if args.edge_metrics:
+        ds_cfg["edge_metrics"] = True
     dataset = DATASETS.build(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir)
     tester = Tester(cfg, runner, dataset, model)
