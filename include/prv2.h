@@ -610,6 +610,61 @@ int prv2_boundary_stats(const uint8_t* gt_edges, const uint8_t* pred_edges, cons
                         const int32_t* d2_pred, const uint8_t* gt_ext, const uint8_t* pred_ext, int32_t n, int32_t h, int32_t w,
                         double th_edges_acc, double* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Output stage (csrc/output.hip): the pixel bytes of the files the tester saves (estimator/tester/tester.py:72-106,132-181;
+ * the colour maps of estimator/utils/color.py:95-158), produced on the device from B >= 1 dense frames [n, h, w]
+ * (h, w >= 1; n * h * w < 2^29).  Fixed launch counts, no host synchronisation, bit-deterministic (integer atomics only).
+ * A "scanline buffer" holds, per frame, the deflate-ready image of a PNG: h rows of 1 + bpp * w bytes, the first byte of each
+ * row the filter type 0; frames lie rows_fstride bytes apart (a multiple of 16, at least prv2_rows_bytes(h, w, bpp)), the
+ * buffer is 16-byte aligned and the bytes between a frame's image and the next multiple of 16 are written as zeros.
+ * ------------------------------------------------------------------------------------------ */
+
+/* bytes of workspace prv2_order_stats needs for n frames (-1 for a bad n) */
+int64_t prv2_output_workspace_bytes(int32_t n);
+
+/* h * (1 + bpp * w) rounded up to 16: the smallest frame stride of a scanline buffer (bpp 1 .. 4; -1 for bad arguments) */
+int64_t prv2_rows_bytes(int32_t h, int32_t w, int32_t bpp);
+
+/* exact order statistics of the valid pixels of each frame (color.py:118-125: np.percentile(value[mask], p) needs them).
+ * valid: mask[i] != 0 when ``mask`` is given, value[i] != invalid_val otherwise (a NaN invalid_val keeps every pixel); with
+ * ``gate`` also !((double)gate[i] < gate_thr) (tester.py:164-166: pixels enough tiles cover).  counts: DEVICE int64 [n], the
+ * valid pixels of each frame.  ranks_host: HOST int64 [n_ranks <= 8], the same for every frame: k >= 0 the k-th smallest,
+ * k < 0 the (count + k)-th (-1: the largest), clamped to [0, count - 1].  out: DEVICE fp32 [n, n_ranks] = np.sort(valid)[k]
+ * (np.sort's order: -0.0 before +0.0, every NaN last and returned as the default NaN; NaN for a frame without a valid pixel).
+ * Radix select over a monotone 32-bit key, 4 passes of 8 bits; n_ranks == 0 counts only. */
+int prv2_order_stats(const float* value, const uint8_t* mask, float invalid_val, const float* gate, double gate_thr, int32_t n, int32_t h,
+                     int32_t w, const int64_t* ranks_host, int32_t n_ranks, int64_t* counts, float* out, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* colorize (color.py:95-158) into RGB scanlines (bpp 3): x = (v - vmin) / (vmax - vmin) in correctly rounded fp32, v * 0 when
+ * vmin == vmax (norm: DEVICE fp32 [n, 2] = vmin, vmax of each frame); matplotlib's index rule (xa = x * ncolors; xa == ncolors
+ * -> ncolors - 1; xa < 0 -> under; xa >= ncolors -> over; NaN -> bad; else truncation) into lut: DEVICE uint8
+ * [ncolors + 3, 4] = (cmap._lut * 255).astype(uint8) (rows ncolors .. ncolors + 2: under, over, bad).  Invalid pixels
+ * (invalid_mask[i] != 0 when given, v == invalid_val otherwise) get background_rgb = r | g << 8 | b << 16. */
+int prv2_colorize_rows(const float* value, const uint8_t* invalid_mask, float invalid_val, int32_t n, int32_t h, int32_t w, const float* norm,
+                       const uint8_t* lut, int32_t ncolors, uint32_t background_rgb, uint8_t* rows, int64_t rows_fstride, void* stream);
+
+/* 16-bit big-endian gray scanlines (bpp 2) of value * scale (tester.py:89-91 scale 256): truncation, == numpy's
+ * astype(uint16), where 0 <= value * scale < 65536; outside it the result saturates to 0 / 65535 and NaN gives 0 (numpy's
+ * cast is platform-defined there) */
+int prv2_quantize16_rows(const float* value, int32_t n, int32_t h, int32_t w, float scale, uint8_t* rows, int64_t rows_fstride, void* stream);
+
+/* the pseudo-label uncertainty (tester.py:160-176) in float64: u = (uncertainty - lo) / (hi - lo), 0 when !(hi > lo), then 1
+ * where count_map < thr.  params: DEVICE float64 [n, 5] = lo, hi, thr, umin, umax (lo / hi: extrema of the frame's uncertainty,
+ * thr = count_thr * tiles, umin / umax: extrema of u).  rows16: clip(floor(u * 256), 0, 65535) as 16-bit scanlines; rows_rgb:
+ * u coloured like prv2_colorize_rows between umin and umax (float64 arithmetic, as colorize of a float64 map). */
+int prv2_pl_uncertainty_rows(const float* uncertainty, const float* count_map, int32_t n, int32_t h, int32_t w, const double* params,
+                             const uint8_t* lut, int32_t ncolors, uint8_t* rows16, int64_t rows16_fstride, uint8_t* rows_rgb,
+                             int64_t rows_rgb_fstride, void* stream);
+
+/* a 0/1 mask as 0 / 255 gray scanlines (bpp 1): <name>_edge.png (tester.py:99-106) */
+int prv2_mask_rows(const uint8_t* mask, int32_t n, int32_t h, int32_t w, uint8_t* rows, int64_t rows_fstride, void* stream);
+
+/* F.interpolate(mode='bilinear', align_corners=False) of fp32 maps [n, ph, pw] -> [n, oh, ow]: the coarse prediction at the
+ * raw resolution (tester.py:93-96) */
+int prv2_upsample_bilinear_map(const float* x, int32_t n, int32_t ph, int32_t pw, float* y, int32_t oh, int32_t ow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1005,6 +1005,99 @@ Tensor boundary_stats(const Tensor& gt, const Tensor& pred, const Tensor& valid,
   return out;
 }
 
+// output stage (include/prv2.h "Output stage"): order statistics, PNG scanlines [n, prv2_rows_bytes] and the bilinear resize of
+// the coarse map, of dense frames [n, h, w]
+const uint8_t* opt_mask(const optional<Tensor>& t, const Tensor& like, const char* name) {
+  if (!t.has_value()) return nullptr;
+  dev_frames(*t, name, at::kBool, at::kByte);
+  same_frames(like, *t, name);
+  return (const uint8_t*)t->data_ptr();
+}
+Tensor alloc_rows(const Tensor& like, int bpp) {
+  const int64_t bytes = prv2_rows_bytes((int)like.size(1), (int)like.size(2), bpp);
+  TORCH_CHECK(bytes > 0, "prv2: bad frame shape ", like.sizes());
+  return at::empty({like.size(0), bytes}, like.options().dtype(at::kByte));
+}
+const uint8_t* lut_ptr(const Tensor& lut) {
+  TORCH_CHECK(lut.is_cuda() && lut.scalar_type() == at::kByte && lut.dim() == 2 && lut.size(1) == 4 && lut.size(0) >= 4 && lut.is_contiguous(),
+              "prv2: lut must be a contiguous GPU uint8 [ncolors + 3, 4] tensor");
+  return (const uint8_t*)lut.data_ptr();
+}
+std::tuple<Tensor, Tensor> order_stats(const Tensor& value, const optional<Tensor>& mask, double invalid_val, const optional<Tensor>& gate,
+                                       double gate_thr, at::ArrayRef<int64_t> ranks) {
+  dev_frames(value, "value", at::kFloat);
+  const uint8_t* m = opt_mask(mask, value, "mask");
+  const float* g = nullptr;
+  if (gate.has_value()) {
+    dev_frames(*gate, "gate", at::kFloat);
+    same_frames(value, *gate, "gate");
+    g = gate->data_ptr<float>();
+  }
+  const int64_t bytes = prv2_output_workspace_bytes((int)value.size(0));
+  TORCH_CHECK(bytes > 0, "prv2::order_stats: bad frame count ", value.size(0));
+  Tensor ws = at::empty({bytes}, value.options().dtype(at::kByte));
+  Tensor counts = at::empty({value.size(0)}, value.options().dtype(at::kLong));
+  Tensor out = at::empty({value.size(0), (int64_t)ranks.size()}, value.options());
+  Launch L(value);
+  ok(prv2_order_stats(value.data_ptr<float>(), m, (float)invalid_val, g, gate_thr, (int)value.size(0), (int)value.size(1), (int)value.size(2),
+                      ranks.data(), (int)ranks.size(), counts.data_ptr<int64_t>(), out.data_ptr<float>(), ws.data_ptr(), ws.numel(), L.stream),
+     "order_stats");
+  return {counts, out};
+}
+Tensor colorize_rows(const Tensor& value, const optional<Tensor>& invalid_mask, double invalid_val, const Tensor& norm, const Tensor& lut,
+                     int64_t background_rgb) {
+  dev_frames(value, "value", at::kFloat);
+  const uint8_t* m = opt_mask(invalid_mask, value, "invalid_mask");
+  TORCH_CHECK(norm.is_cuda() && norm.scalar_type() == at::kFloat && norm.is_contiguous() && norm.dim() == 2 && norm.size(0) == value.size(0) &&
+                  norm.size(1) == 2, "prv2::colorize_rows: norm must be a contiguous GPU fp32 [n, 2] tensor");
+  const uint8_t* l = lut_ptr(lut);
+  Tensor rows = alloc_rows(value, 3);
+  Launch L(value);
+  ok(prv2_colorize_rows(value.data_ptr<float>(), m, (float)invalid_val, (int)value.size(0), (int)value.size(1), (int)value.size(2),
+                        norm.data_ptr<float>(), l, (int)lut.size(0) - 3, (uint32_t)background_rgb, (uint8_t*)rows.data_ptr(), rows.size(1), L.stream),
+     "colorize_rows");
+  return rows;
+}
+Tensor quantize16_rows(const Tensor& value, double scale) {
+  dev_frames(value, "value", at::kFloat);
+  Tensor rows = alloc_rows(value, 2);
+  Launch L(value);
+  ok(prv2_quantize16_rows(value.data_ptr<float>(), (int)value.size(0), (int)value.size(1), (int)value.size(2), (float)scale,
+                          (uint8_t*)rows.data_ptr(), rows.size(1), L.stream), "quantize16_rows");
+  return rows;
+}
+std::tuple<Tensor, Tensor> pl_uncertainty_rows(const Tensor& uncertainty, const Tensor& count_map, const Tensor& params, const Tensor& lut) {
+  dev_frames(uncertainty, "uncertainty", at::kFloat);
+  dev_frames(count_map, "count_map", at::kFloat);
+  same_frames(uncertainty, count_map, "count_map");
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == at::kDouble && params.is_contiguous() && params.dim() == 2 &&
+                  params.size(0) == uncertainty.size(0) && params.size(1) == 5, "prv2::pl_uncertainty_rows: params must be a contiguous GPU float64 [n, 5] tensor");
+  const uint8_t* l = lut_ptr(lut);
+  Tensor r16 = alloc_rows(uncertainty, 2), rgb = alloc_rows(uncertainty, 3);
+  Launch L(uncertainty);
+  ok(prv2_pl_uncertainty_rows(uncertainty.data_ptr<float>(), count_map.data_ptr<float>(), (int)uncertainty.size(0), (int)uncertainty.size(1),
+                              (int)uncertainty.size(2), params.data_ptr<double>(), l, (int)lut.size(0) - 3, (uint8_t*)r16.data_ptr(), r16.size(1),
+                              (uint8_t*)rgb.data_ptr(), rgb.size(1), L.stream), "pl_uncertainty_rows");
+  return {r16, rgb};
+}
+Tensor mask_rows(const Tensor& mask) {
+  dev_frames(mask, "mask", at::kBool, at::kByte);
+  Tensor rows = alloc_rows(mask, 1);
+  Launch L(mask);
+  ok(prv2_mask_rows((const uint8_t*)mask.data_ptr(), (int)mask.size(0), (int)mask.size(1), (int)mask.size(2), (uint8_t*)rows.data_ptr(), rows.size(1),
+                    L.stream), "mask_rows");
+  return rows;
+}
+Tensor upsample_bilinear_map(const Tensor& x, int64_t oh, int64_t ow) {
+  dev_frames(x, "x", at::kFloat);
+  TORCH_CHECK(oh >= 1 && ow >= 1, "prv2::upsample_bilinear_map: bad output shape ", oh, " x ", ow);
+  Tensor y = at::empty({x.size(0), oh, ow}, x.options());
+  Launch L(x);
+  ok(prv2_upsample_bilinear_map(x.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), y.data_ptr<float>(), (int)oh, (int)ow, L.stream),
+     "upsample_bilinear_map");
+  return y;
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1135,6 +1228,13 @@ TORCH_LIBRARY(prv2, m) {
   m.def("binary_dilate(Tensor mask, int k) -> Tensor");
   m.def("boundary_stats(Tensor gt_edges, Tensor pred_edges, Tensor valid, Tensor d2_target, Tensor d2_pred, Tensor gt_ext, Tensor pred_ext, "
         "float th_edges_acc) -> Tensor");
+  // output stage: exact order statistics, PNG scanlines and the coarse map's bilinear resize of B frames [n, h, w]
+  m.def("order_stats(Tensor value, Tensor? mask, float invalid_val, Tensor? gate, float gate_thr, int[] ranks) -> (Tensor, Tensor)");
+  m.def("colorize_rows(Tensor value, Tensor? invalid_mask, float invalid_val, Tensor norm, Tensor lut, int background_rgb) -> Tensor");
+  m.def("quantize16_rows(Tensor value, float scale) -> Tensor");
+  m.def("pl_uncertainty_rows(Tensor uncertainty, Tensor count_map, Tensor params, Tensor lut) -> (Tensor, Tensor)");
+  m.def("mask_rows(Tensor mask) -> Tensor");
+  m.def("upsample_bilinear_map(Tensor x, int oh, int ow) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1206,4 +1306,10 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("edt_sq", &edt_sq);
   m.impl("binary_dilate", &binary_dilate);
   m.impl("boundary_stats", &boundary_stats);
+  m.impl("order_stats", &order_stats);
+  m.impl("colorize_rows", &colorize_rows);
+  m.impl("quantize16_rows", &quantize16_rows);
+  m.impl("pl_uncertainty_rows", &pl_uncertainty_rows);
+  m.impl("mask_rows", &mask_rows);
+  m.impl("upsample_bilinear_map", &upsample_bilinear_map);
 }

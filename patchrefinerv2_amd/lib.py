@@ -145,6 +145,15 @@ SIGNATURES = {
     "prv2_edt_sq": (_I, [_P, _I, _I, _I, _P, _P, _L, _P]),
     "prv2_binary_dilate": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "prv2_boundary_stats": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _P, _P, _L, _P]),
+    # output stage (csrc/output.hip): order statistics, PNG scanlines of B frames [n, h, w], bilinear resize of the coarse map
+    "prv2_output_workspace_bytes": (_L, [_I]),
+    "prv2_rows_bytes": (_L, [_I, _I, _I]),
+    "prv2_order_stats": (_I, [_P, _P, _F, _P, _D, _I, _I, _I, _P, _I, _P, _P, _P, _L, _P]),
+    "prv2_colorize_rows": (_I, [_P, _P, _F, _I, _I, _I, _P, _P, _I, C.c_uint32, _P, _L, _P]),
+    "prv2_quantize16_rows": (_I, [_P, _I, _I, _I, _F, _P, _L, _P]),
+    "prv2_pl_uncertainty_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _L, _P, _L, _P]),
+    "prv2_mask_rows": (_I, [_P, _I, _I, _I, _P, _L, _P]),
+    "prv2_upsample_bilinear_map": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -1683,3 +1683,102 @@ def boundary_stats(gt_edges, pred_edges, valid, d2_target, d2_pred, gt_ext, pred
     L.check(L.load().prv2_boundary_stats(g.data_ptr(), p.data_ptr(), v.data_ptr(), dt.data_ptr(), dp.data_ptr(), ge.data_ptr(), pe.data_ptr(),
                                          *g.shape, float(th_edges_acc), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "boundary_stats")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Output stage (csrc/output.hip): frames [B, H, W] on the device, both dispatch routes.  Scanline buffers are uint8
+# [B, prv2_rows_bytes(H, W, bpp)]: frame f's deflate-ready PNG image is rows[f, :H * (1 + bpp * W)].
+# ------------------------------------------------------------------------------------------------------------------
+def _rows(x, bpp):
+    return torch.empty((x.shape[0], L.load().prv2_rows_bytes(x.shape[1], x.shape[2], bpp)), dtype=torch.uint8, device=x.device)
+
+
+def _opt_frames(t, like, dtype):
+    if t is None:
+        return None
+    t = _edge_frames(t, dtype)
+    if t.shape != like.shape:
+        raise ValueError(f"shape {tuple(t.shape)} does not match the frames {tuple(like.shape)}")
+    return t
+
+
+def order_stats(value, ranks, mask=None, invalid_val=-99.0, gate=None, gate_thr=0.0):
+    """exact order statistics of the valid pixels of fp32 frames [B, H, W] -> (counts int64 [B], values fp32 [B, len(ranks)]), both
+    on the device.  valid: ``mask`` (bool) when given, value != invalid_val otherwise; with ``gate`` also not (gate < gate_thr).
+    ranks: k >= 0 the k-th smallest, k < 0 counted from the largest, clamped into the frame's valid count (include/prv2.h
+    prv2_order_stats)"""
+    v = _edge_frames(value, torch.float32)
+    m, g = _opt_frames(mask, v, torch.bool), _opt_frames(gate, v, torch.float32)
+    ranks = [int(r) for r in ranks]
+    if DISPATCH == "torch":
+        return _tops().order_stats(v, m, float(invalid_val), g, float(gate_thr), ranks)
+    lib = L.load()
+    ws = torch.empty((lib.prv2_output_workspace_bytes(v.shape[0]),), dtype=torch.uint8, device=v.device)
+    counts = torch.empty((v.shape[0],), dtype=torch.int64, device=v.device)
+    out = torch.empty((v.shape[0], len(ranks)), dtype=torch.float32, device=v.device)
+    rk = np.asarray(ranks, dtype=np.int64)
+    L.check(lib.prv2_order_stats(v.data_ptr(), _ptr(m), float(invalid_val), _ptr(g), float(gate_thr), *v.shape, rk.ctypes.data, len(ranks),
+                                 counts.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "order_stats")
+    return counts, out
+
+
+def colorize_rows(value, norm, lut, invalid_mask=None, invalid_val=-99.0, background_rgb=(128, 128, 128)):
+    """metrics.colorize of fp32 frames [B, H, W] between norm[f] = (vmin, vmax) (device fp32 [B, 2]) through the colour table
+    ``lut`` (device uint8 [N + 3, 4]) -> RGB scanline buffer"""
+    v = _edge_frames(value, torch.float32)
+    m = _opt_frames(invalid_mask, v, torch.bool)
+    bg = int(background_rgb[0]) | int(background_rgb[1]) << 8 | int(background_rgb[2]) << 16
+    norm = norm.to(torch.float32).contiguous()
+    if DISPATCH == "torch":
+        return _tops().colorize_rows(v, m, float(invalid_val), norm, lut, bg)
+    if tuple(norm.shape) != (v.shape[0], 2) or lut.dtype != torch.uint8 or lut.dim() != 2 or lut.shape[1] != 4 or not lut.is_contiguous():
+        raise ValueError("colorize_rows: norm is fp32 [B, 2], lut uint8 [N + 3, 4]")
+    rows = _rows(v, 3)
+    L.check(L.load().prv2_colorize_rows(v.data_ptr(), _ptr(m), float(invalid_val), *v.shape, norm.data_ptr(), lut.data_ptr(), lut.shape[0] - 3,
+                                        bg, rows.data_ptr(), rows.shape[1], _stream()), "colorize_rows")
+    return rows
+
+
+def quantize16_rows(value, scale=256.0):
+    """(value * scale).astype(uint16) of fp32 frames [B, H, W] as big-endian 16-bit scanlines (saturating; NaN -> 0)"""
+    v = _edge_frames(value, torch.float32)
+    if DISPATCH == "torch":
+        return _tops().quantize16_rows(v, float(scale))
+    rows = _rows(v, 2)
+    L.check(L.load().prv2_quantize16_rows(v.data_ptr(), *v.shape, float(scale), rows.data_ptr(), rows.shape[1], _stream()), "quantize16_rows")
+    return rows
+
+
+def pl_uncertainty_rows(uncertainty, count_map, params, lut):
+    """tester.pseudo_label_uncertainty on the device -> (16-bit scanlines of floor(u * 256), RGB scanlines of u through ``lut``);
+    params: device float64 [B, 5] = lo, hi, thr, umin, umax (include/prv2.h prv2_pl_uncertainty_rows)"""
+    u = _edge_frames(uncertainty, torch.float32)
+    c = _opt_frames(count_map, u, torch.float32)
+    if DISPATCH == "torch":
+        return _tops().pl_uncertainty_rows(u, c, params, lut)
+    if tuple(params.shape) != (u.shape[0], 5) or params.dtype != torch.float64 or not params.is_contiguous():
+        raise ValueError("pl_uncertainty_rows: params is float64 [B, 5]")
+    r16, rgb = _rows(u, 2), _rows(u, 3)
+    L.check(L.load().prv2_pl_uncertainty_rows(u.data_ptr(), c.data_ptr(), *u.shape, params.data_ptr(), lut.data_ptr(), lut.shape[0] - 3,
+                                              r16.data_ptr(), r16.shape[1], rgb.data_ptr(), rgb.shape[1], _stream()), "pl_uncertainty_rows")
+    return r16, rgb
+
+
+def mask_rows(mask):
+    """bool frames [B, H, W] as 0 / 255 gray scanlines"""
+    m = _edge_frames(mask, torch.bool)
+    if DISPATCH == "torch":
+        return _tops().mask_rows(m)
+    rows = _rows(m, 1)
+    L.check(L.load().prv2_mask_rows(m.data_ptr(), *m.shape, rows.data_ptr(), rows.shape[1], _stream()), "mask_rows")
+    return rows
+
+
+def upsample_bilinear_map(x, oh, ow):
+    """F.interpolate(mode='bilinear', align_corners=False) of fp32 maps [B, h, w] -> [B, oh, ow]"""
+    x = _edge_frames(x, torch.float32)
+    if DISPATCH == "torch":
+        return _tops().upsample_bilinear_map(x, int(oh), int(ow))
+    y = torch.empty((x.shape[0], int(oh), int(ow)), dtype=torch.float32, device=x.device)
+    L.check(L.load().prv2_upsample_bilinear_map(x.data_ptr(), *x.shape, y.data_ptr(), int(oh), int(ow), _stream()), "upsample_bilinear_map")
+    return y

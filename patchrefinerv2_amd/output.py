@@ -1,0 +1,327 @@
+"""GPU output stage of the tester (opt-in: ``runner_info.device_output`` / ``tools/test.py --device-output``).
+
+The files ``Tester.run(save=True)`` and ``Tester.generate_pl(save=True)`` write are PNGs of per-pixel functions of maps that
+are already on the device.  This module produces the deflate-ready scanlines of every file there (csrc/output.hip through
+ops.py), copies only those packed bytes into pinned host memory and hands them to a bounded pool of writer threads
+(``zlib.compress`` releases the GIL), while the next frame computes.  Chunk layout, zlib level and the single IDAT chunk are
+those of ``tester.write_png16`` / ``write_png8``: equal pixels give byte-identical files.
+
+percentile_from_sorted   np.percentile(method='linear') of a float32 array from two neighbouring order statistics (host)
+colormap_lut / lut_index matplotlib's byte table and index rule (host restatement: the spec of prv2_colorize_rows)
+percentile_device        np.percentile(value[mask], q) of a device map (exact order statistics + the host interpolation)
+colorize_device          metrics.colorize of a device map -> device uint8 [H, W, 3] view + its scanline buffer
+OutputStage              side stream, ring of pinned staging slots, writer pool
+"""
+from __future__ import annotations
+
+import os
+import struct
+import threading
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+MAX_WORKERS = 16  # the cap of the writer pool (never sized from os.cpu_count(): a shared box reports every core of the machine)
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+F32 = np.float32
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# host restatements (no GPU)
+# ------------------------------------------------------------------------------------------------------------------
+def percentile_ranks(n: int, p: float):
+    """(lo, hi, g): np.percentile(a, p) of a float32 array of n values is _lerp(sort(a)[lo], sort(a)[hi], g).  numpy computes the
+    virtual index in the array's dtype: q = float32(p) / float32(100), pos = float32(n - 1) * q (a float64 index does not
+    reproduce it)."""
+    if n < 1:
+        raise ValueError("percentile of an empty set")
+    q32 = F32(p) / F32(100)
+    pos = F32(n - 1) * q32
+    lo = int(np.floor(pos))
+    g = F32(pos - F32(lo))
+    lo = min(max(lo, 0), n - 1)
+    return lo, min(lo + 1, n - 1), g
+
+
+def lerp_f32(a, b, g):
+    """numpy's _lerp on float32 scalars: a + (b - a) * g, and b - (b - a) * (1 - g) from g >= 0.5"""
+    a, b, g = F32(a), F32(b), F32(g)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = F32(b - a)
+        return F32(b - d * F32(F32(1) - g)) if g >= F32(0.5) else F32(a + d * g)
+
+
+def percentile_from_sorted(s_lo, s_hi, s_last, n: int, p: float):
+    """np.percentile of n float32 values given sort(a)[lo], sort(a)[hi] (``percentile_ranks``) and the largest: NaN sorts last and
+    makes every percentile NaN"""
+    if np.isnan(s_last):
+        return F32(np.nan)
+    return lerp_f32(s_lo, s_hi, percentile_ranks(n, p)[2])
+
+
+def colormap_lut(cmap: str) -> np.ndarray:
+    """(N + 3) x 4 uint8: what matplotlib's Colormap.__call__(bytes=True) looks its indices up in (rows N, N + 1, N + 2 =
+    under, over, bad)"""
+    import matplotlib
+    cm = matplotlib.colormaps[cmap]
+    if not cm._isinit:
+        cm._init()
+    return np.ascontiguousarray((cm._lut * 255).astype(np.uint8))
+
+
+def lut_index(x: np.ndarray, n: int) -> np.ndarray:
+    """matplotlib's index rule for float data: xa = x * N in x's dtype; xa == N -> N - 1; xa < 0 -> under (N); xa >= N -> over
+    (N + 1); NaN -> bad (N + 2); else truncation"""
+    xa = np.array(x, copy=True)
+    with np.errstate(invalid="ignore", over="ignore"):
+        xa *= n
+        xa[xa == n] = n - 1
+        under, over, bad = xa < 0, xa >= n, np.isnan(xa)
+        idx = xa.astype(np.int64)
+    idx[under], idx[over], idx[bad] = n, n + 1, n + 2
+    return idx
+
+
+def png_bytes(header: bytes, rows) -> bytes:
+    """the file ``write_png16`` / ``write_png8`` write for these scanlines: signature, IHDR, one IDAT (zlib level 6), IEND"""
+    def chunk(tag, data):
+        c = struct.pack(">I", len(data)) + tag + data
+        return c + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    return PNG_SIGNATURE + chunk(b"IHDR", header) + chunk(b"IDAT", zlib.compress(rows, 6)) + chunk(b"IEND", b"")
+
+
+def ihdr(w: int, h: int, bpp: int) -> bytes:
+    """bpp 1: 8-bit gray, 2: 16-bit gray, 3: 8-bit RGB"""
+    depth, ctype = {1: (8, 0), 2: (16, 0), 3: (8, 2)}[bpp]
+    return struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# device functions
+# ------------------------------------------------------------------------------------------------------------------
+_LUTS = {}
+
+
+def _lut_device(cmap: str, device) -> torch.Tensor:
+    key = (cmap, str(device))
+    if key not in _LUTS:
+        _LUTS[key] = torch.from_numpy(colormap_lut(cmap)).to(device)
+    return _LUTS[key]
+
+
+def _frames(value: torch.Tensor) -> torch.Tensor:
+    """one map [H, W] / [1, 1, H, W] -> contiguous [1, H, W]"""
+    if not isinstance(value, torch.Tensor) or not value.is_cuda:
+        raise ValueError("the device output stage takes GPU tensors (metrics.colorize is the host route)")
+    if value.dtype != torch.float32:
+        raise TypeError(f"the device output stage takes float32 maps (got {value.dtype})")
+    if value.dim() < 2 or any(int(s) != 1 for s in value.shape[:-2]):
+        raise ValueError(f"one map [H, W] expected (got {tuple(value.shape)})")
+    return value.reshape(1, value.shape[-2], value.shape[-1]).contiguous()
+
+
+@torch.no_grad()
+def percentile_device(value: torch.Tensor, q, mask=None, invalid_val=-99):
+    """np.percentile(value[mask], q) of one fp32 device map (``mask``: bool, True = take; without it value != invalid_val): a
+    float32 scalar, or a list of them for a sequence ``q``.  Exact: the order statistics come from the radix select of
+    prv2_order_stats, the interpolation is numpy's.  Percentiles 0 and 100 need one call, others a count first."""
+    from . import ops
+    v = _frames(value)
+    seq = isinstance(q, (list, tuple, np.ndarray))
+    qs = list(q) if seq else [q]
+    m = None if mask is None else mask.reshape(v.shape)
+    if all(float(p) in (0.0, 100.0) for p in qs):
+        # rank pairs known without the count: (0, 1) and (n - 1, n - 1)
+        counts, out = ops.order_stats(v, [0, 1, -1], mask=m, invalid_val=invalid_val)
+        n, (s0, s1, sl) = int(counts[0]), out[0].cpu().numpy()
+        if n == 0:
+            res = [F32(np.nan) for _ in qs]
+        else:
+            res = [percentile_from_sorted(s0, s1, sl, n, p) if float(p) == 0.0 else percentile_from_sorted(sl, sl, sl, n, p) for p in qs]
+    else:
+        counts, _ = ops.order_stats(v, [], mask=m, invalid_val=invalid_val)
+        n = int(counts[0])
+        if n == 0:
+            res = [F32(np.nan) for _ in qs]
+        else:
+            res = []
+            for i in range(0, len(qs), 3):  # (at most 8 ranks per call: 2 per percentile + the largest)
+                part = qs[i:i + 3]
+                ranks = [r for p in part for r in percentile_ranks(n, p)[:2]] + [-1]
+                s = ops.order_stats(v, ranks, mask=m, invalid_val=invalid_val)[1][0].cpu().numpy()
+                res += [percentile_from_sorted(s[2 * j], s[2 * j + 1], s[-1], n, p) for j, p in enumerate(part)]
+    return res if seq else res[0]
+
+
+@torch.no_grad()
+def colorize_device(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None,
+                    background_color=(128, 128, 128, 255), gamma_corrected=False, value_transform=None, vminp=2, vmaxp=95):
+    """``metrics.colorize`` of one fp32 device map -> (device uint8 [H, W, 3] view of the scanline buffer, the buffer itself:
+    uint8 [1, prv2_rows_bytes(H, W, 3)], whose first H * (1 + 3 W) bytes are the deflate-ready image).  RGB only (every caller
+    drops colorize's alpha).  vmin / vmax given by the caller are taken as float32.  ``gamma_corrected`` and
+    ``value_transform`` are not built on the device: ValueError."""
+    from . import ops
+    if gamma_corrected or value_transform is not None:
+        raise ValueError("colorize_device: gamma_corrected / value_transform are host-only (metrics.colorize)")
+    v = _frames(value)
+    h, w = v.shape[1:]
+    inv = None if invalid_mask is None else torch.as_tensor(invalid_mask).to(v.device).bool().reshape(v.shape)
+    if vmin is None or vmax is None:
+        valid = None if inv is None else ~inv
+        need = ([vminp] if vmin is None else []) + ([vmaxp] if vmax is None else [])
+        got = percentile_device(v, need, mask=valid, invalid_val=invalid_val)
+        if vmin is None:
+            vmin = got.pop(0)
+        if vmax is None:
+            vmax = got.pop(0)
+    norm = torch.from_numpy(np.array([[F32(vmin), F32(vmax)]], dtype=F32)).to(v.device)
+    rows = ops.colorize_rows(v, norm, _lut_device(cmap, v.device), invalid_mask=inv, invalid_val=invalid_val, background_rgb=background_color[:3])
+    img = rows[0, :h * (1 + 3 * w)].view(h, 1 + 3 * w)[:, 1:].view(h, w, 3)
+    return img, rows
+
+
+class OutputStage:
+    """Writer of the tester's PNG files from device maps.  ``submit_*`` enqueue the scanline kernels on a side stream (after the
+    producer's current stream), copy the buffers into one of ``depth`` pinned staging slots and hand (path, IHDR, rows) to a
+    pool of ``workers`` threads that wait for the copy, deflate (level 6) and write the file.  A slot is reused only after its
+    files are written: the ring bounds memory and gives backpressure.  ``flush()`` waits for every file and re-raises the first
+    worker exception."""
+
+    def __init__(self, work_dir: str, workers: int = 8, depth: int = 2):
+        self.work_dir = work_dir
+        self.workers = max(1, min(int(workers), MAX_WORKERS))
+        self.depth = max(1, int(depth))
+        self.pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="prv2-png")
+        self.stream = None
+        self._slots = [dict(buf=None, futures=[]) for _ in range(self.depth)]
+        self._loose = []  # files queued from host rows (write_rows)
+        self._next = 0
+        self._error = None
+        self._lock = threading.Lock()
+        self.bytes_d2h = 0  # packed scanline bytes copied to the host so far
+        self.files = 0
+        os.makedirs(work_dir, exist_ok=True)
+
+    # ---- pool -----------------------------------------------------------------------------------------------------
+    def _write(self, path, header, rows, event=None):
+        try:
+            if event is not None:
+                event.synchronize()  # the D2H copy of this slot
+            data = png_bytes(header, rows)
+            with open(path, "wb") as f:
+                f.write(data)
+        except BaseException as e:  # kept for flush()
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
+    def write_rows(self, path: str, w: int, h: int, bpp: int, rows, event=None, _slot=None):
+        """queue one file from host scanlines (a bytes-like of h * (1 + bpp * w) bytes)"""
+        self.files += 1
+        fut = self.pool.submit(self._write, path, ihdr(w, h, bpp), rows, event)
+        (self._loose if _slot is None else _slot["futures"]).append(fut)
+        return fut
+
+    def flush(self):
+        """wait for every queued file; re-raise the first worker exception"""
+        for futures in [s["futures"] for s in self._slots] + [self._loose]:
+            for f in futures:
+                f.result()
+            del futures[:]
+        with self._lock:
+            err, self._error = self._error, None
+        if err is not None:
+            raise err
+
+    def close(self):
+        try:
+            self.flush()
+        finally:
+            self.pool.shutdown(wait=True)
+
+    # ---- device side ----------------------------------------------------------------------------------------------
+    def _begin(self, device):
+        """order the side stream after the producer's current stream and take the next staging slot"""
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device)
+        self.stream.wait_stream(torch.cuda.current_stream(device))
+        slot = self._slots[self._next]
+        self._next = (self._next + 1) % self.depth
+        for f in slot["futures"]:  # backpressure: the slot's previous files must be on disk
+            f.result()
+        slot["futures"] = []
+        return slot
+
+    def _stage(self, slot, jobs):
+        """jobs: [(path, w, h, bpp, device rows uint8 [1, bytes])] -> one pinned buffer, one event, one pool task per file"""
+        total = sum(int(r.shape[1]) for *_, r in jobs)
+        if slot["buf"] is None or slot["buf"].numel() < total:
+            slot["buf"] = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        off, views = 0, []
+        for path, w, h, bpp, r in jobs:
+            n = int(r.shape[1])
+            slot["buf"][off:off + n].copy_(r[0], non_blocking=True)
+            views.append((path, w, h, bpp, off))
+            off += n
+        self.bytes_d2h += total
+        ev = torch.cuda.Event()
+        ev.record(self.stream)
+        host = slot["buf"].numpy()
+        for path, w, h, bpp, o in views:
+            self.write_rows(path, w, h, bpp, memoryview(host[o:o + h * (1 + bpp * w)]), ev, slot)
+
+    @torch.no_grad()
+    def submit_frame(self, base: str, result: torch.Tensor, coarse, image_raw_shape, cmap="Spectral", percentiles=(0, 100)):
+        """the files of ``Tester._emit``: <base>_uint16.png, <base>.png, <base>_edge.png and, with ``coarse`` ([1, 1, ph, pw]),
+        <base>_coarse.png"""
+        from . import ops
+        dev = result.device
+        slot = self._begin(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(self.stream):
+            d = _frames(result)
+            h, w = d.shape[1:]
+            jobs = [(base + "_uint16.png", w, h, 2, ops.quantize16_rows(d, 256.0)),
+                    (base + ".png", w, h, 3, colorize_device(d, cmap=cmap, vminp=percentiles[0], vmaxp=percentiles[1])[1])]
+            edges = ops.binary_dilate(ops.canny(ops.depth_preprocess(d, "log"), sigma=1.0), 3)  # tester.py:99-106
+            jobs.append((base + "_edge.png", w, h, 1, ops.mask_rows(edges)))
+            if coarse is not None:
+                ch, cw = int(image_raw_shape[0]), int(image_raw_shape[1])
+                up = ops.upsample_bilinear_map(coarse.reshape(1, *coarse.shape[-2:]).float(), ch, cw)
+                jobs.append((base + "_coarse.png", cw, ch, 3, colorize_device(up, cmap="Spectral", vminp=0, vmaxp=100)[1]))
+            self._stage(slot, jobs)
+            for t in (result, coarse):
+                if t is not None:
+                    t.record_stream(self.stream)
+
+    @torch.no_grad()
+    def submit_pseudo_label(self, base: str, depth, uncertainty, count_map, n_tiles: int, count_thr: float, cmap="magma_r"):
+        """the five files of ``Tester._write_pl``"""
+        from . import ops
+        dev = depth.device
+        slot = self._begin(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(self.stream):
+            d, u, c = _frames(depth), _frames(uncertainty), _frames(count_map)
+            h, w = d.shape[1:]
+            thr = float(count_thr) * n_tiles
+            # extrema of the uncertainty: of the whole map, and of the pixels enough tiles cover (u is monotone in it there, 1 elsewhere)
+            _, s_all = ops.order_stats(u, [0, -1], invalid_val=float("nan"))
+            n_in, s_in = ops.order_stats(u, [0, -1], invalid_val=float("nan"), gate=c, gate_thr=thr)
+            lo, hi = (float(x) for x in s_all[0].cpu().numpy().astype(np.float64))
+            n_in = int(n_in[0])
+            in_lo, in_hi = (float(x) for x in s_in[0].cpu().numpy().astype(np.float64))
+
+            def unit(x):
+                return (x - lo) / (hi - lo) if hi > lo else 0.0
+            vals = ([unit(in_lo), unit(in_hi)] if n_in > 0 else []) + ([1.0] if n_in < h * w else [])
+            prm = torch.tensor([[lo, hi, thr, min(vals), max(vals)]], dtype=torch.float64).to(dev)
+            r16, rgb = ops.pl_uncertainty_rows(u, c, prm, _lut_device("jet", dev))
+            jobs = [(base + ".png", w, h, 3, colorize_device(d, cmap=cmap, vminp=0, vmaxp=100)[1]),
+                    (base + "_uint16.png", w, h, 2, ops.quantize16_rows(d, 256.0)),
+                    (base + "_uncert_uint16.png", w, h, 2, r16),
+                    (base + "_uncert.png", w, h, 3, rgb),
+                    (base + "_count_uint16.png", w, h, 2, ops.quantize16_rows(c, 256.0))]
+            self._stage(slot, jobs)
+            for t in (depth, uncertainty, count_map):
+                t.record_stream(self.stream)

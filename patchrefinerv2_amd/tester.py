@@ -4,6 +4,8 @@ Tester.run          estimator/tester/tester.py:52-127 (frame loop, model call co
 Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, uncertainty and tile-count PNGs)
 ImageDataset        estimator/datasets/general_dataset.py:161-234 (folder of images -> image_hr / image_lr)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
+``runner_info.device_output`` (tools/test.py --device-output) routes the saved files through output.OutputStage: scanlines made on
+the GPU, deflate on a writer pool; the default is the host route below.
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) -- colour maps and metrics in metrics.py, PNGs through a
 dependency-free encoder.  Not built: <name>_edge.png (cv2.Canny + kornia blur, both un-vendored, :98-106) and the
@@ -222,6 +224,7 @@ class Tester:
         prefetch = bool(getattr(self.model, "needs_coarse", False))
         todo = list(range(len(self.dataloader))) if patches else list(range(rank, len(self.dataloader), world))
         groups = [todo[i:i + fb] for i in range(0, len(todo), fb)]
+        stage = self._output_stage()
 
         def load(idxs):
             items = [self.dataloader[idx] for idx in idxs]
@@ -242,6 +245,8 @@ class Tester:
             # with ground truth the frame is scored on the device (metrics.compute_metrics_device): ask for the device map
             if any(item.get("depth_gt") is not None for item in items) and getattr(self.model, "supports_return_device", False):
                 kw.update(return_device=True)
+            if stage is not None:  # the device output stage reads the maps where they are
+                kw.update(return_device=True)
             if patches:
                 kw.update(shard=(rank, world), gather_dst=0)
             if prefetch and nxt is not None:
@@ -254,7 +259,9 @@ class Tester:
             for f, item in enumerate(items):
                 one = len(items) == 1
                 self._emit(results, item, result if one else result[f:f + 1], coarse if one or coarse is None else coarse[f:f + 1],
-                           image_raw_shape)
+                           image_raw_shape, stage)
+        if stage is not None:
+            stage.close()  # every file is on disk (or its error raised) before run returns
         if not patches:
             # collect results from all ranks (tester.py:124-127: collect_results_gpu); rank 0 evaluates the whole dataset
             allr = collect_results(results, len(self.dataloader))
@@ -264,8 +271,36 @@ class Tester:
             self.last_eval = evaluate([r["metrics"] for r in results])
         return results
 
-    def _emit(self, results, item, result, coarse, image_raw_shape):
+    def _output_stage(self):
+        """the run's ``output.OutputStage`` when ``runner_info.device_output`` and ``save`` are set (``output_workers`` threads,
+        default 8), else None.  The stage needs the maps on the device: a model without ``return_device`` is rejected."""
+        if not (getattr(self.runner_info, "device_output", False) and self.runner_info.save):
+            return None
+        if not getattr(self.model, "supports_return_device", False):
+            raise ValueError(f"device_output: {type(self.model).__name__} cannot return a device map (no return_device); use the host route")
+        from .output import OutputStage
+        return OutputStage(self.runner_info.work_dir, workers=getattr(self.runner_info, "output_workers", 8))
+
+    def _emit_device(self, results, item, result, coarse, image_raw_shape, stage):
+        """``_emit`` through the device output stage: the same files from scanlines produced on the GPU, the same result entry
+        (its mean is a float64 sum on the device: equal to the host's float32 mean within that sum's rounding)"""
+        if not result.is_cuda:
+            raise ValueError("device_output: the model returned a host map")
+        base = os.path.join(self.runner_info.work_dir, item["img_file_basename"])
+        if getattr(self.runner_info, "gray_scale", False):
+            cmap, pct = "gray_r", (2, 95)  # colorize's defaults, as _emit
+        else:
+            cmap, pct = ("magma_r" if getattr(self.dataloader, "dataset_name", "") == "cityscapes" else "Spectral"), (0, 100)
+        stage.submit_frame(base, result, coarse, image_raw_shape, cmap=cmap, percentiles=pct)
+        entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(result.mean(dtype=torch.float64)))
+        if item.get("depth_gt") is not None:
+            entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result, disp_gt_edges=item.get("boundary"))
+        results.append(entry)
+
+    def _emit(self, results, item, result, coarse, image_raw_shape, stage=None):
         """one frame's outputs: PNGs (--save), its metrics and its result entry"""
+        if stage is not None:
+            return self._emit_device(results, item, result, coarse, image_raw_shape, stage)
         result_dev = result if result.is_cuda else None
         result = result.cpu()  # BaselinePretrain(target='coarse') hands back the device tensor (baseline_pretrain.py:464)
         if self.runner_info.save:
@@ -313,6 +348,7 @@ class Tester:
         todo = list(range(rank, len(self.dataloader), world))
         groups = [todo[i:i + fb] for i in range(0, len(todo), fb)]
         device = getattr(self.model, "device", "cuda")
+        stage = self._output_stage()
 
         def load(idxs):
             items = [self.dataloader[idx] for idx in idxs]
@@ -324,6 +360,8 @@ class Tester:
             items, hr, lr = nxt
             nxt = load(groups[n + 1]) if n + 1 < len(groups) else None
             kw = dict(return_uncertainty=True)
+            if stage is not None:
+                kw.update(return_device=True)
             if seed is not None:
                 if len(idxs) == 1:
                     random.seed(seed)
@@ -337,12 +375,22 @@ class Tester:
             # the plan's tile count (every frame of a call has the same passes; only random positions differ)
             n_tiles = sum(len(p["raw"]) for p in self.model.last_plan)
             for f, item in enumerate(items):
+                if stage is not None:  # the five files from scanlines produced on the GPU
+                    depth = result[f:f + 1]
+                    cmap = "gray_r" if getattr(self.runner_info, "gray_scale", False) else "magma_r"
+                    stage.submit_pseudo_label(os.path.join(self.runner_info.work_dir, item["img_file_basename"]), depth,
+                                              log["uncertainty"][f:f + 1], log["count_map"][f:f + 1], n_tiles, count_thr, cmap=cmap)
+                    results.append(dict(name=item["img_file_basename"], shape=tuple(depth.shape),
+                                        mean=float(depth.mean(dtype=torch.float64)), n_tiles=n_tiles))
+                    continue
                 depth = result[f:f + 1].cpu()
                 entry = dict(name=item["img_file_basename"], shape=tuple(depth.shape), mean=float(depth.mean()), n_tiles=n_tiles)
                 if self.runner_info.save:
                     self._write_pl(item["img_file_basename"], depth, log["uncertainty"][f:f + 1].cpu(), log["count_map"][f:f + 1].cpu(),
                                    n_tiles, count_thr)
                 results.append(entry)
+        if stage is not None:
+            stage.close()
         return results
 
     def _write_pl(self, name, depth, uncertainty, count_map, n_tiles, count_thr):

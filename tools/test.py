@@ -8,6 +8,7 @@ CONFIG is an MMEngine-style python config (``model=dict(type=..., config=dict(..
 Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``--prec``, ``--process-num``, ``--max-batch``, ``--streams``.
 ``--frame-batch N``: N frames per model call on one GPU (per rank in a frame-sharded run), outputs split per frame.
 ``--generate-pl [--count-thr T]``: Tester.generate_pl instead of run -- pseudo labels with per-pixel uncertainty and tile counts.
+``--device-output [--output-workers N]``: with ``--save``, the output files' pixels are produced on the GPU and written by a thread pool.
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
@@ -75,6 +76,10 @@ def main():
     ap.add_argument("--edge-metrics", action="store_true",
                     help="with ground truth (dataset gt_dir): add the boundary metrics (EdgeAcc, EdgeComp, precision, recall, f1_score, hamming, "
                          "acc) and the edge_* / noedge_* split of every depth metric (metric.py:210-272, scannet_dataset.py:221-243)")
+    ap.add_argument("--device-output", action="store_true",
+                    help="with --save: produce the PNG scanlines on the GPU and deflate / write them on a pool of threads while the next "
+                         "frame computes (patchrefinerv2_amd/output.py); the files are the host route's")
+    ap.add_argument("--output-workers", type=int, default=8, metavar="N", help="--device-output: writer threads (at most 16)")
     ap.add_argument("--benchmark-iters", nargs=2, type=int, default=[20, 50], metavar=("WARMUP", "TOTAL"))
     args = ap.parse_args()
     if args.test_type != "general":
@@ -111,7 +116,8 @@ def main():
     if args.edge_metrics:
         ds_cfg["edge_metrics"] = True
     dataset = DATASETS.build(ds_cfg)
-    runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir)
+    runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
+                        device_output=args.device_output, output_workers=args.output_workers)
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
         for r in tester.run_consistency(image_raw_shape=args.image_raw_shape, patch_split_num=args.patch_split_num, overlap=args.consistency):
