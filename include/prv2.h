@@ -665,6 +665,34 @@ int prv2_mask_rows(const uint8_t* mask, int32_t n, int32_t h, int32_t w, uint8_t
  * raw resolution (tester.py:93-96) */
 int prv2_upsample_bilinear_map(const float* x, int32_t n, int32_t ph, int32_t pw, float* y, int32_t oh, int32_t ow, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device deflate (csrc/deflate.hip): zlib streams (RFC 1950 / 1951) of byte buffers that are already on the device -- the IDAT
+ * payload of a scanline buffer, so that only compressed bytes are copied to the host.  Frames convention of the output stage:
+ * rows [n, rows_fstride] with len valid bytes per frame (what prv2_*_rows write); every frame becomes one stream.  A frame is cut
+ * into independent segments of prv2_deflate_segment() bytes (one workgroup each; no match crosses a segment; every segment but
+ * the last ends byte-aligned with an empty stored block); greedy LZ77 in LDS (lengths 3 .. 258, every match verified byte for
+ * byte), dynamic Huffman codes per block of 4096 positions, a stored block where that is smaller.  Three launches, no host
+ * synchronisation, deterministic: the same bytes give the same stream on every call.  The streams differ from zlib's own
+ * (zlib.decompress restores the input; the Adler-32 trailer is that of the len input bytes).
+ * ------------------------------------------------------------------------------------------ */
+
+/* input bytes per segment (a compile-time constant >= 32768) */
+int32_t prv2_deflate_segment(void);
+
+/* upper bound of a stream's size for any input of len bytes: a multiple of 16, at most len + len / 512 + 64 (-1 for len < 0 or
+ * len >= 2^31) */
+int64_t prv2_deflate_bound(int64_t len);
+
+/* bytes of workspace prv2_deflate_rows needs for n frames of len bytes (-1 for bad arguments) */
+int64_t prv2_deflate_workspace_bytes(int32_t n, int64_t len);
+
+/* rows: DEVICE uint8 [n, rows_fstride], 16-byte aligned, rows_fstride a multiple of 16 and >= len; bytes behind len are not read
+ * into the stream.  out: DEVICE uint8 [n, out_fstride], 16-byte aligned, out_fstride a multiple of 16 and >= prv2_deflate_bound(len):
+ * frame f's stream is out[f, 0 .. out_bytes[f]).  out_bytes: DEVICE int64 [n].  workspace: 16-byte aligned.  len == 0 gives the
+ * stream of an empty input.  Every argument is checked before the first launch. */
+int prv2_deflate_rows(const uint8_t* rows, int32_t n, int64_t len, int64_t rows_fstride, uint8_t* out, int64_t out_fstride, int64_t* out_bytes,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1098,6 +1098,21 @@ Tensor upsample_bilinear_map(const Tensor& x, int64_t oh, int64_t ow) {
   return y;
 }
 
+// device deflate (include/prv2.h "Device deflate"): one zlib stream per frame of a scanline buffer [n, stride], len bytes each
+std::tuple<Tensor, Tensor> deflate_rows(const Tensor& rows, int64_t len) {
+  TORCH_CHECK(rows.is_cuda() && rows.scalar_type() == at::kByte && rows.dim() == 2 && rows.is_contiguous() && rows.size(0) >= 1,
+              "prv2::deflate_rows: rows must be a contiguous GPU uint8 [n, stride] tensor");
+  const int64_t bound = prv2_deflate_bound(len), bytes = prv2_deflate_workspace_bytes((int)rows.size(0), len);
+  TORCH_CHECK(bound > 0 && bytes > 0 && rows.size(0) <= 65535, "prv2::deflate_rows: bad length ", len, " or frame count ", rows.size(0));
+  Tensor out = at::empty({rows.size(0), bound}, rows.options());
+  Tensor out_bytes = at::empty({rows.size(0)}, rows.options().dtype(at::kLong));
+  Tensor ws = at::empty({bytes}, rows.options());
+  Launch L(rows);
+  ok(prv2_deflate_rows((const uint8_t*)rows.data_ptr(), (int)rows.size(0), len, rows.size(1), (uint8_t*)out.data_ptr(), bound,
+                       out_bytes.data_ptr<int64_t>(), ws.data_ptr(), ws.numel(), L.stream), "deflate_rows");
+  return {out, out_bytes};
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1235,6 +1250,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("pl_uncertainty_rows(Tensor uncertainty, Tensor count_map, Tensor params, Tensor lut) -> (Tensor, Tensor)");
   m.def("mask_rows(Tensor mask) -> Tensor");
   m.def("upsample_bilinear_map(Tensor x, int oh, int ow) -> Tensor");
+  m.def("deflate_rows(Tensor rows, int len) -> (Tensor, Tensor)");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1311,5 +1327,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("quantize16_rows", &quantize16_rows);
   m.impl("pl_uncertainty_rows", &pl_uncertainty_rows);
   m.impl("mask_rows", &mask_rows);
+  m.impl("deflate_rows", &deflate_rows);
   m.impl("upsample_bilinear_map", &upsample_bilinear_map);
 }

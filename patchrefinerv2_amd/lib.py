@@ -154,6 +154,10 @@ SIGNATURES = {
     "prv2_pl_uncertainty_rows": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _L, _P, _L, _P]),
     "prv2_mask_rows": (_I, [_P, _I, _I, _I, _P, _L, _P]),
     "prv2_upsample_bilinear_map": (_I, [_P, _I, _I, _I, _P, _I, _I, _P]),
+    "prv2_deflate_segment": (_I, []),
+    "prv2_deflate_bound": (_L, [_L]),
+    "prv2_deflate_workspace_bytes": (_L, [_I, _L]),
+    "prv2_deflate_rows": (_I, [_P, _I, _L, _L, _P, _L, _P, _P, _L, _P]),
 }
 
 _lib = None

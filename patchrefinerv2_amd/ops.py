@@ -1782,3 +1782,25 @@ def upsample_bilinear_map(x, oh, ow):
     y = torch.empty((x.shape[0], int(oh), int(ow)), dtype=torch.float32, device=x.device)
     L.check(L.load().prv2_upsample_bilinear_map(x.data_ptr(), *x.shape, y.data_ptr(), int(oh), int(ow), _stream()), "upsample_bilinear_map")
     return y
+
+
+def deflate_rows(rows, length):
+    """zlib streams of byte frames that are on the device: ``rows`` uint8 [B, stride] (a scanline buffer: stride a multiple of
+    16), ``length`` <= stride valid bytes per frame -> (out uint8 [B, prv2_deflate_bound(length)], out_bytes int64 [B]), both on
+    the device: frame f's stream is out[f, :out_bytes[f]].  zlib.decompress restores rows[f, :length]; the stream is not zlib's
+    own (include/prv2.h prv2_deflate_rows) and is the same on every call."""
+    if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError("deflate_rows: rows is a contiguous GPU uint8 [B, stride] tensor")
+    length = int(length)
+    if DISPATCH == "torch":
+        return _tops().deflate_rows(rows, length)
+    lib = L.load()
+    bound, wsb = lib.prv2_deflate_bound(length), lib.prv2_deflate_workspace_bytes(rows.shape[0], length)
+    if bound < 0 or wsb < 0:
+        raise ValueError(f"deflate_rows: bad length {length} or frame count {rows.shape[0]}")
+    out = torch.empty((rows.shape[0], bound), dtype=torch.uint8, device=rows.device)
+    out_bytes = torch.empty((rows.shape[0],), dtype=torch.int64, device=rows.device)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=rows.device)
+    L.check(lib.prv2_deflate_rows(rows.data_ptr(), rows.shape[0], length, rows.shape[1], out.data_ptr(), bound, out_bytes.data_ptr(),
+                                  ws.data_ptr(), wsb, _stream()), "deflate_rows")
+    return out, out_bytes

@@ -6,10 +6,16 @@ ops.py), copies only those packed bytes into pinned host memory and hands them t
 (``zlib.compress`` releases the GIL), while the next frame computes.  Chunk layout, zlib level and the single IDAT chunk are
 those of ``tester.write_png16`` / ``write_png8``: equal pixels give byte-identical files.
 
+``device_deflate`` (``runner_info.device_deflate`` / ``tools/test.py --device-deflate``, on top of the device route) also produces
+the zlib stream of every file on the GPU (csrc/deflate.hip through ``ops.deflate_rows``): only compressed bytes are copied to the
+host and the writer threads compute the chunk CRC and write.  Such files hold the same pixels as the device route's but NOT the
+same bytes: the IDAT payload is the device encoder's stream, not zlib level 6's (and usually larger).
+
 percentile_from_sorted   np.percentile(method='linear') of a float32 array from two neighbouring order statistics (host)
 colormap_lut / lut_index matplotlib's byte table and index rule (host restatement: the spec of prv2_colorize_rows)
 percentile_device        np.percentile(value[mask], q) of a device map (exact order statistics + the host interpolation)
 colorize_device          metrics.colorize of a device map -> device uint8 [H, W, 3] view + its scanline buffer
+png_bytes_from_stream    the PNG container around a given IDAT payload
 OutputStage              side stream, ring of pinned staging slots, writer pool
 """
 from __future__ import annotations
@@ -84,12 +90,17 @@ def lut_index(x: np.ndarray, n: int) -> np.ndarray:
     return idx
 
 
+def png_bytes_from_stream(header: bytes, zstream) -> bytes:
+    """signature, IHDR, one IDAT whose payload is ``zstream`` (a zlib stream of the scanlines, taken as given), IEND"""
+    def chunk(tag, data):
+        crc = zlib.crc32(data, zlib.crc32(tag)) & 0xFFFFFFFF
+        return struct.pack(">I", len(data)) + tag + bytes(data) + struct.pack(">I", crc)
+    return PNG_SIGNATURE + chunk(b"IHDR", header) + chunk(b"IDAT", zstream) + chunk(b"IEND", b"")
+
+
 def png_bytes(header: bytes, rows) -> bytes:
     """the file ``write_png16`` / ``write_png8`` write for these scanlines: signature, IHDR, one IDAT (zlib level 6), IEND"""
-    def chunk(tag, data):
-        c = struct.pack(">I", len(data)) + tag + data
-        return c + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
-    return PNG_SIGNATURE + chunk(b"IHDR", header) + chunk(b"IDAT", zlib.compress(rows, 6)) + chunk(b"IEND", b"")
+    return png_bytes_from_stream(header, zlib.compress(rows, 6))
 
 
 def ihdr(w: int, h: int, bpp: int) -> bytes:
@@ -187,20 +198,27 @@ class OutputStage:
     producer's current stream), copy the buffers into one of ``depth`` pinned staging slots and hand (path, IHDR, rows) to a
     pool of ``workers`` threads that wait for the copy, deflate (level 6) and write the file.  A slot is reused only after its
     files are written: the ring bounds memory and gives backpressure.  ``flush()`` waits for every file and re-raises the first
-    worker exception."""
+    worker exception.
 
-    def __init__(self, work_dir: str, workers: int = 8, depth: int = 2):
+    ``device_deflate``: the side stream also deflates every scanline buffer (``ops.deflate_rows``).  The main thread does not
+    wait for the stream sizes: they go to pinned memory with an event, the file's writer thread waits for it, copies exactly that
+    many bytes on the stage's copy stream, computes the chunk CRC and writes.  Same pixels as without it, different file bytes
+    (the IDAT payload is the device encoder's zlib stream)."""
+
+    def __init__(self, work_dir: str, workers: int = 8, depth: int = 2, device_deflate: bool = False):
         self.work_dir = work_dir
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.depth = max(1, int(depth))
         self.pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="prv2-png")
+        self.device_deflate = bool(device_deflate)
         self.stream = None
-        self._slots = [dict(buf=None, futures=[]) for _ in range(self.depth)]
+        self.copy_stream = None  # device_deflate: the writer threads' D2H copies
+        self._slots = [dict(buf=None, sizes=None, futures=[]) for _ in range(self.depth)]
         self._loose = []  # files queued from host rows (write_rows)
         self._next = 0
         self._error = None
         self._lock = threading.Lock()
-        self.bytes_d2h = 0  # packed scanline bytes copied to the host so far
+        self.bytes_d2h = 0  # bytes copied to the host so far: packed scanlines, or compressed streams and their sizes
         self.files = 0
         os.makedirs(work_dir, exist_ok=True)
 
@@ -210,6 +228,27 @@ class OutputStage:
             if event is not None:
                 event.synchronize()  # the D2H copy of this slot
             data = png_bytes(header, rows)
+            with open(path, "wb") as f:
+                f.write(data)
+        except BaseException as e:  # kept for flush()
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
+    def _write_stream(self, path, header, out, k, sizes, event, host):
+        """device_deflate: wait for the sizes, copy stream k's bytes into the pinned view ``host``, add the CRC, write"""
+        try:
+            event.synchronize()  # the deflate kernels and the copy of the sizes
+            nb = int(sizes[k])
+            with torch.cuda.device(out.device), torch.cuda.stream(self.copy_stream):
+                out.record_stream(self.copy_stream)
+                host[:nb].copy_(out[0, :nb], non_blocking=True)
+                done = torch.cuda.Event()
+                done.record(self.copy_stream)
+            done.synchronize()
+            with self._lock:
+                self.bytes_d2h += nb
+            data = png_bytes_from_stream(header, memoryview(host.numpy())[:nb])
             with open(path, "wb") as f:
                 f.write(data)
         except BaseException as e:  # kept for flush()
@@ -246,6 +285,8 @@ class OutputStage:
         """order the side stream after the producer's current stream and take the next staging slot"""
         if self.stream is None:
             self.stream = torch.cuda.Stream(device)
+            if self.device_deflate:
+                self.copy_stream = torch.cuda.Stream(device)
         self.stream.wait_stream(torch.cuda.current_stream(device))
         slot = self._slots[self._next]
         self._next = (self._next + 1) % self.depth
@@ -256,6 +297,8 @@ class OutputStage:
 
     def _stage(self, slot, jobs):
         """jobs: [(path, w, h, bpp, device rows uint8 [1, bytes])] -> one pinned buffer, one event, one pool task per file"""
+        if self.device_deflate:
+            return self._stage_deflate(slot, jobs)
         total = sum(int(r.shape[1]) for *_, r in jobs)
         if slot["buf"] is None or slot["buf"].numel() < total:
             slot["buf"] = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
@@ -271,6 +314,27 @@ class OutputStage:
         host = slot["buf"].numpy()
         for path, w, h, bpp, o in views:
             self.write_rows(path, w, h, bpp, memoryview(host[o:o + h * (1 + bpp * w)]), ev, slot)
+
+    def _stage_deflate(self, slot, jobs):
+        """``_stage`` with the zlib streams made on the side stream: nothing but the sizes is copied here"""
+        from . import ops
+        streams = [ops.deflate_rows(r, h * (1 + bpp * w)) for _, w, h, bpp, r in jobs]
+        total = sum(int(o.shape[1]) for o, _ in streams)  # the bounds: room for any stream
+        if slot["buf"] is None or slot["buf"].numel() < total:
+            slot["buf"] = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        if slot["sizes"] is None or slot["sizes"].numel() < len(jobs):
+            slot["sizes"] = torch.empty((max(8, len(jobs)),), dtype=torch.int64, pin_memory=True)
+        sizes = slot["sizes"]
+        sizes[:len(jobs)].copy_(torch.cat([nb for _, nb in streams]), non_blocking=True)
+        self.bytes_d2h += 8 * len(jobs)
+        ev = torch.cuda.Event()
+        ev.record(self.stream)
+        off = 0
+        for k, ((path, w, h, bpp, _), (out, _)) in enumerate(zip(jobs, streams)):
+            self.files += 1
+            host = slot["buf"][off:off + int(out.shape[1])]
+            slot["futures"].append(self.pool.submit(self._write_stream, path, ihdr(w, h, bpp), out, k, sizes, ev, host))
+            off += int(out.shape[1])
 
     @torch.no_grad()
     def submit_frame(self, base: str, result: torch.Tensor, coarse, image_raw_shape, cmap="Spectral", percentiles=(0, 100)):

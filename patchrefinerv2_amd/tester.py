@@ -5,7 +5,9 @@ Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, un
 ImageDataset        estimator/datasets/general_dataset.py:161-234 (folder of images -> image_hr / image_lr)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 ``runner_info.device_output`` (tools/test.py --device-output) routes the saved files through output.OutputStage: scanlines made on
-the GPU, deflate on a writer pool; the default is the host route below.
+the GPU, deflate on a writer pool; the default is the host route below.  ``runner_info.device_deflate`` (--device-deflate, needs
+device_output) makes the zlib streams on the GPU as well: the files hold the device route's pixels, but not its bytes (the deflate
+stream differs from zlib's).
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) -- colour maps and metrics in metrics.py, PNGs through a
 dependency-free encoder.  Not built: <name>_edge.png (cv2.Canny + kornia blur, both un-vendored, :98-106) and the
@@ -224,7 +226,7 @@ class Tester:
         prefetch = bool(getattr(self.model, "needs_coarse", False))
         todo = list(range(len(self.dataloader))) if patches else list(range(rank, len(self.dataloader), world))
         groups = [todo[i:i + fb] for i in range(0, len(todo), fb)]
-        stage = self._output_stage()
+        stage = self.last_output_stage = self._output_stage()  # (kept: its bytes_d2h / files counters)
 
         def load(idxs):
             items = [self.dataloader[idx] for idx in idxs]
@@ -273,13 +275,16 @@ class Tester:
 
     def _output_stage(self):
         """the run's ``output.OutputStage`` when ``runner_info.device_output`` and ``save`` are set (``output_workers`` threads,
-        default 8), else None.  The stage needs the maps on the device: a model without ``return_device`` is rejected."""
+        default 8; ``device_deflate``: zlib streams from the GPU too -- same pixels, other file bytes), else None.  The stage needs the maps on the device: a model without ``return_device`` is rejected."""
+        deflate = bool(getattr(self.runner_info, "device_deflate", False))
+        if deflate and not getattr(self.runner_info, "device_output", False):
+            raise ValueError("device_deflate needs device_output (the zlib streams are made from the device route's scanlines)")
         if not (getattr(self.runner_info, "device_output", False) and self.runner_info.save):
             return None
         if not getattr(self.model, "supports_return_device", False):
             raise ValueError(f"device_output: {type(self.model).__name__} cannot return a device map (no return_device); use the host route")
         from .output import OutputStage
-        return OutputStage(self.runner_info.work_dir, workers=getattr(self.runner_info, "output_workers", 8))
+        return OutputStage(self.runner_info.work_dir, workers=getattr(self.runner_info, "output_workers", 8), device_deflate=deflate)
 
     def _emit_device(self, results, item, result, coarse, image_raw_shape, stage):
         """``_emit`` through the device output stage: the same files from scanlines produced on the GPU, the same result entry
@@ -348,7 +353,7 @@ class Tester:
         todo = list(range(rank, len(self.dataloader), world))
         groups = [todo[i:i + fb] for i in range(0, len(todo), fb)]
         device = getattr(self.model, "device", "cuda")
-        stage = self._output_stage()
+        stage = self.last_output_stage = self._output_stage()  # (kept: its bytes_d2h / files counters)
 
         def load(idxs):
             items = [self.dataloader[idx] for idx in idxs]

@@ -36,7 +36,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # edge-aware evaluation (Canny, distance transform, dilation, boundary statistics of B frames)
        "depth_preprocess", "canny", "edt_sq", "binary_dilate", "boundary_stats",
        # output stage (order statistics, PNG scanlines, bilinear resize of the coarse map)
-       "order_stats", "colorize_rows", "quantize16_rows", "pl_uncertainty_rows", "mask_rows", "upsample_bilinear_map")
+       "order_stats", "colorize_rows", "quantize16_rows", "pl_uncertainty_rows", "mask_rows", "upsample_bilinear_map",
+       # device deflate: zlib streams of scanline buffers
+       "deflate_rows")
 _loaded = False
 
 

@@ -9,6 +9,7 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--frame-batch N``: N frames per model call on one GPU (per rank in a frame-sharded run), outputs split per frame.
 ``--generate-pl [--count-thr T]``: Tester.generate_pl instead of run -- pseudo labels with per-pixel uncertainty and tile counts.
 ``--device-output [--output-workers N]``: with ``--save``, the output files' pixels are produced on the GPU and written by a thread pool.
+``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
@@ -79,9 +80,14 @@ def main():
     ap.add_argument("--device-output", action="store_true",
                     help="with --save: produce the PNG scanlines on the GPU and deflate / write them on a pool of threads while the next "
                          "frame computes (patchrefinerv2_amd/output.py); the files are the host route's")
+    ap.add_argument("--device-deflate", action="store_true",
+                    help="with --device-output: deflate the scanlines on the GPU as well (csrc/deflate.hip): only compressed bytes are copied "
+                         "to the host; the files hold the same pixels as --device-output's, their bytes differ (another deflate stream)")
     ap.add_argument("--output-workers", type=int, default=8, metavar="N", help="--device-output: writer threads (at most 16)")
     ap.add_argument("--benchmark-iters", nargs=2, type=int, default=[20, 50], metavar=("WARMUP", "TOTAL"))
     args = ap.parse_args()
+    if args.device_deflate and not args.device_output:
+        ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
     if args.test_type != "general":
         raise SystemExit("only --test-type general (folder of images, optional .npy ground truth via dataset gt_dir) is built")
 
@@ -117,7 +123,7 @@ def main():
         ds_cfg["edge_metrics"] = True
     dataset = DATASETS.build(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
-                        device_output=args.device_output, output_workers=args.output_workers)
+                        device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate)
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
         for r in tester.run_consistency(image_raw_shape=args.image_raw_shape, patch_split_num=args.patch_split_num, overlap=args.consistency):
