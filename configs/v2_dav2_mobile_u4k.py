@@ -29,4 +29,21 @@ general_dataloader = dict(
     dataset=dict(type='ImageDataset', rgb_image_dir='', dataset_name='', gt_dir=None,
                  network_process_size=(448, 448), resize_mode='depth-anything'))
 
+# the U4K splits (the reference's configs/_base_/datasets/u4k.py with this config's overrides): tools/test.py --test-type normal /
+# test_in / test_out
+val_dataloader = dict(
+    batch_size=1, num_workers=2,
+    dataset=dict(type='UnrealStereo4kDataset', mode='infer', data_root='./data/u4k', split='./data/u4k/splits/val.txt',
+                 min_depth=1e-3, max_depth=80, resize_mode='depth-anything', transform_cfg=dict(network_process_size=[448, 448])))
+
+test_in_dataloader = dict(
+    batch_size=1, num_workers=2,
+    dataset=dict(type='UnrealStereo4kDataset', mode='infer', data_root='./data/u4k', split='./data/u4k/splits/test.txt',
+                 min_depth=1e-3, max_depth=80, transform_cfg=dict(network_process_size=[384, 512])))
+
+test_out_dataloader = dict(
+    batch_size=1, num_workers=2,
+    dataset=dict(type='UnrealStereo4kDataset', mode='infer', data_root='./data/u4k', split='./data/u4k/splits/test_out.txt',
+                 min_depth=1e-3, max_depth=80, transform_cfg=dict(network_process_size=[384, 512])))
+
 collect_input_args = ['image_lr', 'image_hr', 'crops_image_hr', 'depth_gt', 'crop_depths', 'bboxs']

@@ -693,6 +693,42 @@ int64_t prv2_deflate_workspace_bytes(int32_t n, int64_t len);
 int prv2_deflate_rows(const uint8_t* rows, int32_t n, int64_t len, int64_t rows_fstride, uint8_t* out, int64_t out_fstride, int64_t* out_bytes,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ground-truth evaluation (csrc/evalgt.hip): the device half of UnrealStereo4kDataset (estimator/datasets/u4k_dataset.py) and the
+ * sums behind compute_metrics (estimator/utils/metric.py:11-149).  Dense maps, h, w >= 1, fewer than 2^31 pixels per call.  Fixed
+ * launch counts, no host synchronisation, no floating-point atomics: every output is the same bits on every call.  Added without
+ * an ABI bump (additive, as the edge / output / deflate sections).
+ * ------------------------------------------------------------------------------------------ */
+
+/* u4k_dataset.py:125-147: image.astype(np.float32)[:, :, ::-1].copy() / 255.0, then to_tensor.  src: uint8 [h, w, 3]; dst: fp32
+ * [3, h, w]; dst[c] = float(src[swap_rb ? 2 - c : c]) / 255.0f, a correctly rounded fp32 division (bit-equal to numpy's). */
+int prv2_u8_image(const uint8_t* src, int32_t h, int32_t w, int32_t swap_rb, float* dst, void* stream);
+
+/* u4k_dataset.py:128-129,216: depth = factor / disp (fp32 IEEE division: disp == 0 gives inf, as numpy) and, in the same pass,
+ * boundary = get_boundaries(disp, th, dilation=0) (metric.py:74-85) as uint8 0/1 [h, w]: a pixel is set when the absolute
+ * difference to its upper, lower, left or right neighbour exceeds th; a frame border has no neighbour on that side; a comparison
+ * with NaN is false. */
+int prv2_disp_gt(const float* disp, int32_t h, int32_t w, float factor, float th, float* depth, uint8_t* boundary, void* stream);
+
+/* bytes of workspace prv2_depth_metrics needs for n frames of h x w (-1 for a bad shape) */
+int64_t prv2_depth_metrics_workspace_bytes(int32_t n, int32_t h, int32_t w);
+
+/* compute_metrics (metric.py:87-149: clamping and masks; compute_errors :11-50; soft_edge_error(radius=1) :53-72) of n frames as
+ * sums.  gt, pred: fp32 [n, h, w]; boundary, region: uint8 [n, h, w] (non-zero = set) or NULL.  pred is cleaned in the reference's
+ * order (NaN -> min_depth, clamp to [min_depth, max_depth], inf -> max_depth); a pixel is valid when min_depth < gt < max_depth
+ * (fp32 comparisons) inside the crop rows [y0, y1) x columns [x0, x1) (0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w: the garg / kitti /
+ * eigen crops of metric.py:108-120, the whole frame for none).  sums: DEVICE float64 [n, S, 12], S = 1 without region, else 3: set
+ * 0 all valid pixels, set 1 those inside the region, set 2 those outside (cityscapes_dataset.py / scannet_dataset.py:221-243's
+ * three scoring calls from one read).  With g, p the fp32 values as float64, d = g - p, err = log p - log g:
+ *   0 valid count   1..3 counts of max(g / p, p / g) < 1.25, 1.25^2, 1.25^3   4 sum |d| / g   5 sum d^2
+ *   6 sum |log10 g - log10 p|   7 sum err^2   8 sum err   9 sum d^2 / g
+ *   10 count of valid pixels on the boundary   11 sum over them of the fp32 minimum over the 3 x 3 shifts of gt (zero outside the
+ *   frame) of |shift(gt) - p| (NaN propagates, as np.minimum).
+ * Per-block partials in the workspace, summed in block order by a second launch. */
+int prv2_depth_metrics(const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n, int32_t h,
+                       int32_t w, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* sums,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,308 @@
+// Dataset evaluation with ground truth (include/prv2.h "Ground-truth evaluation"): the device half of UnrealStereo4kDataset
+// (estimator/datasets/u4k_dataset.py:120-233) and the sums behind compute_metrics (estimator/utils/metric.py:11-149).
+//
+//   u8_image_kernel       raw BGR bytes [h, w, 3] -> CHW fp32 / 255                                (u4k_dataset.py:125-147)
+//   disp_gt_kernel        disparity -> depth = factor / disp and the boundary map, one pass        (u4k_dataset.py:128-129,216)
+//   depth_metrics_kernel  the twelve sums of compute_errors + soft_edge_error of B frames, for up to three pixel sets at once
+//   metrics_final_kernel  the per-block partials of a frame summed in block order
+//
+// The metrics kernel is one streaming read of gt / pred / boundary / region: a block owns a fixed run of rows, a thread four pixels
+// of a row at a time (float4 / uchar4 loads when the rows are 16-byte aligned), the per-pixel terms are float64 from the float32
+// values, each thread keeps its 12 x S accumulators in registers, a wave reduces by shuffles, the four waves through LDS, and every
+// block stores its partial; the final kernel adds the partials in block order.  No floating-point atomics anywhere: the sums are the
+// same bits on every call.  Only boundary pixels (sparse) look at the 3 x 3 neighbourhood of gt, straight from L2.
+#include <limits.h>
+
+#include "common.h"
+
+namespace prv2 {
+namespace {
+
+constexpr int kTerms = 12;        // sums per pixel set (include/prv2.h prv2_depth_metrics)
+constexpr int kMaxSets = 3;       // all / inside the region / outside it
+constexpr int kMaxBlocks = 1024;  // row blocks per frame
+
+static inline int rows_per_block(int h) { return (int)cdiv(h, kMaxBlocks); }
+static inline int row_blocks(int h) { return (int)cdiv(h, rows_per_block(h)); }
+
+// ------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) u8_image_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int64_t hw, int swap_rb,
+                                                       int vec) {
+  const int64_t quads = (hw + 3) / 4;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p0 = q * 4;
+    if (vec) {  // hw % 4 == 0, src 4-byte and dst 16-byte aligned: 12 bytes in, one float4 per plane out
+      const uint32_t* s = reinterpret_cast<const uint32_t*>(src + p0 * 3);
+      const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];
+      uint8_t b[12];
+      for (int k = 0; k < 4; ++k) {
+        b[k] = (uint8_t)(w0 >> (8 * k));
+        b[4 + k] = (uint8_t)(w1 >> (8 * k));
+        b[8 + k] = (uint8_t)(w2 >> (8 * k));
+      }
+      for (int c = 0; c < 3; ++c) {
+        const int sc = swap_rb ? 2 - c : c;
+        float4 v;
+        v.x = (float)b[sc] / 255.0f;  // IEEE division (hipcc's default): numpy's float32 / 255.0
+        v.y = (float)b[3 + sc] / 255.0f;
+        v.z = (float)b[6 + sc] / 255.0f;
+        v.w = (float)b[9 + sc] / 255.0f;
+        *reinterpret_cast<float4*>(dst + c * hw + p0) = v;
+      }
+    } else {
+      for (int k = 0; k < 4 && p0 + k < hw; ++k)
+        for (int c = 0; c < 3; ++c) dst[c * hw + p0 + k] = (float)src[(p0 + k) * 3 + (swap_rb ? 2 - c : c)] / 255.0f;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// four pixels x0 .. x0 + 3 of row y per thread; the neighbours above / below come as rows, left / right as single loads
+__device__ __forceinline__ void load4(const float* __restrict__ row, int x0, int w, int vec, float* v) {
+  if (vec) {
+    const float4 t = *reinterpret_cast<const float4*>(row + x0);
+    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
+  } else {
+    for (int k = 0; k < 4; ++k) v[k] = x0 + k < w ? row[x0 + k] : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(256) disp_gt_kernel(const float* __restrict__ disp, float* __restrict__ depth, uint8_t* __restrict__ boundary,
+                                                      int h, int w, float factor, float th, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    const float* row = disp + (int64_t)y * w;
+    float c[4], up[4], dn[4];
+    load4(row, x0, w, vec, c);
+    if (y > 0) load4(row - w, x0, w, vec, up);
+    if (y + 1 < h) load4(row + w, x0, w, vec, dn);
+    const float left = x0 > 0 ? row[x0 - 1] : 0.f, right = x0 + 4 < w ? row[x0 + 4] : 0.f;
+    float d[4];
+    uint8_t e[4];
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + k;
+      d[k] = factor / c[k];  // IEEE: disp == 0 -> inf, NaN stays
+      bool b = false;        // |difference| > th; a comparison with NaN is false, a frame border has no neighbour
+      if (y > 0) b |= fabsf(c[k] - up[k]) > th;
+      if (y + 1 < h) b |= fabsf(dn[k] - c[k]) > th;
+      if (x > 0) b |= fabsf(c[k] - (k ? c[k - 1] : left)) > th;
+      if (x + 1 < w) b |= fabsf((k < 3 ? c[k + 1] : right) - c[k]) > th;
+      e[k] = b ? 1 : 0;
+    }
+    const int64_t o = (int64_t)y * w + x0;
+    if (vec) {
+      *reinterpret_cast<float4*>(depth + o) = make_float4(d[0], d[1], d[2], d[3]);
+      *reinterpret_cast<uint32_t*>(boundary + o) = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16 | (uint32_t)e[3] << 24;
+    } else {
+      for (int k = 0; k < 4 && x0 + k < w; ++k) {
+        depth[o + k] = d[k];
+        boundary[o + k] = e[k];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+struct MetricArgs {
+  const float* gt;
+  const float* pred;
+  const uint8_t* boundary;  // may be null
+  const uint8_t* region;    // may be null (then one set)
+  int h, w, rows_per_block, vec;
+  float mn, mx;
+  int y0, y1, x0, x1;
+};
+
+// NaN-propagating minimum (np.minimum / torch.minimum)
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (b < a ? b : a); }
+
+// soft_edge_error(radius=1) at one pixel: min over the 3 x 3 shifts of gt (zero outside the frame) of |shift(gt) - pred|, fp32
+__device__ __forceinline__ float soft_edge(const float* __restrict__ g, int h, int w, int y, int x, float p) {
+  float best = 0.f;
+  bool first = true;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int yy = y + dy, xx = x + dx;
+      const float v = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? g[(int64_t)yy * w + xx] : 0.f;
+      const float d = fabsf(v - p);
+      best = first ? d : min_nan(best, d);
+      first = false;
+    }
+  return best;
+}
+
+template <int S>
+__global__ void __launch_bounds__(256) depth_metrics_kernel(MetricArgs a, double* __restrict__ part) {
+  __shared__ double sh[4][S * kTerms];
+  const int f = blockIdx.y, h = a.h, w = a.w;
+  const int64_t fb = (int64_t)f * h * w;
+  const float* __restrict__ gt = a.gt + fb;
+  const float* __restrict__ pred = a.pred + fb;
+  const uint8_t* __restrict__ bnd = a.boundary ? a.boundary + fb : nullptr;
+  const uint8_t* __restrict__ reg = a.region ? a.region + fb : nullptr;
+  double acc[S][kTerms];
+  for (int s = 0; s < S; ++s)
+    for (int k = 0; k < kTerms; ++k) acc[s][k] = 0.0;
+
+  const int r0 = blockIdx.x * a.rows_per_block;
+  const int ya = max(r0, a.y0), yb = min(min(r0 + a.rows_per_block, h), a.y1);
+  const int q0 = a.x0 / 4, q1 = (min(a.x1, w) + 3) / 4;  // the quads that touch the crop's columns
+  for (int y = ya; y < yb; ++y) {
+    const int64_t ro = (int64_t)y * w;
+    for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
+      const int x0 = q * 4;
+      float g[4], p[4];
+      uint8_t b[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
+      load4(gt + ro, x0, w, a.vec, g);
+      load4(pred + ro, x0, w, a.vec, p);
+      if (a.vec) {
+        if (bnd) {
+          const uint32_t t = *reinterpret_cast<const uint32_t*>(bnd + ro + x0);
+          for (int k = 0; k < 4; ++k) b[k] = (uint8_t)(t >> (8 * k));
+        }
+        if (S > 1) {
+          const uint32_t t = *reinterpret_cast<const uint32_t*>(reg + ro + x0);
+          for (int k = 0; k < 4; ++k) r[k] = (uint8_t)(t >> (8 * k));
+        }
+      } else {
+        for (int k = 0; k < 4 && x0 + k < w; ++k) {
+          if (bnd) b[k] = bnd[ro + x0 + k];
+          if (S > 1) r[k] = reg[ro + x0 + k];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int x = x0 + k;
+        const float gk = g[k];
+        if (!(x >= a.x0 && x < a.x1 && x < w && gk > a.mn && gk < a.mx)) continue;  // a NaN gt is not valid
+        float pk = p[k];  // the reference's order: NaN -> min, clamp, inf -> max (the clamp has done it)
+        pk = pk != pk ? a.mn : pk;
+        pk = pk < a.mn ? a.mn : pk;
+        pk = pk > a.mx ? a.mx : pk;
+        const double G = (double)gk, P = (double)pk;
+        const double ratio = fmax(G / P, P / G);
+        const double d = G - P, err = log(P) - log(G), d2 = d * d;
+        double t[kTerms];
+        t[0] = 1.0;
+        t[1] = ratio < 1.25 ? 1.0 : 0.0;
+        t[2] = ratio < 1.5625 ? 1.0 : 0.0;
+        t[3] = ratio < 1.953125 ? 1.0 : 0.0;
+        t[4] = fabs(d) / G;
+        t[5] = d2;
+        t[6] = fabs(log10(G) - log10(P));
+        t[7] = err * err;
+        t[8] = err;
+        t[9] = d2 / G;
+        t[10] = 0.0;
+        t[11] = 0.0;
+        if (b[k]) {
+          t[10] = 1.0;
+          t[11] = (double)soft_edge(gt, h, w, y, x, pk);
+        }
+        // the set index never addresses the registers: adding 0.0 leaves a sum's bits alone
+        const bool in = S > 1 && r[k] != 0;
+#pragma unroll
+        for (int j = 0; j < kTerms; ++j) {
+          acc[0][j] += t[j];
+          if (S > 1) {
+            acc[1][j] += in ? t[j] : 0.0;
+            acc[S - 1][j] += in ? 0.0 : t[j];
+          }
+        }
+      }
+    }
+  }
+  // wave: shuffles (fixed tree); block: the four waves' sums through LDS, added in wave order
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < S; ++s)
+#pragma unroll
+    for (int j = 0; j < kTerms; ++j) {
+      double v = acc[s][j];
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+      if (lane == 0) sh[wave][s * kTerms + j] = v;
+    }
+  __syncthreads();
+  if (threadIdx.x < S * kTerms) {
+    const int j = threadIdx.x;
+    part[((int64_t)f * gridDim.x + blockIdx.x) * (S * kTerms) + j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
+  }
+}
+
+__global__ void __launch_bounds__(64) metrics_final_kernel(const double* __restrict__ part, double* __restrict__ sums, int nblk, int nval) {
+  const int f = blockIdx.x, j = threadIdx.x;
+  if (j >= nval) return;
+  double s = 0.0;
+  for (int b = 0; b < nblk; ++b) s += part[((int64_t)f * nblk + b) * nval + j];
+  sums[(int64_t)f * nval + j] = s;
+}
+
+static inline bool aligned(const void* p, int bytes) { return p == nullptr || ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
+
+}  // namespace
+}  // namespace prv2
+
+using namespace prv2;
+
+extern "C" int prv2_u8_image(const uint8_t* src, int32_t h, int32_t w, int32_t swap_rb, float* dst, void* stream) {
+  const char* name = "u8_image";
+  PRV2_REQUIRE(src && dst, "%s: null pointer", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE((int64_t)h * w * 3 < (int64_t)INT_MAX, "%s: %d x %d x 3 exceeds 2^31 bytes", name, h, w);
+  const int64_t hw = (int64_t)h * w;
+  const int vec = hw % 4 == 0 && aligned(src, 4) && aligned(dst, 16);
+  hipLaunchKernelGGL(u8_image_kernel, dim3(flat_grid(cdiv(hw, 4), 256)), dim3(256), 0, (hipStream_t)stream, src, dst, hw, swap_rb ? 1 : 0, vec);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_disp_gt(const float* disp, int32_t h, int32_t w, float factor, float th, float* depth, uint8_t* boundary, void* stream) {
+  const char* name = "disp_gt";
+  PRV2_REQUIRE(disp && depth && boundary, "%s: null pointer", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE((int64_t)h * w < (int64_t)INT_MAX, "%s: %d x %d exceeds 2^31 pixels", name, h, w);
+  const int vec = w % 4 == 0 && aligned(disp, 16) && aligned(depth, 16) && aligned(boundary, 4);
+  hipLaunchKernelGGL(disp_gt_kernel, dim3(flat_grid((int64_t)h * cdiv(w, 4), 256)), dim3(256), 0, (hipStream_t)stream, disp, depth, boundary,
+                     (int)h, (int)w, factor, th, vec);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int64_t prv2_depth_metrics_workspace_bytes(int32_t n, int32_t h, int32_t w) {
+  if (n < 1 || n > 65535 || h < 1 || w < 1) return -1;
+  return (int64_t)n * row_blocks(h) * kMaxSets * kTerms * (int64_t)sizeof(double);
+}
+
+extern "C" int prv2_depth_metrics(const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n, int32_t h,
+                                  int32_t w, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* sums,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* name = "depth_metrics";
+  PRV2_REQUIRE(gt && pred && sums, "%s: null pointer", name);
+  PRV2_REQUIRE(n >= 1 && n <= 65535, "%s: frame count %d out of range [1, 65535]", name, n);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE((int64_t)n * h * w < (int64_t)INT_MAX, "%s: %d frames of %d x %d exceed 2^31 pixels", name, n, h, w);
+  PRV2_REQUIRE(y0 >= 0 && y0 <= y1 && y1 <= h && x0 >= 0 && x0 <= x1 && x1 <= w, "%s: crop rows [%d, %d) columns [%d, %d) outside %d x %d", name,
+               y0, y1, x0, x1, h, w);
+  PRV2_REQUIRE(workspace != nullptr, "%s: null workspace", name);
+  const int64_t need = prv2_depth_metrics_workspace_bytes(n, h, w);
+  PRV2_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes < %lld (prv2_depth_metrics_workspace_bytes)", name,
+               (long long)workspace_bytes, (long long)need);
+  MetricArgs a;
+  a.gt = gt, a.pred = pred, a.boundary = boundary, a.region = region;
+  a.h = h, a.w = w, a.rows_per_block = rows_per_block(h);
+  a.vec = w % 4 == 0 && aligned(gt, 16) && aligned(pred, 16) && aligned(boundary, 4) && aligned(region, 4);
+  a.mn = min_depth, a.mx = max_depth;
+  a.y0 = y0, a.y1 = y1, a.x0 = x0, a.x1 = x1;
+  const int nblk = row_blocks(h), sets = region ? kMaxSets : 1;
+  double* part = (double*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  if (region)
+    hipLaunchKernelGGL(depth_metrics_kernel<kMaxSets>, dim3(nblk, n), dim3(256), 0, s, a, part);
+  else
+    hipLaunchKernelGGL(depth_metrics_kernel<1>, dim3(nblk, n), dim3(256), 0, s, a, part);
+  hipLaunchKernelGGL(metrics_final_kernel, dim3(n), dim3(64), 0, s, part, sums, nblk, sets * kTerms);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}

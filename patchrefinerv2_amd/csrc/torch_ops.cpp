@@ -1113,6 +1113,43 @@ std::tuple<Tensor, Tensor> deflate_rows(const Tensor& rows, int64_t len) {
   return {out, out_bytes};
 }
 
+// ground-truth evaluation (include/prv2.h "Ground-truth evaluation"): raw image / disparity decode and the fused scoring sums
+Tensor u8_image(const Tensor& src, bool swap_rb) {
+  TORCH_CHECK(src.is_cuda(), "prv2: src must be a GPU tensor (there is no CPU path)");
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 3 && src.size(2) == 3 && src.is_contiguous(),
+              "prv2::u8_image: src must be a contiguous uint8 [h, w, 3] tensor");
+  Tensor dst = at::empty({3, src.size(0), src.size(1)}, src.options().dtype(at::kFloat));
+  Launch L(src);
+  ok(prv2_u8_image((const uint8_t*)src.data_ptr(), (int)src.size(0), (int)src.size(1), swap_rb ? 1 : 0, dst.data_ptr<float>(), L.stream), "u8_image");
+  return dst;
+}
+std::tuple<Tensor, Tensor> disp_gt(const Tensor& disp, double factor, double th) {
+  dev_f32(disp, "disp");
+  TORCH_CHECK(disp.dim() == 2 && disp.is_contiguous(), "prv2::disp_gt: disp must be a contiguous [h, w] tensor");
+  Tensor depth = at::empty_like(disp), boundary = at::empty(disp.sizes(), disp.options().dtype(at::kByte));
+  Launch L(disp);
+  ok(prv2_disp_gt(disp.data_ptr<float>(), (int)disp.size(0), (int)disp.size(1), (float)factor, (float)th, depth.data_ptr<float>(),
+                  (uint8_t*)boundary.data_ptr(), L.stream), "disp_gt");
+  return {depth, boundary};
+}
+Tensor depth_metrics(const Tensor& gt, const Tensor& pred, const optional<Tensor>& boundary, const optional<Tensor>& region, double min_depth,
+                     double max_depth, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
+  dev_frames(gt, "gt", at::kFloat);
+  dev_frames(pred, "pred", at::kFloat);
+  same_frames(gt, pred, "pred");
+  const uint8_t* b = opt_mask(boundary, gt, "boundary");
+  const uint8_t* r = opt_mask(region, gt, "region");
+  const int64_t bytes = prv2_depth_metrics_workspace_bytes((int)gt.size(0), (int)gt.size(1), (int)gt.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::depth_metrics: bad frame shape ", gt.sizes());
+  Tensor ws = at::empty({bytes}, gt.options().dtype(at::kByte));
+  Tensor sums = at::empty({gt.size(0), r ? 3 : 1, 12}, gt.options().dtype(at::kDouble));
+  Launch L(gt);
+  ok(prv2_depth_metrics(gt.data_ptr<float>(), pred.data_ptr<float>(), b, r, (int)gt.size(0), (int)gt.size(1), (int)gt.size(2), (float)min_depth,
+                        (float)max_depth, (int)y0, (int)y1, (int)x0, (int)x1, sums.data_ptr<double>(), ws.data_ptr(), ws.numel(), L.stream),
+     "depth_metrics");
+  return sums;
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1251,6 +1288,11 @@ TORCH_LIBRARY(prv2, m) {
   m.def("mask_rows(Tensor mask) -> Tensor");
   m.def("upsample_bilinear_map(Tensor x, int oh, int ow) -> Tensor");
   m.def("deflate_rows(Tensor rows, int len) -> (Tensor, Tensor)");
+  // ground-truth evaluation: the U4K files' decode and the sums of compute_metrics of B frames [n, h, w] (S = 3 sets with a region)
+  m.def("u8_image(Tensor src, bool swap_rb) -> Tensor");
+  m.def("disp_gt(Tensor disp, float factor, float th) -> (Tensor, Tensor)");
+  m.def("depth_metrics(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, int x0, "
+        "int x1) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1329,4 +1371,7 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("mask_rows", &mask_rows);
   m.impl("deflate_rows", &deflate_rows);
   m.impl("upsample_bilinear_map", &upsample_bilinear_map);
+  m.impl("u8_image", &u8_image);
+  m.impl("disp_gt", &disp_gt);
+  m.impl("depth_metrics", &depth_metrics);
 }

@@ -158,6 +158,11 @@ SIGNATURES = {
     "prv2_deflate_bound": (_L, [_L]),
     "prv2_deflate_workspace_bytes": (_L, [_I, _L]),
     "prv2_deflate_rows": (_I, [_P, _I, _L, _L, _P, _L, _P, _P, _L, _P]),
+    # ground-truth evaluation (csrc/evalgt.hip): raw image / disparity decode, the sums of compute_metrics of B frames
+    "prv2_u8_image": (_I, [_P, _I, _I, _I, _P, _P]),
+    "prv2_disp_gt": (_I, [_P, _I, _I, _F, _F, _P, _P, _P]),
+    "prv2_depth_metrics_workspace_bytes": (_L, [_I, _I, _I]),
+    "prv2_depth_metrics": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
 }
 
 _lib = None

@@ -5,6 +5,7 @@ soft_edge_error     estimator/utils/metric.py:53-72   (min |gt shifted - pred| o
 get_boundaries      estimator/utils/metric.py:74-85   (disparity jumps > th; dilation needs cv2 -> dilation=0 only)
 compute_metrics     estimator/utils/metric.py:87-149  (resize, clamp, valid / crop masks, optional SEE on gt edges)
 colorize            estimator/utils/color.py:95-158   (percentile normalisation + matplotlib colour map, RGBA uint8)
+compute_metrics_fused  the same metrics from one fused GPU pass (csrc/evalgt.hip), optionally for three pixel sets at once
 
 Pinned by tests/golden/output_stage.npz (the reference functions imported by oracle/make_golden.py).
 """
@@ -144,6 +145,75 @@ def compute_metrics_device(gt: torch.Tensor, pred: torch.Tensor, interpolate=Tru
     keys = list(out)
     vals = torch.stack([out[k].double() for k in keys]).cpu().tolist()  # one D2H of ten scalars
     return dict(zip(keys, vals))
+
+
+def _eval_crop(h, w, garg_crop, eigen_crop, dataset):
+    """the rows / columns compute_metrics keeps (metric.py:108-120) as (y0, y1, x0, x1), clipped to the frame like numpy's slices"""
+    if not (garg_crop or eigen_crop):
+        return 0, h, 0, w
+    if garg_crop:
+        y0, y1, x0, x1 = int(0.40810811 * h), int(0.99189189 * h), int(0.03594771 * w), int(0.96405229 * w)
+    elif dataset == "kitti":
+        y0, y1, x0, x1 = int(0.3324324 * h), int(0.91351351 * h), int(0.0359477 * w), int(0.96405229 * w)
+    else:
+        y0, y1, x0, x1 = 45, 471, 41, 601
+    y0, y1, x0, x1 = min(y0, h), min(y1, h), min(x0, w), min(x1, w)
+    return y0, max(y0, y1), x0, max(x0, x1)
+
+
+def metrics_from_sums(s, with_see: bool) -> dict:
+    """one pixel set's twelve sums (ops.depth_metrics) -> the dict of compute_errors (+ ``see``): means over the valid count, NaN when
+    it is zero (numpy's mean of an empty array); silog from the sums of err^2 and err; see 0 without a valid boundary pixel"""
+    n, c1, c2, c3, abs_rel, d2, l10, e2, e1, sq_rel, n_see, see = (float(v) for v in s)
+    nan = float("nan")
+
+    def mean(v):
+        return v / n if n else nan
+    var = mean(e2) - mean(e1) ** 2 if n else nan
+    out = dict(a1=mean(c1), a2=mean(c2), a3=mean(c3), abs_rel=mean(abs_rel), rmse=float(np.sqrt(mean(d2))), log_10=mean(l10),
+               rmse_log=float(np.sqrt(mean(e2))), silog=float(np.sqrt(var)) * 100 if not var < 0 else nan, sq_rel=mean(sq_rel))
+    if with_see:
+        out["see"] = see / n_see if n_see else 0.0
+    return out
+
+
+@torch.no_grad()
+def compute_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu",
+                          min_depth_eval=0.1, max_depth_eval=10, disp_gt_edges=None, additional_mask=None, region=None):
+    """``compute_metrics`` (estimator/utils/metric.py:87-149) from one fused pass on the GPU (csrc/evalgt.hip, ops.depth_metrics): the
+    same clamping, masks, crops, error formulas and soft-edge error as ``compute_metrics_device``, as twelve float64 sums per frame
+    and ONE D2H of them per call.  ``region`` (a mask) adds ``edge_*`` (inside it) and ``noedge_*`` (outside it) copies of every key
+    from the same read -- the three scoring calls of tester.ImageDataset._edge_metrics in one.  ``additional_mask`` scores inside
+    that mask only, as in compute_metrics.  A dict for one map ([H, W] / [1, 1, H, W]), a list of dicts for B maps.  Inputs that
+    are on the host are copied to the GPU: there is no CPU path."""
+    from . import ops
+    if additional_mask is not None and region is not None:
+        raise ValueError("compute_metrics_fused: give additional_mask or region, not both")
+    dev = pred.device if pred.is_cuda else (gt.device if gt.is_cuda else torch.device("cuda"))
+    gt, pred = gt.to(dev), pred.to(dev)
+    if gt.shape[-2:] != pred.shape[-2:] and interpolate:
+        p4 = pred if pred.dim() == 4 else pred.reshape(-1, 1, *pred.shape[-2:])
+        pred = F.interpolate(p4.float(), gt.shape[-2:], mode="bilinear", align_corners=False)
+    g, single = _frames_of(gt.float())
+    p = pred.float().reshape(g.shape)
+
+    def mask(m):
+        return None if m is None else torch.as_tensor(m).to(dev).reshape(g.shape)
+    inside = region if region is not None else additional_mask
+    crop = _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
+    sums = ops.depth_metrics(g, p, mask(disp_gt_edges), mask(inside), min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
+    see = disp_gt_edges is not None
+    rows = []
+    for f in range(g.shape[0]):
+        if additional_mask is not None:
+            out = metrics_from_sums(sums[f, 1], see)
+        else:
+            out = metrics_from_sums(sums[f, 0], see)
+            if region is not None:
+                for name, k in (("edge", 1), ("noedge", 2)):
+                    out.update({f"{name}_{key}": v for key, v in metrics_from_sums(sums[f, k], see).items()})
+        rows.append(out)
+    return rows[0] if single else rows
 
 
 def evaluate(per_frame: list) -> dict:

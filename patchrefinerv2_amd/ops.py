@@ -1804,3 +1804,67 @@ def deflate_rows(rows, length):
     L.check(lib.prv2_deflate_rows(rows.data_ptr(), rows.shape[0], length, rows.shape[1], out.data_ptr(), bound, out_bytes.data_ptr(),
                                   ws.data_ptr(), wsb, _stream()), "deflate_rows")
     return out, out_bytes
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Ground-truth evaluation (csrc/evalgt.hip): the device half of UnrealStereo4kDataset and the sums behind compute_metrics, both
+# dispatch routes.
+# ------------------------------------------------------------------------------------------------------------------
+def u8_image(src, swap_rb=True):
+    """uint8 [H, W, 3] on the device -> fp32 [3, H, W] = float(src) / 255 (correctly rounded), channels reversed with ``swap_rb``
+    (u4k_dataset.py:125-147: bit-equal to ``image.astype(np.float32)[:, :, ::-1].copy() / 255.0`` + to_tensor)"""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3:
+        raise ValueError("u8_image: src is a GPU uint8 [H, W, 3] tensor")
+    src = src.contiguous()
+    if DISPATCH == "torch":
+        return _tops().u8_image(src, bool(swap_rb))
+    dst = torch.empty((3, src.shape[0], src.shape[1]), dtype=torch.float32, device=src.device)
+    L.check(L.load().prv2_u8_image(src.data_ptr(), src.shape[0], src.shape[1], int(bool(swap_rb)), dst.data_ptr(), _stream()), "u8_image")
+    return dst
+
+
+def disp_gt(disp, factor, th=1.0):
+    """fp32 disparity [H, W] -> (depth = factor / disp fp32 [H, W], boundary uint8 [H, W] = metrics.get_boundaries(disp, th, 0)) in
+    one pass (u4k_dataset.py:128-129,216)"""
+    if not isinstance(disp, torch.Tensor) or not disp.is_cuda or disp.dtype != torch.float32 or disp.dim() != 2:
+        raise ValueError("disp_gt: disp is a GPU fp32 [H, W] tensor")
+    disp = disp.contiguous()
+    if DISPATCH == "torch":
+        return _tops().disp_gt(disp, float(factor), float(th))
+    depth, boundary = torch.empty_like(disp), torch.empty(disp.shape, dtype=torch.uint8, device=disp.device)
+    L.check(L.load().prv2_disp_gt(disp.data_ptr(), *disp.shape, float(factor), float(th), depth.data_ptr(), boundary.data_ptr(), _stream()),
+            "disp_gt")
+    return depth, boundary
+
+
+def _mask_u8(t, like, name):
+    if t is None:
+        return None
+    t = _edge_frames(t)
+    if t.dtype not in (torch.bool, torch.uint8):
+        t = t != 0
+    if t.shape != like.shape:
+        raise ValueError(f"depth_metrics: {name} has shape {tuple(t.shape)}, the frames {tuple(like.shape)}")
+    return t
+
+
+def depth_metrics(gt, pred, boundary=None, region=None, min_depth=1e-3, max_depth=80.0, crop=None):
+    """the sums of compute_metrics (metric.py:11-149) of fp32 frames [B, H, W] -> float64 [B, S, 12] on the device, S = 3 (all /
+    inside / outside) with a ``region`` map, else 1; ``crop`` = (y0, y1, x0, x1), None: the whole frame.  The twelve sums: include/prv2.h
+    prv2_depth_metrics.  Bit-identical from call to call."""
+    g, p = _edge_frames(gt, torch.float32), _edge_frames(pred, torch.float32)
+    if g.shape != p.shape:
+        raise ValueError(f"depth_metrics: gt {tuple(g.shape)} and pred {tuple(p.shape)} differ in shape")
+    b, r = _mask_u8(boundary, g, "boundary"), _mask_u8(region, g, "region")
+    y0, y1, x0, x1 = (0, g.shape[1], 0, g.shape[2]) if crop is None else (int(v) for v in crop)
+    if DISPATCH == "torch":
+        return _tops().depth_metrics(g, p, b, r, float(min_depth), float(max_depth), y0, y1, x0, x1)
+    lib = L.load()
+    wsb = lib.prv2_depth_metrics_workspace_bytes(*g.shape)
+    if wsb < 0:
+        raise ValueError(f"depth_metrics: bad frame shape {tuple(g.shape)}")
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+    out = torch.empty((g.shape[0], 3 if r is not None else 1, 12), dtype=torch.float64, device=g.device)
+    L.check(lib.prv2_depth_metrics(g.data_ptr(), p.data_ptr(), _ptr(b), _ptr(r), *g.shape, float(min_depth), float(max_depth), y0, y1, x0, x1,
+                                   out.data_ptr(), ws.data_ptr(), wsb, _stream()), "depth_metrics")
+    return out

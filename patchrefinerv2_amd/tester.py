@@ -3,6 +3,7 @@
 Tester.run          estimator/tester/tester.py:52-127 (frame loop, model call contract, uint16 PNG x256)
 Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, uncertainty and tile-count PNGs)
 ImageDataset        estimator/datasets/general_dataset.py:161-234 (folder of images -> image_hr / image_lr)
+UnrealStereo4kDataset  estimator/datasets/u4k_dataset.py:20-233 (split file -> image_hr / depth_gt / boundary, decoded on the GPU)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 ``runner_info.device_output`` (tools/test.py --device-output) routes the saved files through output.OutputStage: scanlines made on
 the GPU, deflate on a writer pool; the default is the host route below.  ``runner_info.device_deflate`` (--device-deflate, needs
@@ -165,6 +166,144 @@ class ImageDataset:
         for name, mask in (("edge", region), ("noedge", ~region)):
             out.update({f"{name}_{k}": v for k, v in score(depth_gt, result, additional_mask=mask, **common).items()})
         return out
+
+
+@DATASETS.register_module()
+class UnrealStereo4kDataset:
+    """estimator/datasets/u4k_dataset.py:20-233, inference mode: the frames of a split file with their ground truth, decoded on the
+    GPU.  Per item the host only reads the two files (``<image>.raw``: BGR bytes; ``Disp0/*.npy``: disparity) into pinned staging
+    buffers and copies them to the device; ops.u8_image makes ``image_hr`` (RGB / 255, CHW, bit-equal to the reference's numpy
+    expression) and ops.disp_gt makes ``depth_gt`` = depth_factor / disparity and ``boundary`` = get_boundaries(disparity, th=1) in
+    one pass.  The files of the NEXT index are read one item ahead on a single background thread (files and host memory only: it
+    never touches the GPU).  ``get_metrics`` is metrics.compute_metrics_fused.  ``image_raw_shape`` replaces the reshape the
+    reference hard-codes to (2160, 3840).  Not built: ``mode='train'`` (augmentation, crops) and ``consistency=True``."""
+
+    dataset_name = "u4k"
+
+    def __init__(self, mode, data_root, split, transform_cfg, min_depth, max_depth, consistency=False, overlap=0, patch_raw_shape=(540, 960),
+                 resize_mode="zoe", pre_norm_bbox=True, image_raw_shape=(2160, 3840)):
+        if mode == "train":
+            raise NotImplementedError("UnrealStereo4kDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / "
+                                      "random_crop, u4k_dataset.py:131-213) is not built; inference modes only")
+        if consistency:
+            raise NotImplementedError("UnrealStereo4kDataset(consistency=True): the consistency crops (u4k_dataset.py:159-184) are not "
+                                      "built; Tester.run_consistency makes its crops itself")
+        if resize_mode not in ("zoe", "depth-anything"):
+            raise NotImplementedError(f"UnrealStereo4kDataset(resize_mode={resize_mode!r})")  # u4k_dataset.py:48-55
+        self.mode, self.data_root, self.split = mode, data_root, split
+        self.min_depth, self.max_depth = min_depth, max_depth
+        self.transform_cfg = transform_cfg
+        self.network_process_size = tuple(transform_cfg["network_process_size"])
+        self.resize_mode = resize_mode
+        self.image_raw_shape = (int(image_raw_shape[0]), int(image_raw_shape[1]))
+        self.data_infos = self.load_data_list()
+        self._pool = self._slots = None
+        self._pending = None   # (index, slot, future) of the read that is one ahead
+        self._last = None      # the index asked for last: the next one is guessed from the step between the two
+
+    def load_data_list(self):
+        """u4k_dataset.py:68-117: 'img_l img_r disp_l disp_r' per line; the image's suffix becomes ``raw``; focal length and baseline
+        from the Extrinsics0 / Extrinsics1 text files beside the disparity; sorted by image path"""
+        if self.split is None:
+            raise NotImplementedError("UnrealStereo4kDataset needs a split file (u4k_dataset.py:113-114)")
+        infos = []
+        with open(self.split) as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                img_l, _img_r, disp_l, _disp_r = line.strip().split(" ")
+                img_l = img_l[:-3] + "raw"
+                info = dict(depth_map_path=os.path.join(self.data_root, disp_l), img_path=os.path.join(self.data_root, img_l), filename=img_l)
+                ext = []
+                for cam in ("Extrinsics0", "Extrinsics1"):
+                    with open(info["depth_map_path"].replace("Disp0", cam).replace("npy", "txt")) as fe:
+                        ext.append(fe.readlines())
+                info["focal"] = float(ext[0][0].split(" ")[0])
+                info["depth_factor"] = abs(float(ext[0][1].split(" ")[3]) - float(ext[1][1].split(" ")[3])) * info["focal"]
+                info["img_file_basename"] = os.path.splitext(img_l)[0].replace("/", "_")[1:]  # u4k_dataset.py:155-156
+                infos.append(info)
+        return sorted(infos, key=lambda x: x["img_path"])
+
+    def __len__(self):
+        return len(self.data_infos)
+
+    def _read(self, idx, slot):
+        """the two files of frame ``idx`` into staging slot ``slot`` (runs on the background thread: host memory only)"""
+        img, disp, _ = self._slots[slot]
+        info = self.data_infos[idx]
+        view = img.numpy().reshape(-1)
+        with open(info["img_path"], "rb") as f:
+            n = f.readinto(memoryview(view))
+        if n != view.size or os.path.getsize(info["img_path"]) != view.size:
+            raise ValueError(f"{info['img_path']}: {os.path.getsize(info['img_path'])} bytes, expected {view.size} "
+                             f"({self.image_raw_shape[0]} x {self.image_raw_shape[1]} x 3)")
+        d = np.load(info["depth_map_path"], mmap_mode="r")
+        if d.shape != self.image_raw_shape:
+            raise ValueError(f"{info['depth_map_path']}: disparity {d.shape}, expected {self.image_raw_shape}")
+        np.copyto(disp.numpy(), d, casting="unsafe")  # == .astype(np.float32)
+
+    def _start(self):
+        from concurrent.futures import ThreadPoolExecutor
+        h, w = self.image_raw_shape
+        # two slots: the one being copied to the device and the one the reader fills; the event marks the copies out of a slot
+        self._slots = [[torch.empty((h, w, 3), dtype=torch.uint8).pin_memory(), torch.empty((h, w), dtype=torch.float32).pin_memory(), None]
+                       for _ in range(2)]
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="u4k-read")
+
+    def _wait_copies(self, slot):
+        """a slot is refilled only after the H2D copies out of it have finished"""
+        if self._slots[slot][2] is not None:
+            self._slots[slot][2].synchronize()
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = self._slots = self._pending = None
+
+    def __getitem__(self, idx):
+        from . import ops
+        idx = int(idx)
+        if not 0 <= idx < len(self):
+            raise IndexError(idx)
+        if self._pool is None:
+            self._start()
+        slot = 0
+        if self._pending is not None:
+            p_idx, p_slot, fut = self._pending
+            self._pending = None
+            fut.result()  # (a failed read raises here)
+            slot = p_slot
+            if p_idx != idx:  # a wrong guess: read into the other slot now
+                slot = 1 - p_slot
+                self._wait_copies(slot)
+                self._read(idx, slot)
+        else:
+            self._wait_copies(slot)
+            self._read(idx, slot)
+        img, disp, _ = self._slots[slot]
+        raw = img.cuda(non_blocking=True)
+        d = disp.cuda(non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._slots[slot][2] = ev
+        info = self.data_infos[idx]
+        depth, boundary = ops.disp_gt(d, info["depth_factor"], 1.0)
+        item = dict(image_hr=ops.u8_image(raw, swap_rb=True), depth_gt=depth[None, None], boundary=boundary,
+                    img_file_basename=info["img_file_basename"])
+        # one ahead: the index the same step further, into the other slot (once the copies out of it are done)
+        step = idx - self._last if self._last is not None and idx > self._last else 1
+        self._last = idx
+        if idx + step < len(self):
+            other = 1 - slot
+            self._wait_copies(other)
+            self._pending = (idx + step, other, self._pool.submit(self._read, idx + step, other))
+        return item
+
+    def get_metrics(self, depth_gt, result, disp_gt_edges=None, **kw):
+        """u4k_dataset.py:232-233 through the fused kernel (a host ``result`` is copied to the device first)"""
+        from .metrics import compute_metrics_fused
+        return compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth, max_depth_eval=self.max_depth,
+                                     garg_crop=False, eigen_crop=False, dataset="")
 
 
 def pseudo_label_uncertainty(uncertainty: np.ndarray, count_map: np.ndarray, n_tiles: int, count_thr: float):

@@ -38,7 +38,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # output stage (order statistics, PNG scanlines, bilinear resize of the coarse map)
        "order_stats", "colorize_rows", "quantize16_rows", "pl_uncertainty_rows", "mask_rows", "upsample_bilinear_map",
        # device deflate: zlib streams of scanline buffers
-       "deflate_rows")
+       "deflate_rows",
+       # ground-truth evaluation: raw image / disparity decode and the fused scoring sums
+       "u8_image", "disp_gt", "depth_metrics")
 _loaded = False
 
 

@@ -11,6 +11,8 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--device-output [--output-workers N]``: with ``--save``, the output files' pixels are produced on the GPU and written by a thread pool.
 ``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
+``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
+disparities decoded and scored on the GPU; prints a1 ... sq_rel and see); ``general`` is the folder of images.
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
 """
@@ -40,6 +42,31 @@ def parse_opts(opts):
     return out
 
 
+# --test-type -> the config section whose ``dataset`` is built (the reference's tools/test.py: normal / test_in / test_out / general)
+TEST_TYPES = dict(general="general_dataloader", normal="val_dataloader", test_in="test_in_dataloader", test_out="test_out_dataloader")
+
+
+def dataset_config(cfg, args):
+    """the dataset dict ``--test-type`` selects, with the CLI's overrides (exits with a message when it cannot be built)"""
+    if args.test_type not in TEST_TYPES:
+        raise SystemExit(f"--test-type {args.test_type}: one of {', '.join(TEST_TYPES)}")
+    section = TEST_TYPES[args.test_type]
+    if section not in cfg or "dataset" not in cfg[section]:
+        raise SystemExit(f"--test-type {args.test_type} needs {section}.dataset in the config; {args.config} has none")
+    ds_cfg = cfg[section].dataset.to_dict()
+    kind = ds_cfg.get("type")
+    if kind not in DATASETS:
+        raise SystemExit(f"--test-type {args.test_type}: dataset type {kind} is not built (built: ImageDataset, UnrealStereo4kDataset; the "
+                         "cityscapes, kitti, scannet and eth decoders are not)")
+    if kind == "UnrealStereo4kDataset":
+        ds_cfg["image_raw_shape"] = args.image_raw_shape
+    else:
+        ds_cfg["image_resolution"] = args.image_raw_shape
+        if args.edge_metrics:
+            ds_cfg["edge_metrics"] = True
+    return ds_cfg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
@@ -48,7 +75,8 @@ def main():
     ap.add_argument("--cfg-option", nargs="+", default=None)
     ap.add_argument("--save", action="store_true")
     ap.add_argument("--work-dir", default="./work_dir/predictions")
-    ap.add_argument("--test-type", default="general")
+    ap.add_argument("--test-type", default="general", help="general: general_dataloader (a folder of images); normal / test_in / test_out: "
+                    "val_dataloader / test_in_dataloader / test_out_dataloader (a dataset with ground truth, e.g. UnrealStereo4kDataset)")
     ap.add_argument("--gray-scale", action="store_true")
     ap.add_argument("--image-raw-shape", nargs=2, type=int, default=[2160, 3840])
     ap.add_argument("--patch-split-num", nargs=2, type=int, default=[4, 4])
@@ -88,11 +116,10 @@ def main():
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
-    if args.test_type != "general":
-        raise SystemExit("only --test-type general (folder of images, optional .npy ground truth via dataset gt_dir) is built")
 
     cfg = Config.fromfile(args.config)
     cfg.merge_from_dict(parse_opts(args.cfg_option))
+    ds_cfg = dataset_config(cfg, args)
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
     if world > 1:  # estimator/utils/dist.py:31-33 (init_dist(launcher, backend='nccl')); nccl == RCCL on ROCm
@@ -117,10 +144,6 @@ def main():
     else:
         raise SystemExit("give --ckp-path or --synthetic-weights")
 
-    ds_cfg = cfg.general_dataloader.dataset.to_dict()
-    ds_cfg["image_resolution"] = args.image_raw_shape
-    if args.edge_metrics:
-        ds_cfg["edge_metrics"] = True
     dataset = DATASETS.build(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
                         device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate)
@@ -154,7 +177,9 @@ def main():
     if rank == 0 or world == 1:  # (frame-sharded runs: rank 0 holds every rank's results, collected like collect_results_gpu)
         for r in results:
             print(f"[rank {rank}] {r['name']}: depth {r['shape']} mean {r['mean']:.4f}")
-        if getattr(tester, "last_eval", None):  # frames that came with ground truth (dataset gt_dir)
+            if args.test_type != "general" and "metrics" in r:  # a dataset evaluation: the frame's own row
+                print(f"[rank {rank}] {r['name']}: " + ", ".join(f"{k} {float(v):.6f}" for k, v in r["metrics"].items()))
+        if getattr(tester, "last_eval", None):  # frames that came with ground truth (dataset gt_dir, or a dataset with its own)
             print(f"[rank {rank}] " + ", ".join(f"{k} {v:.4f}" for k, v in tester.last_eval.items()))
     if world > 1:
         import torch.distributed as dist
