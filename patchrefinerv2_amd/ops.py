@@ -1,7 +1,12 @@
-"""Host-side wrappers over the C ABI: torch supplies device memory and the stream, nothing else.
+"""Host-side wrappers over the kernels: torch supplies device memory and the stream, nothing else.
 
 ``Feat`` is an NHWC activation view (optionally a channel slice of a wider buffer) -- the
 mechanism that makes every ``torch.cat`` of the reference free: producers write into slices.
+
+Every wrapper has one shape: validate, allocate, then ONE callable whose two arms are the two routes to the same kernel
+(``DISPATCH``: ``_tops().X(...)`` / ``_c("X", ...)``), handed to at most ONE ``PROFILER.launch`` / ``launch_aux`` with the tag, the
+FLOP or byte count and the shape string computed once.  Single-frame and B-frame forms of an op share that body and differ in the
+entry point's name and a leading frame count.  ``_conv_desc`` / ``_ups_src`` build the two descriptors of the C ABI.
 """
 from __future__ import annotations
 
@@ -10,6 +15,7 @@ import math
 import numpy as np
 import os
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import torch
@@ -18,14 +24,11 @@ from . import lib as L
 from .lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, ACT_SOFTPLUS, PREC_F32  # noqa: F401
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 # How the host mirror reaches the kernels: "torch" = through the PyTorch-ROCm custom ops torch.ops.prv2.* (csrc/torch_ops.cpp ->
-# libprv2_torch.so: at::Tensor in / out on torch's current stream), "ctypes" = straight through the C ABI (lib.py).  Every entry
-# point a frame uses exists on both routes; same kernels, same results bit for bit (tests/test_hip_models.py::
-# test_models_through_torch_custom_ops).  PRV2_DISPATCH selects the default (INTEGRATION.md has the measured per-frame difference).
+# libprv2_torch.so: at::Tensor in / out on torch's current stream; ``_tops()``), "ctypes" = straight through the C ABI (lib.py;
+# ``_c``).  Every entry point a frame uses exists on both routes; same kernels, same results bit for bit (tests/test_hip_models.py::
+# test_models_through_torch_custom_ops) and the same profiler records (tests/test_ops_routes_gpu.py).  The wrappers read DISPATCH when
+# they are called.  PRV2_DISPATCH selects the default (INTEGRATION.md has the measured per-frame difference).
 DISPATCH = os.environ.get("PRV2_DISPATCH", "torch")
 assert DISPATCH in ("ctypes", "torch"), DISPATCH
 
@@ -33,6 +36,23 @@ assert DISPATCH in ("ctypes", "torch"), DISPATCH
 def _tops():
     from . import torch_ops
     return torch_ops.load()
+
+
+_CFN: dict = {}  # entry point -> its bound ctypes function (resolved on first use)
+
+
+def _c(name: str, *args, what: Optional[str] = None):
+    """the ctypes route: prv2_<name>(*args, current stream), a non-zero status raised as ``<what> failed`` (``what``: the name to report
+    when it is not the entry point's)"""
+    fn = _CFN.get(name)
+    if fn is None:
+        fn = _CFN[name] = getattr(L.load(), "prv2_" + name)
+    L.check(fn(*args, torch.cuda.current_stream().cuda_stream), what or name)
+
+
+def _last_kernel() -> str:
+    """a profiler tag evaluated after the launch: the kernel the library dispatched the last call to"""
+    return L.load().prv2_last_kernel().decode()
 
 
 class Profiler:
@@ -102,6 +122,10 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _ld(f) -> int:
+    return 0 if f is None else f.ld
+
+
 def _require_dev(*ts):
     for t in ts:
         if t is not None and (not t.is_cuda or t.dtype != torch.float32):
@@ -157,7 +181,7 @@ class Feat:
             if DISPATCH == "torch":
                 _tops().zero_pad_channels_(buf, c)
             else:
-                L.check(L.load().prv2_zero_pad_channels(buf.data_ptr(), n * h * w, c, ld, _stream()), "zero_pad_channels")
+                _c("zero_pad_channels", buf.data_ptr(), n * h * w, c, ld)
         return Feat(buf, c)
 
     @property
@@ -205,8 +229,7 @@ class Feat:
         if DISPATCH == "torch":
             return _tops().nhwc_to_nchw(self.view())
         out = torch.empty((self.n, self.c, self.h, self.w), device=self.device, dtype=torch.float32)
-        L.check(L.load().prv2_nhwc_to_nchw(self.ptr, self.n, self.c, self.h, self.w, self.ld, out.data_ptr(),
-                                           _stream()), "nhwc_to_nchw")
+        _c("nhwc_to_nchw", self.ptr, self.n, self.c, self.h, self.w, self.ld, out.data_ptr())
         return out
 
     @staticmethod
@@ -218,7 +241,7 @@ class Feat:
             y = _tops().nchw_to_nhwc(x)
             return _feat_of(y, c)
         f = Feat.alloc(n, h, w, c, x.device, pad_to)
-        L.check(L.load().prv2_nchw_to_nhwc(x.data_ptr(), n, c, h, w, f.ptr, f.ld, _stream()), "nchw_to_nhwc")
+        _c("nchw_to_nhwc", x.data_ptr(), n, c, h, w, f.ptr, f.ld)
         return f
 
 
@@ -259,8 +282,7 @@ def pack_conv(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, stride:
     else:
         nbytes = lib.prv2_packed_weight_bytes(cout, cin, kh, kw, convt_k, prec)
         packed = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
-        L.check(lib.prv2_pack_conv_weight(w.data_ptr(), _ptr(sc), packed.data_ptr(), cout, cin, kh, kw, convt_k, prec,
-                                          _stream()), "pack_conv_weight")
+        _c("pack_conv_weight", w.data_ptr(), _ptr(sc), packed.data_ptr(), cout, cin, kh, kw, convt_k, prec)
     b = bias.detach().to(device=device, dtype=torch.float32).contiguous() if bias is not None else None
     return ConvW(packed, b, cout, cin, kh, kw, convt_k if convt_k else stride, pad, convt_k, prec, same_pad)
 
@@ -275,6 +297,11 @@ class ConvWF6:
     w_scale: float          # the weights were multiplied by this before the fp16 / fp6 split (max |w w_scale| in [1, 2))
     x_scale: float = 1.0    # what the loader multiplies the activations with (calibration: ``range``)
     range: Optional[torch.Tensor] = None  # device uint32[1]: float bits of the largest |relu(x) x_scale| any launch saw
+    kh = kw = 3  # (not fields: the one layer shape the kernels take, named as ``ConvW`` names it for ``_conv_desc``)
+    stride = pad = 1
+    convt_k = 0
+    prec = L.PREC_F16F6
+    same_pad = False
 
 
 F16F6 = os.environ.get("PRV2_F16F6", "0") == "1"  # the fp16 + fp6 arithmetic for the layers that have a kernel for it (default: bf16x3)
@@ -373,7 +400,7 @@ def pack_conv3x3_f6(weight: torch.Tensor, bias: Optional[torch.Tensor] = None, d
     if DISPATCH == "torch":
         _tops().pack_conv3x3_f6_weight(w, w_scale, packed)
     else:
-        L.check(lib.prv2_pack_conv3x3_f6_weight(w.data_ptr(), w_scale, packed.data_ptr(), cout, cin, _stream()), "pack_conv3x3_f6_weight")
+        _c("pack_conv3x3_f6_weight", w.data_ptr(), w_scale, packed.data_ptr(), cout, cin)
     b = bias.detach().to(device=device, dtype=torch.float32).contiguous() if bias is not None else None
     cw = ConvWF6(packed, b, cout, cin, w_scale, 1.0, None)
     cw.range = F6Range.slot(device, cw)
@@ -384,9 +411,7 @@ def conv3x3_f6_supported(x: Feat, cout: int, cin: int, allow_x2: bool = False) -
     """shape contract of the fp16 + fp6 kernels (a property of the layer, never of the batch); ``allow_x2``: the gate-tail kernel also takes pre-split input"""
     if (getattr(x, "x2", False) and not allow_x2) or x.c != cin or x.ld % 4:
         return False
-    d = L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cin, cout=cout, kh=3, kw=3, stride=1, pad=1, ldx=x.ld, ldy=roundup(cout, 4), x_bstride=0, y_bstride=0,
-                   relu_in=0, act=ACT_NONE, convt_k=0, ld_mul=0, ld_res=0, ld_res2=0, prec=L.PREC_F16F6, force_generic=0, ln_eps=1e-6, part=0,
-                   same_pad=0, fmt=0)
+    d = _conv_desc(x, ConvWF6(None, None, cout, cin, 1.0), roundup(cout, 4))
     return bool(L.load().prv2_conv3x3_f6_supported(C.byref(d)))
 
 
@@ -397,20 +422,16 @@ def conv3x3_f6(x: Feat, cw: ConvWF6, out: Optional[Feat] = None, *, relu_in: boo
         out = Feat.alloc(x.n, x.h, x.w, cw.cout, x.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, cw.cout)
     assert res is None or ((res.n, res.h, res.w, res.c) == (out.n, out.h, out.w, out.c) and not res.x2)
-    d = L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=3, kw=3, stride=1, pad=1, ldx=x.ld, ldy=out.ld, x_bstride=0, y_bstride=0,
-                   relu_in=int(relu_in), act=ACT_NONE, convt_k=0, ld_mul=0, ld_res=res.ld if res is not None else 0, ld_res2=0, prec=L.PREC_F16F6,
-                   force_generic=0, ln_eps=1e-6, part=0, same_pad=0, fmt=L.FMT_Y_X2 if out.x2 else 0)
+    d = _conv_desc(x, cw, out.ld, relu_in=relu_in, ld_res=_ld(res), fmt=L.FMT_Y_X2 if out.x2 else 0)
     out_scale = 1.0 / (cw.x_scale * cw.w_scale)
 
     def call():
         if DISPATCH == "torch":
             _tops().conv3x3_f6(x.view(), cw.w, cw.bias, res.view() if res is not None else None, relu_in, cw.x_scale, out_scale, cw.range, out.raw(), d.fmt)
-            return
-        L.check(L.load().prv2_conv3x3_f6(C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(res), cw.x_scale, out_scale, _ptr(cw.range), out.ptr, _stream()),
-                "conv3x3_f6")
+        else:
+            _c("conv3x3_f6", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(res), cw.x_scale, out_scale, _ptr(cw.range), out.ptr)
 
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), 2.0 * x.n * x.h * x.w * cw.cout * cw.cin * 9, call,
-                    shape=f"{cw.cin}->{cw.cout} k3s1 {x.n}x{x.h}x{x.w}")
+    PROFILER.launch(_last_kernel, 2.0 * x.n * x.h * x.w * cw.cout * cw.cin * 9, call, shape=f"{cw.cin}->{cw.cout} k3s1 {x.n}x{x.h}x{x.w}")
     return out
 
 
@@ -422,11 +443,29 @@ def conv_out_hw(cw: ConvW, h: int, w: int):
     return (h + 2 * cw.pad - cw.kh) // cw.stride + 1, (w + 2 * cw.pad - cw.kw) // cw.stride + 1
 
 
+def _conv_desc(x, cw, ldy: int, *, act: int = ACT_NONE, relu_in: bool = False, ld_mul: int = 0, ld_res: int = 0, ld_res2: int = 0,
+               ln_eps: float = 1e-6, x_bstride: int = 0, force_generic: bool = False, fmt: int = 0) -> "L.ConvDesc":
+    """the prv2_conv_desc of the layer ``cw`` (ConvW / ConvWF6) on the input ``x`` (anything with n, h, w, ld) writing rows of pitch ``ldy``"""
+    return L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad, ldx=x.ld, ldy=ldy,
+                      x_bstride=x_bstride, y_bstride=0, relu_in=int(relu_in), act=act, convt_k=cw.convt_k, ld_mul=ld_mul, ld_res=ld_res,
+                      ld_res2=ld_res2, prec=cw.prec, force_generic=int(force_generic), ln_eps=ln_eps, part=0, same_pad=int(cw.same_pad), fmt=fmt)
+
+
+def _ups_src(u) -> "L.UpsSrc":
+    """the prv2_ups_src of a low-resolution map that a kernel interpolates itself"""
+    return L.UpsSrc(x=u.ptr, h=u.h, w=u.w, ld=u.ld, channels=u.c, bstride=0)
+
+
+def _gate_fmt(x, mul=None) -> int:
+    """prv2_conv_desc.fmt of the 256-column conv kernels: which of x / mul are pre-split (X2) buffers"""
+    return (L.FMT_X_X2 if getattr(x, "x2", False) else 0) | (L.FMT_MUL_X2 if mul is not None and mul.x2 else 0)
+
+
 def _c256(x: Feat, cw: ConvW) -> bool:
     """does the library run this conv on its 256-channel 3x3 kernel (which fuses the LayerNorm at that width)?"""
     if x.c != cw.cin or x.ld % 4 or cw.cout != 256 or os.environ.get("PRV2_NO_C256"):
         return False
-    return bool(L.load().prv2_conv3x3_ln_gate_supported(C.byref(_gate_desc(x, cw, roundup(cw.cout, 4), False, ACT_NONE, None, None, 1e-6))))
+    return bool(L.load().prv2_conv3x3_ln_gate_supported(C.byref(_conv_desc(x, cw, roundup(cw.cout, 4), fmt=_gate_fmt(x)))))
 
 
 def conv2d(x: Feat, cw: ConvW, out: Optional[Feat] = None, *, relu_in: bool = False, act: int = ACT_NONE,
@@ -446,11 +485,8 @@ def conv2d(x: Feat, cw: ConvW, out: Optional[Feat] = None, *, relu_in: bool = Fa
     if out is None:
         out = Feat.alloc(x.n, oh, ow, cw.cout, x.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, oh, ow, cw.cout), ((out.n, out.h, out.w, out.c), (x.n, oh, ow, cw.cout))
-    d = L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad,
-                   ldx=x.ld, ldy=out.ld, x_bstride=x_bstride, y_bstride=0, relu_in=int(relu_in), act=act,
-                   convt_k=cw.convt_k, ld_mul=mul.ld if mul is not None else 0, ld_res=res.ld if res is not None else 0,
-                   ld_res2=res2.ld if res2 is not None else 0, prec=cw.prec, force_generic=int(force_generic),
-                   ln_eps=ln_eps, part=0, same_pad=int(cw.same_pad), fmt=0)
+    d = _conv_desc(x, cw, out.ld, act=act, relu_in=relu_in, ld_mul=_ld(mul), ld_res=_ld(res), ld_res2=_ld(res2), ln_eps=ln_eps,
+                   x_bstride=x_bstride, force_generic=force_generic)
     for aux in (mul, res, res2):
         if aux is not None:
             assert (aux.n, aux.h, aux.w, aux.c) == (out.n, out.h, out.w, out.c) and not aux.x2
@@ -463,44 +499,32 @@ def conv2d(x: Feat, cw: ConvW, out: Optional[Feat] = None, *, relu_in: bool = Fa
     m_rows = x.n * (x.h * x.w if cw.convt_k else oh * ow)
     halo = (cw.kh == 3 and cw.kw == 3 and cw.stride == 1 and (cw.pad == 1 or cw.same_pad) and not cw.convt_k and x.w >= 24 and x.h >= 4
             and not force_generic)  # only for the f32-mode strip split below; kernel names come from prv2_last_kernel()
-    via_torch = DISPATCH == "torch"
+    lnw, lnb = (ln[0], ln[1]) if ln is not None else (None, None)
 
     def call():
-        if via_torch:
+        if DISPATCH == "torch":
             v = lambda f: None if f is None else f.view()  # noqa: E731
-            _tops().conv2d(x.view(), cw.w, cw.bias, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, act, relu_in,
-                           ln[0] if ln is not None else None, ln[1] if ln is not None else None, gamma, v(mul), v(res), v(res2),
+            _tops().conv2d(x.view(), cw.w, cw.bias, cw.cout, cw.kh, cw.kw, cw.stride, cw.pad, act, relu_in, lnw, lnb, gamma, v(mul), v(res), v(res2),
                            cw.convt_k, cw.prec, ln_eps, cw.same_pad, out.raw(), d.fmt, force_generic, d.part)
-            return
-        L.check(L.load().prv2_conv2d(C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(ln[0]) if ln is not None else None,
-                                     _ptr(ln[1]) if ln is not None else None, _ptr(gamma), _ptr(mul), _ptr(res), _ptr(res2),
-                                     out.ptr, _stream()), "conv2d")
+        else:
+            _c("conv2d", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(lnw), _ptr(lnb), _ptr(gamma), _ptr(mul), _ptr(res), _ptr(res2), out.ptr)
 
     shape = f"{cw.cin}->{cw.cout} k{cw.kh}s{cw.stride}{'T' if cw.convt_k else ''} {x.n}x{x.h}x{x.w}"
-    tag = lambda: L.load().prv2_last_kernel().decode()  # noqa: E731  (the kernel the library dispatched this call to)
     rem = x.w % 32
     if halo and PROFILER.enabled and 0 < rem <= 8 and x.w >= 64 and cw.prec == PREC_F32:
         # f32 mode: the library runs this conv as 32-pixel tiles + a remainder strip on the generic kernel (csrc/igemm.hip;
         # the bf16 modes do both in one launch); when launches are timed the two kernels are issued and accounted separately
         full = 2.0 * m_rows * ncols * cw.cin * taps
         d.part = 1
-        PROFILER.launch(tag, full * (x.w - rem) / x.w, call, shape=shape)
+        PROFILER.launch(_last_kernel, full * (x.w - rem) / x.w, call, shape=shape)
         d.part = 2
-        PROFILER.launch(tag, full * rem / x.w, call, shape=shape + f" strip{rem}")
+        PROFILER.launch(_last_kernel, full * rem / x.w, call, shape=shape + f" strip{rem}")
         return out
-    PROFILER.launch(tag, 2.0 * m_rows * ncols * cw.cin * taps, call, shape=shape, algo=algo)
+    PROFILER.launch(_last_kernel, 2.0 * m_rows * ncols * cw.cin * taps, call, shape=shape, algo=algo)
     return out
 
 
 UPS_FUSION = os.environ.get("PRV2_UPS_FUSION", "1") != "0"  # A/B and test switch: bilinear upsample fused into the consumer conv's loader
-
-
-def _ups_desc(x: Feat, u: Feat, cw: ConvW, out_ld: int, act: int, res_ld: int, ln_eps: float):
-    d = L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad, ldx=x.ld, ldy=out_ld,
-                   x_bstride=0, y_bstride=0, relu_in=0, act=act, convt_k=cw.convt_k, ld_mul=0, ld_res=res_ld, ld_res2=0, prec=cw.prec,
-                   force_generic=0, ln_eps=ln_eps, part=0, same_pad=int(cw.same_pad), fmt=0)
-    us = L.UpsSrc(x=u.ptr, h=u.h, w=u.w, ld=u.ld, channels=u.c, bstride=0)
-    return d, us
 
 
 class UpsOnly:
@@ -515,8 +539,7 @@ def conv2d_ups_supported(x, u: Feat, cw: ConvW) -> bool:
     layer (channels, per-image size, arithmetic mode) -- never of the batch."""
     if not UPS_FUSION or type(x) not in (Feat, UpsOnly) or type(u) is not Feat or x.n != u.n or (x.h, x.w) == (u.h, u.w):
         return False
-    d, us = _ups_desc(x, u, cw, roundup(cw.cout, 4), ACT_NONE, 0, 1e-6)
-    return bool(L.load().prv2_conv2d_ups_supported(C.byref(d), C.byref(us)))
+    return bool(L.load().prv2_conv2d_ups_supported(C.byref(_conv_desc(x, cw, roundup(cw.cout, 4))), C.byref(_ups_src(u))))
 
 
 UPCONV = os.environ.get("PRV2_UPCONV", "1") != "0"  # A/B and test switch: 3x3 convs of an upsampled tensor computed at the low resolution
@@ -526,8 +549,7 @@ def upconv3x3_supported(u: Feat, h: int, w: int, cw: ConvW) -> bool:
     """can ``upconv3x3`` take conv3x3(bilinear_align_corners(u -> h x w); cw)?  A property of the layer (channels, per-image sizes, mode)."""
     if not UPCONV or type(u) is not Feat or (cw.kh, cw.kw, cw.stride, cw.pad, cw.convt_k) != (3, 3, 1, 1, 0) or cw.cin != u.c or cw.same_pad:
         return False
-    us = L.UpsSrc(x=u.ptr, h=u.h, w=u.w, ld=u.ld, channels=u.c, bstride=0)
-    return bool(L.load().prv2_upconv3x3_supported(C.byref(us), u.n, h, w, cw.cout, cw.prec))
+    return bool(L.load().prv2_upconv3x3_supported(C.byref(_ups_src(u)), u.n, h, w, cw.cout, cw.prec))
 
 
 def upconv3x3(u: Feat, h: int, w: int, cw: ConvW, out: Optional[Feat] = None, *, act: int = ACT_NONE, bias: bool = True, add: Optional[Feat] = None) -> Feat:
@@ -544,18 +566,15 @@ def upconv3x3(u: Feat, h: int, w: int, cw: ConvW, out: Optional[Feat] = None, *,
     def call():
         if DISPATCH == "torch":
             _tops().upconv3x3(u.view(), cw.w, b, cw.cout, h, w, act, cw.prec, out.view(), add.view() if add is not None else None)
-            return
-        us = L.UpsSrc(x=u.ptr, h=u.h, w=u.w, ld=u.ld, channels=u.c, bstride=0)
-        L.check(L.load().prv2_upconv3x3(C.byref(us), cw.w.data_ptr(), _ptr(b), _ptr(add), add.ld if add is not None else 0, u.n, h, w, cw.cout, act, cw.prec,
-                                        out.ptr, out.ld, 0, _stream()), "upconv3x3")
+        else:
+            _c("upconv3x3", C.byref(_ups_src(u)), cw.w.data_ptr(), _ptr(b), _ptr(add), _ld(add), u.n, h, w, cw.cout, act, cw.prec, out.ptr, out.ld, 0)
 
     # executed: the tap GEMMs over every tile's 192-pixel source footprint (16 x 28 output tiles, 32-channel passes); algo: the reference
     # graph's nine taps at the OUTPUT resolution
     wide = (u.h - 1) * 2 <= (h - 1) and (u.w - 1) * 2 <= (w - 1)  # (csrc/upconv.hip: 16 x 28 output tiles up to a source step of 1/2, else 14 x 24)
     tiles = -(-h // 16) * -(-w // 28) if wide else -(-h // 14) * -(-w // 24)
     shape = f"{cw.cin}->{cw.cout} k3s1 {u.n}x{h}x{w} (lowres {u.c}ch {u.h}x{u.w})"
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), 2.0 * u.n * tiles * 192 * 9 * cw.cin * roundup(cw.cout, 32), call, shape=shape,
-                    algo=2.0 * u.n * h * w * cw.cout * cw.cin * 9)
+    PROFILER.launch(_last_kernel, 2.0 * u.n * tiles * 192 * 9 * cw.cin * roundup(cw.cout, 32), call, shape=shape, algo=2.0 * u.n * h * w * cw.cout * cw.cin * 9)
     return out
 
 
@@ -605,8 +624,7 @@ def compose_upconv5x5(w1: torch.Tensor, b1: torch.Tensor, tap_bias: Optional[tor
 def upconv5x5_supported(u: Feat, h: int, w: int, cw5: dict) -> bool:
     if not UPCONV5 or type(u) is not Feat or cw5["w5"].cin != u.c:
         return False
-    us = L.UpsSrc(x=u.ptr, h=u.h, w=u.w, ld=u.ld, channels=u.c, bstride=0)
-    return bool(L.load().prv2_upconv5x5_supported(C.byref(us), u.n, h, w, cw5["cout"], cw5["w5"].prec))
+    return bool(L.load().prv2_upconv5x5_supported(C.byref(_ups_src(u)), u.n, h, w, cw5["cout"], cw5["w5"].prec))
 
 
 def upconv5x5(u: Feat, h: int, w: int, cw5: dict, out: Optional[Feat] = None, *, act: int = ACT_NONE) -> Feat:
@@ -617,30 +635,32 @@ def upconv5x5(u: Feat, h: int, w: int, cw5: dict, out: Optional[Feat] = None, *,
     if out is None:
         out = Feat.alloc(u.n, h, w, co, u.device)
     assert (out.n, out.h, out.w, out.c) == (u.n, h, w, co) and not out.x2
-    us = L.UpsSrc(x=u.ptr, h=u.h, w=u.w, ld=u.ld, channels=u.c, bstride=0)
+    us = _ups_src(u)
 
     def main():
         if DISPATCH == "torch":
             _tops().upconv5x5(u.view(), cw.w, cw5["bias_map"], co, h, w, act, cw.prec, out.view())
-            return
-        L.check(L.load().prv2_upconv5x5(C.byref(us), cw.w.data_ptr(), cw5["bias_map"].data_ptr(), u.n, h, w, co, act, cw.prec, out.ptr, out.ld, 0, _stream()), "upconv5x5")
+        else:
+            _c("upconv5x5", C.byref(us), cw.w.data_ptr(), cw5["bias_map"].data_ptr(), u.n, h, w, co, act, cw.prec, out.ptr, out.ld, 0)
 
     tiles = -(-h // 14) * -(-w // 24)  # (csrc/upconv5.hip: 14 x 24 output tiles, 192-pixel source footprint, five 160-column kernel-row passes)
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), 2.0 * u.n * tiles * 192 * 25 * cw.cin * 32, main,
+    PROFILER.launch(_last_kernel, 2.0 * u.n * tiles * 192 * 25 * cw.cin * 32, main,
                     shape=f"{cw.cin}->(128)->{co} k5 {u.n}x{h}x{w} (lowres {u.c}ch {u.h}x{u.w})", algo=cw5.get("algo_per_px", 0.0) * u.n * h * w)
-    # the ring: the four border lines of up(u) at u's resolution -> tap GEMMs of the edges -> 1-D gather on the ring pixels
-    npos = 2 * u.w + 2 * u.h
+    _upconv5x5_ring(u, us, h, w, cw5["edge"], out, act)
+    return out
+
+
+def _upconv5x5_ring(u: Feat, us, h: int, w: int, edge: ConvW, out: Feat, act: int):
+    """the ring of ``upconv5x5``: the four border lines of up(u) at u's resolution -> tap GEMMs of the edges -> 1-D gather on the ring pixels"""
     if DISPATCH == "torch":
         lines = Feat(_tops().upconv5x5_lines(u.view(), h, w))
-    else:
-        lines = Feat(torch.empty((u.n, 1, npos, u.c), device=u.device, dtype=torch.float32))
-        L.check(L.load().prv2_upconv5x5_lines(C.byref(us), u.n, h, w, lines.ptr, _stream()), "upconv5x5_lines")
-    ge = conv2d(lines, cw5["edge"], algo=0.0)
-    if DISPATCH == "torch":
+        ge = conv2d(lines, edge, algo=0.0)
         _tops().upconv5x5_ring_(out.view(), ge.view(), u.h, u.w, act)
     else:
-        L.check(L.load().prv2_upconv5x5_ring(out.ptr, out.ld, 0, u.n, h, w, co, ge.ptr, ge.ld, u.h, u.w, act, _stream()), "upconv5x5_ring")
-    return out
+        lines = Feat(torch.empty((u.n, 1, 2 * u.w + 2 * u.h, u.c), device=u.device, dtype=torch.float32))
+        _c("upconv5x5_lines", C.byref(us), u.n, h, w, lines.ptr)
+        ge = conv2d(lines, edge, algo=0.0)
+        _c("upconv5x5_ring", out.ptr, out.ld, 0, u.n, h, w, out.c, ge.ptr, ge.ld, u.h, u.w, act)
 
 
 def conv2d_ups(x: Feat, u: Feat, cw: ConvW, out: Optional[Feat] = None, *, act: int = ACT_NONE, res: Optional[Feat] = None, ln=None,
@@ -654,36 +674,28 @@ def conv2d_ups(x: Feat, u: Feat, cw: ConvW, out: Optional[Feat] = None, *, act: 
     if out is None:
         out = Feat.alloc(x.n, oh, ow, cw.cout, x.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, oh, ow, cw.cout)
-    d, us = _ups_desc(x, u, cw, out.ld, act, res.ld if res is not None else 0, ln_eps)
+    d, us = _conv_desc(x, cw, out.ld, act=act, ld_res=_ld(res), ln_eps=ln_eps), _ups_src(u)
+    lnw, lnb = (ln[0], ln[1]) if ln is not None else (None, None)
 
     def call():
         if DISPATCH == "torch":
-            _tops().conv3x3_ups(None if type(x) is UpsOnly else x.view(), u.view(), cw.w, cw.bias, cw.cout, x.h, x.w, act, ln[0] if ln is not None else None,
-                                ln[1] if ln is not None else None, res.view() if res is not None else None, cw.prec, ln_eps, out.view())
-            return
-        L.check(L.load().prv2_conv2d_ups(C.byref(d), x.ptr, C.byref(us), cw.w.data_ptr(), _ptr(cw.bias), _ptr(ln[0]) if ln is not None else None,
-                                         _ptr(ln[1]) if ln is not None else None, _ptr(res), out.ptr, _stream()), "conv2d_ups")
+            _tops().conv3x3_ups(None if type(x) is UpsOnly else x.view(), u.view(), cw.w, cw.bias, cw.cout, x.h, x.w, act, lnw, lnb,
+                                res.view() if res is not None else None, cw.prec, ln_eps, out.view())
+        else:
+            _c("conv2d_ups", C.byref(d), x.ptr, C.byref(us), cw.w.data_ptr(), _ptr(cw.bias), _ptr(lnw), _ptr(lnb), _ptr(res), out.ptr)
 
-    shape = f"{cw.cin}->{cw.cout} k3s1 {x.n}x{x.h}x{x.w} (+up {u.c}ch {u.h}x{u.w})"
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), 2.0 * x.n * oh * ow * cw.cout * cw.cin * 9, call, shape=shape)
+    PROFILER.launch(_last_kernel, 2.0 * x.n * oh * ow * cw.cout * cw.cin * 9, call, shape=f"{cw.cin}->{cw.cout} k3s1 {x.n}x{x.h}x{x.w} (+up {u.c}ch {u.h}x{u.w})")
     return out
 
 
 TAIL_FUSION = os.environ.get("PRV2_TAIL_FUSION", "1") != "0"  # A/B and test switch: [pred1 | pred2] tails written by the conv that fills the row
 
 
-def _tail_desc(x: Feat, cw: ConvW, out: Feat, act: int, res_ld: int, ln_eps: float):
-    return L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad, ldx=x.ld, ldy=out.ld,
-                      x_bstride=0, y_bstride=0, relu_in=0, act=act, convt_k=cw.convt_k, ld_mul=0, ld_res=res_ld, ld_res2=0, prec=cw.prec,
-                      force_generic=0, ln_eps=ln_eps, part=0, same_pad=int(cw.same_pad), fmt=0)
-
-
 def conv2d_tail_supported(x: Feat, cw: ConvW, out: Feat) -> bool:
     """can ``conv2d_tail`` close the [.. | pred1 | pred2 | 0 | 0] row behind this conv's output slice?  (a property of the layer)"""
     if not TAIL_FUSION or not DIRECT_PLACEMENT or type(x) is not Feat or out.ld != out.c0 + cw.cout + 4 or (out.c0 + cw.cout) % 4:
         return False
-    d = _tail_desc(x, cw, out, ACT_NONE, 0, 1e-6)
-    return bool(L.load().prv2_conv2d_tail_supported(C.byref(d)))
+    return bool(L.load().prv2_conv2d_tail_supported(C.byref(_conv_desc(x, cw, out.ld))))
 
 
 def conv2d_tail(x: Feat, cw: ConvW, out: Feat, p1: Feat, p2: Feat, *, act: int = ACT_NONE, ln=None, ln_eps: float = 1e-6) -> Feat:
@@ -692,18 +704,17 @@ def conv2d_tail(x: Feat, cw: ConvW, out: Feat, p1: Feat, p2: Feat, *, act: int =
     conv2d + depth_pair_fill"""
     assert x.c == cw.cin and (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, cw.cout) and out.ld == out.c0 + cw.cout + 4
     assert p1.c == 1 and p2.c == 1 and p1.ld == 1 and p2.ld == 1 and (p1.n, p1.h, p1.w) == (p2.n, p2.h, p2.w) and p1.n == x.n
-    d = _tail_desc(x, cw, out, act, 0, ln_eps)
+    d = _conv_desc(x, cw, out.ld, act=act, ln_eps=ln_eps)
+    lnw, lnb = (ln[0], ln[1]) if ln is not None else (None, None)
 
     def call():
         if DISPATCH == "torch":
-            _tops().conv3x3_tail(x.view(), cw.w, cw.bias, cw.cout, act, ln[0] if ln is not None else None, ln[1] if ln is not None else None, None,
-                                 p1.buf.view(p1.n, p1.h, p1.w), p2.buf.view(p2.n, p2.h, p2.w), cw.prec, ln_eps, out.view())
-            return
-        L.check(L.load().prv2_conv2d_tail(C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(ln[0]) if ln is not None else None,
-                                          _ptr(ln[1]) if ln is not None else None, None, p1.ptr, p2.ptr, p1.h, p1.w, out.ptr, _stream()), "conv2d_tail")
+            _tops().conv3x3_tail(x.view(), cw.w, cw.bias, cw.cout, act, lnw, lnb, None, p1.buf.view(p1.n, p1.h, p1.w), p2.buf.view(p2.n, p2.h, p2.w),
+                                 cw.prec, ln_eps, out.view())
+        else:
+            _c("conv2d_tail", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(lnw), _ptr(lnb), None, p1.ptr, p2.ptr, p1.h, p1.w, out.ptr)
 
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), 2.0 * x.n * x.h * x.w * cw.cout * cw.cin * 9, call,
-                    shape=f"{cw.cin}->{cw.cout} k3s1 {x.n}x{x.h}x{x.w} (+tail)")
+    PROFILER.launch(_last_kernel, 2.0 * x.n * x.h * x.w * cw.cout * cw.cin * 9, call, shape=f"{cw.cin}->{cw.cout} k3s1 {x.n}x{x.h}x{x.w} (+tail)")
     return out
 
 
@@ -722,23 +733,15 @@ def pack_gate(weight: torch.Tensor) -> torch.Tensor:
         return _tops().pack_gate_weight(w)
     dst = torch.empty(L.load().prv2_gate_weight_bytes(c) // 4, device=w.device, dtype=torch.float32)
     _require_dev(w)
-    L.check(L.load().prv2_pack_gate_weight(w.data_ptr(), dst.data_ptr(), c, c, _stream()), "pack_gate_weight")
+    _c("pack_gate_weight", w.data_ptr(), dst.data_ptr(), c, c)
     return dst
-
-
-def _gate_desc(x: Feat, cw: ConvW, out_ld: int, relu_in, act, mul, res, ln_eps):
-    fmt = (L.FMT_X_X2 if getattr(x, "x2", False) else 0) | (L.FMT_MUL_X2 if mul is not None and mul.x2 else 0)
-    return L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad,
-                      ldx=x.ld, ldy=out_ld, x_bstride=0, y_bstride=0, relu_in=int(relu_in), act=act, convt_k=cw.convt_k,
-                      ld_mul=mul.ld if mul is not None else 0, ld_res=res.ld if res is not None else 0, ld_res2=0, prec=cw.prec,
-                      force_generic=0, ln_eps=ln_eps, part=0, same_pad=int(cw.same_pad), fmt=fmt)
 
 
 def conv3x3_ln_gate_supported(x: Feat, cw: ConvW) -> bool:
     """shape contract of the fused kernel (layer shape per image only: the choice never depends on the batch)"""
     if not GATE_FUSION or x.c != cw.cin or x.ld % 4 or cw.cout not in GATE_CHANNELS:
         return False
-    return bool(L.load().prv2_conv3x3_ln_gate_supported(C.byref(_gate_desc(x, cw, roundup(cw.cout, 4), False, ACT_NONE, None, None, 1e-6))))
+    return bool(L.load().prv2_conv3x3_ln_gate_supported(C.byref(_conv_desc(x, cw, roundup(cw.cout, 4), fmt=_gate_fmt(x)))))
 
 
 def conv3x3_ln_gate(x: Feat, cw: ConvW, ln, gate_w: Optional[torch.Tensor], gate_bias: Optional[torch.Tensor], out: Optional[Feat] = None,
@@ -752,7 +755,7 @@ def conv3x3_ln_gate(x: Feat, cw: ConvW, ln, gate_w: Optional[torch.Tensor], gate
     assert (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, cw.cout) and x.c == cw.cin
     for aux in (mul, res):
         assert aux is None or (aux.n, aux.h, aux.w, aux.c) == (out.n, out.h, out.w, out.c)
-    d = _gate_desc(x, cw, out.ld, relu_in, act, mul, res, ln_eps)
+    d = _conv_desc(x, cw, out.ld, act=act, relu_in=relu_in, ld_mul=_ld(mul), ld_res=_ld(res), ln_eps=ln_eps, fmt=_gate_fmt(x, mul))
     assert not out.x2 and (res is None or not res.x2)
     flops = 2.0 * x.n * x.h * x.w * cw.cout * (cw.cin * 9 + (cw.cout if gate_w is not None else 0))
     if pre is not None:
@@ -763,12 +766,12 @@ def conv3x3_ln_gate(x: Feat, cw: ConvW, ln, gate_w: Optional[torch.Tensor], gate
             r = lambda f: None if f is None else f.raw()  # noqa: E731
             _tops().conv3x3_ln_gate(x.raw(), cw.w, cw.bias, ln[0], ln[1], gate_w, gate_bias, r(mul), r(res), act, relu_in, cw.prec, ln_eps, out.view(),
                                     r(pre), d.fmt)
-            return
-        L.check(L.load().prv2_conv3x3_ln_gate_pre(C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(pre), pre.ld if pre is not None else 0, _ptr(ln[0]),
-                                                  _ptr(ln[1]), _ptr(gate_w), _ptr(gate_bias), _ptr(mul), _ptr(res), out.ptr, _stream()), "conv3x3_ln_gate")
+        else:
+            _c("conv3x3_ln_gate_pre", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(pre), _ld(pre), _ptr(ln[0]), _ptr(ln[1]), _ptr(gate_w),
+               _ptr(gate_bias), _ptr(mul), _ptr(res), out.ptr, what="conv3x3_ln_gate")
 
     coarse = f"(+{pre_cin} coarse)" if pre is not None else ""
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), flops, call,
+    PROFILER.launch(_last_kernel, flops, call,
                     shape=f"{cw.cin}{coarse}->{cw.cout}{'->' + str(cw.cout) + ' gate' if gate_w is not None else ''} k3s1 {x.n}x{x.h}x{x.w}",
                     algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9 if pre is not None else None)
     return out
@@ -786,10 +789,7 @@ def conv3x3_ln_gate_f6(x: Feat, cw: ConvWF6, ln, gate_w: torch.Tensor, gate_bias
     assert (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, cw.cout) and not out.x2 and (res is None or not res.x2)
     for aux in (mul, res, pre):
         assert aux is None or (aux.n, aux.h, aux.w, aux.c) == (out.n, out.h, out.w, out.c)
-    d = L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=3, kw=3, stride=1, pad=1, ldx=x.ld, ldy=out.ld, x_bstride=0, y_bstride=0,
-                   relu_in=0, act=act, convt_k=0, ld_mul=mul.ld if mul is not None else 0, ld_res=res.ld if res is not None else 0, ld_res2=0,
-                   prec=L.PREC_F16F6, force_generic=0, ln_eps=ln_eps, part=0, same_pad=0,
-                   fmt=(L.FMT_X_X2 | (L.FMT_MUL_X2 if mul is not None else 0)) if x2 else 0)
+    d = _conv_desc(x, cw, out.ld, act=act, ld_mul=_ld(mul), ld_res=_ld(res), ln_eps=ln_eps, fmt=_gate_fmt(x, mul))
     out_scale = 1.0 / (cw.x_scale * cw.w_scale)
     flops = 2.0 * x.n * x.h * x.w * cw.cout * (cw.cin * 9 + cw.cout)
 
@@ -798,13 +798,12 @@ def conv3x3_ln_gate_f6(x: Feat, cw: ConvWF6, ln, gate_w: torch.Tensor, gate_bias
             r = lambda f: None if f is None else f.raw()  # noqa: E731
             _tops().conv3x3_ln_gate_f6(x.raw(), cw.w, cw.bias, r(pre), ln[0], ln[1], gate_w, gate_bias, r(mul), r(res), act, ln_eps, cw.x_scale, out_scale,
                                        cw.range, out.view(), d.fmt)
-            return
-        L.check(L.load().prv2_conv3x3_ln_gate_f6(C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(pre), pre.ld if pre is not None else 0, _ptr(ln[0]),
-                                                 _ptr(ln[1]), _ptr(gate_w), _ptr(gate_bias), _ptr(mul), _ptr(res), cw.x_scale, out_scale, _ptr(cw.range),
-                                                 out.ptr, _stream()), "conv3x3_ln_gate_f6")
+        else:
+            _c("conv3x3_ln_gate_f6", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(pre), _ld(pre), _ptr(ln[0]), _ptr(ln[1]), _ptr(gate_w),
+               _ptr(gate_bias), _ptr(mul), _ptr(res), cw.x_scale, out_scale, _ptr(cw.range), out.ptr)
 
     coarse = f"(+{pre_cin} coarse)" if pre is not None else ""
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), flops, call, shape=f"{cw.cin}{coarse}->{cw.cout}->{cw.cout} gate k3s1 {x.n}x{x.h}x{x.w}",
+    PROFILER.launch(_last_kernel, flops, call, shape=f"{cw.cin}{coarse}->{cw.cout}->{cw.cout} gate k3s1 {x.n}x{x.h}x{x.w}",
                     algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9 if pre is not None else None)
     return out
 
@@ -833,9 +832,8 @@ def conv2d_cout1(x: Feat, weight: torch.Tensor, bias: Optional[torch.Tensor], k:
     def call():
         if DISPATCH == "torch":
             _tops().conv_cout1(x.view(), weight, bias, k, act, scale, res, clamp0, y)
-            return
-        L.check(L.load().prv2_conv2d_cout1(x.ptr, x.n, x.h, x.w, x.c, x.ld, weight.data_ptr(), k, _ptr(bias), act, scale, _ptr(res), int(clamp0),
-                                           y.data_ptr(), _stream()), "conv2d_cout1")
+        else:
+            _c("conv2d_cout1", x.ptr, x.n, x.h, x.w, x.c, x.ld, weight.data_ptr(), k, _ptr(bias), act, scale, _ptr(res), int(clamp0), y.data_ptr())
 
     PROFILER.launch("conv_cout1_kernel", 2.0 * x.n * x.h * x.w * x.c * k * k, call)
     return y
@@ -850,34 +848,31 @@ def dwconv2d(x: Feat, w_tapmajor: torch.Tensor, bias: Optional[torch.Tensor], k:
     else:
         oh = (x.h + 2 * (k // 2) - k) // stride + 1
         ow = (x.w + 2 * (k // 2) - k) // stride + 1
+    box = []  # the output: the tensor the torch op allocates, or the Feat allocated here
     if DISPATCH == "torch":
-        box = []
-        PROFILER.launch("dwconv_kernel", 2.0 * x.n * oh * ow * x.c * k * k,
-                        lambda: box.append(_tops().dwconv2d(x.view(), w_tapmajor, bias, k, stride, act, same_pad)))
-        y = box[0]
-        return _feat_of(y, x.c)
-    out = Feat.alloc(x.n, oh, ow, x.c, x.device)
-    PROFILER.launch("dwconv_kernel", 2.0 * x.n * oh * ow * x.c * k * k,
-                    lambda: L.check(L.load().prv2_dwconv2d_ex(x.ptr, x.n, x.h, x.w, x.c, x.ld, w_tapmajor.data_ptr(),
-                                                              _ptr(bias), k, stride, act, int(same_pad), out.ptr, out.ld,
-                                                              _stream()), "dwconv2d"))
-    return out
+        call = lambda: box.append(_tops().dwconv2d(x.view(), w_tapmajor, bias, k, stride, act, same_pad))  # noqa: E731
+    else:
+        out = Feat.alloc(x.n, oh, ow, x.c, x.device)
+        box.append(out)
+        call = lambda: _c("dwconv2d_ex", x.ptr, x.n, x.h, x.w, x.c, x.ld, w_tapmajor.data_ptr(), _ptr(bias), k, stride, act, int(same_pad),  # noqa: E731
+                          out.ptr, out.ld, what="dwconv2d")
+    PROFILER.launch("dwconv_kernel", 2.0 * x.n * oh * ow * x.c * k * k, call)
+    return box[0] if isinstance(box[0], Feat) else _feat_of(box[0], x.c)
 
 
 def global_avgpool(x: Feat) -> torch.Tensor:
     """[n, c] mean over the pixels (the squeeze of timm's SqueezeExcite: x.mean((2, 3)))"""
     assert x.c % 4 == 0
+    box = []  # the output: what the torch op returns, or the buffer allocated here
     if DISPATCH == "torch":
-        box = []
-        PROFILER.launch_aux("global_avgpool", 4.0 * x.n * x.h * x.w * x.c, lambda: box.append(_tops().global_avgpool(x.view())), f"{x.c}ch {x.n}x{x.h}x{x.w}")
-        return box[0]
-    out = torch.empty((x.n, x.c), device=x.device, dtype=torch.float32)
-    ws = torch.empty(L.load().prv2_global_avgpool_workspace_floats(x.n, x.h * x.w, x.c), device=x.device, dtype=torch.float32)
-    PROFILER.launch_aux("global_avgpool", 4.0 * x.n * x.h * x.w * x.c,
-                        lambda: L.check(L.load().prv2_global_avgpool(x.ptr, x.n, x.h * x.w, x.c, x.ld, out.data_ptr(), ws.data_ptr(),
-                                                                      _stream()),
-                                        "global_avgpool"), f"{x.c}ch {x.n}x{x.h}x{x.w}")
-    return out
+        call = lambda: box.append(_tops().global_avgpool(x.view()))  # noqa: E731
+    else:
+        out = torch.empty((x.n, x.c), device=x.device, dtype=torch.float32)
+        ws = torch.empty(L.load().prv2_global_avgpool_workspace_floats(x.n, x.h * x.w, x.c), device=x.device, dtype=torch.float32)
+        box.append(out)
+        call = lambda: _c("global_avgpool", x.ptr, x.n, x.h * x.w, x.c, x.ld, out.data_ptr(), ws.data_ptr())  # noqa: E731
+    PROFILER.launch_aux("global_avgpool", 4.0 * x.n * x.h * x.w * x.c, call, f"{x.c}ch {x.n}x{x.h}x{x.w}")
+    return box[0]
 
 
 def se_gate(mean: torch.Tensor, w1: torch.Tensor, b1, w2t: torch.Tensor, b2) -> torch.Tensor:
@@ -886,26 +881,28 @@ def se_gate(mean: torch.Tensor, w1: torch.Tensor, b1, w2t: torch.Tensor, b2) -> 
     n, c = mean.shape
     cse = w1.shape[0]
     assert w1.shape == (cse, c) and w2t.shape == (cse, c) and w1.is_contiguous() and w2t.is_contiguous()
+    box = []
     if DISPATCH == "torch":
-        box = []
-        PROFILER.launch_aux("se_gate", 4.0 * (n * c + 2 * c * cse), lambda: box.append(_tops().se_gate(mean, w1, b1, w2t, b2)), f"{c}->{cse}->{c} x{n}")
-        return box[0]
-    g = torch.empty((n, c), device=mean.device, dtype=torch.float32)
-    ws = torch.empty((n, cse), device=mean.device, dtype=torch.float32)
-    PROFILER.launch_aux("se_gate", 4.0 * (n * c + 2 * c * cse),
-                        lambda: L.check(L.load().prv2_se_gate(mean.data_ptr(), n, c, w1.data_ptr(), _ptr(b1), cse, w2t.data_ptr(),
-                                                               _ptr(b2), g.data_ptr(), ws.data_ptr(), _stream()), "se_gate"),
-                        f"{c}->{cse}->{c} x{n}")
-    return g
+        call = lambda: box.append(_tops().se_gate(mean, w1, b1, w2t, b2))  # noqa: E731
+    else:
+        g = torch.empty((n, c), device=mean.device, dtype=torch.float32)
+        ws = torch.empty((n, cse), device=mean.device, dtype=torch.float32)
+        box.append(g)
+        call = lambda: _c("se_gate", mean.data_ptr(), n, c, w1.data_ptr(), _ptr(b1), cse, w2t.data_ptr(), _ptr(b2), g.data_ptr(), ws.data_ptr())  # noqa: E731
+    PROFILER.launch_aux("se_gate", 4.0 * (n * c + 2 * c * cse), call, f"{c}->{cse}->{c} x{n}")
+    return box[0]
 
 
 def channel_scale_(x: Feat, s: torch.Tensor) -> Feat:
     """x *= s[n, c] in place (the excite of SqueezeExcite)"""
     assert s.shape == (x.n, x.c) and s.is_contiguous() and x.c % 4 == 0
-    PROFILER.launch_aux("channel_scale", 8.0 * x.n * x.h * x.w * x.c,
-                        (lambda: _tops().channel_scale_(x.view(), s)) if DISPATCH == "torch" else
-                        (lambda: L.check(L.load().prv2_channel_scale(x.ptr, x.n, x.h * x.w, x.c, x.ld, s.data_ptr(), _stream()), "channel_scale")),
-                        f"{x.c}ch {x.n}x{x.h}x{x.w}")
+    def call():
+        if DISPATCH == "torch":
+            _tops().channel_scale_(x.view(), s)
+        else:
+            _c("channel_scale", x.ptr, x.n, x.h * x.w, x.c, x.ld, s.data_ptr())
+
+    PROFILER.launch_aux("channel_scale", 8.0 * x.n * x.h * x.w * x.c, call, f"{x.c}ch {x.n}x{x.h}x{x.w}")
     return x
 
 
@@ -915,26 +912,23 @@ def layernorm_rows(x: torch.Tensor, rows: int, c: int, ldx: int, weight, bias, e
         _tops().layernorm(torch.as_strided(x, (rows, c), (ldx, 1), x.storage_offset() + x_off), weight, bias, eps, act,
                           torch.as_strided(y, (rows, c), (ldy, 1), y.storage_offset() + y_off))
         return
-    L.check(L.load().prv2_layernorm(x.data_ptr() + 4 * x_off, rows, c, ldx, weight.data_ptr(), bias.data_ptr(), eps,
-                                    act, y.data_ptr() + 4 * y_off, ldy, _stream()), "layernorm")
+    _c("layernorm", x.data_ptr() + 4 * x_off, rows, c, ldx, weight.data_ptr(), bias.data_ptr(), eps, act, y.data_ptr() + 4 * y_off, ldy)
 
 
 def layernorm_feat(x: Feat, weight, bias, eps: float = 1e-6, act: int = ACT_NONE, out: Optional[Feat] = None) -> Feat:
     """channels-first LayerNorm of the reference == row LayerNorm in NHWC (convs.py:21-29)."""
     if out is None:
         out = x
-    if DISPATCH == "torch":
-        rows = x.n * x.h * x.w
-        PROFILER.launch_aux("layernorm", 8.0 * rows * x.c,
-                            lambda: _tops().layernorm(x.view().reshape(rows, x.c) if x.ld == x.c else torch.as_strided(x.buf, (rows, x.c), (x.ld, 1), x.buf.storage_offset() + x.c0),
-                                                      weight, bias, eps, act,
-                                                      torch.as_strided(out.buf, (rows, out.c), (out.ld, 1), out.buf.storage_offset() + out.c0)),
-                            f"{x.c}ch {x.n}x{x.h}x{x.w}")
-        return out
-    PROFILER.launch_aux("layernorm", 8.0 * x.n * x.h * x.w * x.c,
-                        lambda: L.check(L.load().prv2_layernorm(x.ptr, x.n * x.h * x.w, x.c, x.ld, weight.data_ptr(),
-                                                                 bias.data_ptr(), eps, act, out.ptr, out.ld, _stream()),
-                                        "layernorm"), f"{x.c}ch {x.n}x{x.h}x{x.w}")
+    rows = x.n * x.h * x.w
+
+    def call():
+        if DISPATCH == "torch":
+            _tops().layernorm(x.view().reshape(rows, x.c) if x.ld == x.c else torch.as_strided(x.buf, (rows, x.c), (x.ld, 1), x.buf.storage_offset() + x.c0),
+                              weight, bias, eps, act, torch.as_strided(out.buf, (rows, out.c), (out.ld, 1), out.buf.storage_offset() + out.c0))
+        else:
+            _c("layernorm", x.ptr, rows, x.c, x.ld, weight.data_ptr(), bias.data_ptr(), eps, act, out.ptr, out.ld)
+
+    PROFILER.launch_aux("layernorm", 8.0 * rows * x.c, call, f"{x.c}ch {x.n}x{x.h}x{x.w}")
     return out
 
 
@@ -952,15 +946,14 @@ def split_ss(x2d: torch.Tensor) -> torch.Tensor:
     if DISPATCH == "torch":
         return _tops().split_ss(x2d)
     out = torch.empty((M, K), device=x2d.device, dtype=torch.float32)
-    L.check(L.load().prv2_split_ss(x2d.data_ptr(), M, K, x2d.stride(0), out.data_ptr(), _stream()), "split_ss")
+    _c("split_ss", x2d.data_ptr(), M, K, x2d.stride(0), out.data_ptr())
     return out
 
 
 def layernorm_ss(x: torch.Tensor, rows: int, c: int, ldx: int, weight, bias, eps: float, y_ss: torch.Tensor):
     if DISPATCH == "torch":
         return _tops().layernorm_ss(torch.as_strided(x, (rows, c), (ldx, 1)), weight, bias, eps, y_ss)
-    L.check(L.load().prv2_layernorm_ss(x.data_ptr(), rows, c, ldx, weight.data_ptr(), bias.data_ptr(), eps, y_ss.data_ptr(),
-                                       _stream()), "layernorm_ss")
+    _c("layernorm_ss", x.data_ptr(), rows, c, ldx, weight.data_ptr(), bias.data_ptr(), eps, y_ss.data_ptr())
 
 
 def gemm_ss(a_ss: torch.Tensor, cw: ConvW, out: Optional[torch.Tensor] = None, *, out_ss: bool = False, act: int = ACT_NONE,
@@ -970,16 +963,15 @@ def gemm_ss(a_ss: torch.Tensor, cw: ConvW, out: Optional[torch.Tensor] = None, *
     assert cw.prec == L.PREC_BF16X3 and cw.kh == 1 and cw.kw == 1 and cw.cin == K and K % 32 == 0, (cw.prec, cw.cin, K)
     if out is None:
         out = torch.empty((M, cw.cout), device=a_ss.device, dtype=torch.float32)
-    lib = L.load()
 
     def call():
         if DISPATCH == "torch":
             _tops().gemm_ss(a_ss, cw.w, cw.cout, cw.bias, gamma, res, act, out_ss, out)
-            return
-        L.check(lib.prv2_gemm_ss(a_ss.data_ptr(), M, K, cw.w.data_ptr(), cw.cout, _ptr(cw.bias), _ptr(gamma), _ptr(res),
-                                 res.stride(0) if res is not None else 0, act, None if out_ss else out.data_ptr(), out.stride(0),
-                                 out.data_ptr() if out_ss else None, _stream()), "gemm_ss")
-    PROFILER.launch(lambda: lib.prv2_last_kernel().decode(), 2.0 * M * K * cw.cout, call, shape=f"{K}->{cw.cout} k1s1 1x{M}x1")
+        else:
+            _c("gemm_ss", a_ss.data_ptr(), M, K, cw.w.data_ptr(), cw.cout, _ptr(cw.bias), _ptr(gamma), _ptr(res), res.stride(0) if res is not None else 0, act,
+               None if out_ss else out.data_ptr(), out.stride(0), out.data_ptr() if out_ss else None)
+
+    PROFILER.launch(_last_kernel, 2.0 * M * K * cw.cout, call, shape=f"{K}->{cw.cout} k1s1 1x{M}x1")
     return out
 
 
@@ -992,24 +984,22 @@ def gemm_ss_qkv(a_ss: torch.Tensor, cw: ConvW, heads: int) -> torch.Tensor:
     ``attention_qkv_ss`` (include/prv2.h::prv2_gemm_ss_qkv)"""
     M, K = a_ss.shape
     assert cw.prec == L.PREC_BF16X3 and cw.kh == 1 and cw.kw == 1 and cw.cin == K and K % 32 == 0 and cw.cout == 3 * heads * 64, (cw.prec, cw.cin, K, cw.cout)
-    lib = L.load()
-    q_scale = Q_SCALE
     res = []
 
     def call():
         if DISPATCH == "torch":
-            res.append(_tops().gemm_ss_qkv(a_ss, cw.w, cw.cout, cw.bias, heads * 64, q_scale))
+            res.append(_tops().gemm_ss_qkv(a_ss, cw.w, cw.cout, cw.bias, heads * 64, Q_SCALE))
             return
         out = torch.empty((M, cw.cout), device=a_ss.device, dtype=torch.float32)
-        L.check(lib.prv2_gemm_ss_qkv(a_ss.data_ptr(), M, K, cw.w.data_ptr(), cw.cout, _ptr(cw.bias), heads * 64, q_scale, out.data_ptr(), _stream()), "gemm_ss_qkv")
+        _c("gemm_ss_qkv", a_ss.data_ptr(), M, K, cw.w.data_ptr(), cw.cout, _ptr(cw.bias), heads * 64, Q_SCALE, out.data_ptr())
         res.append(out)
-    PROFILER.launch(lambda: lib.prv2_last_kernel().decode(), 2.0 * M * K * cw.cout, call, shape=f"{K}->{cw.cout} k1s1 1x{M}x1")
+
+    PROFILER.launch(_last_kernel, 2.0 * M * K * cw.cout, call, shape=f"{K}->{cw.cout} k1s1 1x{M}x1")
     return res[0]
 
 
 def attention_qkv_ss(qkv_ss: torch.Tensor, b: int, ntok: int, heads: int, bias=None, out_ss: bool = True) -> torch.Tensor:
     """softmax(q k^T + bias) v on ``gemm_ss_qkv``'s rows (bf16x3); bit-equal to ``attention`` on the fp32 rows of the same Linear"""
-    lib = L.load()
     image = isinstance(bias, AttnBiasImage)
     if image:
         assert (bias.heads, bias.ntok) == (heads, ntok)
@@ -1027,9 +1017,9 @@ def attention_qkv_ss(qkv_ss: torch.Tensor, b: int, ntok: int, heads: int, bias=N
             res.append(_tops().attention_qkv_ss(qkv_ss, b, ntok, heads, bias_t, image, out_ss))
             return
         out = torch.empty((b * ntok, heads * 64), device=qkv_ss.device, dtype=torch.float32)
-        L.check(lib.prv2_attention_qkv_ss(qkv_ss.data_ptr(), b, ntok, heads, 64, _ptr(bias_t), ld_bias, None if out_ss else out.data_ptr(),
-                                          out.data_ptr() if out_ss else None, _stream()), "attention_qkv_ss")
+        _c("attention_qkv_ss", qkv_ss.data_ptr(), b, ntok, heads, 64, _ptr(bias_t), ld_bias, None if out_ss else out.data_ptr(), out.data_ptr() if out_ss else None)
         res.append(out)
+
     PROFILER.launch("attention_qkvss_kernel", 4.0 * b * heads * ntok * ntok * 64, call)
     return res[0]
 
@@ -1039,7 +1029,7 @@ def patchify(img: Feat, p: int, ldo: int) -> torch.Tensor:
     if DISPATCH == "torch":
         return _tops().patchify(img.view(), p, ldo)
     rows = torch.empty((img.n * gh * gw, ldo), device=img.device, dtype=torch.float32)
-    L.check(L.load().prv2_patchify(img.ptr, img.n, gh, gw, p, img.ld, rows.data_ptr(), ldo, _stream()), "patchify")
+    _c("patchify", img.ptr, img.n, gh, gw, p, img.ld, rows.data_ptr(), ldo)
     return rows
 
 
@@ -1047,8 +1037,7 @@ def assemble_tokens(emb: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, b: 
     if DISPATCH == "torch":
         return _tops().assemble_tokens(emb, cls, pos, b, np_, dim)
     tok = torch.empty((b, np_ + 1, dim), device=emb.device, dtype=torch.float32)
-    L.check(L.load().prv2_assemble_tokens(emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), b, np_, dim, tok.data_ptr(),
-                                          _stream()), "assemble_tokens")
+    _c("assemble_tokens", emb.data_ptr(), cls.data_ptr(), pos.data_ptr(), b, np_, dim, tok.data_ptr())
     return tok
 
 
@@ -1071,7 +1060,7 @@ def pack_attention_bias(bias: torch.Tensor, ntok: int):
         return AttnBiasImage(_tops().pack_attention_bias(bias, ntok), heads, ntok)
     lib = L.load()
     img = torch.empty(lib.prv2_attention_bias_image_bytes(heads, ntok) // 4, device=bias.device, dtype=torch.float32)
-    L.check(lib.prv2_pack_attention_bias(bias.data_ptr(), heads, ntok, bias.shape[2], img.data_ptr(), _stream()), "pack_attention_bias")
+    _c("pack_attention_bias", bias.data_ptr(), heads, ntok, bias.shape[2], img.data_ptr())
     return AttnBiasImage(img, heads, ntok)
 
 
@@ -1093,23 +1082,19 @@ def attention(qkv: torch.Tensor, b: int, ntok: int, heads: int, prec: int = PREC
         bias_t, ld_bias = bias, bias.shape[2]
     else:
         bias_t, ld_bias = None, 0
-    if DISPATCH == "torch":
-        res = []
-        PROFILER.launch("attention_f32_kernel" if prec == PREC_F32 else "attention_bf16x3_kernel", 4.0 * b * heads * ntok * ntok * 64,
-                        lambda: res.append(_tops().attention_ss(qkv, b, ntok, heads, bias_t, image) if out_ss else
-                                           _tops().attention_fwd(qkv, b, ntok, heads, prec, bias_t, image)))
-        return res[0]
-    if out_ss:
-        assert prec == L.PREC_BF16X3
-        PROFILER.launch("attention_bf16x3_kernel", 4.0 * b * heads * ntok * ntok * 64,
-                        lambda: L.check(lib.prv2_attention_ss(qkv.data_ptr(), b, ntok, heads, 64, _ptr(bias_t), ld_bias, out.data_ptr(), _ptr(ws),
-                                                              nbytes, _stream()), "attention_ss"))
-        return out
-    PROFILER.launch("attention_f32_kernel" if prec == PREC_F32 else "attention_bf16x3_kernel",
-                    4.0 * b * heads * ntok * ntok * 64,
-                    lambda: L.check(lib.prv2_attention_bias(qkv.data_ptr(), b, ntok, heads, 64, _ptr(bias_t), ld_bias, out.data_ptr(), prec,
-                                                            _ptr(ws), nbytes, _stream()), "attention"))
-    return out
+    res = []  # (the torch ops allocate their own output)
+
+    def call():
+        if DISPATCH == "torch":
+            res.append(_tops().attention_ss(qkv, b, ntok, heads, bias_t, image) if out_ss else _tops().attention_fwd(qkv, b, ntok, heads, prec, bias_t, image))
+        elif out_ss:
+            assert prec == L.PREC_BF16X3
+            _c("attention_ss", qkv.data_ptr(), b, ntok, heads, 64, _ptr(bias_t), ld_bias, out.data_ptr(), _ptr(ws), nbytes)
+        else:
+            _c("attention_bias", qkv.data_ptr(), b, ntok, heads, 64, _ptr(bias_t), ld_bias, out.data_ptr(), prec, _ptr(ws), nbytes, what="attention")
+
+    PROFILER.launch("attention_f32_kernel" if prec == PREC_F32 else "attention_bf16x3_kernel", 4.0 * b * heads * ntok * ntok * 64, call)
+    return res[0] if res else out
 
 
 def crop_resize(img_chw: torch.Tensor, tiles: torch.Tensor, ch: int, cw: int, oh: int, ow: int,
@@ -1119,25 +1104,16 @@ def crop_resize(img_chw: torch.Tensor, tiles: torch.Tensor, ch: int, cw: int, oh
     _require_dev(img_chw)
     assert tiles.dtype == torch.int32 and tiles.is_cuda and img_chw.is_contiguous()
     k = tiles.shape[0]
-    if img_chw.dim() == 4:
+    frames = img_chw.dim() == 4
+    if frames:
         assert tiles.shape[1] == 3, "crop_resize of B frames takes tiles (frame, h, w)"
-        if DISPATCH == "torch":
-            _tops().crop_resize_frames(img_chw, tiles.contiguous(), ch, cw, oh, ow, list(mean) if mean is not None else None,
-                                       list(std) if std is not None else None, out.slice(0, 3).view())
-            return
-        m = (C.c_float * 3)(*mean) if mean is not None else None
-        s = (C.c_float * 3)(*std) if std is not None else None
-        L.check(L.load().prv2_crop_resize_frames(img_chw.data_ptr(), img_chw.shape[0], img_chw.shape[2], img_chw.shape[3], tiles.data_ptr(), k,
-                                                 ch, cw, oh, ow, m, s, out.ptr, out.ld, _stream()), "crop_resize_frames")
-        return
     if DISPATCH == "torch":
-        _tops().crop_resize_bilinear(img_chw, tiles.contiguous(), ch, cw, oh, ow, list(mean) if mean is not None else None,
-                                     list(std) if std is not None else None, out.slice(0, 3).view())
+        m, s = (list(v) if v is not None else None for v in (mean, std))
+        (_tops().crop_resize_frames if frames else _tops().crop_resize_bilinear)(img_chw, tiles.contiguous(), ch, cw, oh, ow, m, s, out.slice(0, 3).view())
         return
-    m = (C.c_float * 3)(*mean) if mean is not None else None
-    s = (C.c_float * 3)(*std) if std is not None else None
-    L.check(L.load().prv2_crop_resize(img_chw.data_ptr(), img_chw.shape[1], img_chw.shape[2], tiles.data_ptr(), k, ch,
-                                      cw, oh, ow, m, s, out.ptr, out.ld, _stream()), "crop_resize")
+    m, s = ((C.c_float * 3)(*v) if v is not None else None for v in (mean, std))
+    _c("crop_resize_frames" if frames else "crop_resize", img_chw.data_ptr(), *img_chw.shape[:-3], img_chw.shape[-2], img_chw.shape[-1], tiles.data_ptr(), k,
+       ch, cw, oh, ow, m, s, out.ptr, out.ld)
 
 
 def bicubic_resize(img_hwc: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
@@ -1150,8 +1126,7 @@ def bicubic_resize(img_hwc: torch.Tensor, oh: int, ow: int) -> torch.Tensor:
     if DISPATCH == "torch":
         return _tops().bicubic_resize(img_hwc, oh, ow)
     out = torch.empty((3, oh, ow), device=img_hwc.device, dtype=torch.float32)
-    L.check(L.load().prv2_bicubic_resize(img_hwc.data_ptr(), int(img_hwc.dtype == torch.uint8), img_hwc.shape[0], img_hwc.shape[1],
-                                         out.data_ptr(), oh, ow, _stream()), "bicubic_resize")
+    _c("bicubic_resize", img_hwc.data_ptr(), int(img_hwc.dtype == torch.uint8), img_hwc.shape[0], img_hwc.shape[1], out.data_ptr(), oh, ow)
     return out
 
 
@@ -1163,28 +1138,18 @@ def roi_align(feat: Feat, boxes: torch.Tensor, spatial_scale: float, oh: int, ow
     k = boxes.shape[0]
     if out is None:
         out = Feat.alloc(k, oh, ow, feat.c, feat.device)
-    if frames:
+    nf = (feat.n,) if frames else ()  # (the B-frame entry points take the frame count first; one map: feat.n == 1)
+    what = "roi_align_frames" if frames else "roi_align"
+
+    def call():
         if DISPATCH == "torch":
-            PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.n * feat.h * feat.w + k * oh * ow),
-                                lambda: _tops().roi_align_frames(feat.view(), boxes.contiguous(), float(spatial_scale), oh, ow, out.raw(), out.x2),
-                                f"{feat.c}ch {feat.n}x{feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
-            return out
-        fn = L.load().prv2_roi_align_x2_frames if out.x2 else L.load().prv2_roi_align_frames
-        PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.n * feat.h * feat.w + k * oh * ow),
-                            lambda: L.check(fn(feat.ptr, feat.n, feat.h, feat.w, feat.c, feat.ld, boxes.data_ptr(), k,
-                                               spatial_scale, oh, ow, out.ptr, out.ld, _stream()), "roi_align_frames"),
-                            f"{feat.c}ch {feat.n}x{feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
-        return out
-    if DISPATCH == "torch":
-        PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.h * feat.w + k * oh * ow),
-                            lambda: _tops().roi_align(feat.view(), boxes.contiguous(), float(spatial_scale), oh, ow, out.raw(), out.x2),
-                            f"{feat.c}ch {feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
-        return out
-    fn = L.load().prv2_roi_align_x2 if out.x2 else L.load().prv2_roi_align  # (x2: the pre-split format of the gate kernel's input)
-    PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.h * feat.w + k * oh * ow),
-                        lambda: L.check(fn(feat.ptr, feat.h, feat.w, feat.c, feat.ld, boxes.data_ptr(), k,
-                                           spatial_scale, oh, ow, out.ptr, out.ld, _stream()), "roi_align"),
-                        f"{feat.c}ch {feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
+            (_tops().roi_align_frames if frames else _tops().roi_align)(feat.view(), boxes.contiguous(), float(spatial_scale), oh, ow, out.raw(), out.x2)
+        else:  # (x2: the pre-split format of the gate kernel's input)
+            _c(what.replace("align", "align_x2") if out.x2 else what, feat.ptr, *nf, feat.h, feat.w, feat.c, feat.ld, boxes.data_ptr(), k, spatial_scale, oh, ow,
+               out.ptr, out.ld, what=what)
+
+    PROFILER.launch_aux("roi_align", 4.0 * feat.c * (feat.n * feat.h * feat.w + k * oh * ow), call,
+                        f"{feat.c}ch {f'{feat.n}x' if frames else ''}{feat.h}x{feat.w}->{k}x{oh}x{ow}{' x2' if out.x2 else ''}")
     return out
 
 
@@ -1192,31 +1157,23 @@ def upsample_bilinear(x: Feat, oh: int, ow: int, out: Optional[Feat] = None) -> 
     if out is None:
         out = Feat.alloc(x.n, oh, ow, x.c, x.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, oh, ow, x.c)
-    if DISPATCH == "torch":
-        PROFILER.launch_aux("upsample_bilinear", 4.0 * x.n * x.c * (x.h * x.w + oh * ow),
-                            lambda: _tops().upsample_bilinear_ac(x.view(), oh, ow, out.view()), f"{x.c}ch {x.n}x{x.h}x{x.w}->{oh}x{ow}")
-        return out
-    PROFILER.launch_aux("upsample_bilinear", 4.0 * x.n * x.c * (x.h * x.w + oh * ow),
-                        lambda: L.check(L.load().prv2_upsample_bilinear(x.ptr, x.n, x.h, x.w, x.c, x.ld, oh, ow, out.ptr,
-                                                                         out.ld, _stream()), "upsample_bilinear"),
-                        f"{x.c}ch {x.n}x{x.h}x{x.w}->{oh}x{ow}")
+
+    def call():
+        if DISPATCH == "torch":
+            _tops().upsample_bilinear_ac(x.view(), oh, ow, out.view())
+        else:
+            _c("upsample_bilinear", x.ptr, x.n, x.h, x.w, x.c, x.ld, oh, ow, out.ptr, out.ld)
+
+    PROFILER.launch_aux("upsample_bilinear", 4.0 * x.n * x.c * (x.h * x.w + oh * ow), call, f"{x.c}ch {x.n}x{x.h}x{x.w}->{oh}x{ow}")
     return out
-
-
-def _pre_desc(x: Feat, cw: ConvW, out_ld: int, act: int, res_ld: int, ln_eps: float):
-    return L.ConvDesc(n=x.n, h=x.h, w=x.w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad, ldx=x.ld, ldy=out_ld,
-                      x_bstride=0, y_bstride=0, relu_in=0, act=act, convt_k=cw.convt_k, ld_mul=0, ld_res=res_ld, ld_res2=0, prec=cw.prec,
-                      force_generic=0, ln_eps=ln_eps, part=0, same_pad=int(cw.same_pad), fmt=0)
 
 
 def conv2d_pre_supported(h: int, w: int, cw: ConvW, ln: bool) -> bool:
     """can ``conv2d_pre`` add a pre-epilogue addend to this 3x3 conv on h x w images (a property of the layer)?"""
     if ln and cw.cout > 128 and cw.cout != 256:
         return False
-    d = L.ConvDesc(n=1, h=h, w=w, cin=cw.cin, cout=cw.cout, kh=cw.kh, kw=cw.kw, stride=cw.stride, pad=cw.pad, ldx=roundup(cw.cin, 4),
-                   ldy=roundup(cw.cout, 4), x_bstride=0, y_bstride=0, relu_in=0, act=ACT_NONE, convt_k=cw.convt_k, ld_mul=0, ld_res=0, ld_res2=0,
-                   prec=cw.prec, force_generic=0, ln_eps=1e-6, part=0, same_pad=int(cw.same_pad), fmt=0)
-    return bool(L.load().prv2_conv2d_pre_supported(C.byref(d)))
+    x = SimpleNamespace(n=1, h=h, w=w, ld=roundup(cw.cin, 4))  # (one dense image of the layer's input)
+    return bool(L.load().prv2_conv2d_pre_supported(C.byref(_conv_desc(x, cw, roundup(cw.cout, 4)))))
 
 
 def conv2d_pre(x: Feat, cw: ConvW, pre: Feat, out: Optional[Feat] = None, *, act: int = ACT_NONE, res: Optional[Feat] = None, ln=None,
@@ -1227,17 +1184,17 @@ def conv2d_pre(x: Feat, cw: ConvW, pre: Feat, out: Optional[Feat] = None, *, act
     if out is None:
         out = Feat.alloc(x.n, x.h, x.w, cw.cout, x.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, cw.cout) and not out.x2
-    d = _pre_desc(x, cw, out.ld, act, res.ld if res is not None else 0, ln_eps)
+    d = _conv_desc(x, cw, out.ld, act=act, ld_res=_ld(res), ln_eps=ln_eps)
+    lnw, lnb = (ln[0], ln[1]) if ln is not None else (None, None)
     flops = 2.0 * x.n * x.h * x.w * cw.cout * cw.cin * 9
+
     def call():
         if DISPATCH == "torch":
-            _tops().conv3x3_pre(x.view(), cw.w, cw.bias, pre.view(), cw.cout, act, ln[0] if ln is not None else None, ln[1] if ln is not None else None,
-                                res.view() if res is not None else None, cw.prec, ln_eps, out.view())
-            return
-        L.check(L.load().prv2_conv2d_pre(C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), pre.ptr, pre.ld, _ptr(ln[0]) if ln is not None else None,
-                                         _ptr(ln[1]) if ln is not None else None, _ptr(res), out.ptr, _stream()), "conv2d_pre")
+            _tops().conv3x3_pre(x.view(), cw.w, cw.bias, pre.view(), cw.cout, act, lnw, lnb, res.view() if res is not None else None, cw.prec, ln_eps, out.view())
+        else:
+            _c("conv2d_pre", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), pre.ptr, pre.ld, _ptr(lnw), _ptr(lnb), _ptr(res), out.ptr)
 
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), flops, call,
+    PROFILER.launch(_last_kernel, flops, call,
                     shape=f"{cw.cin}(+{pre_cin} coarse)->{cw.cout} k3s1 {x.n}x{x.h}x{x.w}", algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9)
     return out
 
@@ -1255,7 +1212,7 @@ def pack_chain32(weight: torch.Tensor, kind: int, device=None) -> torch.Tensor:
         return _tops().pack_chain32_weight(w, kind)
     lib = L.load()
     packed = torch.empty(lib.prv2_chain32_weight_bytes(kind, taps) // 4, device=w.device, dtype=torch.float32)
-    L.check(lib.prv2_pack_chain32_weight(w.data_ptr(), w.shape[1], taps, kind, packed.data_ptr(), _stream()), "pack_chain32_weight")
+    _c("pack_chain32_weight", w.data_ptr(), w.shape[1], taps, kind, packed.data_ptr())
     return packed
 
 
@@ -1293,13 +1250,12 @@ def chain32_c2f(x: Feat, cw: dict, pre: Optional[Feat], out: Optional[Feat] = No
         if DISPATCH == "torch":
             _tops().chain32_c2f(x.view(), cw["w1"], cw["w2"], cw["wg"], cw["wo"], cw["consts"], cw["b3"], pre.view() if pre is not None else None, ln_eps,
                                 out.view(), depth)
-            return
-        d = _chain32_desc(x, cw["w1"], cw["w2"], cw["wg"], cw["wo"], cw["consts"], pre, None, None, out, depth, cw["b3"], ln_eps)
-        L.check(L.load().prv2_chain32_c2f(C.byref(d), _stream()), "chain32_c2f")
+        else:
+            _c("chain32_c2f", C.byref(_chain32_desc(x, cw["w1"], cw["w2"], cw["wg"], cw["wo"], cw["consts"], pre, None, None, out, depth, cw["b3"], ln_eps)))
 
     px = float(x.n * x.h * x.w)
     flops = 2.0 * px * (2 * 9 * 32 * 32 + 2 * 32 * 32 + 32)
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), flops, call, shape=f"32->32->32(+{pre_cin} coarse)->gate->32->1 k3s1 {x.n}x{x.h}x{x.w}",
+    PROFILER.launch(_last_kernel, flops, call, shape=f"32->32->32(+{pre_cin} coarse)->gate->32->1 k3s1 {x.n}x{x.h}x{x.w}",
                     algo=flops + 2.0 * px * 9 * 32 * pre_cin)
     return out, depth
 
@@ -1315,13 +1271,12 @@ def chain32_enc(x: Feat, cw: dict, pre: Feat, p1: torch.Tensor, p2: torch.Tensor
     def call():
         if DISPATCH == "torch":
             _tops().chain32_enc(x.view(), cw["w1"], cw["w2"], cw["wt"], cw["consts"], pre.view(), p1, p2, ln_eps, out.view())
-            return
-        d = _chain32_desc(x, cw["w1"], cw["w2"], cw["wt"], None, cw["consts"], pre, p1, p2, out, None, 0.0, ln_eps)
-        L.check(L.load().prv2_chain32_enc(C.byref(d), _stream()), "chain32_enc")
+        else:
+            _c("chain32_enc", C.byref(_chain32_desc(x, cw["w1"], cw["w2"], cw["wt"], None, cw["consts"], pre, p1, p2, out, None, 0.0, ln_eps)))
 
     px = float(x.n * x.h * x.w)
     flops = 2.0 * px * (9 * 32 * 32 + 9 * 34 * 32)
-    PROFILER.launch(lambda: L.load().prv2_last_kernel().decode(), flops, call, shape=f"32(+{pre_cin} coarse)->32->34->32 k3s1 {x.n}x{x.h}x{x.w}",
+    PROFILER.launch(_last_kernel, flops, call, shape=f"32(+{pre_cin} coarse)->32->34->32 k3s1 {x.n}x{x.h}x{x.w}",
                     algo=flops + 2.0 * px * 9 * 32 * pre_cin)
     return out
 
@@ -1338,34 +1293,23 @@ class CoarseTaps:
     def __init__(self, g: Feat, cout: int, kb):
         assert g.c == 9 * cout and 0 < kb[0] <= 0.5 and 0 < kb[1] <= 0.5
         self.g, self.cout, self.kb = g, cout, (float(kb[0]), float(kb[1]))
-        if g.n > 1:
-            if DISPATCH == "torch":
-                box = []
-                PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.n * g.h * g.w * 18 * cout,
-                                    lambda: box.append(_tops().coarse_tap_knots_frames(g.view(), cout, self.kb[0], self.kb[1])), f"{cout}ch {g.n}x{g.h}x{g.w}")
-                self.v = Feat(box[0])
-                return
-            self.v = Feat(torch.empty((g.n, 3 * g.h, 3 * g.w, cout), device=g.device, dtype=torch.float32))
-            PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.n * g.h * g.w * 18 * cout,
-                                lambda: L.check(L.load().prv2_coarse_tap_knots_frames(g.ptr, g.n, g.h, g.w, cout, g.ld, self.kb[0], self.kb[1], self.v.ptr,
-                                                                                      self.v.ld, _stream()), "coarse_tap_knots_frames"), f"{cout}ch {g.n}x{g.h}x{g.w}")
-            return
+        self.nf = (g.n,) if g.n > 1 else ()  # (B frames: the entry points take the frame count first)
+        box = []  # the table: the tensor the torch op allocates, or the one allocated here
         if DISPATCH == "torch":
-            box = []
-            PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.h * g.w * 18 * cout, lambda: box.append(_tops().coarse_tap_knots(g.view(), cout, self.kb[0], self.kb[1])),
-                                f"{cout}ch {g.h}x{g.w}")
-            self.v = Feat(box[0])
-            return
-        self.v = Feat(torch.empty((1, 3 * g.h, 3 * g.w, cout), device=g.device, dtype=torch.float32))
-        PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.h * g.w * 18 * cout,
-                            lambda: L.check(L.load().prv2_coarse_tap_knots(g.ptr, g.h, g.w, cout, g.ld, self.kb[0], self.kb[1], self.v.ptr, self.v.ld,
-                                                                           _stream()), "coarse_tap_knots"), f"{cout}ch {g.h}x{g.w}")
+            op = _tops().coarse_tap_knots_frames if self.nf else _tops().coarse_tap_knots
+            call = lambda: box.append(op(g.view(), cout, *self.kb))  # noqa: E731
+        else:
+            v = torch.empty((g.n, 3 * g.h, 3 * g.w, cout), device=g.device, dtype=torch.float32)
+            box.append(v)
+            call = lambda: _c("coarse_tap_knots_frames" if self.nf else "coarse_tap_knots", g.ptr, *self.nf, g.h, g.w, cout, g.ld, *self.kb,  # noqa: E731
+                              v.data_ptr(), cout)
+        PROFILER.launch_aux("coarse_tap_knots", 4.0 * g.n * g.h * g.w * 18 * cout, call, f"{cout}ch {f'{g.n}x' if self.nf else ''}{g.h}x{g.w}")
+        self.v = Feat(box[0])
 
     def gather(self, boxes: torch.Tensor, spatial_scale: float, oh: int, ow: int, out: Optional[Feat] = None) -> Feat:
         """the conv's coarse half for the tiles ``boxes`` (as roi_align takes them): [k, oh, ow, cout], zero padding at the tile border
         included (prv2_coarse_tap_gather).  Tables of B frames: boxes (frame, x1, y1, x2, y2) (prv2_coarse_tap_gather_frames)."""
-        frames = self.g.n > 1
-        assert boxes.dtype == torch.float32 and boxes.is_cuda and boxes.shape[1] == (5 if frames else 4)
+        assert boxes.dtype == torch.float32 and boxes.is_cuda and boxes.shape[1] == (5 if self.nf else 4)
         k = boxes.shape[0]
         # The knot-grid algebra holds when consecutive output pixels are exactly ``kb`` coarse pixels apart (ROI bin == knot spacing): every
         # box must span kb * (g.h, g.w) * (oh, ow) / spatial_scale frame pixels.  The boxes live on the device (no host sync on the frame
@@ -1380,28 +1324,18 @@ class CoarseTaps:
         if out is None:
             out = Feat(torch.empty((k, oh, ow, self.cout), device=self.g.device, dtype=torch.float32))
         assert (out.n, out.h, out.w, out.c) == (k, oh, ow, self.cout) and not out.x2
-        g, v = self.g, self.v
-        if frames:
+        g, v, nf = self.g, self.v, self.nf
+
+        def call():
             if DISPATCH == "torch":
-                PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.n * g.h * g.w + k * oh * ow),
-                                    lambda: _tops().coarse_tap_gather_frames(v.view(), g.view(), self.kb[0], self.kb[1], boxes.contiguous(), float(spatial_scale),
-                                                                             oh, ow, out.view()),
-                                    f"{self.cout}ch {g.n}x{g.h}x{g.w}->{k}x{oh}x{ow}")
-                return out
-            PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.n * g.h * g.w + k * oh * ow),
-                                lambda: L.check(L.load().prv2_coarse_tap_gather_frames(v.ptr, g.ptr, g.n, g.h, g.w, self.cout, v.ld, g.ld, self.kb[0], self.kb[1],
-                                                                                       boxes.data_ptr(), k, spatial_scale, oh, ow, out.ptr, out.ld, _stream()),
-                                                "coarse_tap_gather_frames"), f"{self.cout}ch {g.n}x{g.h}x{g.w}->{k}x{oh}x{ow}")
-            return out
-        if DISPATCH == "torch":
-            PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.h * g.w + k * oh * ow),
-                                lambda: _tops().coarse_tap_gather(v.view(), g.view(), self.kb[0], self.kb[1], boxes.contiguous(), float(spatial_scale), oh, ow, out.view()),
-                                f"{self.cout}ch {g.h}x{g.w}->{k}x{oh}x{ow}")
-            return out
-        PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.h * g.w + k * oh * ow),
-                            lambda: L.check(L.load().prv2_coarse_tap_gather(v.ptr, g.ptr, g.h, g.w, self.cout, v.ld, g.ld, self.kb[0], self.kb[1],
-                                                                            boxes.data_ptr(), k, spatial_scale, oh, ow, out.ptr, out.ld, _stream()),
-                                            "coarse_tap_gather"), f"{self.cout}ch {g.h}x{g.w}->{k}x{oh}x{ow}")
+                (_tops().coarse_tap_gather_frames if nf else _tops().coarse_tap_gather)(v.view(), g.view(), *self.kb, boxes.contiguous(), float(spatial_scale),
+                                                                                        oh, ow, out.view())
+            else:
+                _c("coarse_tap_gather_frames" if nf else "coarse_tap_gather", v.ptr, g.ptr, *nf, g.h, g.w, self.cout, v.ld, g.ld, *self.kb, boxes.data_ptr(), k,
+                   spatial_scale, oh, ow, out.ptr, out.ld)
+
+        PROFILER.launch_aux("coarse_tap_gather", 4.0 * self.cout * (9 * g.n * g.h * g.w + k * oh * ow), call,
+                            f"{self.cout}ch {f'{g.n}x' if nf else ''}{g.h}x{g.w}->{k}x{oh}x{ow}")
         return out
 
 
@@ -1445,79 +1379,71 @@ class RoiSource:
 def conv_border_bias(y: Feat, tap_bias: torch.Tensor):
     """y -= the folded bias of the 3x3 taps that the zero padding hides at the image border (include/prv2.h::prv2_conv_border_bias)"""
     assert tap_bias.shape == (9, y.c) and tap_bias.is_contiguous()
-    if DISPATCH == "torch":
-        return PROFILER.launch_aux("conv_border_bias", 8.0 * y.n * 2 * (y.h + y.w) * y.c, lambda: _tops().conv_border_bias_(y.view(), tap_bias), f"{y.c}ch {y.n}x{y.h}x{y.w}")
-    PROFILER.launch_aux("conv_border_bias", 8.0 * y.n * 2 * (y.h + y.w) * y.c,
-                        lambda: L.check(L.load().prv2_conv_border_bias(y.ptr, y.n, y.h, y.w, y.c, y.ld, tap_bias.data_ptr(), _stream()),
-                                        "conv_border_bias"), f"{y.c}ch {y.n}x{y.h}x{y.w}")
+
+    def call():
+        if DISPATCH == "torch":
+            _tops().conv_border_bias_(y.view(), tap_bias)
+        else:
+            _c("conv_border_bias", y.ptr, y.n, y.h, y.w, y.c, y.ld, tap_bias.data_ptr())
+
+    PROFILER.launch_aux("conv_border_bias", 8.0 * y.n * 2 * (y.h + y.w) * y.c, call, f"{y.c}ch {y.n}x{y.h}x{y.w}")
 
 
 def depth_pair_fill(p1: Feat, p2: Feat, buf: Feat, c0: int):
     """channels c0, c0 + 1 of ``buf`` <- (p1, p2) resized to the buffer's size, channels c0 + 2, c0 + 3 (the pad) <- 0"""
     assert p1.c == 1 and p2.c == 1 and p1.ld == 1 and p2.ld == 1 and (p1.n, p1.h, p1.w) == (p2.n, p2.h, p2.w) == (buf.n, p1.h, p1.w)
     assert buf.ld == buf.c0 + c0 + 4 and (buf.c0 + c0) % 4 == 0, (buf.ld, buf.c0, c0)
-    if DISPATCH == "torch":
-        return PROFILER.launch_aux("depth_pair_fill", 16.0 * buf.n * buf.h * buf.w,
-                                   lambda: _tops().depth_pair_fill(p1.buf.view(p1.n, p1.h, p1.w), p2.buf.view(p2.n, p2.h, p2.w), buf.buf[..., buf.c0 + c0:buf.c0 + c0 + 4]),
-                                   f"{buf.n}x{p1.h}x{p1.w}->{buf.h}x{buf.w}")
-    PROFILER.launch_aux("depth_pair_fill", 16.0 * buf.n * buf.h * buf.w,
-                        lambda: L.check(L.load().prv2_depth_pair_fill(p1.ptr, p2.ptr, p1.n, p1.h, p1.w, buf.h, buf.w, buf.ptr + 4 * c0, buf.ld,
-                                                                      _stream()), "depth_pair_fill"), f"{buf.n}x{p1.h}x{p1.w}->{buf.h}x{buf.w}")
+
+    def call():
+        if DISPATCH == "torch":
+            _tops().depth_pair_fill(p1.buf.view(p1.n, p1.h, p1.w), p2.buf.view(p2.n, p2.h, p2.w), buf.buf[..., buf.c0 + c0:buf.c0 + c0 + 4])
+        else:
+            _c("depth_pair_fill", p1.ptr, p2.ptr, p1.n, p1.h, p1.w, buf.h, buf.w, buf.ptr + 4 * c0, buf.ld)
+
+    PROFILER.launch_aux("depth_pair_fill", 16.0 * buf.n * buf.h * buf.w, call, f"{buf.n}x{p1.h}x{p1.w}->{buf.h}x{buf.w}")
 
 
 def blend_paste(avg, cnt, pred, mask, tiles, th, tw):
     if DISPATCH == "torch":
         return _tops().blend_init(avg, cnt, pred.contiguous(), mask, tiles.contiguous(), th, tw)
-    L.check(L.load().prv2_blend_paste(avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], pred.data_ptr(),
-                                      pred.shape[-2], pred.shape[-1], mask.data_ptr(), tiles.data_ptr(), tiles.shape[0],
-                                      th, tw, _stream()), "blend_paste")
+    _c("blend_paste", avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], pred.data_ptr(), pred.shape[-2], pred.shape[-1], mask.data_ptr(),
+       tiles.data_ptr(), tiles.shape[0], th, tw)
 
 
 def blend_update(avg, cnt, pred, mask, tiles, th, tw):
     if DISPATCH == "torch":
         return _tops().blend_update(avg, cnt, pred.contiguous(), mask, tiles.contiguous(), th, tw)
-    L.check(L.load().prv2_blend_update(avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], pred.data_ptr(),
-                                       pred.shape[-2], pred.shape[-1], mask.data_ptr(), tiles.data_ptr(), tiles.shape[0],
-                                       th, tw, _stream()), "blend_update")
+    _c("blend_update", avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], pred.data_ptr(), pred.shape[-2], pred.shape[-1], mask.data_ptr(),
+       tiles.data_ptr(), tiles.shape[0], th, tw)
 
 
-def _blend_frames(paste, avg, cnt, pred, mask, tiles, th, tw):
-    """one pass step of the blend for B maps avg / cnt [B, H, W]: pred [B, k, ph, pw] and tiles int32 [B, k, 2] are frame f's slice of
+def _blend_frames(step, maps, pred, mask, tiles, th, tw, kind="frames"):
+    """one pass step (``step``: "paste" / "update") of the blend for B maps [B, H, W] -- ``maps`` = (avg, cnt), or (avg, cnt, m2, ntl) with
+    the overlap statistics (``kind`` "stats": prv2_blend_*_stats): pred [B, k, ph, pw] and tiles int32 [B, k, 2] are frame f's slice of
     frame-major lists (any frame stride: ``preds.view(B, n, ph, pw)[:, o:o + k]``, no copies)"""
     B, k = pred.shape[0], pred.shape[1]
-    assert avg.dim() == 3 and tiles.shape[:2] == (B, k) and pred.stride(1) == pred.shape[2] * pred.shape[3] and tiles.stride(1) == 2
+    assert maps[0].dim() == 3 and tiles.shape[:2] == (B, k) and pred.stride(1) == pred.shape[2] * pred.shape[3] and tiles.stride(1) == 2
     if DISPATCH == "torch":
-        return (_tops().blend_init_frames if paste else _tops().blend_update_frames)(avg, cnt, pred, mask, tiles, th, tw)
-    fn = L.load().prv2_blend_paste_frames if paste else L.load().prv2_blend_update_frames
-    L.check(fn(avg.data_ptr(), cnt.data_ptr(), B, avg.shape[1], avg.shape[2], pred.data_ptr(), pred.shape[-2], pred.shape[-1],
-               pred.stride(0) if B > 1 else k * pred.shape[2] * pred.shape[3], mask.data_ptr(), tiles.data_ptr(),
-               tiles.stride(0) // 2 if B > 1 else k, k, th, tw, _stream()), "blend_paste_frames" if paste else "blend_update_frames")
+        return getattr(_tops(), f"blend_{'init' if step == 'paste' else step}_{kind}")(*maps, pred, mask, tiles, th, tw)
+    _c(f"blend_{step}_{kind}", *(t.data_ptr() for t in maps), B, maps[0].shape[1], maps[0].shape[2], pred.data_ptr(), pred.shape[-2], pred.shape[-1],
+       pred.stride(0) if B > 1 else k * pred.shape[2] * pred.shape[3], mask.data_ptr(), tiles.data_ptr(), tiles.stride(0) // 2 if B > 1 else k, k, th, tw)
 
 
 def blend_paste_frames(avg, cnt, pred, mask, tiles, th, tw):
-    _blend_frames(True, avg, cnt, pred, mask, tiles, th, tw)
+    _blend_frames("paste", (avg, cnt), pred, mask, tiles, th, tw)
 
 
 def blend_update_frames(avg, cnt, pred, mask, tiles, th, tw):
-    _blend_frames(False, avg, cnt, pred, mask, tiles, th, tw)
+    _blend_frames("update", (avg, cnt), pred, mask, tiles, th, tw)
 
 
 def blend_resize(avg, cnt, oh, ow):
     """[H, W] maps, or B maps [B, H, W] in one launch (prv2_blend_resize_frames)"""
-    if avg.dim() == 3:
-        if DISPATCH == "torch":
-            return _tops().blend_resize_frames(avg, cnt, oh, ow)
-        a = torch.empty((avg.shape[0], oh, ow), device=avg.device, dtype=torch.float32)
-        c = torch.empty((avg.shape[0], oh, ow), device=avg.device, dtype=torch.float32)
-        L.check(L.load().prv2_blend_resize_frames(avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], avg.shape[2], a.data_ptr(),
-                                                  c.data_ptr(), oh, ow, _stream()), "blend_resize_frames")
-        return a, c
+    frames = avg.dim() == 3
     if DISPATCH == "torch":
-        return _tops().blend_resize(avg, cnt, oh, ow)
-    a = torch.empty((oh, ow), device=avg.device, dtype=torch.float32)
-    c = torch.empty((oh, ow), device=avg.device, dtype=torch.float32)
-    L.check(L.load().prv2_blend_resize(avg.data_ptr(), cnt.data_ptr(), avg.shape[0], avg.shape[1], a.data_ptr(),
-                                       c.data_ptr(), oh, ow, _stream()), "blend_resize")
+        return (_tops().blend_resize_frames if frames else _tops().blend_resize)(avg, cnt, oh, ow)
+    a, c = (torch.empty((*avg.shape[:-2], oh, ow), device=avg.device, dtype=torch.float32) for _ in range(2))
+    _c("blend_resize_frames" if frames else "blend_resize", avg.data_ptr(), cnt.data_ptr(), *avg.shape, a.data_ptr(), c.data_ptr(), oh, ow)
     return a, c
 
 
@@ -1531,29 +1457,21 @@ def _as_frames(avg, pred, tiles):
     return avg, pred, tiles
 
 
-def _blend_stats(paste, avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
-    """one pass step of the blend with the overlap statistics m2 / ntl (prv2_blend_*_stats): maps [H, W] with pred [k, ph, pw] /
-    tiles [k, 2], or B maps [B, H, W] with frame-major slices pred [B, k, ph, pw] / tiles [B, k, 2] as ``blend_paste_frames``"""
+def _blend_stats(step, avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
+    """one pass step of the blend with the overlap statistics m2 / ntl: maps [H, W] with pred [k, ph, pw] / tiles [k, 2], or B maps
+    [B, H, W] with frame-major slices pred [B, k, ph, pw] / tiles [B, k, 2] as ``blend_paste_frames``"""
     a3, pred, tiles = _as_frames(avg, pred, tiles)
-    c3, s3, n3 = (t.view(a3.shape) for t in (cnt, m2, ntl))
-    B, k = pred.shape[0], pred.shape[1]
-    assert tiles.shape[:2] == (B, k) and pred.stride(1) == pred.shape[2] * pred.shape[3] and tiles.stride(1) == 2
-    if DISPATCH == "torch":
-        return (_tops().blend_init_stats if paste else _tops().blend_update_stats)(a3, c3, s3, n3, pred, mask, tiles, th, tw)
-    fn = L.load().prv2_blend_paste_stats if paste else L.load().prv2_blend_update_stats
-    L.check(fn(a3.data_ptr(), c3.data_ptr(), s3.data_ptr(), n3.data_ptr(), B, a3.shape[1], a3.shape[2], pred.data_ptr(), pred.shape[-2],
-               pred.shape[-1], pred.stride(0) if B > 1 else k * pred.shape[2] * pred.shape[3], mask.data_ptr(), tiles.data_ptr(),
-               tiles.stride(0) // 2 if B > 1 else k, k, th, tw, _stream()), "blend_paste_stats" if paste else "blend_update_stats")
+    _blend_frames(step, (a3, *(t.view(a3.shape) for t in (cnt, m2, ntl))), pred, mask, tiles, th, tw, "stats")
 
 
 def blend_paste_stats(avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
     """paste: avg = p, cnt = ct, m2 = 0, ntl = 1 under every tile"""
-    _blend_stats(True, avg, cnt, m2, ntl, pred, mask, tiles, th, tw)
+    _blend_stats("paste", avg, cnt, m2, ntl, pred, mask, tiles, th, tw)
 
 
 def blend_update_stats(avg, cnt, m2, ntl, pred, mask, tiles, th, tw):
     """update: avg / cnt as ``blend_update``; ntl += 1 under every tile, m2 += ct (p - avg_old)(p - avg_new) where ct > 0"""
-    _blend_stats(False, avg, cnt, m2, ntl, pred, mask, tiles, th, tw)
+    _blend_stats("update", avg, cnt, m2, ntl, pred, mask, tiles, th, tw)
 
 
 def blend_resize_stats(avg, cnt, m2, ntl, oh, ow):
@@ -1566,8 +1484,7 @@ def blend_resize_stats(avg, cnt, m2, ntl, oh, ow):
         out = _tops().blend_resize_stats(a3, c3, s3, n3, oh, ow)
     else:
         out = tuple(torch.empty((B, oh, ow), device=avg.device, dtype=torch.float32) for _ in range(4))
-        L.check(L.load().prv2_blend_resize_stats(a3.data_ptr(), c3.data_ptr(), s3.data_ptr(), n3.data_ptr(), B, a3.shape[1], a3.shape[2],
-                                                 *(t.data_ptr() for t in out), oh, ow, _stream()), "blend_resize_stats")
+        _c("blend_resize_stats", a3.data_ptr(), c3.data_ptr(), s3.data_ptr(), n3.data_ptr(), B, a3.shape[1], a3.shape[2], *(t.data_ptr() for t in out), oh, ow)
     return tuple(t[0] for t in out) if one else tuple(out)
 
 
@@ -1583,7 +1500,7 @@ def add(a: Feat, b: Feat, out: Optional[Feat] = None) -> Feat:
     if DISPATCH == "torch":
         _tops().add_nhwc(a.view(), b.view(), out.view())
         return out
-    L.check(L.load().prv2_add(a.ptr, a.ld, b.ptr, b.ld, a.n * a.h * a.w, a.c, out.ptr, out.ld, _stream()), "add")
+    _c("add", a.ptr, a.ld, b.ptr, b.ld, a.n * a.h * a.w, a.c, out.ptr, out.ld)
     return out
 
 
@@ -1593,8 +1510,7 @@ def zoe_attractor(attr: Feat, bins: Feat, alpha: float = 300.0) -> Feat:
         y = _tops().zoe_attractor(attr.view(), bins.view(), alpha)
         return _feat_of(y, bins.c)
     out = Feat.alloc(bins.n, bins.h, bins.w, bins.c, bins.device)
-    L.check(L.load().prv2_zoe_attractor(attr.ptr, attr.ld, attr.c, bins.ptr, bins.ld, bins.c, alpha,
-                                        bins.n * bins.h * bins.w, out.ptr, out.ld, _stream()), "zoe_attractor")
+    _c("zoe_attractor", attr.ptr, attr.ld, attr.c, bins.ptr, bins.ld, bins.c, alpha, bins.n * bins.h * bins.w, out.ptr, out.ld)
     return out
 
 
@@ -1603,8 +1519,7 @@ def zoe_logbinom_depth(pt: Feat, centers: Feat, min_temp: float, max_temp: float
     if DISPATCH == "torch":
         return _tops().zoe_bins_head(pt.view(), centers.view(), min_temp, max_temp)
     depth = torch.empty((pt.n, 1, pt.h, pt.w), device=pt.device, dtype=torch.float32)
-    L.check(L.load().prv2_zoe_logbinom_depth(pt.ptr, pt.ld, centers.ptr, centers.ld, centers.c, min_temp, max_temp,
-                                             pt.n * pt.h * pt.w, depth.data_ptr(), _stream()), "zoe_logbinom_depth")
+    _c("zoe_logbinom_depth", pt.ptr, pt.ld, centers.ptr, centers.ld, centers.c, min_temp, max_temp, pt.n * pt.h * pt.w, depth.data_ptr())
     return depth
 
 
@@ -1635,8 +1550,7 @@ def depth_preprocess(depth, preprocess="log"):
     if DISPATCH == "torch":
         return _tops().depth_preprocess(d, EDGE_PRE[preprocess])
     out, ws = torch.empty_like(d), _edge_ws(d)
-    L.check(L.load().prv2_depth_preprocess(d.data_ptr(), *d.shape, EDGE_PRE[preprocess], out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-            "depth_preprocess")
+    _c("depth_preprocess", d.data_ptr(), *d.shape, EDGE_PRE[preprocess], out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 
@@ -1647,8 +1561,7 @@ def canny(image, sigma=1.0, low_threshold=0.1, high_threshold=0.2):
     if DISPATCH == "torch":
         return _tops().canny(x, gw.tolist(), float(low_threshold), float(high_threshold))
     out, ws = torch.empty(x.shape, dtype=torch.bool, device=x.device), _edge_ws(x)
-    L.check(L.load().prv2_canny(x.data_ptr(), *x.shape, gw.ctypes.data, len(gw) - 1, low_threshold, high_threshold, out.data_ptr(), ws.data_ptr(),
-                                ws.numel(), _stream()), "canny")
+    _c("canny", x.data_ptr(), *x.shape, gw.ctypes.data, len(gw) - 1, low_threshold, high_threshold, out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 
@@ -1658,7 +1571,7 @@ def edt_sq(mask):
     if DISPATCH == "torch":
         return _tops().edt_sq(m)
     out, ws = torch.empty(m.shape, dtype=torch.int32, device=m.device), _edge_ws(m)
-    L.check(L.load().prv2_edt_sq(m.data_ptr(), *m.shape, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "edt_sq")
+    _c("edt_sq", m.data_ptr(), *m.shape, out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 
@@ -1668,7 +1581,7 @@ def binary_dilate(mask, k):
     if DISPATCH == "torch":
         return _tops().binary_dilate(m, k)
     out = torch.empty_like(m)
-    L.check(L.load().prv2_binary_dilate(m.data_ptr(), *m.shape, k, out.data_ptr(), _stream()), "binary_dilate")
+    _c("binary_dilate", m.data_ptr(), *m.shape, k, out.data_ptr())
     return out
 
 
@@ -1680,8 +1593,8 @@ def boundary_stats(gt_edges, pred_edges, valid, d2_target, d2_pred, gt_ext, pred
     if DISPATCH == "torch":
         return _tops().boundary_stats(g, p, v, dt, dp, ge, pe, float(th_edges_acc))
     out, ws = torch.empty((g.shape[0], 8), dtype=torch.float64, device=g.device), _edge_ws(g)
-    L.check(L.load().prv2_boundary_stats(g.data_ptr(), p.data_ptr(), v.data_ptr(), dt.data_ptr(), dp.data_ptr(), ge.data_ptr(), pe.data_ptr(),
-                                         *g.shape, float(th_edges_acc), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "boundary_stats")
+    _c("boundary_stats", g.data_ptr(), p.data_ptr(), v.data_ptr(), dt.data_ptr(), dp.data_ptr(), ge.data_ptr(), pe.data_ptr(), *g.shape,
+       float(th_edges_acc), out.data_ptr(), ws.data_ptr(), ws.numel())
     return out
 
 
@@ -1717,8 +1630,8 @@ def order_stats(value, ranks, mask=None, invalid_val=-99.0, gate=None, gate_thr=
     counts = torch.empty((v.shape[0],), dtype=torch.int64, device=v.device)
     out = torch.empty((v.shape[0], len(ranks)), dtype=torch.float32, device=v.device)
     rk = np.asarray(ranks, dtype=np.int64)
-    L.check(lib.prv2_order_stats(v.data_ptr(), _ptr(m), float(invalid_val), _ptr(g), float(gate_thr), *v.shape, rk.ctypes.data, len(ranks),
-                                 counts.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "order_stats")
+    _c("order_stats", v.data_ptr(), _ptr(m), float(invalid_val), _ptr(g), float(gate_thr), *v.shape, rk.ctypes.data, len(ranks), counts.data_ptr(),
+       out.data_ptr(), ws.data_ptr(), ws.numel())
     return counts, out
 
 
@@ -1734,8 +1647,7 @@ def colorize_rows(value, norm, lut, invalid_mask=None, invalid_val=-99.0, backgr
     if tuple(norm.shape) != (v.shape[0], 2) or lut.dtype != torch.uint8 or lut.dim() != 2 or lut.shape[1] != 4 or not lut.is_contiguous():
         raise ValueError("colorize_rows: norm is fp32 [B, 2], lut uint8 [N + 3, 4]")
     rows = _rows(v, 3)
-    L.check(L.load().prv2_colorize_rows(v.data_ptr(), _ptr(m), float(invalid_val), *v.shape, norm.data_ptr(), lut.data_ptr(), lut.shape[0] - 3,
-                                        bg, rows.data_ptr(), rows.shape[1], _stream()), "colorize_rows")
+    _c("colorize_rows", v.data_ptr(), _ptr(m), float(invalid_val), *v.shape, norm.data_ptr(), lut.data_ptr(), lut.shape[0] - 3, bg, rows.data_ptr(), rows.shape[1])
     return rows
 
 
@@ -1745,7 +1657,7 @@ def quantize16_rows(value, scale=256.0):
     if DISPATCH == "torch":
         return _tops().quantize16_rows(v, float(scale))
     rows = _rows(v, 2)
-    L.check(L.load().prv2_quantize16_rows(v.data_ptr(), *v.shape, float(scale), rows.data_ptr(), rows.shape[1], _stream()), "quantize16_rows")
+    _c("quantize16_rows", v.data_ptr(), *v.shape, float(scale), rows.data_ptr(), rows.shape[1])
     return rows
 
 
@@ -1759,8 +1671,8 @@ def pl_uncertainty_rows(uncertainty, count_map, params, lut):
     if tuple(params.shape) != (u.shape[0], 5) or params.dtype != torch.float64 or not params.is_contiguous():
         raise ValueError("pl_uncertainty_rows: params is float64 [B, 5]")
     r16, rgb = _rows(u, 2), _rows(u, 3)
-    L.check(L.load().prv2_pl_uncertainty_rows(u.data_ptr(), c.data_ptr(), *u.shape, params.data_ptr(), lut.data_ptr(), lut.shape[0] - 3,
-                                              r16.data_ptr(), r16.shape[1], rgb.data_ptr(), rgb.shape[1], _stream()), "pl_uncertainty_rows")
+    _c("pl_uncertainty_rows", u.data_ptr(), c.data_ptr(), *u.shape, params.data_ptr(), lut.data_ptr(), lut.shape[0] - 3, r16.data_ptr(), r16.shape[1],
+       rgb.data_ptr(), rgb.shape[1])
     return r16, rgb
 
 
@@ -1770,7 +1682,7 @@ def mask_rows(mask):
     if DISPATCH == "torch":
         return _tops().mask_rows(m)
     rows = _rows(m, 1)
-    L.check(L.load().prv2_mask_rows(m.data_ptr(), *m.shape, rows.data_ptr(), rows.shape[1], _stream()), "mask_rows")
+    _c("mask_rows", m.data_ptr(), *m.shape, rows.data_ptr(), rows.shape[1])
     return rows
 
 
@@ -1780,7 +1692,7 @@ def upsample_bilinear_map(x, oh, ow):
     if DISPATCH == "torch":
         return _tops().upsample_bilinear_map(x, int(oh), int(ow))
     y = torch.empty((x.shape[0], int(oh), int(ow)), dtype=torch.float32, device=x.device)
-    L.check(L.load().prv2_upsample_bilinear_map(x.data_ptr(), *x.shape, y.data_ptr(), int(oh), int(ow), _stream()), "upsample_bilinear_map")
+    _c("upsample_bilinear_map", x.data_ptr(), *x.shape, y.data_ptr(), int(oh), int(ow))
     return y
 
 
@@ -1801,8 +1713,7 @@ def deflate_rows(rows, length):
     out = torch.empty((rows.shape[0], bound), dtype=torch.uint8, device=rows.device)
     out_bytes = torch.empty((rows.shape[0],), dtype=torch.int64, device=rows.device)
     ws = torch.empty((wsb,), dtype=torch.uint8, device=rows.device)
-    L.check(lib.prv2_deflate_rows(rows.data_ptr(), rows.shape[0], length, rows.shape[1], out.data_ptr(), bound, out_bytes.data_ptr(),
-                                  ws.data_ptr(), wsb, _stream()), "deflate_rows")
+    _c("deflate_rows", rows.data_ptr(), rows.shape[0], length, rows.shape[1], out.data_ptr(), bound, out_bytes.data_ptr(), ws.data_ptr(), wsb)
     return out, out_bytes
 
 
@@ -1819,7 +1730,7 @@ def u8_image(src, swap_rb=True):
     if DISPATCH == "torch":
         return _tops().u8_image(src, bool(swap_rb))
     dst = torch.empty((3, src.shape[0], src.shape[1]), dtype=torch.float32, device=src.device)
-    L.check(L.load().prv2_u8_image(src.data_ptr(), src.shape[0], src.shape[1], int(bool(swap_rb)), dst.data_ptr(), _stream()), "u8_image")
+    _c("u8_image", src.data_ptr(), src.shape[0], src.shape[1], int(bool(swap_rb)), dst.data_ptr())
     return dst
 
 
@@ -1832,8 +1743,7 @@ def disp_gt(disp, factor, th=1.0):
     if DISPATCH == "torch":
         return _tops().disp_gt(disp, float(factor), float(th))
     depth, boundary = torch.empty_like(disp), torch.empty(disp.shape, dtype=torch.uint8, device=disp.device)
-    L.check(L.load().prv2_disp_gt(disp.data_ptr(), *disp.shape, float(factor), float(th), depth.data_ptr(), boundary.data_ptr(), _stream()),
-            "disp_gt")
+    _c("disp_gt", disp.data_ptr(), *disp.shape, float(factor), float(th), depth.data_ptr(), boundary.data_ptr())
     return depth, boundary
 
 
@@ -1865,6 +1775,5 @@ def depth_metrics(gt, pred, boundary=None, region=None, min_depth=1e-3, max_dept
         raise ValueError(f"depth_metrics: bad frame shape {tuple(g.shape)}")
     ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
     out = torch.empty((g.shape[0], 3 if r is not None else 1, 12), dtype=torch.float64, device=g.device)
-    L.check(lib.prv2_depth_metrics(g.data_ptr(), p.data_ptr(), _ptr(b), _ptr(r), *g.shape, float(min_depth), float(max_depth), y0, y1, x0, x1,
-                                   out.data_ptr(), ws.data_ptr(), wsb, _stream()), "depth_metrics")
+    _c("depth_metrics", g.data_ptr(), p.data_ptr(), _ptr(b), _ptr(r), *g.shape, float(min_depth), float(max_depth), y0, y1, x0, x1, out.data_ptr(), ws.data_ptr(), wsb)
     return out

@@ -452,3 +452,47 @@ def test_winograd_f23_study_identity_and_error_growth():
     err = {(k, mode): np.sqrt(((f(x, w, mode) - ref) ** 2).mean()) / den for k, f in (("direct", m.direct), ("winograd", m.winograd)) for mode in ("bf16x3", "f16f6")}
     assert err[("winograd", "bf16x3")] < 2.0 * err[("direct", "bf16x3")] < 1.2e-5
     assert err[("winograd", "f16f6")] < 2.0 * err[("direct", "f16f6")] and err[("winograd", "bf16x3")] < err[("direct", "f16f6")]
+
+
+def test_conv_desc_and_ups_src_fill_every_field_of_the_c_structs():
+    """ops._conv_desc / ops._ups_src are the only places that build prv2_conv_desc / prv2_ups_src: every field of the two ctypes structs
+    (iterated from ``_fields_``: a field added later fails here until it is listed) for the keyword sets of the five kinds of caller"""
+    from types import SimpleNamespace
+
+    from patchrefinerv2_amd import lib as L
+    from patchrefinerv2_amd import ops
+    x = SimpleNamespace(n=2, h=20, w=33, c=34, ld=36, ptr=0x7000)
+    cw = ops.ConvW(w=None, bias=None, cout=40, cin=34, kh=3, kw=5, stride=2, pad=1, convt_k=0, prec=L.PREC_BF16X3, same_pad=True)
+    base = dict(n=2, h=20, w=33, cin=34, cout=40, kh=3, kw=5, stride=2, pad=1, ldx=36, ldy=44, x_bstride=0, y_bstride=0, relu_in=0, act=0, convt_k=0,
+                ld_mul=0, ld_res=0, ld_res2=0, prec=1, force_generic=0, ln_eps=float(np.float32(1e-6)), part=0, same_pad=1, fmt=0)
+    eps = 2.0 ** -10
+    callers = {
+        "supported": (dict(), base),
+        "conv2d": (dict(act=ops.ACT_GELU, relu_in=True, ld_mul=48, ld_res=52, ld_res2=56, ln_eps=eps, x_bstride=1 << 33, force_generic=True),
+                   dict(base, act=2, relu_in=1, ld_mul=48, ld_res=52, ld_res2=56, ln_eps=eps, x_bstride=1 << 33, force_generic=1)),
+        "conv2d_ups": (dict(act=ops.ACT_RELU, ld_res=52, ln_eps=eps), dict(base, act=1, ld_res=52, ln_eps=eps)),
+        "conv2d_tail": (dict(act=ops.ACT_SILU, ln_eps=eps), dict(base, act=5, ln_eps=eps)),
+        "conv2d_pre": (dict(act=ops.ACT_SIGMOID, ld_res=44, ln_eps=eps), dict(base, act=3, ld_res=44, ln_eps=eps)),
+        "conv3x3_ln_gate": (dict(act=ops.ACT_RELU, relu_in=True, ld_mul=256, ld_res=260, ln_eps=eps, fmt=L.FMT_X_X2 | L.FMT_MUL_X2),
+                            dict(base, act=1, relu_in=1, ld_mul=256, ld_res=260, ln_eps=eps, fmt=3)),
+    }
+    names = [name for name, _ in L.ConvDesc._fields_]
+    assert sorted(names) == sorted(base)
+    for caller, (kw, want) in callers.items():
+        d = ops._conv_desc(x, cw, 44, **kw)
+        for name in names:
+            assert getattr(d, name) == want[name], (caller, name)
+    # the fp16 + fp6 layers: a ConvWF6 has one layer shape
+    d = ops._conv_desc(x, ops.ConvWF6(None, None, 256, 64, 1.0), 256, relu_in=True, ld_res=260, fmt=L.FMT_Y_X2)
+    want = dict(base, cin=64, cout=256, kh=3, kw=3, stride=1, pad=1, ldy=256, relu_in=1, ld_res=260, prec=3, same_pad=0, fmt=4)
+    for name in names:
+        assert getattr(d, name) == want[name], ("conv3x3_f6", name)
+    assert ops._gate_fmt(SimpleNamespace(x2=True), SimpleNamespace(x2=True)) == 3 and ops._gate_fmt(SimpleNamespace(x2=True)) == 1
+    assert ops._gate_fmt(x, SimpleNamespace(x2=False)) == 0
+
+    u = SimpleNamespace(n=2, h=10, w=17, c=32, ld=36, ptr=0x7000)
+    us, want = ops._ups_src(u), dict(x=0x7000, h=10, w=17, ld=36, channels=32, bstride=0)
+    names = [name for name, _ in L.UpsSrc._fields_]
+    assert sorted(names) == sorted(want)
+    for name in names:
+        assert getattr(us, name) == want[name], name
