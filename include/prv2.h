@@ -729,6 +729,37 @@ int prv2_depth_metrics(const float* gt, const float* pred, const uint8_t* bounda
                        int32_t w, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* sums,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The ground-truth formats of the general dataset (estimator/datasets/general_dataset.py:75-158, class DepthMap), decoded from the
+ * raw samples as the host read them from the file.  Additive as well: the ABI version does not change. */
+enum prv2_gt_kind {
+  PRV2_GT_ETH3D = 0,      /* :103-111  fp32 depth; non-finite -> 0; edges of the cleaned depth                              */
+  PRV2_GT_MIDDLEBURY = 1, /* :113-139 + datasets/utils.py:5-60  fp32 PFM payload (disparity); edges of the disparity with +inf -> 0 */
+  PRV2_GT_CITYSCAPES = 2  /* :141-151  uint16 disparity PNG samples; edges of the depth                                      */
+};
+
+/* One pass over src [h, w] (fp32 for ETH3D / MIDDLEBURY, uint16 for CITYSCAPES) -> depth fp32 [h, w] and boundary uint8 0/1 [h, w]
+ * = get_boundaries(e, th, dilation=0) (metric.py:74-85; the rule of prv2_disp_gt) of the map e the reference takes its edges from.
+ * Every fp32 operation is numpy's IEEE operation in numpy's order (divisions are divisions):
+ *   ETH3D       d = isfinite(v) ? v : 0                                   depth = d;  e = d
+ *   MIDDLEBURY  inv = (v == +inf);  t = (factor / (v + doffs)) / 1000      depth = inv ? 0 : t;  e = inv ? 0 : v
+ *   CITYSCAPES  f = float(v);  t = v > 0 ? (f - 1) / 256 : f;  q = factor / t    depth = isfinite(q) ? q : 0;  e = depth
+ * (the reference's factor there is float32(0.209313 * 2262.52); doffs is read by MIDDLEBURY only).  flip != 0: the rows of src
+ * are bottom-to-top (a PFM payload): output row y reads source row h - 1 - y.  byteswap != 0: the samples are of the other byte
+ * order and are swapped as they are read. */
+int prv2_gt_decode(const void* src, int32_t kind, int32_t h, int32_t w, float factor, float doffs, float th, int32_t flip,
+                   int32_t byteswap, float* depth, uint8_t* boundary, void* stream);
+
+/* prv2_depth_metrics for a prediction of another resolution (compute_metrics' F.interpolate(pred, gt.shape, mode='bilinear',
+ * align_corners=False), metric.py:94-95, taken into the scoring kernel: the resized map is never written).  pred: fp32 [n, ph, pw];
+ * everything else as prv2_depth_metrics, workspace of prv2_depth_metrics_workspace_bytes(n, h, w) bytes.  The value at (y, x), in
+ * fp32 and PyTorch's formulation: sy = max(0, (ph / h) * (y + 0.5) - 0.5) (the scale an fp32 division), y0 = (int)sy,
+ * y1 = min(y0 + 1, ph - 1), ly = sy - y0, the same in x, and
+ *   p = (1 - ly) * ((1 - lx) * pred[y0, x0] + lx * pred[y0, x1]) + ly * ((1 - lx) * pred[y1, x0] + lx * pred[y1, x1]);
+ * NaN -> min_depth and the clamps apply to p.  ph == h and pw == w runs prv2_depth_metrics itself (the same bits). */
+int prv2_depth_metrics_lowres(const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n, int32_t h,
+                              int32_t w, int32_t ph, int32_t pw, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0,
+                              int32_t x1, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 //
 //   u8_image_kernel       raw BGR bytes [h, w, 3] -> CHW fp32 / 255                                (u4k_dataset.py:125-147)
 //   disp_gt_kernel        disparity -> depth = factor / disp and the boundary map, one pass        (u4k_dataset.py:128-129,216)
+//   gt_decode_kernel      the general dataset's ground truth (ETH3D / Middlebury PFM / Cityscapes PNG samples) -> depth and the
+//                         boundary map, one pass                                                   (general_dataset.py:103-151)
 //   depth_metrics_kernel  the twelve sums of compute_errors + soft_edge_error of B frames, for up to three pixel sets at once
 //   metrics_final_kernel  the per-block partials of a frame summed in block order
 //
@@ -11,6 +13,8 @@
 // values, each thread keeps its 12 x S accumulators in registers, a wave reduces by shuffles, the four waves through LDS, and every
 // block stores its partial; the final kernel adds the partials in block order.  No floating-point atomics anywhere: the sums are the
 // same bits on every call.  Only boundary pixels (sparse) look at the 3 x 3 neighbourhood of gt, straight from L2.
+// The LOWRES instances sample a prediction of another resolution where the others load it (bilinear, align_corners=False, the
+// operations of PyTorch's upsample_bilinear2d kernel): the resized map is never written.
 #include <limits.h>
 
 #include "common.h"
@@ -105,6 +109,111 @@ __global__ void __launch_bounds__(256) disp_gt_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// gt_decode: the raw samples of four pixels as 32-bit words (a uint16 sample zero-extended), zero behind the row's end
+template <int KIND>
+__device__ __forceinline__ void load_raw4(const void* __restrict__ src, int64_t row, int x0, int w, int vec, int bswap, uint32_t* r) {
+  if (KIND == PRV2_GT_CITYSCAPES) {
+    const uint16_t* s = reinterpret_cast<const uint16_t*>(src) + row * w;
+    if (vec) {
+      const uint2 t = *reinterpret_cast<const uint2*>(s + x0);
+      r[0] = t.x & 0xffffu, r[1] = t.x >> 16, r[2] = t.y & 0xffffu, r[3] = t.y >> 16;
+    } else {
+      for (int k = 0; k < 4; ++k) r[k] = x0 + k < w ? s[x0 + k] : 0u;
+    }
+    if (bswap)
+      for (int k = 0; k < 4; ++k) r[k] = ((r[k] & 0xffu) << 8) | (r[k] >> 8);
+  } else {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(src) + row * w;
+    if (vec) {
+      const uint4 t = *reinterpret_cast<const uint4*>(s + x0);
+      r[0] = t.x, r[1] = t.y, r[2] = t.z, r[3] = t.w;
+    } else {
+      for (int k = 0; k < 4; ++k) r[k] = x0 + k < w ? s[x0 + k] : 0u;
+    }
+    if (bswap)
+      for (int k = 0; k < 4; ++k) r[k] = __builtin_bswap32(r[k]);
+  }
+}
+
+template <int KIND>
+__device__ __forceinline__ uint32_t load_raw1(const void* __restrict__ src, int64_t row, int x, int w, int bswap) {
+  if (KIND == PRV2_GT_CITYSCAPES) {
+    const uint32_t v = reinterpret_cast<const uint16_t*>(src)[row * w + x];
+    return bswap ? ((v & 0xffu) << 8) | (v >> 8) : v;
+  }
+  const uint32_t v = reinterpret_cast<const uint32_t*>(src)[row * w + x];
+  return bswap ? __builtin_bswap32(v) : v;
+}
+
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// one sample -> its depth and the value the reference takes its edges from (numpy's float32 operations in numpy's order)
+template <int KIND>
+__device__ __forceinline__ void gt_decode1(uint32_t raw, float factor, float doffs, float& depth, float& edge) {
+  if (KIND == PRV2_GT_ETH3D) {  // np.nan_to_num(depth, posinf=0., neginf=0., nan=0.)
+    const float v = __uint_as_float(raw);
+    depth = edge = finite_f32(v) ? v : 0.f;
+  } else if (KIND == PRV2_GT_MIDDLEBURY) {  // invalid = disp == inf; depth = factor / (disp + doffs) / 1000; both 0 where invalid
+    const float v = __uint_as_float(raw);
+    const bool inv = raw == 0x7f800000u;
+    const float t = (factor / (v + doffs)) / 1000.0f;
+    depth = inv ? 0.f : t;
+    edge = inv ? 0.f : v;
+  } else {  // img_d[img_d > 0] = (img_d[img_d > 0] - 1) / 256; depth = factor / img_d; nan_to_num
+    const float f = (float)raw;
+    const float t = raw > 0u ? (f - 1.0f) / 256.0f : f;
+    const float q = factor / t;
+    depth = edge = finite_f32(q) ? q : 0.f;
+  }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256) gt_decode_kernel(const void* __restrict__ src, float* __restrict__ depth, uint8_t* __restrict__ boundary,
+                                                        int h, int w, float factor, float doffs, float th, int flip, int bswap, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    // output row y is source row sy; the rows above / below it in the output are sy - sd / sy + sd
+    const int64_t sy = flip ? h - 1 - y : y, sd = flip ? -1 : 1;
+    uint32_t rc[4], ru[4], rd[4];
+    float d[4], c[4], up[4], dn[4], left = 0.f, right = 0.f, unused;
+    load_raw4<KIND>(src, sy, x0, w, vec, bswap, rc);
+    for (int k = 0; k < 4; ++k) gt_decode1<KIND>(rc[k], factor, doffs, d[k], c[k]);
+    if (y > 0) {
+      load_raw4<KIND>(src, sy - sd, x0, w, vec, bswap, ru);
+      for (int k = 0; k < 4; ++k) gt_decode1<KIND>(ru[k], factor, doffs, unused, up[k]);
+    }
+    if (y + 1 < h) {
+      load_raw4<KIND>(src, sy + sd, x0, w, vec, bswap, rd);
+      for (int k = 0; k < 4; ++k) gt_decode1<KIND>(rd[k], factor, doffs, unused, dn[k]);
+    }
+    if (x0 > 0) gt_decode1<KIND>(load_raw1<KIND>(src, sy, x0 - 1, w, bswap), factor, doffs, unused, left);
+    if (x0 + 4 < w) gt_decode1<KIND>(load_raw1<KIND>(src, sy, x0 + 4, w, bswap), factor, doffs, unused, right);
+    uint8_t e[4];
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + k;
+      bool b = false;  // the rule of disp_gt_kernel
+      if (y > 0) b |= fabsf(c[k] - up[k]) > th;
+      if (y + 1 < h) b |= fabsf(dn[k] - c[k]) > th;
+      if (x > 0) b |= fabsf(c[k] - (k ? c[k - 1] : left)) > th;
+      if (x + 1 < w) b |= fabsf((k < 3 ? c[k + 1] : right) - c[k]) > th;
+      e[k] = b ? 1 : 0;
+    }
+    const int64_t o = (int64_t)y * w + x0;
+    if (vec) {
+      *reinterpret_cast<float4*>(depth + o) = make_float4(d[0], d[1], d[2], d[3]);
+      *reinterpret_cast<uint32_t*>(boundary + o) = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16 | (uint32_t)e[3] << 24;
+    } else {
+      for (int k = 0; k < 4 && x0 + k < w; ++k) {
+        depth[o + k] = d[k];
+        boundary[o + k] = e[k];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 struct MetricArgs {
   const float* gt;
   const float* pred;
@@ -113,7 +222,20 @@ struct MetricArgs {
   int h, w, rows_per_block, vec;
   float mn, mx;
   int y0, y1, x0, x1;
+  int ph, pw;        // LOWRES: pred is [n, ph, pw]
+  float sch, scw;    // LOWRES: ph / h and pw / w (fp32 divisions)
 };
+
+// F.interpolate(mode='bilinear', align_corners=False) at one output coordinate, as PyTorch's kernel computes it (its compiler
+// contracts a * b + c, so the fused operations are spelled out here: this file is built with -ffp-contract=off): the source
+// coordinate fma(scale, dst + 0.5, -0.5) clamped at 0, the lower index, whether there is an upper one, and the weight lambda
+__device__ __forceinline__ void bilinear_src(float scale, int dst, int n_in, int& i0, int& step, float& lam) {
+  float s = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
+  s = s < 0.f ? 0.f : s;
+  i0 = min((int)s, n_in - 1);  // (never beyond the map, whatever the rounding of scale)
+  step = i0 < n_in - 1 ? 1 : 0;
+  lam = s - (float)i0;
+}
 
 // NaN-propagating minimum (np.minimum / torch.minimum)
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (b < a ? b : a); }
@@ -133,13 +255,13 @@ __device__ __forceinline__ float soft_edge(const float* __restrict__ g, int h, i
   return best;
 }
 
-template <int S>
+template <int S, bool LOWRES>
 __global__ void __launch_bounds__(256) depth_metrics_kernel(MetricArgs a, double* __restrict__ part) {
   __shared__ double sh[4][S * kTerms];
   const int f = blockIdx.y, h = a.h, w = a.w;
   const int64_t fb = (int64_t)f * h * w;
   const float* __restrict__ gt = a.gt + fb;
-  const float* __restrict__ pred = a.pred + fb;
+  const float* __restrict__ pred = a.pred + (LOWRES ? (int64_t)f * a.ph * a.pw : fb);
   const uint8_t* __restrict__ bnd = a.boundary ? a.boundary + fb : nullptr;
   const uint8_t* __restrict__ reg = a.region ? a.region + fb : nullptr;
   double acc[S][kTerms];
@@ -151,12 +273,32 @@ __global__ void __launch_bounds__(256) depth_metrics_kernel(MetricArgs a, double
   const int q0 = a.x0 / 4, q1 = (min(a.x1, w) + 3) / 4;  // the quads that touch the crop's columns
   for (int y = ya; y < yb; ++y) {
     const int64_t ro = (int64_t)y * w;
+    int sy0 = 0, sys = 0;
+    float ly = 0.f;
+    if (LOWRES) bilinear_src(a.sch, y, a.ph, sy0, sys, ly);
+    const float* __restrict__ pr0 = pred + (int64_t)sy0 * a.pw;  // LOWRES: the two source rows of output row y
+    const float* __restrict__ pr1 = pr0 + (int64_t)sys * a.pw;
     for (int q = q0 + (int)threadIdx.x; q < q1; q += 256) {
       const int x0 = q * 4;
       float g[4], p[4];
       uint8_t b[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
       load4(gt + ro, x0, w, a.vec, g);
-      load4(pred + ro, x0, w, a.vec, p);
+      if (LOWRES) {
+        const float hy = 1.0f - ly;
+        for (int k = 0; k < 4; ++k) {
+          p[k] = 0.f;
+          if (x0 + k >= w) continue;
+          int sx0, sxs;
+          float lx;
+          bilinear_src(a.scw, x0 + k, a.pw, sx0, sxs, lx);
+          const float hx = 1.0f - lx;
+          const float top = __builtin_fmaf(hx, pr0[sx0], lx * pr0[sx0 + sxs]);
+          const float bot = __builtin_fmaf(hx, pr1[sx0], lx * pr1[sx0 + sxs]);
+          p[k] = __builtin_fmaf(hy, top, ly * bot);
+        }
+      } else {
+        load4(pred + ro, x0, w, a.vec, p);
+      }
       if (a.vec) {
         if (bnd) {
           const uint32_t t = *reinterpret_cast<const uint32_t*>(bnd + ro + x0);
@@ -275,34 +417,80 @@ extern "C" int64_t prv2_depth_metrics_workspace_bytes(int32_t n, int32_t h, int3
   return (int64_t)n * row_blocks(h) * kMaxSets * kTerms * (int64_t)sizeof(double);
 }
 
-extern "C" int prv2_depth_metrics(const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n, int32_t h,
-                                  int32_t w, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* sums,
-                                  void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* name = "depth_metrics";
+// prv2_depth_metrics (ph == h, pw == w: the prediction is loaded) and prv2_depth_metrics_lowres (it is sampled)
+static int depth_metrics_impl(const char* name, const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n,
+                              int32_t h, int32_t w, int32_t ph, int32_t pw, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0,
+                              int32_t x1, double* sums, void* workspace, int64_t workspace_bytes, void* stream) {
   PRV2_REQUIRE(gt && pred && sums, "%s: null pointer", name);
   PRV2_REQUIRE(n >= 1 && n <= 65535, "%s: frame count %d out of range [1, 65535]", name, n);
   PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE(ph >= 1 && pw >= 1, "%s: bad prediction shape %d x %d", name, ph, pw);
   PRV2_REQUIRE((int64_t)n * h * w < (int64_t)INT_MAX, "%s: %d frames of %d x %d exceed 2^31 pixels", name, n, h, w);
+  PRV2_REQUIRE((int64_t)n * ph * pw < (int64_t)INT_MAX, "%s: %d predictions of %d x %d exceed 2^31 pixels", name, n, ph, pw);
   PRV2_REQUIRE(y0 >= 0 && y0 <= y1 && y1 <= h && x0 >= 0 && x0 <= x1 && x1 <= w, "%s: crop rows [%d, %d) columns [%d, %d) outside %d x %d", name,
                y0, y1, x0, x1, h, w);
   PRV2_REQUIRE(workspace != nullptr, "%s: null workspace", name);
   const int64_t need = prv2_depth_metrics_workspace_bytes(n, h, w);
   PRV2_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes < %lld (prv2_depth_metrics_workspace_bytes)", name,
                (long long)workspace_bytes, (long long)need);
+  const bool lowres = ph != h || pw != w;
   MetricArgs a;
   a.gt = gt, a.pred = pred, a.boundary = boundary, a.region = region;
   a.h = h, a.w = w, a.rows_per_block = rows_per_block(h);
-  a.vec = w % 4 == 0 && aligned(gt, 16) && aligned(pred, 16) && aligned(boundary, 4) && aligned(region, 4);
+  a.vec = w % 4 == 0 && aligned(gt, 16) && (lowres || aligned(pred, 16)) && aligned(boundary, 4) && aligned(region, 4);
   a.mn = min_depth, a.mx = max_depth;
   a.y0 = y0, a.y1 = y1, a.x0 = x0, a.x1 = x1;
+  a.ph = ph, a.pw = pw;
+  a.sch = (float)ph / (float)h, a.scw = (float)pw / (float)w;
   const int nblk = row_blocks(h), sets = region ? kMaxSets : 1;
   double* part = (double*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  if (region)
-    hipLaunchKernelGGL(depth_metrics_kernel<kMaxSets>, dim3(nblk, n), dim3(256), 0, s, a, part);
+  const dim3 grid(nblk, n), block(256);
+  if (region && lowres)
+    hipLaunchKernelGGL((depth_metrics_kernel<kMaxSets, true>), grid, block, 0, s, a, part);
+  else if (region)
+    hipLaunchKernelGGL((depth_metrics_kernel<kMaxSets, false>), grid, block, 0, s, a, part);
+  else if (lowres)
+    hipLaunchKernelGGL((depth_metrics_kernel<1, true>), grid, block, 0, s, a, part);
   else
-    hipLaunchKernelGGL(depth_metrics_kernel<1>, dim3(nblk, n), dim3(256), 0, s, a, part);
+    hipLaunchKernelGGL((depth_metrics_kernel<1, false>), grid, block, 0, s, a, part);
   hipLaunchKernelGGL(metrics_final_kernel, dim3(n), dim3(64), 0, s, part, sums, nblk, sets * kTerms);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_depth_metrics(const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n, int32_t h,
+                                  int32_t w, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* sums,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return depth_metrics_impl("depth_metrics", gt, pred, boundary, region, n, h, w, h, w, min_depth, max_depth, y0, y1, x0, x1, sums, workspace,
+                            workspace_bytes, stream);
+}
+
+extern "C" int prv2_depth_metrics_lowres(const float* gt, const float* pred, const uint8_t* boundary, const uint8_t* region, int32_t n, int32_t h,
+                                         int32_t w, int32_t ph, int32_t pw, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0,
+                                         int32_t x1, double* sums, void* workspace, int64_t workspace_bytes, void* stream) {
+  return depth_metrics_impl("depth_metrics_lowres", gt, pred, boundary, region, n, h, w, ph, pw, min_depth, max_depth, y0, y1, x0, x1, sums,
+                            workspace, workspace_bytes, stream);
+}
+
+extern "C" int prv2_gt_decode(const void* src, int32_t kind, int32_t h, int32_t w, float factor, float doffs, float th, int32_t flip,
+                              int32_t byteswap, float* depth, uint8_t* boundary, void* stream) {
+  const char* name = "gt_decode";
+  PRV2_REQUIRE(src && depth && boundary, "%s: null pointer", name);
+  PRV2_REQUIRE(kind == PRV2_GT_ETH3D || kind == PRV2_GT_MIDDLEBURY || kind == PRV2_GT_CITYSCAPES, "%s: unknown kind %d (enum prv2_gt_kind)", name,
+               kind);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE((int64_t)h * w < (int64_t)INT_MAX, "%s: %d x %d exceeds 2^31 pixels", name, h, w);
+  const int vec = w % 4 == 0 && aligned(src, kind == PRV2_GT_CITYSCAPES ? 8 : 16) && aligned(depth, 16) && aligned(boundary, 4);
+  const dim3 grid(flat_grid((int64_t)h * cdiv(w, 4), 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  const int fl = flip ? 1 : 0, bs = byteswap ? 1 : 0;
+  if (kind == PRV2_GT_ETH3D)
+    hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_ETH3D>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
+  else if (kind == PRV2_GT_MIDDLEBURY)
+    hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_MIDDLEBURY>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
+  else
+    hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_CITYSCAPES>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }

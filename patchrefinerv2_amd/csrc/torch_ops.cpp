@@ -1149,6 +1149,38 @@ Tensor depth_metrics(const Tensor& gt, const Tensor& pred, const optional<Tensor
      "depth_metrics");
   return sums;
 }
+// the general dataset's ground truth (enum prv2_gt_kind): fp32 (ETH3D, Middlebury) or uint16 (Cityscapes) samples [h, w]
+std::tuple<Tensor, Tensor> gt_decode(const Tensor& src, int64_t kind, double factor, double doffs, double th, bool flip, bool byteswap) {
+  TORCH_CHECK(src.is_cuda(), "prv2: src must be a GPU tensor (there is no CPU path)");
+  TORCH_CHECK(kind == PRV2_GT_ETH3D || kind == PRV2_GT_MIDDLEBURY || kind == PRV2_GT_CITYSCAPES, "prv2::gt_decode: unknown kind ", kind);
+  const auto want = kind == PRV2_GT_CITYSCAPES ? at::kUInt16 : at::kFloat;
+  TORCH_CHECK(src.scalar_type() == want && src.dim() == 2 && src.is_contiguous(), "prv2::gt_decode: src must be a contiguous [h, w] tensor of ",
+              kind == PRV2_GT_CITYSCAPES ? "uint16" : "float32");
+  Tensor depth = at::empty(src.sizes(), src.options().dtype(at::kFloat)), boundary = at::empty(src.sizes(), src.options().dtype(at::kByte));
+  Launch L(src);
+  ok(prv2_gt_decode(src.data_ptr(), (int)kind, (int)src.size(0), (int)src.size(1), (float)factor, (float)doffs, (float)th, flip ? 1 : 0,
+                    byteswap ? 1 : 0, depth.data_ptr<float>(), (uint8_t*)boundary.data_ptr(), L.stream), "gt_decode");
+  return {depth, boundary};
+}
+Tensor depth_metrics_lowres(const Tensor& gt, const Tensor& pred, const optional<Tensor>& boundary, const optional<Tensor>& region,
+                            double min_depth, double max_depth, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
+  dev_frames(gt, "gt", at::kFloat);
+  dev_frames(pred, "pred", at::kFloat);
+  TORCH_CHECK(pred.size(0) == gt.size(0) && pred.device() == gt.device(), "prv2::depth_metrics_lowres: pred must hold gt's ", gt.size(0),
+              " frames on its device");
+  const uint8_t* b = opt_mask(boundary, gt, "boundary");
+  const uint8_t* r = opt_mask(region, gt, "region");
+  const int64_t bytes = prv2_depth_metrics_workspace_bytes((int)gt.size(0), (int)gt.size(1), (int)gt.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::depth_metrics_lowres: bad frame shape ", gt.sizes());
+  Tensor ws = at::empty({bytes}, gt.options().dtype(at::kByte));
+  Tensor sums = at::empty({gt.size(0), r ? 3 : 1, 12}, gt.options().dtype(at::kDouble));
+  Launch L(gt);
+  ok(prv2_depth_metrics_lowres(gt.data_ptr<float>(), pred.data_ptr<float>(), b, r, (int)gt.size(0), (int)gt.size(1), (int)gt.size(2),
+                               (int)pred.size(1), (int)pred.size(2), (float)min_depth, (float)max_depth, (int)y0, (int)y1, (int)x0, (int)x1,
+                               sums.data_ptr<double>(), ws.data_ptr(), ws.numel(), L.stream),
+     "depth_metrics_lowres");
+  return sums;
+}
 
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
@@ -1293,6 +1325,9 @@ TORCH_LIBRARY(prv2, m) {
   m.def("disp_gt(Tensor disp, float factor, float th) -> (Tensor, Tensor)");
   m.def("depth_metrics(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, int x0, "
         "int x1) -> Tensor");
+  m.def("gt_decode(Tensor src, int kind, float factor, float doffs, float th, bool flip, bool byteswap) -> (Tensor, Tensor)");
+  m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
+        "int x0, int x1) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1374,4 +1409,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("u8_image", &u8_image);
   m.impl("disp_gt", &disp_gt);
   m.impl("depth_metrics", &depth_metrics);
+  m.impl("gt_decode", &gt_decode);
+  m.impl("depth_metrics_lowres", &depth_metrics_lowres);
 }

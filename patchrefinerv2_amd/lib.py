@@ -163,6 +163,8 @@ SIGNATURES = {
     "prv2_disp_gt": (_I, [_P, _I, _I, _F, _F, _P, _P, _P]),
     "prv2_depth_metrics_workspace_bytes": (_L, [_I, _I, _I]),
     "prv2_depth_metrics": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
+    "prv2_gt_decode": (_I, [_P, _I, _I, _I, _F, _F, _F, _I, _I, _P, _P, _P]),
+    "prv2_depth_metrics_lowres": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
 }
 
 _lib = None

@@ -5,7 +5,8 @@ soft_edge_error     estimator/utils/metric.py:53-72   (min |gt shifted - pred| o
 get_boundaries      estimator/utils/metric.py:74-85   (disparity jumps > th; dilation needs cv2 -> dilation=0 only)
 compute_metrics     estimator/utils/metric.py:87-149  (resize, clamp, valid / crop masks, optional SEE on gt edges)
 colorize            estimator/utils/color.py:95-158   (percentile normalisation + matplotlib colour map, RGBA uint8)
-compute_metrics_fused  the same metrics from one fused GPU pass (csrc/evalgt.hip), optionally for three pixel sets at once
+compute_metrics_fused  the same metrics from one fused GPU pass (csrc/evalgt.hip), optionally for three pixel sets at once and with the
+                       resize of a low-resolution prediction inside that pass (fuse_resize)
 
 Pinned by tests/golden/output_stage.npz (the reference functions imported by oracle/make_golden.py).
 """
@@ -179,29 +180,33 @@ def metrics_from_sums(s, with_see: bool) -> dict:
 
 @torch.no_grad()
 def compute_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu",
-                          min_depth_eval=0.1, max_depth_eval=10, disp_gt_edges=None, additional_mask=None, region=None):
+                          min_depth_eval=0.1, max_depth_eval=10, disp_gt_edges=None, additional_mask=None, region=None, fuse_resize=False):
     """``compute_metrics`` (estimator/utils/metric.py:87-149) from one fused pass on the GPU (csrc/evalgt.hip, ops.depth_metrics): the
     same clamping, masks, crops, error formulas and soft-edge error as ``compute_metrics_device``, as twelve float64 sums per frame
     and ONE D2H of them per call.  ``region`` (a mask) adds ``edge_*`` (inside it) and ``noedge_*`` (outside it) copies of every key
     from the same read -- the three scoring calls of tester.ImageDataset._edge_metrics in one.  ``additional_mask`` scores inside
     that mask only, as in compute_metrics.  A dict for one map ([H, W] / [1, 1, H, W]), a list of dicts for B maps.  Inputs that
-    are on the host are copied to the GPU: there is no CPU path."""
+    are on the host are copied to the GPU: there is no CPU path.  ``fuse_resize``: a prediction of another resolution is sampled inside
+    the scoring kernel (ops.depth_metrics_lowres: the operations of F.interpolate, without writing the resized map) instead of being
+    resized first; the default keeps the resize."""
     from . import ops
     if additional_mask is not None and region is not None:
         raise ValueError("compute_metrics_fused: give additional_mask or region, not both")
     dev = pred.device if pred.is_cuda else (gt.device if gt.is_cuda else torch.device("cuda"))
     gt, pred = gt.to(dev), pred.to(dev)
-    if gt.shape[-2:] != pred.shape[-2:] and interpolate:
+    lowres = bool(fuse_resize) and interpolate and gt.shape[-2:] != pred.shape[-2:]
+    if gt.shape[-2:] != pred.shape[-2:] and interpolate and not lowres:
         p4 = pred if pred.dim() == 4 else pred.reshape(-1, 1, *pred.shape[-2:])
         pred = F.interpolate(p4.float(), gt.shape[-2:], mode="bilinear", align_corners=False)
     g, single = _frames_of(gt.float())
-    p = pred.float().reshape(g.shape)
+    p = pred.float().reshape(g.shape[0], *pred.shape[-2:]) if lowres else pred.float().reshape(g.shape)
 
     def mask(m):
         return None if m is None else torch.as_tensor(m).to(dev).reshape(g.shape)
     inside = region if region is not None else additional_mask
     crop = _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
-    sums = ops.depth_metrics(g, p, mask(disp_gt_edges), mask(inside), min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
+    score = ops.depth_metrics_lowres if lowres else ops.depth_metrics
+    sums = score(g, p, mask(disp_gt_edges), mask(inside), min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
     see = disp_gt_edges is not None
     rows = []
     for f in range(g.shape[0]):

@@ -1758,6 +1758,31 @@ def _mask_u8(t, like, name):
     return t
 
 
+GT_KINDS = {"eth3d": 0, "mid": 1, "cityscapes": 2}  # enum prv2_gt_kind (tester.ImageDataset's gt_format names)
+CITYSCAPES_FACTOR = float(np.float32(0.209313 * 2262.52))  # general_dataset.py:144: baseline x focal length, met by a float32 array
+
+
+def gt_decode(src, kind, factor=CITYSCAPES_FACTOR, doffs=0.0, th=1.0, flip=False, byteswap=False):
+    """the general dataset's ground truth (general_dataset.py:103-151) from the raw samples [H, W] on the device, one pass ->
+    (depth fp32 [H, W], boundary uint8 [H, W] = metrics.get_boundaries(<the map the reference takes its edges from>, th, 0)).
+    ``kind``: 'eth3d' (fp32 depth; non-finite -> 0), 'mid' (fp32 PFM disparity; depth = factor / (disp + doffs) / 1000, 0 at +inf;
+    ``flip``: rows bottom-to-top, ``byteswap``: the file's byte order is not the host's) or 'cityscapes' (uint16 disparity samples;
+    ``factor`` defaults to the reference's constant) -- include/prv2.h prv2_gt_decode."""
+    if kind not in GT_KINDS:
+        raise ValueError(f"gt_decode: kind {kind!r} is not one of {sorted(GT_KINDS)}")
+    want = torch.uint16 if kind == "cityscapes" else torch.float32
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != want or src.dim() != 2:
+        raise ValueError(f"gt_decode: src is a GPU {want} [H, W] tensor for kind {kind!r}")
+    src = src.contiguous()
+    if DISPATCH == "torch":
+        return _tops().gt_decode(src, GT_KINDS[kind], float(factor), float(doffs), float(th), bool(flip), bool(byteswap))
+    depth = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    boundary = torch.empty(src.shape, dtype=torch.uint8, device=src.device)
+    _c("gt_decode", src.data_ptr(), GT_KINDS[kind], *src.shape, float(factor), float(doffs), float(th), int(bool(flip)), int(bool(byteswap)),
+       depth.data_ptr(), boundary.data_ptr())
+    return depth, boundary
+
+
 def depth_metrics(gt, pred, boundary=None, region=None, min_depth=1e-3, max_depth=80.0, crop=None):
     """the sums of compute_metrics (metric.py:11-149) of fp32 frames [B, H, W] -> float64 [B, S, 12] on the device, S = 3 (all /
     inside / outside) with a ``region`` map, else 1; ``crop`` = (y0, y1, x0, x1), None: the whole frame.  The twelve sums: include/prv2.h
@@ -1776,4 +1801,26 @@ def depth_metrics(gt, pred, boundary=None, region=None, min_depth=1e-3, max_dept
     ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
     out = torch.empty((g.shape[0], 3 if r is not None else 1, 12), dtype=torch.float64, device=g.device)
     _c("depth_metrics", g.data_ptr(), p.data_ptr(), _ptr(b), _ptr(r), *g.shape, float(min_depth), float(max_depth), y0, y1, x0, x1, out.data_ptr(), ws.data_ptr(), wsb)
+    return out
+
+
+def depth_metrics_lowres(gt, pred, boundary=None, region=None, min_depth=1e-3, max_depth=80.0, crop=None):
+    """``depth_metrics`` for a prediction [B, h, w] of another resolution than gt [B, H, W]: every prediction value is sampled in the
+    scoring kernel (bilinear, align_corners=False, the operations of F.interpolate on the device), the resized map is never written
+    (include/prv2.h prv2_depth_metrics_lowres).  Equal shapes run ``depth_metrics``' kernel: the same bits."""
+    g, p = _edge_frames(gt, torch.float32), _edge_frames(pred, torch.float32)
+    if g.shape[0] != p.shape[0]:
+        raise ValueError(f"depth_metrics_lowres: gt {tuple(g.shape)} and pred {tuple(p.shape)} differ in their frame count")
+    b, r = _mask_u8(boundary, g, "boundary"), _mask_u8(region, g, "region")
+    y0, y1, x0, x1 = (0, g.shape[1], 0, g.shape[2]) if crop is None else (int(v) for v in crop)
+    if DISPATCH == "torch":
+        return _tops().depth_metrics_lowres(g, p, b, r, float(min_depth), float(max_depth), y0, y1, x0, x1)
+    lib = L.load()
+    wsb = lib.prv2_depth_metrics_workspace_bytes(*g.shape)
+    if wsb < 0:
+        raise ValueError(f"depth_metrics_lowres: bad frame shape {tuple(g.shape)}")
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+    out = torch.empty((g.shape[0], 3 if r is not None else 1, 12), dtype=torch.float64, device=g.device)
+    _c("depth_metrics_lowres", g.data_ptr(), p.data_ptr(), _ptr(b), _ptr(r), *g.shape, p.shape[1], p.shape[2], float(min_depth), float(max_depth),
+       y0, y1, x0, x1, out.data_ptr(), ws.data_ptr(), wsb)
     return out

@@ -2,7 +2,8 @@
 
 Tester.run          estimator/tester/tester.py:52-127 (frame loop, model call contract, uint16 PNG x256)
 Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, uncertainty and tile-count PNGs)
-ImageDataset        estimator/datasets/general_dataset.py:161-234 (folder of images -> image_hr / image_lr)
+ImageDataset        estimator/datasets/general_dataset.py:64-245 (folder of images -> image_hr / image_lr; with ``gt_format`` the
+                    ground truth of a u4k / eth3d / mid / cityscapes folder, decoded on the GPU -> depth_gt / boundary)
 UnrealStereo4kDataset  estimator/datasets/u4k_dataset.py:20-233 (split file -> image_hr / depth_gt / boundary, decoded on the GPU)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 ``runner_info.device_output`` (tools/test.py --device-output) routes the saved files through output.OutputStage: scanlines made on
@@ -11,8 +12,9 @@ device_output) makes the zlib streams on the GPU as well: the files hold the dev
 stream differs from zlib's).
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) -- colour maps and metrics in metrics.py, PNGs through a
-dependency-free encoder.  Not built: <name>_edge.png (cv2.Canny + kornia blur, both un-vendored, :98-106) and the
-dataset-specific ground-truth decoders (general_dataset.py:74-150); ground truth is accepted as metric depth .npy files.
+dependency-free encoder.  Not built: <name>_edge.png (cv2.Canny + kornia blur, both un-vendored, :98-106), the ``gta`` ground truth
+(general_dataset.py:96-101: .exr files need imageio, which is absent) and the dataset classes KittiDataset, ScanNetDataset,
+CityScapesDataset and ETH3DDataset.  Without ``gt_format`` ground truth is metric depth as <basename>.npy files.
 """
 from __future__ import annotations
 
@@ -98,17 +100,189 @@ def read_image(path, dataset_name="", image_resolution=(2160, 3840)) -> np.ndarr
     return t.squeeze(0).permute(1, 2, 0).numpy()
 
 
+class _ReadAhead:
+    """Two staging slots and ONE background thread that reads files into host memory only (it never touches the GPU): while the
+    caller copies a slot to the device, the thread fills the other one with the item expected next (the same step further).
+    ``make_slot()`` -> a slot's buffers; ``read(idx, slot)`` fills them on the thread; ``prepare(idx, slot)`` runs before every
+    read on the CALLER's thread (pinned allocations belong there).  A slot is refilled only after the H2D copies out of it have
+    finished (the event ``release`` records)."""
+
+    def __init__(self, n, make_slot, read, prepare=None, name="read-ahead"):
+        from concurrent.futures import ThreadPoolExecutor
+        self.n, self._read, self._prepare = n, read, prepare
+        self._slots = [make_slot() for _ in range(2)]
+        self._events = [None, None]
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=name)
+        self._pending = None   # (index, slot, future) of the read that is one ahead
+        self._last = None      # the index asked for last: the next one is guessed from the step between the two
+        self._slot = 0
+
+    def _fill(self, idx, slot, ahead=False):
+        if self._events[slot] is not None:
+            self._events[slot].synchronize()
+        if self._prepare is not None:
+            self._prepare(idx, self._slots[slot])
+        if ahead:
+            return self._pool.submit(self._read, idx, self._slots[slot])
+        self._read(idx, self._slots[slot])
+
+    def acquire(self, idx):
+        """-> the slot that holds item ``idx`` (read now unless it is the one read ahead)"""
+        slot = 0
+        if self._pending is not None:
+            p_idx, p_slot, fut = self._pending
+            self._pending = None
+            fut.result()  # (a failed read raises here)
+            slot = p_slot
+            if p_idx != idx:  # a wrong guess: read into the other slot now
+                slot = 1 - p_slot
+                self._fill(idx, slot)
+        else:
+            self._fill(idx, slot)
+        self._slot = slot
+        return self._slots[slot]
+
+    def release(self, idx):
+        """the copies out of ``idx``'s slot are queued on the current stream: mark them, and read the next item into the other slot"""
+        ev = torch.cuda.Event()
+        ev.record()
+        self._events[self._slot] = ev
+        step = idx - self._last if self._last is not None and idx > self._last else 1
+        self._last = idx
+        if idx + step < self.n:
+            other = 1 - self._slot
+            self._pending = (idx + step, other, self._fill(idx + step, other, ahead=True))
+
+    def close(self):
+        self._pool.shutdown(wait=True)
+        self._pending = None
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the general dataset's ground-truth files (general_dataset.py:75-158): what the host parses; the samples go to ops.gt_decode
+GT_FORMATS = ("u4k", "eth3d", "mid", "cityscapes")
+IMAGE_FORMATS = (None, "mid", "u4k", "cityscapes", "kitti")
+KB_CROP = (352, 1216)  # general_dataset.py:45-50
+
+
+def read_factor_file(path) -> float:
+    """general_dataset.py:84-86: the depth factor is the first line of <val_factor>/<name>.txt"""
+    with open(path, "r") as f:
+        return float(f.readline())
+
+
+def read_mid_calib(path):
+    """general_dataset.py:117-123 -> (depth_factor = baseline x focal length, doffs): line 0 ``cam0=[f 0 cx; ...``, line 2 ``doffs=``,
+    line 3 ``baseline=``, by the reference's own expressions"""
+    with open(path, "r") as f:
+        ext_l = f.readlines()
+    cam_info_f = float(ext_l[0].strip().split(" ")[0].split("[")[1])
+    base = float(ext_l[3].strip().split("=")[1])
+    doffs = float(ext_l[2].strip().split("=")[1])
+    return base * cam_info_f, doffs
+
+
+def read_pfm_header(f):
+    """datasets/utils.py:5-45 on an open binary file -> (width, height, little_endian, scale, payload offset).  ``Pf`` (one channel)
+    only: the reference's own decoder cannot take edges of a colour map.  A malformed header raises ValueError."""
+    import re
+    header = f.readline().rstrip()
+    if header == b"PF":
+        raise ValueError("PFM: a colour map (PF) is no disparity map")
+    if header != b"Pf":
+        raise ValueError("Not a PFM file.")
+    try:
+        dim = re.match(r"^(\d+)\s(\d+)\s$", f.readline().decode("utf-8"))
+    except UnicodeDecodeError:
+        dim = None
+    if not dim:
+        raise ValueError("Malformed PFM header.")
+    width, height = map(int, dim.groups())
+    try:
+        scale = float(f.readline().rstrip().decode("utf-8"))
+    except (UnicodeDecodeError, ValueError):
+        raise ValueError("Malformed PFM header.") from None
+    if width < 1 or height < 1:
+        raise ValueError("Malformed PFM header.")
+    return width, height, scale < 0, abs(scale), f.tell()
+
+
+def strip_image_name(name: str) -> str:
+    """general_dataset.py:70-72"""
+    return name.replace(".jpg", "").replace(".png", "").replace(".jpeg", "")
+
+
+def strip_gt_name(name: str) -> str:
+    """general_dataset.py:156-157"""
+    return name.replace(".npy", "").replace(".exr", "")
+
+
+def _png16_shape(path):
+    """(h, w) of a 16-bit one-channel PNG from its IHDR"""
+    with open(path, "rb") as f:
+        head = f.read(26)
+    if len(head) < 26 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise ValueError(f"{path}: not a PNG file")
+    w, h, depth, ctype = struct.unpack(">IIBB", head[16:26])
+    if depth != 16 or ctype != 0:
+        raise ValueError(f"{path}: bit depth {depth}, colour type {ctype}; a Cityscapes disparity map is 16-bit greyscale")
+    return h, w
+
+
+def decode_image_u8(path, image_format, image_resolution):
+    """the ``read_image`` branches that do not resize (general_dataset.py:23-25, :33-38, :39-53) up to the uint8 pixels ->
+    (uint8 [h, w, 3], swap_rb): 'u4k' raw BGR bytes of ``image_resolution``; 'cityscapes' the RGB image; 'kitti' its kb-crop"""
+    if image_format == "u4k":
+        h, w = image_resolution
+        if os.path.getsize(path) != h * w * 3:
+            raise ValueError(f"{path}: {os.path.getsize(path)} bytes, expected {h * w * 3} ({h} x {w} x 3)")
+        return np.fromfile(path, dtype=np.uint8).reshape(h, w, 3), True
+    from PIL import Image
+    image = Image.open(path).convert("RGB")
+    if image_format == "kitti":
+        if image.height < KB_CROP[0] or image.width < KB_CROP[1]:
+            raise ValueError(f"{path}: {image.height} x {image.width} is smaller than the kb-crop {KB_CROP[0]} x {KB_CROP[1]}")
+        top_margin, left_margin = int(image.height - KB_CROP[0]), int((image.width - KB_CROP[1]) / 2)
+        image = image.crop((left_margin, top_margin, left_margin + KB_CROP[1], top_margin + KB_CROP[0]))
+    return np.array(image), False  # (a writable copy: it becomes a tensor)
+
+
 @DATASETS.register_module()
 class ImageDataset:
+    """general_dataset.py:161-245.  ``gt_format=None``: ground truth is metric depth as <gt_dir>/<basename>.npy.  ``gt_format`` in
+    GT_FORMATS: the reference's DepthMap (:75-158) -- ``gt_files = sorted(listdir(gt_dir))`` paired with the images by position, the
+    factor / calibration files found by its path replacements, the file's samples read into pinned staging buffers one item ahead
+    (_ReadAhead) and decoded on the GPU: ops.disp_gt for 'u4k', ops.gt_decode for 'eth3d' / 'mid' / 'cityscapes' -> ``depth_gt``
+    [1, 1, H, W] and ``boundary`` uint8 [H, W] on the device; ``get_metrics`` then scores with the resize inside the kernel.
+    ``gt_shape`` replaces the reference's literal 4032 x 6048 (ETH3D's raw files carry no shape).  ``image_format`` selects
+    read_image's branch (:22-62): None / 'mid' bicubic to ``image_resolution``; 'u4k' raw BGR bytes of ``image_resolution``;
+    'cityscapes' RGB / 255 as it is; 'kitti' its 352 x 1216 kb-crop -- the last three through ops.u8_image."""
     def __init__(self, rgb_image_dir, mode="", min_depth=1e-3, max_depth=80, gt_dir=None, image_resolution=(2160, 3840),
-                 dataset_name="", network_process_size=(384, 512), resize_mode="zoe", edge_metrics=False):
+                 dataset_name="", network_process_size=(384, 512), resize_mode="zoe", edge_metrics=False, gt_format=None, image_format=None,
+                 gt_shape=(4032, 6048)):
+        if gt_format == "gta":
+            raise NotImplementedError("ImageDataset(gt_format='gta'): the .exr ground truth (general_dataset.py:96-101) needs imageio, "
+                                      "which is not installed")
+        if gt_format is not None and gt_format not in GT_FORMATS:
+            raise ValueError(f"ImageDataset(gt_format={gt_format!r}): one of {', '.join(GT_FORMATS)} or None")
+        if image_format not in IMAGE_FORMATS:
+            raise ValueError(f"ImageDataset(image_format={image_format!r}): one of u4k, mid, cityscapes, kitti or None")
         self.rgb_image_dir = rgb_image_dir
         # edge_metrics: get_metrics adds the boundary metrics and the edge_* / noedge_* splits (metrics.compute_boundary_metrics)
         self.edge_metrics = bool(edge_metrics)
         self.files = sorted(os.listdir(rgb_image_dir))
-        # ground truth: metric depth as <gt_dir>/<basename>.npy (the reference's per-dataset decoders -- u4k disparity +
-        # factor files, gta exr, middlebury pfm ... general_dataset.py:74-150 -- are not built)
+        # ground truth: metric depth as <gt_dir>/<basename>.npy, or (gt_format) the reference's per-dataset files
         self.gt_dir = gt_dir
+        self.gt_format = gt_format if gt_dir is not None else None
+        self.image_format = image_format
+        self.gt_shape = (int(gt_shape[0]), int(gt_shape[1]))
+        self._ahead = None
+        self._meta = {}
+        if self.gt_format is not None:
+            self.gt_files = sorted(os.listdir(gt_dir))  # general_dataset.py:185: paired with the images by position
+            if len(self.gt_files) != len(self.files):
+                raise ValueError(f"ImageDataset: {len(self.files)} images in {rgb_image_dir} but {len(self.gt_files)} ground-truth files in "
+                                 f"{gt_dir} (they are paired by their sorted position)")
         self.min_depth, self.max_depth = min_depth, max_depth
         self.dataset_name = dataset_name
         self.image_resolution = tuple(image_resolution)
@@ -118,11 +292,113 @@ class ImageDataset:
     def __len__(self):
         return len(self.files)
 
-    def __getitem__(self, i):
+    def gt_meta(self, i) -> dict:
+        """what the host parses of ground-truth file ``i`` (no sample is read): ``path``, ``shape`` (h, w), ``nbytes`` and ``offset`` of
+        the samples in the file, and the decode arguments (``factor``, ``doffs``, ``byteswap``)"""
+        if i in self._meta:
+            return self._meta[i]
+        import sys
+        path = os.path.join(self.gt_dir, self.gt_files[i])
+        m = dict(path=path, offset=0, factor=0.0, doffs=0.0, byteswap=False, item=4)
+        if self.gt_format == "u4k":  # :82-89
+            m["factor"] = read_factor_file(path.replace("val_gt", "val_factor").replace(".npy", ".txt"))
+            m["shape"] = tuple(np.load(path, mmap_mode="r").shape)
+            if len(m["shape"]) != 2:
+                raise ValueError(f"{path}: disparity of shape {m['shape']}, expected [H, W]")
+        elif self.gt_format == "eth3d":  # :104-106 (the shape is a literal there)
+            m["shape"] = self.gt_shape
+            if os.path.getsize(path) != self.gt_shape[0] * self.gt_shape[1] * 4:
+                raise ValueError(f"{path}: {os.path.getsize(path)} bytes, expected {self.gt_shape[0]} x {self.gt_shape[1]} float32 (gt_shape)")
+        elif self.gt_format == "mid":  # :115-125
+            m["factor"], m["doffs"] = read_mid_calib(path.replace("gts", "calibs").replace(".pfm", ".txt"))
+            with open(path, "rb") as f:
+                try:
+                    w, h, little, _scale, m["offset"] = read_pfm_header(f)
+                except ValueError as e:
+                    raise ValueError(f"{path}: {e}") from None
+            m["shape"], m["byteswap"] = (h, w), little != (sys.byteorder == "little")
+            if os.path.getsize(path) - m["offset"] != h * w * 4:
+                raise ValueError(f"{path}: {os.path.getsize(path) - m['offset']} payload bytes, expected {h} x {w} float32")
+        else:  # cityscapes :142
+            m["shape"], m["item"] = _png16_shape(path), 2
+        m["nbytes"] = m["shape"][0] * m["shape"][1] * m["item"]
+        self._meta[i] = m
+        return m
+
+    def _prepare(self, i, slot):
+        """(caller's thread) the slot's pinned buffer holds file ``i``'s samples"""
+        need = self.gt_meta(i)["nbytes"]
+        if slot["buf"] is None or slot["buf"].numel() < need:
+            slot["buf"] = torch.empty((need,), dtype=torch.uint8).pin_memory()
+
+    def _read(self, i, slot):
+        """(background thread: files and host memory only) the samples of ground-truth file ``i`` as the file holds them, and the
+        image's pixels when its branch needs no resize"""
+        m = self.gt_meta(i)
+        view = slot["buf"].numpy()[:m["nbytes"]]
+        if self.gt_format == "u4k":
+            np.copyto(view.view(np.float32).reshape(m["shape"]), np.load(m["path"], mmap_mode="r"), casting="unsafe")  # .astype(float32)
+        elif self.gt_format == "cityscapes":
+            from PIL import Image
+            a = np.asarray(Image.open(m["path"]))  # cv2.imread(path, IMREAD_UNCHANGED) of a 16-bit PNG: its uint16 samples
+            if a.shape != m["shape"] or a.dtype.itemsize != 2:
+                raise ValueError(f"{m['path']}: decoded to {a.dtype} {a.shape}, expected uint16 {m['shape']}")
+            np.copyto(view.view(np.uint16).reshape(m["shape"]), a, casting="unsafe")
+        else:
+            with open(m["path"], "rb") as f:
+                f.seek(m["offset"])
+                if f.readinto(memoryview(view)) != m["nbytes"]:
+                    raise ValueError(f"{m['path']}: short read")
+        slot["image"] = None
+        if self.image_format in ("u4k", "cityscapes", "kitti"):
+            slot["image"] = decode_image_u8(os.path.join(self.rgb_image_dir, self.files[i]), self.image_format, self.image_resolution)
+
+    def close(self):
+        if self._ahead is not None:
+            self._ahead.close()
+            self._ahead = None
+
+    def _image(self, name, decoded=None):
+        from . import ops
+        path = os.path.join(self.rgb_image_dir, name)
+        if self.image_format in (None, "mid"):
+            # image_hr is resized on the device (prv2_bicubic_resize); image_lr is produced there too by model.resizer
+            return read_image_device(path, self.image_resolution)
+        pixels, swap = decoded if decoded is not None else decode_image_u8(path, self.image_format, self.image_resolution)
+        return ops.u8_image(torch.from_numpy(np.ascontiguousarray(pixels)).cuda(), swap_rb=swap)
+
+    def _getitem_gt(self, i):
+        """an item with the reference's ground truth: the samples from the staging slot to the device, decoded there"""
+        from . import ops
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        if self._ahead is None:
+            self._ahead = _ReadAhead(len(self), lambda: dict(buf=None, image=None), self._read, self._prepare, name="gt-read")
+        slot = self._ahead.acquire(i)
+        m = self.gt_meta(i)
+        raw = slot["buf"][:m["nbytes"]].cuda(non_blocking=True)
+        decoded = slot["image"]
+        self._ahead.release(i)
+        if self.gt_format == "cityscapes":
+            depth, boundary = ops.gt_decode(raw.view(torch.uint16).reshape(m["shape"]), "cityscapes", th=1.0)
+        else:
+            src = raw.view(torch.float32).reshape(m["shape"])
+            if self.gt_format == "u4k":
+                depth, boundary = ops.disp_gt(src, m["factor"], 1.0)
+            elif self.gt_format == "eth3d":
+                depth, boundary = ops.gt_decode(src, "eth3d", th=1.0)
+            else:  # the PFM payload as the file holds it: bottom-to-top rows, its own byte order
+                depth, boundary = ops.gt_decode(src, "mid", factor=m["factor"], doffs=m["doffs"], th=1.0, flip=True, byteswap=m["byteswap"])
         name = self.files[i]
-        # image_hr is resized on the device (prv2_bicubic_resize); image_lr is produced there too by model.resizer
-        hr = read_image_device(os.path.join(self.rgb_image_dir, name), self.image_resolution)
-        item = dict(image_hr=hr, img_file_basename=os.path.splitext(name)[0])
+        return dict(image_hr=self._image(name, decoded), img_file_basename=strip_image_name(name), depth_gt=depth[None, None],
+                    boundary=boundary)
+
+    def __getitem__(self, i):
+        if self.gt_format is not None:
+            return self._getitem_gt(i)
+        name = self.files[i]
+        item = dict(image_hr=self._image(name), img_file_basename=os.path.splitext(name)[0])
         if self.gt_dir is not None:
             from .metrics import get_boundaries
             gt = np.load(os.path.join(self.gt_dir, item["img_file_basename"] + ".npy")).astype(np.float32)
@@ -134,9 +410,12 @@ class ImageDataset:
         """general_dataset.py:236-245 (a GPU ``result`` is scored where it is: metrics.compute_metrics_device).  With
         ``edge_metrics`` also the boundary metrics (cityscapes_dataset.py:340-403; GT edges = extract_edges(gt, 'log'), no
         segmentation map) and the edge_* / noedge_* splits of every metric (scannet_dataset.py:221-243)."""
-        from .metrics import compute_metrics, compute_metrics_device
+        from .metrics import compute_metrics, compute_metrics_device, compute_metrics_fused
         dev = isinstance(result, torch.Tensor) and result.is_cuda
         score = compute_metrics_device if dev else compute_metrics
+        if self.gt_format is not None:  # the ground truth is on the device: one fused pass, the prediction sampled inside it
+            def score(gt, pred, **kw):
+                return compute_metrics_fused(gt, pred, fuse_resize=True, **kw)
         common = dict(disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth, max_depth_eval=self.max_depth, garg_crop=False,
                       eigen_crop=False, dataset=self.dataset_name)
         out = score(depth_gt, result, **common)
@@ -197,9 +476,7 @@ class UnrealStereo4kDataset:
         self.resize_mode = resize_mode
         self.image_raw_shape = (int(image_raw_shape[0]), int(image_raw_shape[1]))
         self.data_infos = self.load_data_list()
-        self._pool = self._slots = None
-        self._pending = None   # (index, slot, future) of the read that is one ahead
-        self._last = None      # the index asked for last: the next one is guessed from the step between the two
+        self._ahead = None     # the staging slots and their reader (_ReadAhead), made by the first item
 
     def load_data_list(self):
         """u4k_dataset.py:68-117: 'img_l img_r disp_l disp_r' per line; the image's suffix becomes ``raw``; focal length and baseline
@@ -229,7 +506,7 @@ class UnrealStereo4kDataset:
 
     def _read(self, idx, slot):
         """the two files of frame ``idx`` into staging slot ``slot`` (runs on the background thread: host memory only)"""
-        img, disp, _ = self._slots[slot]
+        img, disp = slot
         info = self.data_infos[idx]
         view = img.numpy().reshape(-1)
         with open(info["img_path"], "rb") as f:
@@ -242,62 +519,30 @@ class UnrealStereo4kDataset:
             raise ValueError(f"{info['depth_map_path']}: disparity {d.shape}, expected {self.image_raw_shape}")
         np.copyto(disp.numpy(), d, casting="unsafe")  # == .astype(np.float32)
 
-    def _start(self):
-        from concurrent.futures import ThreadPoolExecutor
+    def _make_slot(self):
         h, w = self.image_raw_shape
-        # two slots: the one being copied to the device and the one the reader fills; the event marks the copies out of a slot
-        self._slots = [[torch.empty((h, w, 3), dtype=torch.uint8).pin_memory(), torch.empty((h, w), dtype=torch.float32).pin_memory(), None]
-                       for _ in range(2)]
-        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="u4k-read")
-
-    def _wait_copies(self, slot):
-        """a slot is refilled only after the H2D copies out of it have finished"""
-        if self._slots[slot][2] is not None:
-            self._slots[slot][2].synchronize()
+        return (torch.empty((h, w, 3), dtype=torch.uint8).pin_memory(), torch.empty((h, w), dtype=torch.float32).pin_memory())
 
     def close(self):
-        if self._pool is not None:
-            self._pool.shutdown(wait=True)
-            self._pool = self._slots = self._pending = None
+        if self._ahead is not None:
+            self._ahead.close()
+            self._ahead = None
 
     def __getitem__(self, idx):
         from . import ops
         idx = int(idx)
         if not 0 <= idx < len(self):
             raise IndexError(idx)
-        if self._pool is None:
-            self._start()
-        slot = 0
-        if self._pending is not None:
-            p_idx, p_slot, fut = self._pending
-            self._pending = None
-            fut.result()  # (a failed read raises here)
-            slot = p_slot
-            if p_idx != idx:  # a wrong guess: read into the other slot now
-                slot = 1 - p_slot
-                self._wait_copies(slot)
-                self._read(idx, slot)
-        else:
-            self._wait_copies(slot)
-            self._read(idx, slot)
-        img, disp, _ = self._slots[slot]
+        if self._ahead is None:
+            self._ahead = _ReadAhead(len(self), self._make_slot, self._read, name="u4k-read")
+        img, disp = self._ahead.acquire(idx)
         raw = img.cuda(non_blocking=True)
         d = disp.cuda(non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self._slots[slot][2] = ev
+        self._ahead.release(idx)  # (the next index, the same step further, is read into the other slot meanwhile)
         info = self.data_infos[idx]
         depth, boundary = ops.disp_gt(d, info["depth_factor"], 1.0)
-        item = dict(image_hr=ops.u8_image(raw, swap_rb=True), depth_gt=depth[None, None], boundary=boundary,
+        return dict(image_hr=ops.u8_image(raw, swap_rb=True), depth_gt=depth[None, None], boundary=boundary,
                     img_file_basename=info["img_file_basename"])
-        # one ahead: the index the same step further, into the other slot (once the copies out of it are done)
-        step = idx - self._last if self._last is not None and idx > self._last else 1
-        self._last = idx
-        if idx + step < len(self):
-            other = 1 - slot
-            self._wait_copies(other)
-            self._pending = (idx + step, other, self._pool.submit(self._read, idx + step, other))
-        return item
 
     def get_metrics(self, depth_gt, result, disp_gt_edges=None, **kw):
         """u4k_dataset.py:232-233 through the fused kernel (a host ``result`` is copied to the device first)"""

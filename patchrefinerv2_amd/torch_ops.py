@@ -40,7 +40,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # device deflate: zlib streams of scanline buffers
        "deflate_rows",
        # ground-truth evaluation: raw image / disparity decode and the fused scoring sums
-       "u8_image", "disp_gt", "depth_metrics")
+       "u8_image", "disp_gt", "depth_metrics",
+       # the general dataset's ground-truth decoders and the scoring of a prediction of another resolution
+       "gt_decode", "depth_metrics_lowres")
 _loaded = False
 
 

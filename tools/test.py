@@ -12,7 +12,10 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
-disparities decoded and scored on the GPU; prints a1 ... sq_rel and see); ``general`` is the folder of images.
+disparities decoded and scored on the GPU; prints a1 ... sq_rel and see); ``general`` is the folder of images -- with
+``--cfg-option general_dataloader.dataset.gt_dir=DIR general_dataloader.dataset.gt_format=u4k|eth3d|mid|cityscapes`` a folder with the
+reference's ground truth (general_dataset.py:75-158), decoded and scored on the GPU (``image_format=u4k|cityscapes|kitti`` selects
+read_image's branch, ``gt_shape=[H,W]`` the shape of ETH3D's raw files).
 Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md:113-130): one process per GPU over RCCL;
 ``--shard frames`` (default, the reference's data parallelism) or ``--shard patches`` (tiles of every frame over the ranks).
 """
@@ -75,7 +78,8 @@ def main():
     ap.add_argument("--cfg-option", nargs="+", default=None)
     ap.add_argument("--save", action="store_true")
     ap.add_argument("--work-dir", default="./work_dir/predictions")
-    ap.add_argument("--test-type", default="general", help="general: general_dataloader (a folder of images); normal / test_in / test_out: "
+    ap.add_argument("--test-type", default="general", help="general: general_dataloader (a folder of images; with dataset.gt_dir and dataset.gt_format = u4k / eth3d / mid / cityscapes "
+                    "set by --cfg-option also the reference's ground truth, decoded and scored on the GPU); normal / test_in / test_out: "
                     "val_dataloader / test_in_dataloader / test_out_dataloader (a dataset with ground truth, e.g. UnrealStereo4kDataset)")
     ap.add_argument("--gray-scale", action="store_true")
     ap.add_argument("--image-raw-shape", nargs=2, type=int, default=[2160, 3840])
