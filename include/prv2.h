@@ -760,6 +760,33 @@ int prv2_depth_metrics_lowres(const float* gt, const float* pred, const uint8_t*
                               int32_t w, int32_t ph, int32_t pw, float min_depth, float max_depth, int32_t y0, int32_t y1, int32_t x0,
                               int32_t x1, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ETHDataset (estimator/datasets/eth_dataset.py), the parts that run on the device.  Additive as well: the ABI version does not
+ * change. */
+
+/* eth_dataset.py:133,150-161: the RGB bytes / 255 (a correctly rounded fp32 division, as prv2_u8_image), then
+ * F.interpolate(mode='bilinear', align_corners=True) to transform_cfg.input_size_shallow, as CHW.  src_hwc: uint8 [h, w, 3];
+ * dst_chw: fp32 [3, H, W].  The fp32 operations of PyTorch's upsample_bilinear2d, none of them contracted: scale = (in - 1) / (out - 1)
+ * (0 for out == 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1, and
+ *   dst = ly0 * (lx0 * v[y0, x0] + lx1 * v[y0, x1]) + ly1 * (lx0 * v[y1, x0] + lx1 * v[y1, x1]).
+ * H == h and W == w gives prv2_u8_image(swap_rb = 0)'s bits. */
+int prv2_u8_image_resize(const uint8_t* src_hwc, int32_t h, int32_t w, float* dst_chw, int32_t H, int32_t W, void* stream);
+
+/* bytes of workspace prv2_image_edge_region needs for an image of h x w (-1 for a bad shape) */
+int64_t prv2_image_edge_region_workspace_bytes(int32_t h, int32_t w);
+
+/* eth_dataset.py:261-272: the edge area get_metrics splits its metrics by, from the IMAGE's gradient.  image_chw: fp32 [3, h, w];
+ * region: uint8 0/1 [H, W] (the ground truth's shape).  Per channel the Sobel derivatives / 8 with replicate padding
+ * (kornia.filters.spatial_gradient's defaults), m_c = sqrt(gx * gx + gy * gy) in fp32 with a correctly rounded sqrt, g = (m_0 + m_1) +
+ * m_2, edge = g >= frac * max(g) (a constant image has max(g) == 0: every pixel is an edge).  The two steps after it need no
+ * floating point: gaussian_blur2d(3 x 3, sigma 3, reflect) > 0 is the 3 x 3 dilation with the window clipped at the frame (positive
+ * weights), and F.interpolate(bilinear, align_corners=True) > 0 at an output pixel is "one of the up to four source taps with a
+ * non-zero weight is set", the taps and weights as prv2_u8_image_resize computes them (the upper tap of an axis counts only when
+ * l1 > 0).  The maximum is an integer atomic maximum on the bits of non-negative floats: the same bits on every call.  Three
+ * launches after a 16-byte memset; workspace 16-byte aligned, of prv2_image_edge_region_workspace_bytes(h, w) bytes; no float map of
+ * H x W is made. */
+int prv2_image_edge_region(const float* image_chw, int32_t h, int32_t w, float frac, uint8_t* region, int32_t H, int32_t W,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,9 @@
 //                         boundary map, one pass                                                   (general_dataset.py:103-151)
 //   depth_metrics_kernel  the twelve sums of compute_errors + soft_edge_error of B frames, for up to three pixel sets at once
 //   metrics_final_kernel  the per-block partials of a frame summed in block order
+//   image_grad_kernel / edge_dilate_kernel / edge_region_kernel   ETHDataset's edge area from the IMAGE gradient: Sobel magnitude summed
+//                         over the channels and its maximum, threshold + 3 x 3 dilation at image size, the non-zero taps of the
+//                         bilinear(align_corners=True) resize at ground-truth size                    (eth_dataset.py:261-272)
 //
 // The metrics kernel is one streaming read of gt / pred / boundary / region: a block owns a fixed run of rows, a thread four pixels
 // of a row at a time (float4 / uchar4 loads when the rows are 16-byte aligned), the per-pixel terms are float64 from the float32
@@ -381,6 +384,88 @@ __global__ void __launch_bounds__(64) metrics_final_kernel(const double* __restr
   sums[(int64_t)f * nval + j] = s;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// ETHDataset.get_metrics' edge area (eth_dataset.py:261-272).  No float map of ground-truth size exists: the gradient and the byte
+// map of the dilated threshold live at image size, the last kernel writes the region's bytes.
+//
+// kornia.filters.spatial_gradient (Sobel / 8, replicate padding) per channel, m_c = sqrt(gx^2 + gy^2) (a correctly rounded sqrt),
+// g = (m_0 + m_1) + m_2; the frame's maximum through an integer atomicMax on the bits of the non-negative floats (order-independent)
+__global__ void __launch_bounds__(256) image_grad_kernel(const float* __restrict__ img, int h, int w, float* __restrict__ grad,
+                                                         uint32_t* __restrict__ max_bits) {
+  __shared__ uint32_t sh[4];
+  const int64_t hw = (int64_t)h * w;
+  uint32_t best = 0u;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hw; i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
+    const int ym = max(y - 1, 0), yp = min(y + 1, h - 1), xm = max(x - 1, 0), xp = min(x + 1, w - 1);
+    float g = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float* p = img + k * hw;
+      const float* ru = p + (int64_t)ym * w;
+      const float* rc = p + (int64_t)y * w;
+      const float* rd = p + (int64_t)yp * w;
+      const float gx = (((ru[xp] - ru[xm]) + 2.0f * (rc[xp] - rc[xm])) + (rd[xp] - rd[xm])) * 0.125f;
+      const float gy = (((rd[xm] - ru[xm]) + 2.0f * (rd[x] - ru[x])) + (rd[xp] - ru[xp])) * 0.125f;
+      const float m = __fsqrt_rn(gx * gx + gy * gy);
+      g = k ? g + m : m;
+    }
+    grad[i] = g;
+    best = max(best, __float_as_uint(g));
+  }
+  for (int o = 32; o > 0; o >>= 1) best = max(best, (uint32_t)__shfl_down((int)best, o, 64));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicMax(max_bits, max(max(sh[0], sh[1]), max(sh[2], sh[3])));
+}
+
+// edge = g >= frac * max(g) (fp32), then gaussian_blur2d(3 x 3, reflect) > 0: every weight is positive and reflect stays inside the
+// window, so it is the 3 x 3 dilation with the window clipped at the frame.  A constant image has max(g) == 0: every pixel is set.
+__global__ void __launch_bounds__(256) edge_dilate_kernel(const float* __restrict__ grad, int h, int w, const uint32_t* __restrict__ max_bits,
+                                                          float frac, uint8_t* __restrict__ wide) {
+  const float thr = __uint_as_float(*max_bits) * frac;
+  const int64_t hw = (int64_t)h * w;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < hw; i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / w), x = (int)(i - (int64_t)y * w);
+    bool any = false;
+    for (int yy = max(y - 1, 0); yy <= min(y + 1, h - 1); ++yy)
+      for (int xx = max(x - 1, 0); xx <= min(x + 1, w - 1); ++xx) any |= grad[(int64_t)yy * w + xx] >= thr;
+    wide[i] = any ? 1 : 0;
+  }
+}
+
+// F.interpolate(bilinear, align_corners=True) > 0 of a non-negative map: one of the up to four taps with a NON-ZERO weight is set.
+// PyTorch's fp32 source coordinate (ac_tap): the lower tap's weight 1 - lambda1 is never zero, the upper one's is lambda1 -- an
+// output that lands exactly on a source pixel does not see the next one.
+__device__ __forceinline__ uint8_t edge_region_at(const uint8_t* __restrict__ r0, const uint8_t* __restrict__ r1, bool up, int X, float sx,
+                                                  int w) {
+  const AxisTap tx = ac_tap(X, sx, w);
+  const bool right = tx.w1 > 0.f;
+  const bool v = r0[tx.i0] || (right && r0[tx.i1]) || (up && (r1[tx.i0] || (right && r1[tx.i1])));
+  return v ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256) edge_region_kernel(const uint8_t* __restrict__ wide, int h, int w, uint8_t* __restrict__ region, int H,
+                                                          int W, float sy, float sx, int vec) {
+  const int wq = (W + 3) / 4;
+  const int64_t quads = (int64_t)H * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int Y = (int)(q / wq), X0 = (int)(q - (int64_t)Y * wq) * 4;
+    const AxisTap ty = ac_tap(Y, sy, h);
+    const uint8_t* r0 = wide + (int64_t)ty.i0 * w;
+    const uint8_t* r1 = wide + (int64_t)ty.i1 * w;
+    const bool up = ty.w1 > 0.f;
+    const int64_t o = (int64_t)Y * W + X0;
+    if (vec) {  // W % 4 == 0 and region 4-byte aligned
+      uint32_t v = 0u;
+      for (int k = 0; k < 4; ++k) v |= (uint32_t)edge_region_at(r0, r1, up, X0 + k, sx, w) << (8 * k);
+      *reinterpret_cast<uint32_t*>(region + o) = v;
+    } else {
+      for (int k = 0; k < 4 && X0 + k < W; ++k) region[o + k] = edge_region_at(r0, r1, up, X0 + k, sx, w);
+    }
+  }
+}
+
 static inline bool aligned(const void* p, int bytes) { return p == nullptr || ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
 
 }  // namespace
@@ -491,6 +576,42 @@ extern "C" int prv2_gt_decode(const void* src, int32_t kind, int32_t h, int32_t 
     hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_MIDDLEBURY>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
   else
     hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_CITYSCAPES>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+// workspace of prv2_image_edge_region: the maximum's word (16 bytes), the gradient fp32 [h, w], the dilated threshold uint8 [h, w]
+extern "C" int64_t prv2_image_edge_region_workspace_bytes(int32_t h, int32_t w) {
+  if (h < 1 || w < 1 || (int64_t)3 * h * w >= (int64_t)INT_MAX) return -1;
+  return 16 + roundup((int64_t)h * w * 4, 16) + roundup((int64_t)h * w, 16);
+}
+
+extern "C" int prv2_image_edge_region(const float* image_chw, int32_t h, int32_t w, float frac, uint8_t* region, int32_t H, int32_t W,
+                                      void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* name = "image_edge_region";
+  PRV2_REQUIRE(image_chw && region, "%s: null pointer", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad image shape %d x %d", name, h, w);
+  PRV2_REQUIRE(H >= 1 && W >= 1, "%s: bad region shape %d x %d", name, H, W);
+  PRV2_REQUIRE((int64_t)3 * h * w < (int64_t)INT_MAX && (int64_t)H * W < (int64_t)INT_MAX, "%s: 3 x %d x %d -> %d x %d exceeds 2^31 pixels", name,
+               h, w, H, W);
+  PRV2_REQUIRE(frac == frac, "%s: frac is NaN", name);
+  PRV2_REQUIRE(workspace != nullptr && aligned(workspace, 16), "%s: null or misaligned workspace", name);
+  const int64_t need = prv2_image_edge_region_workspace_bytes(h, w);
+  PRV2_REQUIRE(workspace_bytes >= need, "%s: workspace of %lld bytes < %lld (prv2_image_edge_region_workspace_bytes)", name,
+               (long long)workspace_bytes, (long long)need);
+  const int64_t hw = (int64_t)h * w;
+  uint32_t* max_bits = (uint32_t*)workspace;
+  float* grad = (float*)((char*)workspace + 16);
+  uint8_t* wide = (uint8_t*)grad + roundup(hw * 4, 16);
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(max_bits, 0, 16, s);
+  PRV2_REQUIRE(e == hipSuccess, "%s: hipMemsetAsync failed: %s", name, hipGetErrorString(e));
+  hipLaunchKernelGGL(image_grad_kernel, dim3(flat_grid(hw, 256)), dim3(256), 0, s, image_chw, (int)h, (int)w, grad, max_bits);
+  hipLaunchKernelGGL(edge_dilate_kernel, dim3(flat_grid(hw, 256)), dim3(256), 0, s, (const float*)grad, (int)h, (int)w,
+                     (const uint32_t*)max_bits, frac, wide);
+  const int vec = W % 4 == 0 && aligned(region, 4);
+  hipLaunchKernelGGL(edge_region_kernel, dim3(flat_grid((int64_t)H * cdiv(W, 4), 256)), dim3(256), 0, s, (const uint8_t*)wide, (int)h, (int)w,
+                     region, (int)H, (int)W, ac_scale(h, H), ac_scale(w, W), vec);
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }

@@ -96,6 +96,28 @@ __global__ void __launch_bounds__(256) bicubic_resize_kernel(const T* __restrict
   }
 }
 
+// ETHDataset's image stage (eth_dataset.py:133,150-161): HWC uint8 RGB -> / 255 -> bilinear(align_corners=True) -> CHW fp32, in the
+// fp32 operations of PyTorch's upsample_bilinear2d, spelled out and never contracted (this file is built with -ffp-contract=off):
+// scale = (in - 1) / (out - 1), src = scale * dst, lambda1 = src - i0, the columns blended first, then the two rows.  A size equal to
+// the source's has lambda1 == 0 everywhere and gives float(src) / 255 itself (prv2_u8_image's bits).
+__global__ void __launch_bounds__(256) u8_image_resize_kernel(const uint8_t* __restrict__ src, int h, int w, float* __restrict__ dst, int H,
+                                                              int W, float sy, float sx) {
+  const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ox >= W) return;
+  const AxisTap tx = ac_tap(ox, sx, w);
+  for (int oy = blockIdx.y; oy < H; oy += gridDim.y) {
+    const AxisTap ty = ac_tap(oy, sy, h);
+    const uint8_t* r0 = src + (int64_t)ty.i0 * w * 3;
+    const uint8_t* r1 = src + (int64_t)ty.i1 * w * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float v00 = (float)r0[tx.i0 * 3 + c] / 255.0f, v01 = (float)r0[tx.i1 * 3 + c] / 255.0f;  // IEEE divisions
+      const float v10 = (float)r1[tx.i0 * 3 + c] / 255.0f, v11 = (float)r1[tx.i1 * 3 + c] / 255.0f;
+      dst[((int64_t)c * H + oy) * W + ox] = ty.w0 * (tx.w0 * v00 + tx.w1 * v01) + ty.w1 * (tx.w0 * v10 + tx.w1 * v11);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // roi_align(aligned=True, sampling_ratio=-1) from ONE feature map to K outputs (no repeat(K))
 // ---------------------------------------------------------------------------------------------
@@ -526,6 +548,19 @@ extern "C" int prv2_bicubic_resize(const void* src_hwc, int32_t src_is_u8, int32
     hipLaunchKernelGGL(bicubic_resize_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src_hwc, h, w, dst_chw,
                        H, W, sy, sx, 1.0);
   PRV2_LAUNCH_CHECK("bicubic_resize");
+  return 0;
+}
+
+extern "C" int prv2_u8_image_resize(const uint8_t* src_hwc, int32_t h, int32_t w, float* dst_chw, int32_t H, int32_t W, void* stream) {
+  const char* name = "u8_image_resize";
+  PRV2_REQUIRE(src_hwc && dst_chw, "%s: null pointer", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1 && H >= 1 && W >= 1, "%s: bad shape %d x %d -> %d x %d", name, h, w, H, W);
+  PRV2_REQUIRE((int64_t)h * w * 3 < (int64_t)INT32_MAX && (int64_t)H * W * 3 < (int64_t)INT32_MAX,
+               "%s: %d x %d -> %d x %d exceeds 2^31 elements", name, h, w, H, W);
+  const dim3 grid((unsigned)cdiv(W, 256), (unsigned)(H < 65535 ? H : 65535));
+  hipLaunchKernelGGL(u8_image_resize_kernel, grid, dim3(256), 0, (hipStream_t)stream, src_hwc, (int)h, (int)w, dst_chw, (int)H, (int)W,
+                     ac_scale(h, H), ac_scale(w, W));
+  PRV2_LAUNCH_CHECK(name);
   return 0;
 }
 

@@ -1181,6 +1181,32 @@ Tensor depth_metrics_lowres(const Tensor& gt, const Tensor& pred, const optional
      "depth_metrics_lowres");
   return sums;
 }
+// ETHDataset (eth_dataset.py:133,150-161 and :261-272): the image stage and the edge area of its metric splits
+Tensor u8_image_resize(const Tensor& src, int64_t oh, int64_t ow) {
+  TORCH_CHECK(src.is_cuda(), "prv2: src must be a GPU tensor (there is no CPU path)");
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 3 && src.size(2) == 3 && src.is_contiguous(),
+              "prv2::u8_image_resize: src must be a contiguous uint8 [h, w, 3] tensor");
+  TORCH_CHECK(oh >= 1 && ow >= 1, "prv2::u8_image_resize: bad size ", oh, " x ", ow);
+  Tensor dst = at::empty({3, oh, ow}, src.options().dtype(at::kFloat));
+  Launch L(src);
+  ok(prv2_u8_image_resize((const uint8_t*)src.data_ptr(), (int)src.size(0), (int)src.size(1), dst.data_ptr<float>(), (int)oh, (int)ow, L.stream),
+     "u8_image_resize");
+  return dst;
+}
+Tensor image_edge_region(const Tensor& image, int64_t H, int64_t W, double frac) {
+  dev_f32(image, "image");
+  TORCH_CHECK(image.dim() == 3 && image.size(0) == 3 && image.is_contiguous(), "prv2::image_edge_region: image must be a contiguous [3, h, w] tensor");
+  TORCH_CHECK(H >= 1 && W >= 1, "prv2::image_edge_region: bad size ", H, " x ", W);
+  const int64_t bytes = prv2_image_edge_region_workspace_bytes((int)image.size(1), (int)image.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::image_edge_region: bad image shape ", image.sizes());
+  Tensor ws = at::empty({bytes}, image.options().dtype(at::kByte));
+  Tensor region = at::empty({H, W}, image.options().dtype(at::kByte));
+  Launch L(image);
+  ok(prv2_image_edge_region(image.data_ptr<float>(), (int)image.size(1), (int)image.size(2), (float)frac,
+                            (uint8_t*)region.data_ptr(), (int)H, (int)W, ws.data_ptr(), ws.numel(), L.stream),
+     "image_edge_region");
+  return region;
+}
 
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
@@ -1326,6 +1352,8 @@ TORCH_LIBRARY(prv2, m) {
   m.def("depth_metrics(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, int x0, "
         "int x1) -> Tensor");
   m.def("gt_decode(Tensor src, int kind, float factor, float doffs, float th, bool flip, bool byteswap) -> (Tensor, Tensor)");
+  m.def("u8_image_resize(Tensor src, int oh, int ow) -> Tensor");
+  m.def("image_edge_region(Tensor image, int H, int W, float frac) -> Tensor");
   m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
         "int x0, int x1) -> Tensor");
 }
@@ -1411,4 +1439,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("depth_metrics", &depth_metrics);
   m.impl("gt_decode", &gt_decode);
   m.impl("depth_metrics_lowres", &depth_metrics_lowres);
+  m.impl("u8_image_resize", &u8_image_resize);
+  m.impl("image_edge_region", &image_edge_region);
 }

@@ -165,6 +165,10 @@ SIGNATURES = {
     "prv2_depth_metrics": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
     "prv2_gt_decode": (_I, [_P, _I, _I, _I, _F, _F, _F, _I, _I, _P, _P, _P]),
     "prv2_depth_metrics_lowres": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
+    # ETHDataset (eth_dataset.py): the image stage and the edge area of its metric splits
+    "prv2_u8_image_resize": (_I, [_P, _I, _I, _P, _I, _I, _P]),
+    "prv2_image_edge_region_workspace_bytes": (_L, [_I, _I]),
+    "prv2_image_edge_region": (_I, [_P, _I, _I, _F, _P, _I, _I, _P, _L, _P]),
 }
 
 _lib = None

@@ -1824,3 +1824,59 @@ def depth_metrics_lowres(gt, pred, boundary=None, region=None, min_depth=1e-3, m
     _c("depth_metrics_lowres", g.data_ptr(), p.data_ptr(), _ptr(b), _ptr(r), *g.shape, p.shape[1], p.shape[2], float(min_depth), float(max_depth),
        y0, y1, x0, x1, out.data_ptr(), ws.data_ptr(), wsb)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# ETHDataset (estimator/datasets/eth_dataset.py): the image stage (csrc/gather.hip) and the edge area its get_metrics splits every
+# metric by (csrc/evalgt.hip), both dispatch routes.
+# ------------------------------------------------------------------------------------------------------------------
+def u8_image_resize(src_hwc_u8, oh, ow):
+    """uint8 RGB [h, w, 3] on the device -> fp32 [3, oh, ow]: bytes / 255, then F.interpolate(mode='bilinear', align_corners=True) in
+    PyTorch's fp32 operations (eth_dataset.py:133,150-161; include/prv2.h prv2_u8_image_resize).  (oh, ow) == (h, w) gives
+    ``u8_image(swap_rb=False)``'s bits."""
+    src = src_hwc_u8
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 3:
+        raise ValueError("u8_image_resize: src is a GPU uint8 [H, W, 3] tensor")
+    oh, ow = int(oh), int(ow)
+    if oh < 1 or ow < 1:
+        raise ValueError(f"u8_image_resize: bad size {oh} x {ow}")
+    src = src.contiguous()
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().u8_image_resize(src, oh, ow))  # noqa: E731
+    else:
+        dst = torch.empty((3, oh, ow), dtype=torch.float32, device=src.device)
+        box.append(dst)
+        call = lambda: _c("u8_image_resize", src.data_ptr(), src.shape[0], src.shape[1], dst.data_ptr(), oh, ow)  # noqa: E731
+    PROFILER.launch_aux("u8_image_resize", 12.0 * oh * ow + 3.0 * src.shape[0] * src.shape[1], call, f"{src.shape[0]}x{src.shape[1]}->{oh}x{ow}")
+    return box[0]
+
+
+def image_edge_region(image_chw, H, W, frac=0.5):
+    """fp32 image [3, h, w] on the device -> uint8 0/1 [H, W]: the edge area of ETHDataset.get_metrics
+    (eth_dataset.py:261-272) -- Sobel gradient magnitude summed over the channels, >= ``frac`` x its maximum, widened by the 3 x 3
+    blur and resized (bilinear, align_corners=True) to the ground truth's shape, > 0.  Exact integer logic after the gradient, the
+    same bits on every call (include/prv2.h prv2_image_edge_region)."""
+    img = image_chw
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or img.dtype != torch.float32:
+        raise ValueError("image_edge_region: image is a GPU fp32 [3, h, w] tensor")
+    if img.dim() != 3 or img.shape[0] != 3:
+        raise ValueError(f"image_edge_region: image of shape {tuple(img.shape)}, expected [3, h, w]")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"image_edge_region: bad size {H} x {W}")
+    img = img.contiguous()
+    h, w = img.shape[1:]
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().image_edge_region(img, H, W, float(frac)))  # noqa: E731
+    else:
+        wsb = L.load().prv2_image_edge_region_workspace_bytes(h, w)
+        if wsb < 0:
+            raise ValueError(f"image_edge_region: bad image shape {tuple(img.shape)}")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=img.device)
+        region = torch.empty((H, W), dtype=torch.uint8, device=img.device)
+        box.append(region)
+        call = lambda: _c("image_edge_region", img.data_ptr(), h, w, float(frac), region.data_ptr(), H, W, ws.data_ptr(), wsb)  # noqa: E731
+    PROFILER.launch_aux("image_edge_region", 21.0 * h * w + 1.0 * H * W, call, f"{h}x{w}->{H}x{W}")
+    return box[0]

@@ -5,16 +5,19 @@ Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, un
 ImageDataset        estimator/datasets/general_dataset.py:64-245 (folder of images -> image_hr / image_lr; with ``gt_format`` the
                     ground truth of a u4k / eth3d / mid / cityscapes folder, decoded on the GPU -> depth_gt / boundary)
 UnrealStereo4kDataset  estimator/datasets/u4k_dataset.py:20-233 (split file -> image_hr / depth_gt / boundary, decoded on the GPU)
+ETHDataset          estimator/datasets/eth_dataset.py:23-385 (split file -> image_hr resized on the GPU / depth_gt / boundary; every
+                    metric also inside and outside the image's edge area, found on the GPU)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 ``runner_info.device_output`` (tools/test.py --device-output) routes the saved files through output.OutputStage: scanlines made on
 the GPU, deflate on a writer pool; the default is the host route below.  ``runner_info.device_deflate`` (--device-deflate, needs
 device_output) makes the zlib streams on the GPU as well: the files hold the device route's pixels, but not its bytes (the deflate
 stream differs from zlib's).
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
-(coarse prediction resized to the raw shape, :93-96) -- colour maps and metrics in metrics.py, PNGs through a
-dependency-free encoder.  Not built: <name>_edge.png (cv2.Canny + kornia blur, both un-vendored, :98-106), the ``gta`` ground truth
-(general_dataset.py:96-101: .exr files need imageio, which is absent) and the dataset classes KittiDataset, ScanNetDataset,
-CityScapesDataset and ETH3DDataset.  Without ``gt_format`` ground truth is metric depth as <basename>.npy files.
+(coarse prediction resized to the raw shape, :93-96) and <name>_edge.png (Canny edges of the log depth, widened by one pixel,
+:98-106; metrics.depth_edges) -- colour maps and metrics in metrics.py, PNGs through a dependency-free encoder.  Not built: the
+``gta`` ground truth (general_dataset.py:96-101: .exr files need imageio, which is absent) and the dataset classes KittiDataset,
+ScanNetDataset and CityScapesDataset; of the reference's dataset classes UnrealStereo4kDataset and ETHDataset are.  Without
+``gt_format`` ground truth is metric depth as <basename>.npy files.
 """
 from __future__ import annotations
 
@@ -551,6 +554,149 @@ class UnrealStereo4kDataset:
                                      garg_crop=False, eigen_crop=False, dataset="")
 
 
+ETH_METRIC_KEYS = ("a1", "a2", "a3", "abs_rel", "rmse", "log_10", "rmse_log", "silog", "sq_rel", "see")  # compute_metrics' order
+
+
+def eth_metric_order(fused: dict) -> dict:
+    """compute_metrics_fused(region=...)'s dict in the reference's order (eth_dataset.py:277-289, :304-335): ``edge_*``, ``noedge_*``, then
+    the plain keys"""
+    plain = [k for k in fused if not k.startswith(("edge_", "noedge_"))]
+    return {pre + k: fused[pre + k] for pre in ("edge_", "noedge_", "") for k in plain}
+
+
+@DATASETS.register_module()
+class ETHDataset:
+    """estimator/datasets/eth_dataset.py:23-385, inference modes: the photographs of a split file with their raw float32 ground truth.
+    One background thread (_ReadAhead: files and host memory only) decodes the NEXT image with PIL (``convert("RGB")``) and reads the
+    raw floats, both into pinned buffers; on the device ops.u8_image_resize makes ``image_hr`` (bytes / 255, bilinear
+    align_corners=True to ``transform_cfg.input_size_shallow`` -- only the bytes cross PCIe; without that key ops.u8_image) and
+    ops.gt_decode('eth3d') makes ``depth_gt`` [1, 1, H, W] (non-finite -> 0) and ``boundary``.  ``get_metrics`` finds the reference's
+    edge area from the IMAGE gradient on the GPU (ops.image_edge_region) and scores inside it, outside it and everywhere in one fused
+    pass.  ``gt_shape`` replaces the reference's literal 4032 x 6048 (the raw files carry no shape).  ``overlap``, ``crop_strategy`` and
+    ``stitcher_stage`` are accepted and stored, but the crops of an item (``crops_image_hr`` / ``crop_depths`` / ``bboxs``, :194-221) are
+    not built: Tester.run_consistency makes its own crops.  Not built: ``mode='train'`` and ``transform_cfg.random_crop``."""
+
+    dataset_name = "eth3d"
+
+    def __init__(self, mode, split, transform_cfg, min_depth, max_depth, stitcher_stage=0, overlap=0, crop_strategy="random",
+                 resize_mode="zoe", gt_shape=(4032, 6048)):
+        if mode == "train":
+            raise NotImplementedError("ETHDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip, "
+                                      "eth_dataset.py:144-167) is not built; inference modes only")
+        if transform_cfg.get("random_crop", False):
+            raise NotImplementedError("ETHDataset(transform_cfg.random_crop): the random crops (eth_dataset.py:179-190) are not built")
+        if resize_mode not in ("zoe", "depth-anything"):
+            raise NotImplementedError(f"ETHDataset(resize_mode={resize_mode!r})")  # eth_dataset.py:49-56
+        self.mode, self.split = mode, split
+        self.min_depth, self.max_depth = min_depth, max_depth
+        self.transform_cfg = transform_cfg
+        self.resize_mode = resize_mode
+        self.stitcher_stage, self.overlap, self.crop_strategy = stitcher_stage, overlap, crop_strategy
+        self.gt_shape = (int(gt_shape[0]), int(gt_shape[1]))
+        shallow = transform_cfg.get("input_size_shallow", None)
+        self.input_size_shallow = None if shallow is None else (int(shallow[0]), int(shallow[1]))
+        self.data_infos = self.load_data_list()
+        self._ahead = None
+
+    def load_data_list(self):
+        """eth_dataset.py:96-126: 'img depth' per line (absolute paths), sorted by image path; the basename of :238-239"""
+        if self.split is None:
+            raise NotImplementedError("ETHDataset needs a split file (eth_dataset.py:121-122)")
+        infos = []
+        with open(self.split) as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                img, depth_map = line.strip().split(" ")
+                infos.append(dict(img_path=img, depth_map_path=depth_map,
+                                  img_file_basename=os.path.splitext(img)[0].replace("/", "_")[1:]))
+        return sorted(infos, key=lambda x: x["img_path"])
+
+    def __len__(self):
+        return len(self.data_infos)
+
+    def check_gt_file(self, idx):
+        """the raw ground truth of item ``idx`` holds gt_shape float32 values, or ValueError naming the file -> its path"""
+        path = self.data_infos[idx]["depth_map_path"]
+        h, w = self.gt_shape
+        if os.path.getsize(path) != h * w * 4:
+            raise ValueError(f"{path}: {os.path.getsize(path)} bytes, expected {h * w * 4} ({h} x {w} float32, gt_shape)")
+        return path
+
+    def _make_slot(self):
+        return dict(img=None, gt=torch.empty(self.gt_shape, dtype=torch.float32).pin_memory(), shape=None)
+
+    def _prepare(self, idx, slot):
+        """(caller's thread) the slot's pinned image buffer holds item ``idx``'s pixels (PIL reads the header only here)"""
+        from PIL import Image
+        with Image.open(self.data_infos[idx]["img_path"]) as im:
+            need = im.height * im.width * 3
+        if slot["img"] is None or slot["img"].numel() < need:
+            slot["img"] = torch.empty((need,), dtype=torch.uint8).pin_memory()
+
+    def _read(self, idx, slot):
+        """(background thread: files and host memory only) the decoded image and the raw floats of item ``idx``"""
+        from PIL import Image
+        info = self.data_infos[idx]
+        a = np.asarray(Image.open(info["img_path"]).convert("RGB"))  # eth_dataset.py:133
+        np.copyto(slot["img"].numpy()[:a.size].reshape(a.shape), a)
+        slot["shape"] = a.shape[:2]
+        path = self.check_gt_file(idx)
+        view = slot["gt"].numpy().reshape(-1).view(np.uint8)
+        with open(path, "rb") as f:
+            if f.readinto(memoryview(view)) != view.size:
+                raise ValueError(f"{path}: short read")
+
+    def close(self):
+        if self._ahead is not None:
+            self._ahead.close()
+            self._ahead = None
+
+    def __getitem__(self, idx):
+        from . import ops
+        idx = int(idx)
+        if not 0 <= idx < len(self):
+            raise IndexError(idx)
+        if self._ahead is None:
+            self._ahead = _ReadAhead(len(self), self._make_slot, self._read, self._prepare, name="eth-read")
+        slot = self._ahead.acquire(idx)
+        h, w = slot["shape"]
+        raw = slot["img"][:h * w * 3].cuda(non_blocking=True).view(h, w, 3)
+        gt = slot["gt"].cuda(non_blocking=True)
+        self._ahead.release(idx)
+        if self.input_size_shallow is not None:  # eth_dataset.py:158-161
+            image = ops.u8_image_resize(raw, *self.input_size_shallow)
+        else:
+            image = ops.u8_image(raw, swap_rb=False)
+        depth, boundary = ops.gt_decode(gt, "eth3d", th=1.0)  # :137-139 and get_boundaries(disp_gt, th=1, dilation=0), :235
+        return dict(image_hr=image, depth_gt=depth[None, None], boundary=boundary, img_file_basename=self.data_infos[idx]["img_file_basename"])
+
+    def get_metrics(self, depth_gt, result, disp_gt_edges=None, image_hr=None, **kw):
+        """eth_dataset.py:259-290: the edge area from the image gradient (ops.image_edge_region), then the reference's three
+        compute_metrics calls as ONE fused pass over the three pixel sets, the prediction's resize inside it -> ``edge_*``,
+        ``noedge_*``, then the plain keys (the reference's order)"""
+        from . import ops
+        from .metrics import compute_metrics_fused
+        if image_hr is None:
+            raise ValueError("ETHDataset.get_metrics needs image_hr: its edge area comes from the image gradient (eth_dataset.py:261)")
+        image = torch.as_tensor(image_hr).cuda().float()
+        region = ops.image_edge_region(image.reshape(3, *image.shape[-2:]), *depth_gt.shape[-2:])  # ([1, 3, h, w] in the reference)
+        m = compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth, max_depth_eval=self.max_depth,
+                                  garg_crop=False, eigen_crop=False, dataset="", region=region, fuse_resize=True)
+        return eth_metric_order(m)
+
+    def evaluate(self, results, **kw):
+        """eth_dataset.py:292-385 without the table: np.nanmean of every key over the frames' metric dicts (a frame whose edge or
+        no-edge set is empty has NaN there and does not poison the mean; a key that is NaN in every frame stays NaN)"""
+        import warnings
+        out = {}
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=RuntimeWarning)  # "Mean of empty slice"
+            for k in results[0]:
+                out[k] = float(np.nanmean([float(r[k]) for r in results]))
+        return out
+
+
 def pseudo_label_uncertainty(uncertainty: np.ndarray, count_map: np.ndarray, n_tiles: int, count_thr: float):
     """-> (u, count) float64: ``uncertainty`` min-max normalised to [0, 1] (0 when it is flat), then 1 wherever fewer than
     ``count_thr * n_tiles`` tiles cover the pixel (tester.py:164-166, whose hard-coded 177 is the tile count of an r128 plan at patch_split_num 4 x 4)"""
@@ -654,7 +800,8 @@ class Tester:
             results = allr if allr is not None else results
         if results and "metrics" in results[0] and rank == 0:
             from .metrics import evaluate
-            self.last_eval = evaluate([r["metrics"] for r in results])
+            own = getattr(self.dataloader, "evaluate", None)  # a dataset's own aggregation (ETHDataset: nanmean)
+            self.last_eval = (own or evaluate)([r["metrics"] for r in results])
         return results
 
     def _output_stage(self):
@@ -683,7 +830,8 @@ class Tester:
         stage.submit_frame(base, result, coarse, image_raw_shape, cmap=cmap, percentiles=pct)
         entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(result.mean(dtype=torch.float64)))
         if item.get("depth_gt") is not None:
-            entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result, disp_gt_edges=item.get("boundary"))
+            entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result, disp_gt_edges=item.get("boundary"),
+                                                           image_hr=item["image_hr"])
         results.append(entry)
 
     def _emit(self, results, item, result, coarse, image_raw_shape, stage=None):
@@ -712,7 +860,7 @@ class Tester:
         entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(result.mean()))
         if item.get("depth_gt") is not None:
             entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], result if result_dev is None else result_dev,
-                                                           disp_gt_edges=item.get("boundary"))
+                                                           disp_gt_edges=item.get("boundary"), image_hr=item["image_hr"])
         results.append(entry)
 
     @torch.no_grad()

@@ -42,7 +42,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # ground-truth evaluation: raw image / disparity decode and the fused scoring sums
        "u8_image", "disp_gt", "depth_metrics",
        # the general dataset's ground-truth decoders and the scoring of a prediction of another resolution
-       "gt_decode", "depth_metrics_lowres")
+       "gt_decode", "depth_metrics_lowres",
+       # ETHDataset: the image stage and the edge area of its metric splits
+       "u8_image_resize", "image_edge_region")
 _loaded = False
 
 

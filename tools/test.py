@@ -12,7 +12,8 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
-disparities decoded and scored on the GPU; prints a1 ... sq_rel and see); ``general`` is the folder of images -- with
+disparities decoded and scored on the GPU; prints a1 ... sq_rel and see.  ETHDataset: photographs resized and raw float32 depth decoded
+on the GPU; prints the thirty keys edge_* / noedge_* / plain, split by the image's edge area); ``general`` is the folder of images -- with
 ``--cfg-option general_dataloader.dataset.gt_dir=DIR general_dataloader.dataset.gt_format=u4k|eth3d|mid|cityscapes`` a folder with the
 reference's ground truth (general_dataset.py:75-158), decoded and scored on the GPU (``image_format=u4k|cityscapes|kitti`` selects
 read_image's branch, ``gt_shape=[H,W]`` the shape of ETH3D's raw files).
@@ -63,6 +64,8 @@ def dataset_config(cfg, args):
                          "cityscapes, kitti, scannet and eth decoders are not)")
     if kind == "UnrealStereo4kDataset":
         ds_cfg["image_raw_shape"] = args.image_raw_shape
+    elif kind == "ETHDataset":  # the image's size is transform_cfg.input_size_shallow, the ground truth's gt_shape
+        pass
     else:
         ds_cfg["image_resolution"] = args.image_raw_shape
         if args.edge_metrics:
