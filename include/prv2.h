@@ -787,6 +787,43 @@ int64_t prv2_image_edge_region_workspace_bytes(int32_t h, int32_t w);
 int prv2_image_edge_region(const float* image_chw, int32_t h, int32_t w, float frac, uint8_t* region, int32_t H, int32_t W,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): compute_scale_and_shift (estimator/models/losses.py:523-544) and the
+ * three modes of ScaleAndShiftInvariantLoss (losses.py:600-700: SSI L1, gradient matching, the 'inverse' gradient-space fit) as
+ * scores of n frames, with the sums of compute_errors (metric.py:11-50) on the aligned prediction.  Additive as well: the ABI version
+ * does not change.
+ * ------------------------------------------------------------------------------------------ */
+
+/* float64 values per frame prv2_ssi_metrics writes */
+#define PRV2_SSI_VALUES 41
+
+/* bytes of workspace prv2_ssi_metrics needs for n frames of h x w (-1 for a bad shape) */
+int64_t prv2_ssi_metrics_workspace_bytes(int32_t n, int32_t h, int32_t w);
+
+/* gt: fp32 [n, h, w]; pred: fp32 [n, ph, pw].  ph == h and pw == w: the prediction is loaded; otherwise it is sampled as
+ * prv2_depth_metrics_lowres samples it (bilinear, align_corners=False: the evaluation's resize of metric.py:94-95, not the loss's).
+ * The mask m is min_depth < gt < max_depth (fp32 comparisons, a NaN is not valid) inside the crop rows [y0, y1) x columns [x0, x1);
+ * the prediction is NOT clamped for the fit and the four scores (losses.py does not), a pixel outside the mask is never looked at.
+ * Every term is float64 from the fp32 values p, g; a pair (y, y + 2) or (x, x + 2) counts when both its pixels are in the mask.
+ * Two passes over the maps, no host round trip between them.  out: DEVICE float64 [n, PRV2_SSI_VALUES]:
+ *    0, 1  scale s and shift t of compute_scale_and_shift(p, g, m) (losses.py:652)
+ *    2, 3  s_v, t_v of the vertical differences p[y] - p[y+2] against g[y] - g[y+2] (losses.py:627-635)
+ *    4, 5  s_h, t_h of the horizontal differences (losses.py:631-638)
+ *    6     N = sum m
+ *    7..21 the normal-equation sums a00 = sum p^2, a01 = sum p, a11 = count, b0 = sum p g, b1 = sum g of the three systems in that
+ *          order; a system with det = a00 a11 - a01^2 <= 0 (or NaN) has scale = shift = 0 (losses.py:537-542)
+ *    22    sum m |s p + t - g|                                                         (ssi=True, losses.py:698)
+ *    23, 24  with d = s p + t - g: sum |d[y] - d[y+2]|, sum |d[x] - d[x+2]| over the pairs    (grad_matching=True, :683-696)
+ *    25, 26  the same two with s = 1, t = 0                                            (ssi=False, grad_matching=True)
+ *    27, 28  sum |s_v (p[y] - p[y+2]) + t_v - (g[y] - g[y+2])|, and the horizontal twin with s_h, t_h   (inverse=True, :623-647)
+ *    29..40  the twelve sums of prv2_depth_metrics on the aligned prediction (float)(s p + t) (rounded once to fp32, then cleaned as
+ *          there: NaN -> min_depth, clamp); 39 and 40 are 0 (no boundary map).
+ * The reference divides every score by N, not by the number of pairs.  Per-block partials in the workspace, summed in block order:
+ * the same bits on every call, and for a frame alone or among others. */
+int prv2_ssi_metrics(const float* gt, const float* pred, int32_t n, int32_t h, int32_t w, int32_t ph, int32_t pw, float min_depth,
+                     float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* out, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,12 +20,12 @@
 // operations of PyTorch's upsample_bilinear2d kernel): the resized map is never written.
 #include <limits.h>
 
-#include "common.h"
+#include "evalgt_terms.h"
 
 namespace prv2 {
 namespace {
 
-constexpr int kTerms = 12;        // sums per pixel set (include/prv2.h prv2_depth_metrics)
+constexpr int kTerms = 12;        // sums per pixel set (include/prv2.h prv2_depth_metrics): kErrTerms error sums, then the boundary's two
 constexpr int kMaxSets = 3;       // all / inside the region / outside it
 constexpr int kMaxBlocks = 1024;  // row blocks per frame
 
@@ -64,16 +64,7 @@ __global__ void __launch_bounds__(256) u8_image_kernel(const uint8_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// four pixels x0 .. x0 + 3 of row y per thread; the neighbours above / below come as rows, left / right as single loads
-__device__ __forceinline__ void load4(const float* __restrict__ row, int x0, int w, int vec, float* v) {
-  if (vec) {
-    const float4 t = *reinterpret_cast<const float4*>(row + x0);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-  } else {
-    for (int k = 0; k < 4; ++k) v[k] = x0 + k < w ? row[x0 + k] : 0.f;
-  }
-}
-
+// four pixels x0 .. x0 + 3 of row y per thread (load4, evalgt_terms.h); the neighbours above / below come as rows, left / right as single loads
 __global__ void __launch_bounds__(256) disp_gt_kernel(const float* __restrict__ disp, float* __restrict__ depth, uint8_t* __restrict__ boundary,
                                                       int h, int w, float factor, float th, int vec) {
   const int wq = (w + 3) / 4;
@@ -229,16 +220,7 @@ struct MetricArgs {
   float sch, scw;    // LOWRES: ph / h and pw / w (fp32 divisions)
 };
 
-// F.interpolate(mode='bilinear', align_corners=False) at one output coordinate, as PyTorch's kernel computes it (its compiler
-// contracts a * b + c, so the fused operations are spelled out here: this file is built with -ffp-contract=off): the source
-// coordinate fma(scale, dst + 0.5, -0.5) clamped at 0, the lower index, whether there is an upper one, and the weight lambda
-__device__ __forceinline__ void bilinear_src(float scale, int dst, int n_in, int& i0, int& step, float& lam) {
-  float s = __builtin_fmaf(scale, (float)dst + 0.5f, -0.5f);
-  s = s < 0.f ? 0.f : s;
-  i0 = min((int)s, n_in - 1);  // (never beyond the map, whatever the rounding of scale)
-  step = i0 < n_in - 1 ? 1 : 0;
-  lam = s - (float)i0;
-}
+// (bilinear_src / bilinear_at, clean_pred and error_terms: evalgt_terms.h, shared with csrc/ssi_eval.hip)
 
 // NaN-propagating minimum (np.minimum / torch.minimum)
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : (b < a ? b : a); }
@@ -287,18 +269,7 @@ __global__ void __launch_bounds__(256) depth_metrics_kernel(MetricArgs a, double
       uint8_t b[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
       load4(gt + ro, x0, w, a.vec, g);
       if (LOWRES) {
-        const float hy = 1.0f - ly;
-        for (int k = 0; k < 4; ++k) {
-          p[k] = 0.f;
-          if (x0 + k >= w) continue;
-          int sx0, sxs;
-          float lx;
-          bilinear_src(a.scw, x0 + k, a.pw, sx0, sxs, lx);
-          const float hx = 1.0f - lx;
-          const float top = __builtin_fmaf(hx, pr0[sx0], lx * pr0[sx0 + sxs]);
-          const float bot = __builtin_fmaf(hx, pr1[sx0], lx * pr1[sx0 + sxs]);
-          p[k] = __builtin_fmaf(hy, top, ly * bot);
-        }
+        for (int k = 0; k < 4; ++k) p[k] = x0 + k < w ? bilinear_at(pr0, pr1, ly, a.scw, x0 + k, a.pw) : 0.f;
       } else {
         load4(pred + ro, x0, w, a.vec, p);
       }
@@ -322,24 +293,9 @@ __global__ void __launch_bounds__(256) depth_metrics_kernel(MetricArgs a, double
         const int x = x0 + k;
         const float gk = g[k];
         if (!(x >= a.x0 && x < a.x1 && x < w && gk > a.mn && gk < a.mx)) continue;  // a NaN gt is not valid
-        float pk = p[k];  // the reference's order: NaN -> min, clamp, inf -> max (the clamp has done it)
-        pk = pk != pk ? a.mn : pk;
-        pk = pk < a.mn ? a.mn : pk;
-        pk = pk > a.mx ? a.mx : pk;
-        const double G = (double)gk, P = (double)pk;
-        const double ratio = fmax(G / P, P / G);
-        const double d = G - P, err = log(P) - log(G), d2 = d * d;
+        const float pk = clean_pred(p[k], a.mn, a.mx);
         double t[kTerms];
-        t[0] = 1.0;
-        t[1] = ratio < 1.25 ? 1.0 : 0.0;
-        t[2] = ratio < 1.5625 ? 1.0 : 0.0;
-        t[3] = ratio < 1.953125 ? 1.0 : 0.0;
-        t[4] = fabs(d) / G;
-        t[5] = d2;
-        t[6] = fabs(log10(G) - log10(P));
-        t[7] = err * err;
-        t[8] = err;
-        t[9] = d2 / G;
+        error_terms(gk, pk, t);
         t[10] = 0.0;
         t[11] = 0.0;
         if (b[k]) {
@@ -465,8 +421,6 @@ __global__ void __launch_bounds__(256) edge_region_kernel(const uint8_t* __restr
     }
   }
 }
-
-static inline bool aligned(const void* p, int bytes) { return p == nullptr || ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0; }
 
 }  // namespace
 }  // namespace prv2

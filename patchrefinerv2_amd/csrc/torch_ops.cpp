@@ -1207,6 +1207,23 @@ Tensor image_edge_region(const Tensor& image, int64_t H, int64_t W, double frac)
      "image_edge_region");
   return region;
 }
+// scale-and-shift-invariant evaluation (losses.py:523-544, :600-700): pred [n, h, w], or [n, ph, pw] sampled inside the kernels
+Tensor ssi_metrics(const Tensor& gt, const Tensor& pred, double min_depth, double max_depth, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
+  dev_frames(gt, "gt", at::kFloat);
+  dev_frames(pred, "pred", at::kFloat);
+  TORCH_CHECK(pred.size(0) == gt.size(0) && pred.device() == gt.device(), "prv2::ssi_metrics: pred must hold gt's ", gt.size(0),
+              " frames on its device");
+  const int64_t bytes = prv2_ssi_metrics_workspace_bytes((int)gt.size(0), (int)gt.size(1), (int)gt.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::ssi_metrics: bad frame shape ", gt.sizes());
+  Tensor ws = at::empty({bytes}, gt.options().dtype(at::kByte));
+  Tensor out = at::empty({gt.size(0), PRV2_SSI_VALUES}, gt.options().dtype(at::kDouble));
+  Launch L(gt);
+  ok(prv2_ssi_metrics(gt.data_ptr<float>(), pred.data_ptr<float>(), (int)gt.size(0), (int)gt.size(1), (int)gt.size(2), (int)pred.size(1),
+                      (int)pred.size(2), (float)min_depth, (float)max_depth, (int)y0, (int)y1, (int)x0, (int)x1, out.data_ptr<double>(),
+                      ws.data_ptr(), ws.numel(), L.stream),
+     "ssi_metrics");
+  return out;
+}
 
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
@@ -1356,6 +1373,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("image_edge_region(Tensor image, int H, int W, float frac) -> Tensor");
   m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
         "int x0, int x1) -> Tensor");
+  m.def("ssi_metrics(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1441,4 +1459,5 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("depth_metrics_lowres", &depth_metrics_lowres);
   m.impl("u8_image_resize", &u8_image_resize);
   m.impl("image_edge_region", &image_edge_region);
+  m.impl("ssi_metrics", &ssi_metrics);
 }

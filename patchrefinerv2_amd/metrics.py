@@ -7,6 +7,10 @@ compute_metrics     estimator/utils/metric.py:87-149  (resize, clamp, valid / cr
 colorize            estimator/utils/color.py:95-158   (percentile normalisation + matplotlib colour map, RGBA uint8)
 compute_metrics_fused  the same metrics from one fused GPU pass (csrc/evalgt.hip), optionally for three pixel sets at once and with the
                        resize of a low-resolution prediction inside that pass (fuse_resize)
+compute_scale_and_shift   estimator/models/losses.py:523-544 (the least-squares scale and shift of a prediction inside a mask)
+compute_ssi_metrics       estimator/models/losses.py:600-700 (ScaleAndShiftInvariantLoss' three modes as evaluation scores) and
+                          compute_errors on the aligned prediction; float64 numpy, the oracle of compute_ssi_metrics_fused
+                          (csrc/ssi_eval.hip: two fused GPU passes, one D2H); pinned by tests/golden/ssi_eval.npz
 
 Pinned by tests/golden/output_stage.npz (the reference functions imported by oracle/make_golden.py).
 """
@@ -218,6 +222,124 @@ def compute_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True
                 for name, k in (("edge", 1), ("noedge", 2)):
                     out.update({f"{name}_{key}": v for key, v in metrics_from_sums(sums[f, k], see).items()})
         rows.append(out)
+    return rows[0] if single else rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Scale-and-shift-invariant evaluation: how good a prediction's structure is once its global scale and offset are taken out.
+#   compute_scale_and_shift        estimator/models/losses.py:523-544
+#   ScaleAndShiftInvariantLoss     estimator/models/losses.py:600-700 (ssi L1; ssi / plain gradient matching; the 'inverse' fit)
+# The mask is compute_metrics' (valid range and crop); the prediction is not clamped (the loss does not clamp it); every score divides
+# by the mask count N, not by the number of pairs; N <= 1 gives NaN everywhere (the loss' ``prediction * 0.0`` there is a training
+# guard).  A pixel outside the mask is never looked at (the reference multiplies by the mask, which lets a NaN there through).
+# Pinned by tests/golden/ssi_eval.npz (tools/make_ssi_golden.py runs the reference's own functions in float64).
+# ------------------------------------------------------------------------------------------------------------------
+SSI_ERROR_KEYS = ("a1", "a2", "a3", "abs_rel", "rmse", "log_10", "rmse_log", "silog", "sq_rel")
+SSI_KEYS = ("ssi_scale", "ssi_shift", "ssi_l1", "ssi_gm", "gm", "ssi_gm_inv") + tuple("ssi_" + k for k in SSI_ERROR_KEYS)
+
+
+def _np64(x) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.asarray(x, dtype=np.float64)
+
+
+def compute_scale_and_shift(pred, gt, mask):
+    """losses.py:523-544 in float64: the (scale, shift) that minimise sum mask (scale * pred + shift - gt)^2 from the 2 x 2 normal
+    equations, both 0 when the determinant is not positive.  [H, W] maps -> two floats; [B, H, W] -> two arrays [B]."""
+    m = np.asarray(mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else mask).astype(bool)
+    p, g = np.where(m, _np64(pred), 0.0), np.where(m, _np64(gt), 0.0)
+    ax = (-2, -1)
+    a00, a01, a11 = (p * p).sum(ax), p.sum(ax), m.sum(ax).astype(np.float64)
+    b0, b1 = (p * g).sum(ax), g.sum(ax)
+    det = a00 * a11 - a01 * a01
+    ok = det > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x0 = np.where(ok, (a11 * b0 - a01 * b1) / det, 0.0)
+        x1 = np.where(ok, (-a01 * b0 + a00 * b1) / det, 0.0)
+    return (float(x0), float(x1)) if x0.ndim == 0 else (x0, x1)
+
+
+def _ssi_scores(p, g, m) -> dict:
+    """one frame: float64 maps p, g and the bool mask m -> scale, shift and the four scores"""
+    n = float(m.sum())
+    p, g = np.where(m, p, 0.0), np.where(m, g, 0.0)  # (outside the mask nothing is looked at)
+    vm, hm = m[:-2] & m[2:], m[:, :-2] & m[:, 2:]
+    s, t = compute_scale_and_shift(p, g, m)
+
+    def gm(d):  # losses.py:683-696: sum(h) + sum(v) over the pairs inside the mask
+        return float(np.abs(d[:, :-2] - d[:, 2:])[hm].sum() + np.abs(d[:-2] - d[2:])[vm].sum())
+    vp, vg, hp, hg = p[:-2] - p[2:], g[:-2] - g[2:], p[:, :-2] - p[:, 2:], g[:, :-2] - g[:, 2:]
+    sv, tv = compute_scale_and_shift(vp, vg, vm)
+    sh, th = compute_scale_and_shift(hp, hg, hm)
+    inv = float(np.abs(sv * vp + tv - vg)[vm].sum() + np.abs(sh * hp + th - hg)[hm].sum())  # :641-644
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return dict(ssi_scale=s, ssi_shift=t, ssi_l1=float(np.abs(s * p + t - g)[m].sum()) / n, ssi_gm=gm((s * p + t - g) * m) / n,
+                    gm=gm((p - g) * m) / n, ssi_gm_inv=inv / n)
+
+
+def compute_ssi_metrics(gt, pred, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu", min_depth_eval=0.1, max_depth_eval=10):
+    """The scale-and-shift-invariant scores of one frame on the host, float64 from the fp32 maps: ``ssi_scale`` / ``ssi_shift``
+    (compute_scale_and_shift inside compute_metrics' mask), ``ssi_l1``, ``ssi_gm``, ``gm`` and ``ssi_gm_inv``
+    (ScaleAndShiftInvariantLoss with ssi / ssi + grad_matching / grad_matching alone / inverse), and ``ssi_a1 ... ssi_sq_rel``:
+    compute_metrics of the aligned prediction (scale * pred + shift rounded once to fp32), the fp32 values widened to float64 so that
+    its sums are float64 too.  A prediction of another shape is resized as compute_metrics resizes it (bilinear, align_corners=False)."""
+    gt, pred = torch.as_tensor(gt).detach().cpu().float(), torch.as_tensor(pred).detach().cpu().float()
+    if gt.shape[-2:] != pred.shape[-2:] and interpolate:
+        pred = F.interpolate(pred.reshape(1, 1, *pred.shape[-2:]), gt.shape[-2:], mode="bilinear", align_corners=False)
+    g32 = gt.reshape(gt.shape[-2:]).numpy()
+    p32 = pred.reshape(pred.shape[-2:]).numpy()
+    h, w = g32.shape
+    y0, y1, x0, x1 = _eval_crop(h, w, garg_crop, eigen_crop, dataset)
+    m = np.zeros((h, w), bool)
+    m[y0:y1, x0:x1] = True
+    with np.errstate(invalid="ignore"):
+        m &= (g32 > np.float32(min_depth_eval)) & (g32 < np.float32(max_depth_eval))  # fp32 comparisons; a NaN is not valid
+    if m.sum() <= 1:
+        return {k: float("nan") for k in SSI_KEYS}
+    p, g = p32.astype(np.float64), g32.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = _ssi_scores(p, g, m)
+        aligned = (out["ssi_scale"] * p + out["ssi_shift"]).astype(np.float32)
+    # (the bounds as the fp32 values an fp32 map is compared with and clamped to: float64 arithmetic, fp32 decisions)
+    errs = compute_metrics(torch.from_numpy(np.where(m, g, 0.0)), torch.from_numpy(aligned.astype(np.float64)), interpolate=False,
+                           garg_crop=garg_crop, eigen_crop=eigen_crop, dataset=dataset, min_depth_eval=float(np.float32(min_depth_eval)),
+                           max_depth_eval=float(np.float32(max_depth_eval)))
+    out.update({"ssi_" + k: float(errs[k]) for k in SSI_ERROR_KEYS})
+    return out
+
+
+def ssi_from_values(v) -> dict:
+    """one frame's row of ops.ssi_metrics (include/prv2.h prv2_ssi_metrics) -> the dict of compute_ssi_metrics"""
+    v = [float(x) for x in v]
+    n = v[6]
+    if n <= 1:
+        return {k: float("nan") for k in SSI_KEYS}
+    out = dict(ssi_scale=v[0], ssi_shift=v[1], ssi_l1=v[22] / n, ssi_gm=(v[24] + v[23]) / n, gm=(v[26] + v[25]) / n,
+               ssi_gm_inv=(v[27] + v[28]) / n)
+    out.update({"ssi_" + k: x for k, x in metrics_from_sums(v[29:41], False).items()})
+    return out
+
+
+@torch.no_grad()
+def compute_ssi_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu",
+                              min_depth_eval=0.1, max_depth_eval=10, fuse_resize=False):
+    """``compute_ssi_metrics`` from two fused passes on the GPU (csrc/ssi_eval.hip, ops.ssi_metrics): the fits are solved on the device
+    between the passes, ONE D2H of 41 float64 values per frame.  A dict for one map ([H, W] / [1, 1, H, W]), a list of dicts for B
+    maps.  Inputs on the host are copied to the GPU.  ``fuse_resize``: a prediction of another resolution is sampled inside the kernels
+    (the operations of F.interpolate, the resized map is never written) instead of being resized first."""
+    from . import ops
+    dev = pred.device if pred.is_cuda else (gt.device if gt.is_cuda else torch.device("cuda"))
+    gt, pred = gt.to(dev), pred.to(dev)
+    lowres = bool(fuse_resize) and interpolate and gt.shape[-2:] != pred.shape[-2:]
+    if gt.shape[-2:] != pred.shape[-2:] and interpolate and not lowres:
+        p4 = pred if pred.dim() == 4 else pred.reshape(-1, 1, *pred.shape[-2:])
+        pred = F.interpolate(p4.float(), gt.shape[-2:], mode="bilinear", align_corners=False)
+    g, single = _frames_of(gt.float())
+    p = pred.float().reshape(g.shape[0], *pred.shape[-2:]) if lowres else pred.float().reshape(g.shape)
+    crop = _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
+    vals = ops.ssi_metrics(g, p, min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
+    rows = [ssi_from_values(v) for v in vals]
     return rows[0] if single else rows
 
 

@@ -1880,3 +1880,36 @@ def image_edge_region(image_chw, H, W, frac=0.5):
         call = lambda: _c("image_edge_region", img.data_ptr(), h, w, float(frac), region.data_ptr(), H, W, ws.data_ptr(), wsb)  # noqa: E731
     PROFILER.launch_aux("image_edge_region", 21.0 * h * w + 1.0 * H * W, call, f"{h}x{w}->{H}x{W}")
     return box[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Scale-and-shift-invariant evaluation (estimator/models/losses.py:523-544, :600-700; csrc/ssi_eval.hip), both dispatch routes.
+# ------------------------------------------------------------------------------------------------------------------
+SSI_VALUES = L.SSI_VALUES
+
+
+def ssi_metrics(gt, pred, min_depth=1e-3, max_depth=80.0, crop=None):
+    """fp32 frames gt [B, H, W] and pred [B, H, W] (or [B, h, w]: sampled inside the kernels as ``depth_metrics_lowres`` samples it) ->
+    float64 [B, 41] on the device: the scale / shift of compute_scale_and_shift for the values and for the vertical / horizontal
+    stride-2 differences, the mask count N, the normal-equation sums, the sums behind ssi_l1 / ssi_gm / gm / ssi_gm_inv and the twelve
+    sums of ``depth_metrics`` on the aligned prediction (the layout: include/prv2.h prv2_ssi_metrics).  The mask is
+    min_depth < gt < max_depth inside ``crop`` = (y0, y1, x0, x1), None: the whole frame.  Two passes, no host synchronisation;
+    bit-identical from call to call and for a frame alone or in a batch."""
+    g, p = _edge_frames(gt, torch.float32), _edge_frames(pred, torch.float32)
+    if g.shape[0] != p.shape[0]:
+        raise ValueError(f"ssi_metrics: gt {tuple(g.shape)} and pred {tuple(p.shape)} differ in their frame count")
+    y0, y1, x0, x1 = (0, g.shape[1], 0, g.shape[2]) if crop is None else (int(v) for v in crop)
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().ssi_metrics(g, p, float(min_depth), float(max_depth), y0, y1, x0, x1))  # noqa: E731
+    else:
+        wsb = L.load().prv2_ssi_metrics_workspace_bytes(*g.shape)
+        if wsb < 0:
+            raise ValueError(f"ssi_metrics: bad frame shape {tuple(g.shape)}")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+        out = torch.empty((g.shape[0], SSI_VALUES), dtype=torch.float64, device=g.device)
+        box.append(out)
+        call = lambda: _c("ssi_metrics", g.data_ptr(), p.data_ptr(), *g.shape, p.shape[1], p.shape[2], float(min_depth), float(max_depth),  # noqa: E731
+                          y0, y1, x0, x1, out.data_ptr(), ws.data_ptr(), wsb)
+    PROFILER.launch_aux("ssi_metrics", 2.0 * (4.0 * g.numel() + 4.0 * p.numel()), call, f"{g.shape[0]}x{g.shape[1]}x{g.shape[2]}<-{p.shape[1]}x{p.shape[2]}")
+    return box[0]

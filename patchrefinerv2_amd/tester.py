@@ -7,6 +7,8 @@ ImageDataset        estimator/datasets/general_dataset.py:64-245 (folder of imag
 UnrealStereo4kDataset  estimator/datasets/u4k_dataset.py:20-233 (split file -> image_hr / depth_gt / boundary, decoded on the GPU)
 ETHDataset          estimator/datasets/eth_dataset.py:23-385 (split file -> image_hr resized on the GPU / depth_gt / boundary; every
                     metric also inside and outside the image's edge area, found on the GPU)
+``ssi_metrics=True`` (tools/test.py --ssi-metrics) on any of the three datasets: get_metrics adds the scale-and-shift-invariant scores
+                    of estimator/models/losses.py:523-544, :600-700 (metrics.SSI_KEYS; two fused GPU passes, csrc/ssi_eval.hip)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 ``runner_info.device_output`` (tools/test.py --device-output) routes the saved files through output.OutputStage: scanlines made on
 the GPU, deflate on a writer pool; the default is the host route below.  ``runner_info.device_deflate`` (--device-deflate, needs
@@ -260,9 +262,11 @@ class ImageDataset:
     ``gt_shape`` replaces the reference's literal 4032 x 6048 (ETH3D's raw files carry no shape).  ``image_format`` selects
     read_image's branch (:22-62): None / 'mid' bicubic to ``image_resolution``; 'u4k' raw BGR bytes of ``image_resolution``;
     'cityscapes' RGB / 255 as it is; 'kitti' its 352 x 1216 kb-crop -- the last three through ops.u8_image."""
+    ssi_metrics = False  # (the constructor's flag; an instance made without it scores as before)
+
     def __init__(self, rgb_image_dir, mode="", min_depth=1e-3, max_depth=80, gt_dir=None, image_resolution=(2160, 3840),
                  dataset_name="", network_process_size=(384, 512), resize_mode="zoe", edge_metrics=False, gt_format=None, image_format=None,
-                 gt_shape=(4032, 6048)):
+                 gt_shape=(4032, 6048), ssi_metrics=False):
         if gt_format == "gta":
             raise NotImplementedError("ImageDataset(gt_format='gta'): the .exr ground truth (general_dataset.py:96-101) needs imageio, "
                                       "which is not installed")
@@ -273,6 +277,8 @@ class ImageDataset:
         self.rgb_image_dir = rgb_image_dir
         # edge_metrics: get_metrics adds the boundary metrics and the edge_* / noedge_* splits (metrics.compute_boundary_metrics)
         self.edge_metrics = bool(edge_metrics)
+        # ssi_metrics: get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS) over the plain pixel set
+        self.ssi_metrics = bool(ssi_metrics)
         self.files = sorted(os.listdir(rgb_image_dir))
         # ground truth: metric depth as <gt_dir>/<basename>.npy, or (gt_format) the reference's per-dataset files
         self.gt_dir = gt_dir
@@ -424,6 +430,13 @@ class ImageDataset:
         out = score(depth_gt, result, **common)
         if self.edge_metrics:
             out.update(self._edge_metrics(depth_gt, result, dev, score, common))
+        if self.ssi_metrics:  # (losses.py:523-544, :600-700) on the device whenever the maps are there, else the host restatement
+            from .metrics import compute_ssi_metrics, compute_ssi_metrics_fused
+            common.pop("disp_gt_edges")
+            if self.gt_format is not None or dev:
+                out.update(compute_ssi_metrics_fused(depth_gt, result, fuse_resize=True, **common))
+            else:
+                out.update(compute_ssi_metrics(depth_gt, result, **common))
         return out
 
     def _edge_metrics(self, depth_gt, result, dev, score, common):
@@ -461,9 +474,10 @@ class UnrealStereo4kDataset:
     reference hard-codes to (2160, 3840).  Not built: ``mode='train'`` (augmentation, crops) and ``consistency=True``."""
 
     dataset_name = "u4k"
+    ssi_metrics = False  # (the constructor's flag)
 
     def __init__(self, mode, data_root, split, transform_cfg, min_depth, max_depth, consistency=False, overlap=0, patch_raw_shape=(540, 960),
-                 resize_mode="zoe", pre_norm_bbox=True, image_raw_shape=(2160, 3840)):
+                 resize_mode="zoe", pre_norm_bbox=True, image_raw_shape=(2160, 3840), ssi_metrics=False):
         if mode == "train":
             raise NotImplementedError("UnrealStereo4kDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / "
                                       "random_crop, u4k_dataset.py:131-213) is not built; inference modes only")
@@ -478,6 +492,7 @@ class UnrealStereo4kDataset:
         self.network_process_size = tuple(transform_cfg["network_process_size"])
         self.resize_mode = resize_mode
         self.image_raw_shape = (int(image_raw_shape[0]), int(image_raw_shape[1]))
+        self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS)
         self.data_infos = self.load_data_list()
         self._ahead = None     # the staging slots and their reader (_ReadAhead), made by the first item
 
@@ -549,9 +564,12 @@ class UnrealStereo4kDataset:
 
     def get_metrics(self, depth_gt, result, disp_gt_edges=None, **kw):
         """u4k_dataset.py:232-233 through the fused kernel (a host ``result`` is copied to the device first)"""
-        from .metrics import compute_metrics_fused
-        return compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth, max_depth_eval=self.max_depth,
-                                     garg_crop=False, eigen_crop=False, dataset="")
+        from .metrics import compute_metrics_fused, compute_ssi_metrics_fused
+        common = dict(min_depth_eval=self.min_depth, max_depth_eval=self.max_depth, garg_crop=False, eigen_crop=False, dataset="")
+        out = compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, **common)
+        if self.ssi_metrics:
+            out.update(compute_ssi_metrics_fused(depth_gt, result, **common))
+        return out
 
 
 ETH_METRIC_KEYS = ("a1", "a2", "a3", "abs_rel", "rmse", "log_10", "rmse_log", "silog", "sq_rel", "see")  # compute_metrics' order
@@ -577,9 +595,10 @@ class ETHDataset:
     not built: Tester.run_consistency makes its own crops.  Not built: ``mode='train'`` and ``transform_cfg.random_crop``."""
 
     dataset_name = "eth3d"
+    ssi_metrics = False  # (the constructor's flag)
 
     def __init__(self, mode, split, transform_cfg, min_depth, max_depth, stitcher_stage=0, overlap=0, crop_strategy="random",
-                 resize_mode="zoe", gt_shape=(4032, 6048)):
+                 resize_mode="zoe", gt_shape=(4032, 6048), ssi_metrics=False):
         if mode == "train":
             raise NotImplementedError("ETHDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip, "
                                       "eth_dataset.py:144-167) is not built; inference modes only")
@@ -593,6 +612,7 @@ class ETHDataset:
         self.resize_mode = resize_mode
         self.stitcher_stage, self.overlap, self.crop_strategy = stitcher_stage, overlap, crop_strategy
         self.gt_shape = (int(gt_shape[0]), int(gt_shape[1]))
+        self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS), plain set only
         shallow = transform_cfg.get("input_size_shallow", None)
         self.input_size_shallow = None if shallow is None else (int(shallow[0]), int(shallow[1]))
         self.data_infos = self.load_data_list()
@@ -676,14 +696,16 @@ class ETHDataset:
         compute_metrics calls as ONE fused pass over the three pixel sets, the prediction's resize inside it -> ``edge_*``,
         ``noedge_*``, then the plain keys (the reference's order)"""
         from . import ops
-        from .metrics import compute_metrics_fused
+        from .metrics import compute_metrics_fused, compute_ssi_metrics_fused
         if image_hr is None:
             raise ValueError("ETHDataset.get_metrics needs image_hr: its edge area comes from the image gradient (eth_dataset.py:261)")
         image = torch.as_tensor(image_hr).cuda().float()
         region = ops.image_edge_region(image.reshape(3, *image.shape[-2:]), *depth_gt.shape[-2:])  # ([1, 3, h, w] in the reference)
-        m = compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, min_depth_eval=self.min_depth, max_depth_eval=self.max_depth,
-                                  garg_crop=False, eigen_crop=False, dataset="", region=region, fuse_resize=True)
-        return eth_metric_order(m)
+        common = dict(min_depth_eval=self.min_depth, max_depth_eval=self.max_depth, garg_crop=False, eigen_crop=False, dataset="", fuse_resize=True)
+        out = eth_metric_order(compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, region=region, **common))
+        if self.ssi_metrics:  # after the reference's thirty keys, over the plain pixel set
+            out.update(compute_ssi_metrics_fused(depth_gt, result, **common))
+        return out
 
     def evaluate(self, results, **kw):
         """eth_dataset.py:292-385 without the table: np.nanmean of every key over the frames' metric dicts (a frame whose edge or

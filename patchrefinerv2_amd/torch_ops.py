@@ -44,7 +44,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # the general dataset's ground-truth decoders and the scoring of a prediction of another resolution
        "gt_decode", "depth_metrics_lowres",
        # ETHDataset: the image stage and the edge area of its metric splits
-       "u8_image_resize", "image_edge_region")
+       "u8_image_resize", "image_edge_region",
+       # scale-and-shift-invariant evaluation: the fits, the SSI scores and the error sums of the aligned prediction
+       "ssi_metrics")
 _loaded = False
 
 

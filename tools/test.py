@@ -11,6 +11,7 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--device-output [--output-workers N]``: with ``--save``, the output files' pixels are produced on the GPU and written by a thread pool.
 ``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
+``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
 ``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
 disparities decoded and scored on the GPU; prints a1 ... sq_rel and see.  ETHDataset: photographs resized and raw float32 depth decoded
 on the GPU; prints the thirty keys edge_* / noedge_* / plain, split by the image's edge area); ``general`` is the folder of images -- with
@@ -70,6 +71,8 @@ def dataset_config(cfg, args):
         ds_cfg["image_resolution"] = args.image_raw_shape
         if args.edge_metrics:
             ds_cfg["edge_metrics"] = True
+    if getattr(args, "ssi_metrics", False):  # every dataset class takes it
+        ds_cfg["ssi_metrics"] = True
     return ds_cfg
 
 
@@ -112,6 +115,10 @@ def main():
     ap.add_argument("--edge-metrics", action="store_true",
                     help="with ground truth (dataset gt_dir): add the boundary metrics (EdgeAcc, EdgeComp, precision, recall, f1_score, hamming, "
                          "acc) and the edge_* / noedge_* split of every depth metric (metric.py:210-272, scannet_dataset.py:221-243)")
+    ap.add_argument("--ssi-metrics", action="store_true",
+                    help="with ground truth (any --test-type): add the scale-and-shift-invariant scores ssi_scale, ssi_shift, ssi_l1, ssi_gm, gm, "
+                         "ssi_gm_inv and ssi_a1 ... ssi_sq_rel (losses.py:523-544, :600-700: the prediction aligned to the ground truth by a "
+                         "least-squares scale and shift), two fused GPU passes per frame")
     ap.add_argument("--device-output", action="store_true",
                     help="with --save: produce the PNG scanlines on the GPU and deflate / write them on a pool of threads while the next "
                          "frame computes (patchrefinerv2_amd/output.py); the files are the host route's")
