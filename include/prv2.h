@@ -824,6 +824,42 @@ int prv2_ssi_metrics(const float* gt, const float* pred, int32_t n, int32_t h, i
                      float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, double* out, void* workspace, int64_t workspace_bytes,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Sparsification (csrc/sparsify.hip): does a per-pixel uncertainty mark the pixels where the depth is wrong?  The sparsification
+ * curves behind AUSE / AURG (Ilg et al. 2018; Poggi et al. 2020) of n frames.  Not in the reference (its tester only writes the
+ * uncertainty, estimator/tester/tester.py:132-181); the definition below is this project's, chosen so that ties need no tie-break,
+ * and metrics.compute_uncertainty_metrics is its numpy statement.  Additive: the ABI version does not change.
+ *   valid        min_depth < gt < max_depth (fp32 comparisons, a NaN is not valid; no crop); n = the number of valid pixels
+ *   pred         cleaned as metric.py:98-101: NaN -> min_depth, < min_depth -> min_depth, > max_depth (inf too) -> max_depth
+ *   key          uncert, +inf where (double)count < min_count (count given); a NaN orders last, as in np.sort
+ *   terms        fp32, correctly rounded, no contraction: e_rel = |gt - pred| / gt, e_sq = (gt - pred) * (gt - pred)
+ *   level k      k = 0 .. L - 1, for a key set K: n_k = n - floor(n k / L), t_k = the n_k-th smallest key (an exact order statistic),
+ *                S_k = {i valid : K_i <= t_k} (ties are kept; every key is <= a NaN t_k)
+ *   three orderings: K = the uncertainty key, K = e_rel (the oracle of abs_rel), K = e_sq (the oracle of rmse)
+ * ------------------------------------------------------------------------------------------ */
+
+#define PRV2_SPARSIFY_MAX_LEVELS 64
+/* float64 values per frame prv2_sparsify writes for L levels */
+#define PRV2_SPARSIFY_VALUES(L) (1 + 10 * (L))
+
+/* bytes of workspace prv2_sparsify needs for n frames of h x w and L levels (-1 for a bad shape or L outside [1, 64]): the three key
+ * maps and the valid mask (13 bytes per pixel), the selection state of prv2_order_stats and the per-block partials */
+int64_t prv2_sparsify_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t levels);
+
+/* gt, pred, uncert: fp32 [n, h, w]; count: fp32 [n, h, w] or NULL (then min_count is not looked at); n * h * w < 2^29.
+ * out: DEVICE float64 [n, PRV2_SPARSIFY_VALUES(L)] per frame:
+ *    0                 n
+ *    1 .. 3L           the thresholds t_k of the uncertainty, the e_rel and the e_sq ordering (fp32 values; NaN for n = 0)
+ *    1 + 3L .. 10L     seven rows of L float64 sums over S_k: |S_k|, sum e_rel, sum e_sq (uncertainty ordering); |S_k|, sum e_rel
+ *                      (e_rel ordering); |S_k|, sum e_sq (e_sq ordering)
+ * One pass makes the key maps and the mask, prv2_order_stats' radix select finds the thresholds (3 ceil(L / 8) selections, the ranks
+ * computed from each frame's count on the device), one pass puts every valid pixel into its bucket (t_{k+1}, t_k] of each ordering,
+ * a last kernel adds the per-block partials in block order and forms the suffix sums.  No host round trip, no floating-point
+ * atomics: the same bits on every call, and for a frame alone or among others. */
+int prv2_sparsify(const float* gt, const float* pred, const float* uncert, const float* count, double min_count, int32_t n, int32_t h,
+                  int32_t w, float min_depth, float max_depth, int32_t levels, double* out, void* workspace, int64_t workspace_bytes,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ struct SelArgs {
   int64_t hw;
   int32_t n_ranks;
   int64_t ranks[kMaxRanks];  // >= 0: from the smallest; < 0: count + rank (-1 = the largest); clamped to [0, count - 1]
+  int32_t levels;            // > 0: ranks[r] is a sparsification level k, the rank (count - floor(count k / levels)) - 1 of each frame's own count
+  int32_t out_stride;        // floats between two frames' rows of ``out``
 };
 
 __device__ __forceinline__ bool sel_valid(const SelArgs& a, int64_t i, float v) {
@@ -122,6 +124,7 @@ __global__ void __launch_bounds__(256) sel_scan_kernel(SelArgs a, SelState* __re
         counts[f] = (int64_t)count;
       }
       int64_t want = a.ranks[r] < 0 ? (int64_t)count + a.ranks[r] : a.ranks[r];
+      if (a.levels > 0) want = (int64_t)count - ((int64_t)count * a.ranks[r]) / a.levels - 1;
       if (want > (int64_t)count - 1) want = (int64_t)count - 1;
       if (want < 0) want = 0;
       k = (uint32_t)want;
@@ -144,7 +147,7 @@ __global__ void __launch_bounds__(256) sel_scan_kernel(SelArgs a, SelState* __re
     prefix = (prefix << 8) | (uint32_t)b;
     k -= cum;
     if (PASS == kPasses - 1) {
-      out[(int64_t)f * a.n_ranks + r] = count > 0 ? value_of(prefix) : __uint_as_float(0x7FC00000u);
+      out[(int64_t)f * a.out_stride + r] = count > 0 ? value_of(prefix) : __uint_as_float(0x7FC00000u);
     } else {
       s->prefix[r] = prefix;
       s->k[r] = k;
@@ -367,7 +370,44 @@ static int check_lut(const char* name, const void* lut, int ncolors) {
   return 0;
 }
 
+// the launches of one selection: a clear, then per digit a histogram and a scan (a count-only call stops after the first pair: still a
+// fixed launch count per argument set)
+static void launch_select(const SelArgs& a, int n, int64_t* counts, float* out, void* workspace, hipStream_t s) {
+  SelState* st = (SelState*)workspace;
+  const int blocks = (int)(cdiv(a.hw, 256) < kSelBlocks ? cdiv(a.hw, 256) : kSelBlocks);
+  const dim3 grid(blocks, n);
+  hipLaunchKernelGGL(sel_clear_kernel, dim3(8, n), dim3(256), 0, s, st);
+  hipLaunchKernelGGL(sel_hist_kernel<0>, grid, dim3(256), 0, s, a, st);
+  hipLaunchKernelGGL(sel_scan_kernel<0>, dim3(n), dim3(256), 0, s, a, st, counts, out);
+  if (a.n_ranks > 0) {
+    hipLaunchKernelGGL(sel_hist_kernel<1>, grid, dim3(256), 0, s, a, st);
+    hipLaunchKernelGGL(sel_scan_kernel<1>, dim3(n), dim3(256), 0, s, a, st, counts, out);
+    hipLaunchKernelGGL(sel_hist_kernel<2>, grid, dim3(256), 0, s, a, st);
+    hipLaunchKernelGGL(sel_scan_kernel<2>, dim3(n), dim3(256), 0, s, a, st, counts, out);
+    hipLaunchKernelGGL(sel_hist_kernel<3>, grid, dim3(256), 0, s, a, st);
+    hipLaunchKernelGGL(sel_scan_kernel<3>, dim3(n), dim3(256), 0, s, a, st, counts, out);
+  }
+}
+
 }  // namespace
+
+// The same selection for csrc/sparsify.hip (declared there): the ranks follow each frame's own count, rank r of a frame with ``count``
+// valid pixels is the n_k-th smallest value, n_k = count - floor(count k / levels), k = k0 + r -- the threshold of sparsification level
+// k.  ``mask`` is required; the arguments are the caller's to check (n frames of hw pixels, n_ranks in [1, 8], a workspace of
+// prv2_output_workspace_bytes(n)).  out[f * out_stride + r]; counts as prv2_order_stats.
+void order_stats_levels(const float* value, const uint8_t* mask, int n, int64_t hw, int levels, int k0, int n_ranks, int64_t* counts,
+                        float* out, int out_stride, void* workspace, hipStream_t s) {
+  SelArgs a{};
+  a.value = value;
+  a.mask = mask;
+  a.hw = hw;
+  a.n_ranks = n_ranks < kMaxRanks ? n_ranks : kMaxRanks;
+  for (int r = 0; r < a.n_ranks; ++r) a.ranks[r] = k0 + r;
+  a.levels = levels;
+  a.out_stride = out_stride;
+  launch_select(a, n, counts, out, workspace, s);
+}
+
 }  // namespace prv2
 
 using namespace prv2;
@@ -403,21 +443,8 @@ extern "C" int prv2_order_stats(const float* value, const uint8_t* mask, float i
   a.hw = (int64_t)h * w;
   a.n_ranks = n_ranks;
   for (int r = 0; r < n_ranks; ++r) a.ranks[r] = ranks_host[r];
-  SelState* st = (SelState*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-  const int blocks = (int)(cdiv(a.hw, 256) < kSelBlocks ? cdiv(a.hw, 256) : kSelBlocks);
-  const dim3 grid(blocks, n);
-  hipLaunchKernelGGL(sel_clear_kernel, dim3(8, n), dim3(256), 0, s, st);
-  hipLaunchKernelGGL(sel_hist_kernel<0>, grid, dim3(256), 0, s, a, st);
-  hipLaunchKernelGGL(sel_scan_kernel<0>, dim3(n), dim3(256), 0, s, a, st, counts, out);
-  if (n_ranks > 0) {  // (a count-only call stops here: still a fixed launch count per argument set)
-    hipLaunchKernelGGL(sel_hist_kernel<1>, grid, dim3(256), 0, s, a, st);
-    hipLaunchKernelGGL(sel_scan_kernel<1>, dim3(n), dim3(256), 0, s, a, st, counts, out);
-    hipLaunchKernelGGL(sel_hist_kernel<2>, grid, dim3(256), 0, s, a, st);
-    hipLaunchKernelGGL(sel_scan_kernel<2>, dim3(n), dim3(256), 0, s, a, st, counts, out);
-    hipLaunchKernelGGL(sel_hist_kernel<3>, grid, dim3(256), 0, s, a, st);
-    hipLaunchKernelGGL(sel_scan_kernel<3>, dim3(n), dim3(256), 0, s, a, st, counts, out);
-  }
+  a.out_stride = n_ranks;
+  launch_select(a, n, counts, out, workspace, (hipStream_t)stream);
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }

@@ -1224,6 +1224,30 @@ Tensor ssi_metrics(const Tensor& gt, const Tensor& pred, double min_depth, doubl
      "ssi_metrics");
   return out;
 }
+// sparsification curves of a per-pixel uncertainty (include/prv2.h "Sparsification"): thresholds, bucket sums, suffix sums
+Tensor sparsify(const Tensor& gt, const Tensor& pred, const Tensor& uncert, const optional<Tensor>& count, double min_count, double min_depth,
+                double max_depth, int64_t levels) {
+  dev_frames(gt, "gt", at::kFloat);
+  dev_frames(pred, "pred", at::kFloat);
+  dev_frames(uncert, "uncert", at::kFloat);
+  if (count) dev_frames(*count, "count", at::kFloat);
+  TORCH_CHECK(pred.sizes() == gt.sizes() && uncert.sizes() == gt.sizes() && (!count || count->sizes() == gt.sizes()),
+              "prv2::sparsify: gt, pred, uncert and count must have one shape, got ", gt.sizes(), " ", pred.sizes(), " ", uncert.sizes());
+  TORCH_CHECK(pred.device() == gt.device() && uncert.device() == gt.device() && (!count || count->device() == gt.device()),
+              "prv2::sparsify: the maps must be on one device");
+  TORCH_CHECK(levels >= 1 && levels <= PRV2_SPARSIFY_MAX_LEVELS, "prv2::sparsify: ", levels, " levels out of range [1, ",
+              PRV2_SPARSIFY_MAX_LEVELS, "]");
+  const int64_t bytes = prv2_sparsify_workspace_bytes((int)gt.size(0), (int)gt.size(1), (int)gt.size(2), (int)levels);
+  TORCH_CHECK(bytes > 0, "prv2::sparsify: bad frame shape ", gt.sizes());
+  Tensor ws = at::empty({bytes}, gt.options().dtype(at::kByte));
+  Tensor out = at::empty({gt.size(0), PRV2_SPARSIFY_VALUES(levels)}, gt.options().dtype(at::kDouble));
+  Launch L(gt);
+  ok(prv2_sparsify(gt.data_ptr<float>(), pred.data_ptr<float>(), uncert.data_ptr<float>(), count ? count->data_ptr<float>() : nullptr, min_count,
+                   (int)gt.size(0), (int)gt.size(1), (int)gt.size(2), (float)min_depth, (float)max_depth, (int)levels, out.data_ptr<double>(),
+                   ws.data_ptr(), ws.numel(), L.stream),
+     "sparsify");
+  return out;
+}
 
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
@@ -1374,6 +1398,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
         "int x0, int x1) -> Tensor");
   m.def("ssi_metrics(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1) -> Tensor");
+  m.def("sparsify(Tensor gt, Tensor pred, Tensor uncert, Tensor? count, float min_count, float min_depth, float max_depth, int levels) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1460,4 +1485,5 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("u8_image_resize", &u8_image_resize);
   m.impl("image_edge_region", &image_edge_region);
   m.impl("ssi_metrics", &ssi_metrics);
+  m.impl("sparsify", &sparsify);
 }

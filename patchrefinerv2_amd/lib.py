@@ -172,8 +172,17 @@ SIGNATURES = {
     # scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): the fits, the four SSI scores and the error sums of the aligned prediction
     "prv2_ssi_metrics_workspace_bytes": (_L, [_I, _I, _I]),
     "prv2_ssi_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
+    # sparsification curves of a per-pixel uncertainty (csrc/sparsify.hip): thresholds by the radix select, bucket sums, suffix sums
+    "prv2_sparsify_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "prv2_sparsify": (_I, [_P, _P, _P, _P, _D, _I, _I, _I, _F, _F, _I, _P, _P, _L, _P]),
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
+SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS
+
+
+def sparsify_values(levels: int) -> int:
+    """PRV2_SPARSIFY_VALUES(L): float64 values per frame of prv2_sparsify"""
+    return 1 + 10 * int(levels)
 
 _lib = None
 

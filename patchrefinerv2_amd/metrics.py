@@ -11,6 +11,9 @@ compute_scale_and_shift   estimator/models/losses.py:523-544 (the least-squares 
 compute_ssi_metrics       estimator/models/losses.py:600-700 (ScaleAndShiftInvariantLoss' three modes as evaluation scores) and
                           compute_errors on the aligned prediction; float64 numpy, the oracle of compute_ssi_metrics_fused
                           (csrc/ssi_eval.hip: two fused GPU passes, one D2H); pinned by tests/golden/ssi_eval.npz
+compute_uncertainty_metrics   NOT in the reference: the sparsification scores AUSE / AURG (Ilg et al. 2018; Poggi et al. 2020) of a
+                          per-pixel uncertainty against ground truth, numpy; the specification and oracle of
+                          compute_uncertainty_metrics_fused (csrc/sparsify.hip: thresholds by the radix select, one D2H)
 
 Pinned by tests/golden/output_stage.npz (the reference functions imported by oracle/make_golden.py).
 """
@@ -340,6 +343,140 @@ def compute_ssi_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=
     crop = _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
     vals = ops.ssi_metrics(g, p, min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
     rows = [ssi_from_values(v) for v in vals]
+    return rows[0] if single else rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Sparsification scores of a per-pixel uncertainty (the pseudo-label writer's ``uncertainty`` / ``count_map``): does a high uncertainty
+# mark the pixels where the depth is wrong?  The definition (include/prv2.h "Sparsification" states it for the kernels):
+#   valid   min < gt < max (compute_metrics' rule, no crop); pred cleaned as metric.py:98-101; n valid pixels, n = 0 -> NaN everywhere
+#   key     uncert, +inf where count < min_count; a NaN orders last (np.sort)
+#   terms   fp32: e_rel = |gt - pred| / gt, e_sq = (gt - pred)^2
+#   level k (0 .. L - 1) of a key set K: n_k = n - floor(n k / L), t_k = the n_k-th smallest key, S_k = {i valid: K_i <= t_k} -- ties
+#           are kept, so no tie-break exists; every key is <= a NaN t_k
+#   spars_abs_rel[k] = mean e_rel over S_k, spars_rmse[k] = sqrt(mean e_sq over S_k) with K = key; oracle_abs_rel with K = e_rel,
+#   oracle_rmse with K = e_sq; kept[k] = |S_k| / n (K = key); sums in float64
+#   ause_X = mean_k(spars_X[k] - oracle_X[k]); aurg_X = mean_k(spars_X[0] - spars_X[k])
+# ------------------------------------------------------------------------------------------------------------------
+UNCERT_KEYS = ("ause_abs_rel", "aurg_abs_rel", "ause_rmse", "aurg_rmse")
+UNCERT_CURVES = ("spars_abs_rel", "spars_rmse", "oracle_abs_rel", "oracle_rmse", "kept")
+UNCERT_MAX_LEVELS = 64
+
+
+def _check_levels(levels) -> int:
+    levels = int(levels)
+    if not 1 <= levels <= UNCERT_MAX_LEVELS:
+        raise ValueError(f"levels = {levels} out of range [1, {UNCERT_MAX_LEVELS}]")
+    return levels
+
+
+def _uncertainty_result(c: dict, curves: bool) -> dict:
+    """the four scores from the five curves (NaN curves: n = 0)"""
+    out = {}
+    with np.errstate(invalid="ignore"):
+        for x in ("abs_rel", "rmse"):
+            sp, orc = c["spars_" + x], c["oracle_" + x]
+            out["ause_" + x] = float(np.mean(sp - orc))
+            out["aurg_" + x] = float(np.mean(sp[0] - sp))
+    out = {k: out[k] for k in UNCERT_KEYS}
+    if curves:
+        out.update(c)
+    return out
+
+
+def _empty_curves(levels) -> dict:
+    c = {k: np.full(levels, np.nan) for k in UNCERT_CURVES}
+    c.update(thresholds=np.full((3, levels), np.nan, np.float32), kept_count=np.zeros(levels, np.int64), n=0)
+    return c
+
+
+def compute_uncertainty_metrics(gt, pred, uncert, count=None, min_count=0, min_depth_eval=0.1, max_depth_eval=10, levels=20, curves=False):
+    """AUSE / AURG of one frame on the host (numpy only, fp32 terms, float64 sums): ``ause_abs_rel, aurg_abs_rel, ause_rmse,
+    aurg_rmse`` by the definition above, through np.sort.  ``curves=True`` adds the five arrays [L] ``spars_abs_rel, spars_rmse,
+    oracle_abs_rel, oracle_rmse, kept`` and, for whoever checks a device route against this one, ``thresholds`` (fp32 [3, L]: the t_k of
+    the uncertainty, e_rel and e_sq ordering), ``kept_count`` (int64 [L]) and ``n``.
+
+    This function is NOT in the reference (its tester only writes the uncertainty maps, tester.py:132-181), so no golden file from the
+    reference can exist: this numpy statement IS the oracle of the device route, checked in tests/test_uncert_eval_host.py against a
+    literal stable-argsort implementation."""
+    levels = _check_levels(levels)
+
+    def f32(x):
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        return np.array(x, dtype=np.float32).reshape(x.shape[-2:])  # (a copy: the cleaning below writes into it)
+    g, p, u = f32(gt), f32(pred), f32(uncert)
+    c = None if count is None else f32(count)
+    for name, t in (("pred", p), ("uncert", u), ("count", c)):
+        if t is not None and t.shape != g.shape:
+            raise ValueError(f"compute_uncertainty_metrics: {name} {t.shape} does not match gt {g.shape}: resize the maps to one shape first")
+    mn, mx = np.float32(min_depth_eval), np.float32(max_depth_eval)
+    with np.errstate(invalid="ignore"):
+        valid = (g > mn) & (g < mx)
+        p[p < mn] = mn           # metric.py:98-101, in its order
+        p[p > mx] = mx
+        p[np.isinf(p)] = mx
+        p[np.isnan(p)] = mn
+        if c is not None:
+            u[c.astype(np.float64) < float(min_count)] = np.inf
+    n = int(valid.sum())
+    if n == 0:
+        return _uncertainty_result(_empty_curves(levels), curves)
+    g, p, key = g[valid], p[valid], u[valid]
+    d = g - p                     # fp32 throughout
+    e_rel, e_sq = np.abs(d) / g, d * d
+    rel64, sq64 = e_rel.astype(np.float64), e_sq.astype(np.float64)
+
+    def kept_sets(K):
+        srt = np.sort(K)          # NaN last
+        with np.errstate(invalid="ignore"):
+            for k in range(levels):
+                t = srt[n - (n * k) // levels - 1]
+                yield t, (np.isnan(t) | (K <= t))
+    out = {k: np.empty(levels) for k in UNCERT_CURVES}
+    out.update(thresholds=np.empty((3, levels), np.float32), kept_count=np.empty(levels, np.int64), n=n)
+    for k, (t, keep) in enumerate(kept_sets(key)):
+        m = int(keep.sum())
+        out["thresholds"][0, k], out["kept_count"][k], out["kept"][k] = t, m, m / n
+        out["spars_abs_rel"][k], out["spars_rmse"][k] = rel64[keep].sum() / m, np.sqrt(sq64[keep].sum() / m)
+    for k, (t, keep) in enumerate(kept_sets(e_rel)):
+        out["thresholds"][1, k], out["oracle_abs_rel"][k] = t, rel64[keep].sum() / keep.sum()
+    for k, (t, keep) in enumerate(kept_sets(e_sq)):
+        out["thresholds"][2, k], out["oracle_rmse"][k] = t, np.sqrt(sq64[keep].sum() / keep.sum())
+    return _uncertainty_result(out, curves)
+
+
+def uncertainty_from_values(v, levels, curves=False) -> dict:
+    """one frame's row of ops.sparsify (include/prv2.h prv2_sparsify) -> the dict of compute_uncertainty_metrics"""
+    L = _check_levels(levels)
+    v = np.asarray(v, dtype=np.float64)
+    n = int(v[0])
+    if n == 0:
+        return _uncertainty_result(_empty_curves(L), curves)
+    thr, q = v[1:1 + 3 * L].reshape(3, L), v[1 + 3 * L:1 + 10 * L].reshape(7, L)
+    c = dict(spars_abs_rel=q[1] / q[0], spars_rmse=np.sqrt(q[2] / q[0]), oracle_abs_rel=q[4] / q[3], oracle_rmse=np.sqrt(q[6] / q[5]),
+             kept=q[0] / n, thresholds=thr.astype(np.float32), kept_count=q[0].astype(np.int64), n=n)
+    return _uncertainty_result(c, curves)
+
+
+@torch.no_grad()
+def compute_uncertainty_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, uncert: torch.Tensor, count=None, min_count=0, min_depth_eval=0.1,
+                                      max_depth_eval=10, levels=20, curves=False):
+    """``compute_uncertainty_metrics`` on the GPU (csrc/sparsify.hip, ops.sparsify): fp32 GPU tensors [H, W] / [1, 1, H, W] (a dict) or
+    [B, H, W] / [B, 1, H, W] (a list of dicts), all of one shape; ONE D2H of 1 + 10 L float64 values per frame.  The thresholds are
+    the exact order statistics of the radix select behind ops.order_stats."""
+    from . import ops
+    levels = _check_levels(levels)
+    maps = dict(gt=gt, pred=pred, uncert=uncert, count=count)
+    for name, t in maps.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda):
+            raise ValueError(f"compute_uncertainty_metrics_fused: {name} must be a GPU tensor (compute_uncertainty_metrics is the host's)")
+        if t is not None and tuple(t.shape[-2:]) != tuple(gt.shape[-2:]):
+            raise ValueError(f"compute_uncertainty_metrics_fused: {name} {tuple(t.shape)} does not match gt {tuple(gt.shape)}: "
+                             "resize the maps to one shape first")
+    g, single = _frames_of(gt)
+    rest = [None if t is None else t.reshape(-1, t.shape[-2], t.shape[-1]) for t in (pred, uncert, count)]
+    vals = ops.sparsify(g, *rest, min_count=min_count, min_depth=min_depth_eval, max_depth=max_depth_eval, levels=levels).cpu().numpy()  # the one D2H
+    rows = [uncertainty_from_values(v, levels, curves) for v in vals]
     return rows[0] if single else rows
 
 

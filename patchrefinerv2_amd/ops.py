@@ -1913,3 +1913,54 @@ def ssi_metrics(gt, pred, min_depth=1e-3, max_depth=80.0, crop=None):
                           y0, y1, x0, x1, out.data_ptr(), ws.data_ptr(), wsb)
     PROFILER.launch_aux("ssi_metrics", 2.0 * (4.0 * g.numel() + 4.0 * p.numel()), call, f"{g.shape[0]}x{g.shape[1]}x{g.shape[2]}<-{p.shape[1]}x{p.shape[2]}")
     return box[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Sparsification curves of a per-pixel uncertainty (AUSE / AURG; csrc/sparsify.hip), both dispatch routes.
+# ------------------------------------------------------------------------------------------------------------------
+SPARSIFY_MAX_LEVELS = L.SPARSIFY_MAX_LEVELS
+
+
+def _sparsify_frames(t, name):
+    """an fp32 map [H, W] or [B, H, W] -> contiguous [B, H, W]; anything else is the caller's error (nothing is converted)"""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"sparsify: {name} must be a tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"sparsify: {name} has dtype {t.dtype}, expected torch.float32")
+    if t.dim() not in (2, 3):
+        raise ValueError(f"sparsify: {name} has shape {tuple(t.shape)}, expected [H, W] or [B, H, W]")
+    return (t[None] if t.dim() == 2 else t).contiguous()
+
+
+def sparsify(gt, pred, uncert, count=None, min_count=0.0, min_depth=1e-3, max_depth=80.0, levels=20):
+    """fp32 frames gt, pred, uncert (and count) [B, H, W] of one shape -> float64 [B, 1 + 10 L] on the device: n, the 3 L thresholds of
+    the uncertainty / e_rel / e_sq ordering and the seven rows of L sums over the kept sets S_k (the layout and the definition:
+    include/prv2.h prv2_sparsify).  Host tensors, another dtype, other dims, maps of different shapes and ``levels`` outside [1, 64] are
+    rejected before anything is launched.  No host synchronisation; bit-identical from call to call and for a frame alone or in a batch."""
+    g = _sparsify_frames(gt, "gt")
+    p, u = _sparsify_frames(pred, "pred"), _sparsify_frames(uncert, "uncert")
+    c = None if count is None else _sparsify_frames(count, "count")
+    for name, t in (("pred", p), ("uncert", u), ("count", c)):
+        if t is not None and t.shape != g.shape:
+            raise ValueError(f"sparsify: {name} {tuple(t.shape)} does not match gt {tuple(g.shape)}: resize the maps to one shape first")
+    levels = int(levels)
+    if not 1 <= levels <= SPARSIFY_MAX_LEVELS:
+        raise ValueError(f"sparsify: {levels} levels out of range [1, {SPARSIFY_MAX_LEVELS}]")
+    for name, t in (("gt", g), ("pred", p), ("uncert", u), ("count", c)):
+        if t is not None and (not t.is_cuda or t.device != g.device):
+            raise ValueError(f"sparsify: {name} must be a GPU tensor on gt's device (there is no CPU path; "
+                             "metrics.compute_uncertainty_metrics is the host's)")
+    wsb = L.load().prv2_sparsify_workspace_bytes(*g.shape, levels)
+    if wsb < 0:
+        raise ValueError(f"sparsify: bad frame shape {tuple(g.shape)}")
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().sparsify(g, p, u, c, float(min_count), float(min_depth), float(max_depth), levels))  # noqa: E731
+    else:
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+        out = torch.empty((g.shape[0], L.sparsify_values(levels)), dtype=torch.float64, device=g.device)
+        box.append(out)
+        call = lambda: _c("sparsify", g.data_ptr(), p.data_ptr(), u.data_ptr(), _ptr(c), float(min_count), *g.shape, float(min_depth),  # noqa: E731
+                          float(max_depth), levels, out.data_ptr(), ws.data_ptr(), ws.numel())
+    PROFILER.launch_aux("sparsify", (42.0 + 60.0 * -(-levels // 8)) * g.numel(), call, f"{g.shape[0]}x{g.shape[1]}x{g.shape[2]} L{levels}")
+    return box[0]

@@ -887,7 +887,7 @@ class Tester:
 
     @torch.no_grad()
     def generate_pl(self, cai_mode="r32", process_num=4, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), count_thr=0.05, seed=None,
-                    frame_batch=1):
+                    frame_batch=1, uncert_metrics=False):
         """Pseudo labels for semi-supervised training (estimator/tester/tester.py:132-181): the model runs over the folder with
         ``return_uncertainty=True`` and, with ``runner_info.save``, writes per image under ``work_dir`` what the pseudo-label loader of
         the semi-supervised configs reads (estimator/datasets/cityscapes_dataset.py:115-123,202-214):
@@ -898,7 +898,14 @@ class Tester:
           <name>_uncert.png         u coloured with jet, percentiles 0..100
           <name>_count_uint16.png   tile count x 256 (saturates at 65535: 256 tiles or more)
         Frames are dealt to the ranks as in ``run`` (frame f on rank f mod world) and grouped ``frame_batch`` per model call.
-        Returns one dict per frame of this rank (name, shape, mean depth, tiles of the plan)."""
+        Returns one dict per frame of this rank (name, shape, mean depth, tiles of the plan).
+        ``uncert_metrics`` (tools/test.py --uncert-metrics; not in the reference): every frame whose item carries ``depth_gt`` is also
+        scored on the device -- does the uncertainty mark the pixels where the depth is wrong? -- with the sparsification scores
+        ``ause_abs_rel, aurg_abs_rel, ause_rmse, aurg_rmse`` (metrics.compute_uncertainty_metrics_fused on the model's ``uncertainty``
+        and ``count_map`` with min_count = count_thr x tiles, inside the dataset's min_depth / max_depth) under the frame's key
+        ``uncert_metrics``; ``self.last_eval`` becomes their per-key nanmean over the scored frames.  Items without ground truth are
+        skipped; a result of another shape than the ground truth (an m-mode at the re-ensemble shape) is an error.  The files and
+        the rest of the dicts do not change."""
         import random
         results = []
         rank, world = self.runner_info.rank, getattr(self.runner_info, "world_size", 1)
@@ -921,6 +928,9 @@ class Tester:
             kw = dict(return_uncertainty=True)
             if stage is not None:
                 kw.update(return_device=True)
+            score = bool(uncert_metrics) and any(item.get("depth_gt") is not None for item in items)
+            if score and getattr(self.model, "supports_return_device", False):  # the maps stay where they are scored
+                kw.update(return_device=True)
             if seed is not None:
                 if len(idxs) == 1:
                     random.seed(seed)
@@ -934,23 +944,49 @@ class Tester:
             # the plan's tile count (every frame of a call has the same passes; only random positions differ)
             n_tiles = sum(len(p["raw"]) for p in self.model.last_plan)
             for f, item in enumerate(items):
+                scored = {}
+                if score and item.get("depth_gt") is not None:
+                    scored = dict(uncert_metrics=self._uncert_metrics(item, result[f:f + 1], log["uncertainty"][f:f + 1],
+                                                                      log["count_map"][f:f + 1], count_thr * n_tiles, cai_mode))
                 if stage is not None:  # the five files from scanlines produced on the GPU
                     depth = result[f:f + 1]
                     cmap = "gray_r" if getattr(self.runner_info, "gray_scale", False) else "magma_r"
                     stage.submit_pseudo_label(os.path.join(self.runner_info.work_dir, item["img_file_basename"]), depth,
                                               log["uncertainty"][f:f + 1], log["count_map"][f:f + 1], n_tiles, count_thr, cmap=cmap)
                     results.append(dict(name=item["img_file_basename"], shape=tuple(depth.shape),
-                                        mean=float(depth.mean(dtype=torch.float64)), n_tiles=n_tiles))
+                                        mean=float(depth.mean(dtype=torch.float64)), n_tiles=n_tiles, **scored))
                     continue
                 depth = result[f:f + 1].cpu()
-                entry = dict(name=item["img_file_basename"], shape=tuple(depth.shape), mean=float(depth.mean()), n_tiles=n_tiles)
+                entry = dict(name=item["img_file_basename"], shape=tuple(depth.shape), mean=float(depth.mean()), n_tiles=n_tiles, **scored)
                 if self.runner_info.save:
                     self._write_pl(item["img_file_basename"], depth, log["uncertainty"][f:f + 1].cpu(), log["count_map"][f:f + 1].cpu(),
                                    n_tiles, count_thr)
                 results.append(entry)
         if stage is not None:
             stage.close()
+        if uncert_metrics:
+            from .metrics import UNCERT_KEYS
+            import warnings
+            rows = [r["uncert_metrics"] for r in results if "uncert_metrics" in r]
+            with warnings.catch_warnings():  # (a key that is NaN in every frame: its mean is NaN, silently)
+                warnings.simplefilter("ignore", RuntimeWarning)
+                self.last_eval = {k: float(np.nanmean([m[k] for m in rows])) for k in UNCERT_KEYS} if rows else {}
         return results
+
+    def _uncert_metrics(self, item, depth, uncertainty, count_map, min_count, cai_mode):
+        """one frame's sparsification scores (``generate_pl(uncert_metrics=True)``): maps [1, 1, H, W], on the device already when the
+        model can return them there"""
+        from .metrics import compute_uncertainty_metrics_fused
+        gt = torch.as_tensor(item["depth_gt"])
+        if tuple(depth.shape[-2:]) != tuple(gt.shape[-2:]):
+            raise ValueError(f"uncert_metrics: {item['img_file_basename']}: the result of cai_mode {cai_mode!r} has shape "
+                             f"{tuple(depth.shape[-2:])} but the ground truth {tuple(gt.shape[-2:])}; the maps are not resized -- r-modes "
+                             "return the raw shape (m-modes the re-ensemble shape): use an r-mode with image_raw_shape = the ground truth's")
+        dev = depth.device if depth.is_cuda else torch.device("cuda")
+        h, w = gt.shape[-2:]
+        g, d, u, c = (t.to(dev).float().reshape(h, w) for t in (gt, depth, uncertainty, count_map))
+        return compute_uncertainty_metrics_fused(g, d, u, count=c, min_count=min_count, min_depth_eval=self.dataloader.min_depth,
+                                                 max_depth_eval=self.dataloader.max_depth)
 
     def _write_pl(self, name, depth, uncertainty, count_map, n_tiles, count_thr):
         """one frame's pseudo-label files (``generate_pl``)"""

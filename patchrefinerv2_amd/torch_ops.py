@@ -46,7 +46,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # ETHDataset: the image stage and the edge area of its metric splits
        "u8_image_resize", "image_edge_region",
        # scale-and-shift-invariant evaluation: the fits, the SSI scores and the error sums of the aligned prediction
-       "ssi_metrics")
+       "ssi_metrics",
+       # sparsification curves (AUSE / AURG) of a per-pixel uncertainty
+       "sparsify")
 _loaded = False
 
 

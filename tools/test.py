@@ -12,6 +12,7 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
+``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
 ``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
 disparities decoded and scored on the GPU; prints a1 ... sq_rel and see.  ETHDataset: photographs resized and raw float32 depth decoded
 on the GPU; prints the thirty keys edge_* / noedge_* / plain, split by the image's edge area); ``general`` is the folder of images -- with
@@ -119,6 +120,10 @@ def main():
                     help="with ground truth (any --test-type): add the scale-and-shift-invariant scores ssi_scale, ssi_shift, ssi_l1, ssi_gm, gm, "
                          "ssi_gm_inv and ssi_a1 ... ssi_sq_rel (losses.py:523-544, :600-700: the prediction aligned to the ground truth by a "
                          "least-squares scale and shift), two fused GPU passes per frame")
+    ap.add_argument("--uncert-metrics", action="store_true",
+                    help="with --generate-pl and ground truth (any --test-type whose dataset has it): score the uncertainty map against the "
+                         "depth error -- ause_abs_rel, aurg_abs_rel, ause_rmse, aurg_rmse (sparsification curves over 20 levels, pixels under "
+                         "--count-thr ordered last), on the GPU; needs a result of the ground truth's shape (an r-mode)")
     ap.add_argument("--device-output", action="store_true",
                     help="with --save: produce the PNG scanlines on the GPU and deflate / write them on a pool of threads while the next "
                          "frame computes (patchrefinerv2_amd/output.py); the files are the host route's")
@@ -130,6 +135,8 @@ def main():
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
+    if args.uncert_metrics and not args.generate_pl:
+        ap.error("--uncert-metrics needs --generate-pl (it scores the pseudo label's uncertainty)")
 
     cfg = Config.fromfile(args.config)
     cfg.merge_from_dict(parse_opts(args.cfg_option))
@@ -179,8 +186,13 @@ def main():
         if args.shard != "frames":
             raise SystemExit("--generate-pl shards frames over the ranks (--shard frames)")
         for r in tester.generate_pl(cai_mode=args.cai_mode, process_num=args.process_num, image_raw_shape=args.image_raw_shape,
-                                    patch_split_num=args.patch_split_num, count_thr=args.count_thr, seed=args.seed, frame_batch=args.frame_batch):
+                                    patch_split_num=args.patch_split_num, count_thr=args.count_thr, seed=args.seed, frame_batch=args.frame_batch,
+                                    uncert_metrics=args.uncert_metrics):
             print(f"[rank {rank}] {r['name']}: pseudo label {r['shape']} mean {r['mean']:.4f} ({r['n_tiles']} tiles)")
+            if "uncert_metrics" in r:
+                print(f"[rank {rank}] {r['name']}: " + ", ".join(f"{k} {float(v):.6f}" for k, v in r["uncert_metrics"].items()))
+        if args.uncert_metrics and getattr(tester, "last_eval", None):  # (this rank's frames: generate_pl does not collect)
+            print(f"[rank {rank}] " + ", ".join(f"{k} {v:.4f}" for k, v in tester.last_eval.items()))
         if world > 1:
             import torch.distributed as dist
             dist.barrier()
