@@ -116,14 +116,9 @@ def compute_metrics_device(gt: torch.Tensor, pred: torch.Tensor, interpolate=Tru
     g = gt.squeeze().float()
     valid = (g > min_depth_eval) & (g < max_depth_eval)
     if garg_crop or eigen_crop:
-        h, w = g.shape
+        y0, y1, x0, x1 = _eval_crop(*g.shape, garg_crop, eigen_crop, dataset)
         m = torch.zeros_like(valid)
-        if garg_crop:
-            m[int(0.40810811 * h):int(0.99189189 * h), int(0.03594771 * w):int(0.96405229 * w)] = True
-        elif dataset == "kitti":
-            m[int(0.3324324 * h):int(0.91351351 * h), int(0.0359477 * w):int(0.96405229 * w)] = True
-        else:
-            m[45:471, 41:601] = True
+        m[y0:y1, x0:x1] = True
         valid &= m
     if additional_mask is not None:
         valid &= additional_mask.squeeze().to(dev).bool()
@@ -185,20 +180,10 @@ def metrics_from_sums(s, with_see: bool) -> dict:
     return out
 
 
-@torch.no_grad()
-def compute_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu",
-                          min_depth_eval=0.1, max_depth_eval=10, disp_gt_edges=None, additional_mask=None, region=None, fuse_resize=False):
-    """``compute_metrics`` (estimator/utils/metric.py:87-149) from one fused pass on the GPU (csrc/evalgt.hip, ops.depth_metrics): the
-    same clamping, masks, crops, error formulas and soft-edge error as ``compute_metrics_device``, as twelve float64 sums per frame
-    and ONE D2H of them per call.  ``region`` (a mask) adds ``edge_*`` (inside it) and ``noedge_*`` (outside it) copies of every key
-    from the same read -- the three scoring calls of tester.ImageDataset._edge_metrics in one.  ``additional_mask`` scores inside
-    that mask only, as in compute_metrics.  A dict for one map ([H, W] / [1, 1, H, W]), a list of dicts for B maps.  Inputs that
-    are on the host are copied to the GPU: there is no CPU path.  ``fuse_resize``: a prediction of another resolution is sampled inside
-    the scoring kernel (ops.depth_metrics_lowres: the operations of F.interpolate, without writing the resized map) instead of being
-    resized first; the default keeps the resize."""
-    from . import ops
-    if additional_mask is not None and region is not None:
-        raise ValueError("compute_metrics_fused: give additional_mask or region, not both")
+def _fused_inputs(gt, pred, interpolate, fuse_resize, garg_crop, eigen_crop, dataset):
+    """the opening of the fused scoring calls -> (g [B, H, W], p, single, lowres, crop): both maps as fp32 frames on the GPU (the
+    prediction's device, else the ground truth's, else 'cuda'); ``lowres``: a prediction of another shape stays as it is (the kernel
+    samples it), otherwise F.interpolate resizes it first"""
     dev = pred.device if pred.is_cuda else (gt.device if gt.is_cuda else torch.device("cuda"))
     gt, pred = gt.to(dev), pred.to(dev)
     lowres = bool(fuse_resize) and interpolate and gt.shape[-2:] != pred.shape[-2:]
@@ -207,11 +192,28 @@ def compute_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True
         pred = F.interpolate(p4.float(), gt.shape[-2:], mode="bilinear", align_corners=False)
     g, single = _frames_of(gt.float())
     p = pred.float().reshape(g.shape[0], *pred.shape[-2:]) if lowres else pred.float().reshape(g.shape)
+    return g, p, single, lowres, _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
+
+
+@torch.no_grad()
+def compute_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu",
+                          min_depth_eval=0.1, max_depth_eval=10, disp_gt_edges=None, additional_mask=None, region=None, fuse_resize=False):
+    """``compute_metrics`` (estimator/utils/metric.py:87-149) from one fused pass on the GPU (csrc/evalgt.hip, ops.depth_metrics): the
+    same clamping, masks, crops, error formulas and soft-edge error as ``compute_metrics_device``, as twelve float64 sums per frame
+    and ONE D2H of them per call.  ``region`` (a mask) adds ``edge_*`` (inside it) and ``noedge_*`` (outside it) copies of every key
+    from the same read -- the three scoring calls of datasets.ImageDataset._edge_metrics in one.  ``additional_mask`` scores inside
+    that mask only, as in compute_metrics.  A dict for one map ([H, W] / [1, 1, H, W]), a list of dicts for B maps.  Inputs that
+    are on the host are copied to the GPU: there is no CPU path.  ``fuse_resize``: a prediction of another resolution is sampled inside
+    the scoring kernel (ops.depth_metrics_lowres: the operations of F.interpolate, without writing the resized map) instead of being
+    resized first; the default keeps the resize."""
+    from . import ops
+    if additional_mask is not None and region is not None:
+        raise ValueError("compute_metrics_fused: give additional_mask or region, not both")
+    g, p, single, lowres, crop = _fused_inputs(gt, pred, interpolate, fuse_resize, garg_crop, eigen_crop, dataset)
 
     def mask(m):
-        return None if m is None else torch.as_tensor(m).to(dev).reshape(g.shape)
+        return None if m is None else torch.as_tensor(m).to(g.device).reshape(g.shape)
     inside = region if region is not None else additional_mask
-    crop = _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
     score = ops.depth_metrics_lowres if lowres else ops.depth_metrics
     sums = score(g, p, mask(disp_gt_edges), mask(inside), min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
     see = disp_gt_edges is not None
@@ -332,15 +334,7 @@ def compute_ssi_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=
     maps.  Inputs on the host are copied to the GPU.  ``fuse_resize``: a prediction of another resolution is sampled inside the kernels
     (the operations of F.interpolate, the resized map is never written) instead of being resized first."""
     from . import ops
-    dev = pred.device if pred.is_cuda else (gt.device if gt.is_cuda else torch.device("cuda"))
-    gt, pred = gt.to(dev), pred.to(dev)
-    lowres = bool(fuse_resize) and interpolate and gt.shape[-2:] != pred.shape[-2:]
-    if gt.shape[-2:] != pred.shape[-2:] and interpolate and not lowres:
-        p4 = pred if pred.dim() == 4 else pred.reshape(-1, 1, *pred.shape[-2:])
-        pred = F.interpolate(p4.float(), gt.shape[-2:], mode="bilinear", align_corners=False)
-    g, single = _frames_of(gt.float())
-    p = pred.float().reshape(g.shape[0], *pred.shape[-2:]) if lowres else pred.float().reshape(g.shape)
-    crop = _eval_crop(g.shape[1], g.shape[2], garg_crop, eigen_crop, dataset)
+    g, p, single, _lowres, crop = _fused_inputs(gt, pred, interpolate, fuse_resize, garg_crop, eigen_crop, dataset)
     vals = ops.ssi_metrics(g, p, min_depth_eval, max_depth_eval, crop).cpu().numpy()  # the one D2H
     rows = [ssi_from_values(v) for v in vals]
     return rows[0] if single else rows

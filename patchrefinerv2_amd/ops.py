@@ -1758,7 +1758,7 @@ def _mask_u8(t, like, name):
     return t
 
 
-GT_KINDS = {"eth3d": 0, "mid": 1, "cityscapes": 2}  # enum prv2_gt_kind (tester.ImageDataset's gt_format names)
+GT_KINDS = {"eth3d": 0, "mid": 1, "cityscapes": 2}  # enum prv2_gt_kind (datasets.ImageDataset's gt_format names)
 CITYSCAPES_FACTOR = float(np.float32(0.209313 * 2262.52))  # general_dataset.py:144: baseline x focal length, met by a float32 array
 
 

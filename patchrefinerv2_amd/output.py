@@ -3,8 +3,8 @@
 The files ``Tester.run(save=True)`` and ``Tester.generate_pl(save=True)`` write are PNGs of per-pixel functions of maps that
 are already on the device.  This module produces the deflate-ready scanlines of every file there (csrc/output.hip through
 ops.py), copies only those packed bytes into pinned host memory and hands them to a bounded pool of writer threads
-(``zlib.compress`` releases the GIL), while the next frame computes.  Chunk layout, zlib level and the single IDAT chunk are
-those of ``tester.write_png16`` / ``write_png8``: equal pixels give byte-identical files.
+(``zlib.compress`` releases the GIL), while the next frame computes.  The host route's ``write_png16`` / ``write_png8`` below go
+through the same container (``png_bytes``): equal pixels give byte-identical files.
 
 ``device_deflate`` (``runner_info.device_deflate`` / ``tools/test.py --device-deflate``, on top of the device route) also produces
 the zlib stream of every file on the GPU (csrc/deflate.hip through ``ops.deflate_rows``): only compressed bytes are copied to the
@@ -16,6 +16,7 @@ colormap_lut / lut_index matplotlib's byte table and index rule (host restatemen
 percentile_device        np.percentile(value[mask], q) of a device map (exact order statistics + the host interpolation)
 colorize_device          metrics.colorize of a device map -> device uint8 [H, W, 3] view + its scanline buffer
 png_bytes_from_stream    the PNG container around a given IDAT payload
+write_png16 / write_png8 a host array as a PNG file (the host route's dependency-free encoder)
 OutputStage              side stream, ring of pinned staging slots, writer pool
 """
 from __future__ import annotations
@@ -99,14 +100,37 @@ def png_bytes_from_stream(header: bytes, zstream) -> bytes:
 
 
 def png_bytes(header: bytes, rows) -> bytes:
-    """the file ``write_png16`` / ``write_png8`` write for these scanlines: signature, IHDR, one IDAT (zlib level 6), IEND"""
+    """the file of these scanlines: signature, IHDR, one IDAT (zlib level 6), IEND"""
     return png_bytes_from_stream(header, zlib.compress(rows, 6))
 
 
 def ihdr(w: int, h: int, bpp: int) -> bytes:
-    """bpp 1: 8-bit gray, 2: 16-bit gray, 3: 8-bit RGB"""
-    depth, ctype = {1: (8, 0), 2: (16, 0), 3: (8, 2)}[bpp]
+    """bpp (bytes per pixel) 1: 8-bit gray, 2: 16-bit gray, 3: 8-bit RGB, 4: 8-bit RGBA"""
+    depth, ctype = {1: (8, 0), 2: (16, 0), 3: (8, 2), 4: (8, 6)}[bpp]
     return struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)
+
+
+def _write_png(path: str, samples: np.ndarray, h: int, w: int, bpp: int):
+    """``samples``: the image's h * w * bpp bytes in file order -> scanlines with filter byte 0 -> ``png_bytes`` -> the file"""
+    rows = np.zeros((h, 1 + bpp * w), dtype=np.uint8)
+    rows[:, 1:] = samples.reshape(h, bpp * w)
+    with open(path, "wb") as f:
+        f.write(png_bytes(ihdr(w, h, bpp), rows.tobytes()))
+
+
+def write_png16(path: str, arr_u16: np.ndarray):
+    """Minimal PNG encoder: 16-bit grayscale (== PIL's Image.fromarray(uint16).save)."""
+    assert arr_u16.dtype == np.uint16 and arr_u16.ndim == 2
+    _write_png(path, arr_u16.astype(">u2").view(np.uint8), *arr_u16.shape, 2)
+
+
+def write_png8(path: str, arr_u8: np.ndarray):
+    """8-bit RGB / RGBA / gray PNG (== cv2.imwrite of the BGR-swapped array the reference builds)."""
+    assert arr_u8.dtype == np.uint8 and arr_u8.ndim in (2, 3)
+    ch = 1 if arr_u8.ndim == 2 else arr_u8.shape[2]
+    if ch not in (1, 3, 4):
+        raise ValueError(f"write_png8: {ch} channels; gray [h, w], RGB [h, w, 3] or RGBA [h, w, 4]")
+    _write_png(path, arr_u8, *arr_u8.shape[:2], ch)
 
 
 # ------------------------------------------------------------------------------------------------------------------

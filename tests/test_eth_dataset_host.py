@@ -348,14 +348,14 @@ def test_unbuilt_modes_raise(tmp_path):
 
 
 def test_key_order_and_missing_image(tmp_path):
-    from patchrefinerv2_amd import tester
+    from patchrefinerv2_amd import datasets
     split, _ = write_eth_tree(str(tmp_path), 1, (12, 20), (7, 11))
     ds = _dataset(split, gt_shape=(7, 11))
     with pytest.raises(ValueError, match="image_hr"):
         ds.get_metrics(torch.zeros(1, 1, 7, 11), torch.zeros(1, 1, 7, 11), torch.zeros(7, 11))
     fused = {pre + k: float(i) for i, (pre, k) in enumerate((pre, k) for pre in ("", "edge_", "noedge_") for k in KEYS)}  # compute_metrics_fused's order
-    ordered = tester.eth_metric_order(fused)
-    assert tuple(ordered) == KEYS30 and ordered == fused and tester.ETH_METRIC_KEYS == KEYS
+    ordered = datasets.eth_metric_order(fused)
+    assert tuple(ordered) == KEYS30 and ordered == fused and datasets.ETH_METRIC_KEYS == KEYS
 
 
 def test_evaluate_is_the_nanmean(tmp_path):

@@ -263,7 +263,7 @@ def _dataset(img_dir, gt_dir, **kw):
 
 @pytest.mark.parametrize("fmt", ["u4k", "eth3d", "mid", "cityscapes"])
 def test_dataset_items_equal_the_spec(tmp_path, fmt):
-    from patchrefinerv2_amd import tester as T
+    from patchrefinerv2_amd import datasets as T
     shape = (64, 96)
     img_dir, gt_dir, specs = write_general_tree(str(tmp_path), fmt, shape, n=3)
     ds = _dataset(img_dir, gt_dir, gt_format=fmt, gt_shape=shape, image_resolution=shape)

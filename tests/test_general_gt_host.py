@@ -193,7 +193,7 @@ def _dataset(img_dir, gt_dir=None, **kw):
 
 # ------------------------------------------------------------------------------------------------------------------ parsing
 def test_factor_and_calibration_files(tmp_path):
-    from patchrefinerv2_amd import tester as T
+    from patchrefinerv2_amd import datasets as T
     p = tmp_path / "f.txt"
     p.write_text("1234.5678\nignored\n")
     assert T.read_factor_file(str(p)) == 1234.5678
@@ -206,7 +206,7 @@ def test_factor_and_calibration_files(tmp_path):
 
 
 def test_pfm_header(tmp_path):
-    from patchrefinerv2_amd import tester as T
+    from patchrefinerv2_amd import datasets as T
     assert T.read_pfm_header(io.BytesIO(b"Pf\n23 17\n-1.0\nDATA")) == (23, 17, True, 1.0, 14)
     assert T.read_pfm_header(io.BytesIO(b"Pf\n640 480\n0.25\n")) == (640, 480, False, 0.25, 16)
     for bad in (b"P5\n23 17\n-1.0\n", b"PF\n23 17\n-1.0\n", b"Pf\n23x17\n-1.0\n", b"Pf\n23 17 3\n-1.0\n", b"Pf\n23 17\nscale\n", b"Pf\n0 17\n1.0\n",
@@ -233,7 +233,8 @@ def test_pfm_header(tmp_path):
 
 
 def test_sorted_pairing_count_mismatch_and_names(tmp_path):
-    from patchrefinerv2_amd import tester as T
+    from patchrefinerv2_amd import datasets as T
+    from patchrefinerv2_amd.tester import write_png8
     img_dir, gt_dir, _ = write_general_tree(str(tmp_path / "u4k"), "u4k", (6, 8), n=3)
     # the pairing is by sorted position, not by name
     os.rename(os.path.join(gt_dir, "frame_001.npy"), os.path.join(gt_dir, "a_first.npy"))
@@ -261,14 +262,14 @@ def test_sorted_pairing_count_mismatch_and_names(tmp_path):
     img_dir, gt_dir, _ = write_general_tree(str(tmp_path / "cs"), "cityscapes", (6, 8))
     m = _dataset(img_dir, gt_dir, gt_format="cityscapes").gt_meta(0)
     assert m["shape"] == (6, 8) and m["nbytes"] == 96
-    T.write_png8(os.path.join(gt_dir, "frame_001.png"), np.zeros((6, 8), np.uint8))
+    write_png8(os.path.join(gt_dir, "frame_001.png"), np.zeros((6, 8), np.uint8))
     with pytest.raises(ValueError, match="16-bit"):
         _dataset(img_dir, gt_dir, gt_format="cityscapes").gt_meta(1)
 
 
 def test_kb_crop_and_image_formats(tmp_path):
     from PIL import Image
-    from patchrefinerv2_amd import tester as T
+    from patchrefinerv2_amd import datasets as T
     rs = np.random.RandomState(0)
     img = rs.randint(0, 256, (375, 1242, 3)).astype(np.uint8)
     Image.fromarray(img).save(tmp_path / "k.png")
@@ -293,7 +294,7 @@ def test_kb_crop_and_image_formats(tmp_path):
 
 # ------------------------------------------------------------------------------------------------------------------ defaults
 def test_default_items_are_unchanged_and_gta_is_not_built(tmp_path, monkeypatch):
-    from patchrefinerv2_amd import metrics as M, tester as T
+    from patchrefinerv2_amd import datasets as T, metrics as M
     img_dir, gt_dir = tmp_path / "img", tmp_path / "gt"
     os.makedirs(img_dir), os.makedirs(gt_dir)
     rs = np.random.RandomState(4)

@@ -84,6 +84,36 @@ def test_writer_pool_files_equal_write_png(tmp_path):
         assert (tmp_path / "out" / name).read_bytes() == (tmp_path / name).read_bytes(), name
 
 
+@pytest.mark.parametrize("kind, depth, ctype", [("gray", 8, 0), ("rgb", 8, 2), ("rgba", 8, 6), ("u16", 16, 0)])
+def test_writers_cover_the_colour_type_table(tmp_path, kind, depth, ctype):
+    """write_png8 / write_png16 against a container assembled here: signature, IHDR, one IDAT of zlib level 6, IEND"""
+    import struct
+    import zlib
+    from PIL import Image
+    from patchrefinerv2_amd.output import write_png8, write_png16
+    h, w = 5, 7
+    rs = np.random.RandomState(11)
+    if kind == "u16":
+        arr = rs.randint(0, 65536, (h, w)).astype(np.uint16)
+        samples = arr.astype(">u2").tobytes()
+    else:
+        arr = rs.randint(0, 256, (h, w) + {"gray": (), "rgb": (3,), "rgba": (4,)}[kind]).astype(np.uint8)
+        samples = arr.tobytes()
+    path = str(tmp_path / f"{kind}.png")
+    (write_png16 if kind == "u16" else write_png8)(path, arr)
+    stride = len(samples) // h
+    rows = b"".join(b"\x00" + samples[y * stride:(y + 1) * stride] for y in range(h))  # filter byte 0 per scanline
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    want = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ctype, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows, 6))
+            + chunk(b"IEND", b""))
+    with open(path, "rb") as f:
+        assert f.read() == want
+    back = np.asarray(Image.open(path))
+    assert back.shape == arr.shape and np.array_equal(back.astype(arr.dtype), arr)
+
+
 def test_worker_error_surfaces_in_flush(tmp_path):
     from patchrefinerv2_amd import output as O
     st = O.OutputStage(str(tmp_path), workers=2)

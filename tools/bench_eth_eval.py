@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Cost of the ETH3D dataset evaluation (tester.ETHDataset): one JSON line (also written to ``--out``, default profiles/eth_eval.json).
+"""Cost of the ETH3D dataset evaluation (datasets.ETHDataset): one JSON line (also written to ``--out``, default profiles/eth_eval.json).
 
   python tools/bench_eth_eval.py [--reps 20] [--maps 4] [--skip-tester] [--out PATH]
 
@@ -23,20 +23,18 @@ Sizes are ETH3D's: a 24 MP photograph (4000 x 6000) resized to 2160 x 3840, grou
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import evalbench as EB  # noqa: E402
+from evalbench import alloc_bytes, wall_ms  # noqa: E402
 MIN_DEPTH, MAX_DEPTH = 1e-3, 80
 PHOTO, RAW, GT = (4000, 6000), (2160, 3840), (4032, 6048)
 STEPS = ("image", "metrics", "tester")
@@ -61,30 +59,6 @@ def depth_map(shape, k=0):
     d[::97, ::89] = np.inf
     d[5::211, 7::193] = np.nan
     return d
-
-
-def wall_ms(fn, reps, warm=2):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ts), 3)
-
-
-def alloc_bytes(fn):
-    """device bytes the caching allocator hands out during one call"""
-    torch.cuda.synchronize()
-    key = "allocated_bytes.all.allocated"
-    b0 = torch.cuda.memory_stats()[key]
-    out = fn()
-    torch.cuda.synchronize()
-    del out
-    return int(torch.cuda.memory_stats()[key] - b0)
 
 
 def step_image(reps):
@@ -161,30 +135,10 @@ def step_metrics(reps):
                 mask_pixels_differing=mask_diff, max_rel_diff_new_vs_parent=float(f"{agree:.3e}"))
 
 
-class _NoGroundTruth:
-    """the dataset with ``depth_gt`` / ``boundary`` dropped from its items: Tester.run then scores nothing"""
-
-    def __init__(self, ds):
-        self.ds = ds
-
-    def __len__(self):
-        return len(self.ds)
-
-    def __getattr__(self, k):
-        return getattr(self.ds, k)
-
-    def __getitem__(self, i):
-        return {k: v for k, v in self.ds[i].items() if k not in ("depth_gt", "boundary")}
-
-
 def step_tester(n_maps):
     from PIL import Image
-    from patchrefinerv2_amd import models, weights as W  # noqa: F401  (registers the model classes)
-    from patchrefinerv2_amd.registry import build_model
-    from patchrefinerv2_amd.tester import ETHDataset, RunnerInfo, Tester
-    from patchrefinerv2_amd.workloads import WORKLOADS, model_config, state_spec
-    name = "v2_zoe_4k_r32"
-    w = WORKLOADS[name]
+    from patchrefinerv2_amd.tester import ETHDataset
+    w, model = EB.workload_model()
     with tempfile.TemporaryDirectory() as root:
         lines = []
         for k in range(n_maps):
@@ -195,25 +149,10 @@ def step_tester(n_maps):
         split = os.path.join(root, "split.txt")
         with open(split, "w") as f:
             f.writelines(lines)
-        model = build_model(model_config(name, prec="f16f6", max_batch=int(w.get("max_batch", 41)), n_streams=3))
-        model.load_state_dict(W.synth_state_dict(state_spec(name), seed=0), strict=True)
         ds = ETHDataset("infer", split, dict(input_size_deep=[384, 512], input_size_shallow=list(w["raw"])), MIN_DEPTH, MAX_DEPTH, gt_shape=GT)
-        out = {}
-        for tag, data in (("with_gt", ds), ("without_gt", _NoGroundTruth(ds))):
-            t = Tester(None, RunnerInfo(), data, model)
-            run = lambda: t.run(cai_mode=w["mode"], image_raw_shape=w["raw"], patch_split_num=w["split"], seed=621)  # noqa: E731
-            run()  # warm-up (kernels, allocator, hipGraphs, page cache)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = run()
-            torch.cuda.synchronize()
-            out[tag] = round(n_maps / (time.perf_counter() - t0), 3)
-            assert ("metrics" in res[0]) == (tag == "with_gt")
-            if tag == "with_gt":
-                keys = len(t.last_eval)
+        out, keys = EB.gt_pair_maps_s(model, ds, w, n_maps)
         ds.close()
-    return dict(workload=name, maps=n_maps, photo=list(PHOTO), gt=list(GT), metric_keys=keys,
-                overhead_pct=round(100 * (out["without_gt"] / out["with_gt"] - 1), 2), **out)
+    return dict(workload=EB.WORKLOAD, maps=n_maps, photo=list(PHOTO), gt=list(GT), metric_keys=keys, **out)
 
 
 def main():
@@ -221,33 +160,14 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--maps", type=int, default=4)
     ap.add_argument("--skip-tester", action="store_true")
-    ap.add_argument("--step-timeout", type=int, default=280, help="seconds each GPU step may take")
-    ap.add_argument("--step", choices=STEPS, default=None, help="(internal) run one step in this process and print its JSON")
+    EB.add_step_arguments(ap, STEPS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eth_eval.json"))
     a = ap.parse_args()
     if a.step:
-        torch.set_grad_enabled(False)
-        from patchrefinerv2_amd import lib
-        lib.load()
-        res = step_tester(a.maps) if a.step == "tester" else (step_image if a.step == "image" else step_metrics)(a.reps)
-        print("RESULT " + json.dumps(res))
-        return 0
-    out = {}
-    for step in STEPS[:2] if a.skip_tester else STEPS:
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(a.reps),
-               "--maps", str(a.maps)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:  # a fault, an abort or the time limit: start nothing more on the GPU
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:] + f"\nstep {step} exited with status {r.returncode}: stopping\n")
-            return r.returncode
-        out[step] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    return 0
+        EB.begin_step()
+        return EB.end_step(step_tester(a.maps) if a.step == "tester" else (step_image if a.step == "image" else step_metrics)(a.reps))
+    out = EB.run_steps(__file__, STEPS[:2] if a.skip_tester else STEPS, a.step_timeout, ["--reps", a.reps, "--maps", a.maps])
+    return EB.report(out, a.out)
 
 
 if __name__ == "__main__":

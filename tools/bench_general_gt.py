@@ -21,19 +21,17 @@ exit with status 0 ends the run (nothing more is started on the GPU) and the too
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import evalbench as EB  # noqa: E402
+from evalbench import alloc_bytes, wall_ms  # noqa: E402
 MIN_DEPTH, MAX_DEPTH = 1e-3, 80
 SIZES = dict(eth3d=((4032, 6048), (2160, 3840)), cityscapes=((1024, 2048), (512, 1024)))
 STEPS = ("eth3d", "cityscapes", "tester")
@@ -56,30 +54,6 @@ def cityscapes_map(shape):
     v = (3000 + 5000 * (x > 0.45 * w) + 2500 * (np.hypot(x - 0.25 * w, y - 0.5 * h) < 0.2 * h) + (x * 7 + y * 3) % 50).astype(np.uint16)
     v[::97, ::89] = 0
     return v
-
-
-def wall_ms(fn, reps, warm=2):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ts), 3)
-
-
-def alloc_bytes(fn):
-    """device bytes the caching allocator hands out during one call"""
-    torch.cuda.synchronize()
-    key = "allocated_bytes.all.allocated"
-    b0 = torch.cuda.memory_stats()[key]
-    out = fn()
-    torch.cuda.synchronize()
-    del out
-    return int(torch.cuda.memory_stats()[key] - b0)
 
 
 def step_routes(kind, reps):
@@ -135,53 +109,21 @@ def step_routes(kind, reps):
                 max_rel_diff_new_vs_parent=float(f"{agree:.3e}"))
 
 
-class _NoGroundTruth:
-    """the dataset with ``depth_gt`` / ``boundary`` dropped from its items: Tester.run then scores nothing"""
-
-    def __init__(self, ds):
-        self.ds = ds
-
-    def __len__(self):
-        return len(self.ds)
-
-    def __getattr__(self, k):
-        return getattr(self.ds, k)
-
-    def __getitem__(self, i):
-        return {k: v for k, v in self.ds[i].items() if k not in ("depth_gt", "boundary")}
-
-
 def step_tester(n_maps):
-    from patchrefinerv2_amd import models, weights as W  # noqa: F401  (registers the model classes)
-    from patchrefinerv2_amd.registry import build_model
-    from patchrefinerv2_amd.tester import ImageDataset, RunnerInfo, Tester
-    from patchrefinerv2_amd.workloads import WORKLOADS, model_config, state_spec
-    name = "v2_zoe_4k_r32"
-    w = WORKLOADS[name]
+    from patchrefinerv2_amd.tester import ImageDataset
     gt_shape = SIZES["eth3d"][0]
+    w, model = EB.workload_model()
     with tempfile.TemporaryDirectory() as root:
         img_dir, gt_dir = os.path.join(root, "images"), os.path.join(root, "gt")
         os.makedirs(img_dir), os.makedirs(gt_dir)
         for k in range(n_maps):
             np.save(os.path.join(img_dir, f"{k:05d}.npy"), np.random.default_rng(k).integers(0, 256, tuple(w["raw"]) + (3,), dtype=np.uint8))
             eth3d_map(gt_shape, k).tofile(os.path.join(gt_dir, f"{k:05d}.raw"))
-        model = build_model(model_config(name, prec="f16f6", max_batch=int(w.get("max_batch", 41)), n_streams=3))
-        model.load_state_dict(W.synth_state_dict(state_spec(name), seed=0), strict=True)
         ds = ImageDataset(img_dir, gt_dir=gt_dir, gt_format="eth3d", gt_shape=gt_shape, image_resolution=w["raw"], min_depth=MIN_DEPTH,
                           max_depth=MAX_DEPTH)
-        out = {}
-        for tag, data in (("with_gt", ds), ("without_gt", _NoGroundTruth(ds))):
-            t = Tester(None, RunnerInfo(), data, model)
-            run = lambda: t.run(cai_mode=w["mode"], image_raw_shape=w["raw"], patch_split_num=w["split"], seed=621)  # noqa: E731
-            run()  # warm-up (kernels, allocator, hipGraphs, page cache)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = run()
-            torch.cuda.synchronize()
-            out[tag] = round(n_maps / (time.perf_counter() - t0), 3)
-            assert ("metrics" in res[0]) == (tag == "with_gt")
+        out, _keys = EB.gt_pair_maps_s(model, ds, w, n_maps)
         ds.close()
-    return dict(workload=name, maps=n_maps, gt=list(gt_shape), overhead_pct=round(100 * (out["without_gt"] / out["with_gt"] - 1), 2), **out)
+    return dict(workload=EB.WORKLOAD, maps=n_maps, gt=list(gt_shape), **out)
 
 
 def main():
@@ -189,32 +131,14 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--maps", type=int, default=4)
     ap.add_argument("--skip-tester", action="store_true")
-    ap.add_argument("--step-timeout", type=int, default=280, help="seconds each GPU step may take")
-    ap.add_argument("--step", choices=STEPS, default=None, help="(internal) run one step in this process and print its JSON")
+    EB.add_step_arguments(ap, STEPS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "general_gt_eval.json"))
     a = ap.parse_args()
     if a.step:
-        torch.set_grad_enabled(False)
-        from patchrefinerv2_amd import lib
-        lib.load()
-        print("RESULT " + json.dumps(step_tester(a.maps) if a.step == "tester" else step_routes(a.step, a.reps)))
-        return 0
-    out = {}
-    for step in STEPS[:2] if a.skip_tester else STEPS:
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(a.reps),
-               "--maps", str(a.maps)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:  # a fault, an abort or the time limit: start nothing more on the GPU
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:] + f"\nstep {step} exited with status {r.returncode}: stopping\n")
-            return r.returncode
-        out[step] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    return 0
+        EB.begin_step()
+        return EB.end_step(step_tester(a.maps) if a.step == "tester" else step_routes(a.step, a.reps))
+    out = EB.run_steps(__file__, STEPS[:2] if a.skip_tester else STEPS, a.step_timeout, ["--reps", a.reps, "--maps", a.maps])
+    return EB.report(out, a.out)
 
 
 if __name__ == "__main__":

@@ -23,19 +23,19 @@ exit with status 0 ends the run (nothing more is started on the GPU) and the too
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
-import subprocess
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))  # (the package's tree is chosen per step, in main)
+import evalbench as EB  # noqa: E402
+from evalbench import alloc_bytes, wall_ms  # noqa: E402
+
 MIN_DEPTH, MAX_DEPTH = 1e-3, 80
 SIZES = {"4k": ((2160, 3840), (2160, 3840)), "eth3d": ((4032, 6048), (2160, 3840)), "cityscapes": ((1024, 2048), (1024, 2048))}  # (gt, pred)
 STEPS = ("fixture", "4k", "eth3d", "cityscapes", "tester", "parent")
@@ -50,30 +50,6 @@ def depth_map(shape, k=0):
     d[::97, ::89] = 0.0
     d[5::211, 7::193] = np.nan
     return d
-
-
-def wall_ms(fn, reps, warm=2):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ts), 3)
-
-
-def alloc_bytes(fn):
-    """device bytes the caching allocator hands out during one call"""
-    torch.cuda.synchronize()
-    key = "allocated_bytes.all.allocated"
-    b0 = torch.cuda.memory_stats()[key]
-    out = fn()
-    torch.cuda.synchronize()
-    del out
-    return int(torch.cuda.memory_stats()[key] - b0)
 
 
 def ssi_torch(gt, pred, mn, mx):
@@ -151,36 +127,23 @@ def step_size(step, reps):
 
 
 def step_tester(n_maps, flags):
-    from patchrefinerv2_amd import models, weights as W  # noqa: F401  (registers the model classes)
-    from patchrefinerv2_amd.registry import build_model
-    from patchrefinerv2_amd.tester import ImageDataset, RunnerInfo, Tester
-    from patchrefinerv2_amd.workloads import WORKLOADS, model_config, state_spec
-    name = "v2_zoe_4k_r32"
-    w = WORKLOADS[name]
+    from patchrefinerv2_amd.tester import ImageDataset
     gt_shape = SIZES["eth3d"][0]
+    w, model = EB.workload_model()
     with tempfile.TemporaryDirectory() as root:
         img_dir, gt_dir = os.path.join(root, "images"), os.path.join(root, "gt")
         os.makedirs(img_dir), os.makedirs(gt_dir)
         for k in range(n_maps):
             np.save(os.path.join(img_dir, f"{k:05d}.npy"), np.random.default_rng(k).integers(0, 256, tuple(w["raw"]) + (3,), dtype=np.uint8))
             depth_map(gt_shape, k).tofile(os.path.join(gt_dir, f"{k:05d}.raw"))
-        model = build_model(model_config(name, prec="f16f6", max_batch=int(w.get("max_batch", 41)), n_streams=3))
-        model.load_state_dict(W.synth_state_dict(state_spec(name), seed=0), strict=True)
         out = {}
         for tag, extra in flags:
             ds = ImageDataset(img_dir, gt_dir=gt_dir, gt_format="eth3d", gt_shape=gt_shape, image_resolution=w["raw"], min_depth=MIN_DEPTH,
                               max_depth=MAX_DEPTH, **extra)
-            t = Tester(None, RunnerInfo(), ds, model)
-            run = lambda: t.run(cai_mode=w["mode"], image_raw_shape=w["raw"], patch_split_num=w["split"], seed=621)  # noqa: E731
-            run()  # warm-up (kernels, allocator, hipGraphs, page cache)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = run()
-            torch.cuda.synchronize()
-            out[tag] = round(n_maps / (time.perf_counter() - t0), 3)
+            out[tag], res, _ = EB.timed_maps_s(model, ds, w, n_maps)
             out[tag + "_keys"] = len(res[0]["metrics"])
             ds.close()
-    return dict(workload=name, maps=n_maps, gt=list(gt_shape), **out)
+    return dict(workload=EB.WORKLOAD, maps=n_maps, gt=list(gt_shape), **out)
 
 
 def main():
@@ -189,15 +152,12 @@ def main():
     ap.add_argument("--maps", type=int, default=3)
     ap.add_argument("--skip-tester", action="store_true")
     ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: Tester.run from its package, as 'parent'")
-    ap.add_argument("--step-timeout", type=int, default=280, help="seconds each GPU step may take")
-    ap.add_argument("--step", choices=STEPS, default=None, help="(internal) run one step in this process and print its JSON")
+    EB.add_step_arguments(ap, STEPS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ssi_eval.json"))
     a = ap.parse_args()
     if a.step:
         sys.path.insert(0, os.path.abspath(a.parent_tree) if a.step == "parent" else ROOT)
-        torch.set_grad_enabled(False)
-        from patchrefinerv2_amd import lib
-        lib.load()
+        EB.begin_step()
         if a.step == "fixture":
             res = step_fixture()
         elif a.step == "tester":
@@ -206,28 +166,14 @@ def main():
             res = step_tester(a.maps, (("ssi_off", {}),))
         else:
             res = step_size(a.step, a.reps)
-        print("RESULT " + json.dumps(res))
-        return 0
+        return EB.end_step(res)
     steps = [s for s in STEPS if not (a.skip_tester and s in ("tester", "parent")) and not (s == "parent" and not a.parent_tree)]
-    out = {}
-    for step in steps:
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(a.reps),
-               "--maps", str(a.maps)] + (["--parent-tree", a.parent_tree] if a.parent_tree else [])
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:  # a fault, an abort or the time limit: start nothing more on the GPU
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:] + f"\nstep {step} exited with status {r.returncode}: stopping\n")
-            return r.returncode
-        out[step] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    out = EB.run_steps(__file__, steps, a.step_timeout,
+                       ["--reps", a.reps, "--maps", a.maps] + (["--parent-tree", a.parent_tree] if a.parent_tree else []))
     if "tester" in out:
         t = out["tester"]
         t["ssi_overhead_pct"] = round(100 * (t["ssi_off"] / t["ssi_on"] - 1), 2)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    return 0
+    return EB.report(out, a.out)
 
 
 if __name__ == "__main__":

@@ -17,18 +17,17 @@ A synthetic U4K tree at 2160 x 3840 (raw BGR images, disparity .npy, extrinsics,
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import evalbench as EB  # noqa: E402
+from evalbench import wall_ms  # noqa: E402
 RAW = (2160, 3840)
 MIN_DEPTH, MAX_DEPTH = 1e-3, 80
 
@@ -54,19 +53,6 @@ def write_tree(root, n, shape=RAW):
     with open(split, "w") as f:
         f.write("\n".join(lines) + "\n")
     return split
-
-
-def wall_ms(fn, reps, warm=2):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ts), 3)
 
 
 def routes_ms(root, reps):
@@ -112,45 +98,13 @@ def routes_ms(root, reps):
     return fused, parent, agree
 
 
-class _NoGroundTruth:
-    """the dataset with ``depth_gt`` / ``boundary`` dropped from its items: Tester.run then scores nothing"""
-
-    def __init__(self, ds):
-        self.ds = ds
-
-    def __len__(self):
-        return len(self.ds)
-
-    def __getattr__(self, k):
-        return getattr(self.ds, k)
-
-    def __getitem__(self, i):
-        return {k: v for k, v in self.ds[i].items() if k not in ("depth_gt", "boundary")}
-
-
 def tester_maps_s(root, split, n_maps):
-    from patchrefinerv2_amd import models, weights as W  # noqa: F401  (registers the model classes)
-    from patchrefinerv2_amd.registry import build_model
-    from patchrefinerv2_amd.tester import RunnerInfo, Tester, UnrealStereo4kDataset
-    from patchrefinerv2_amd.workloads import WORKLOADS, model_config, state_spec
-    name = "v2_zoe_4k_r32"
-    w = WORKLOADS[name]
-    model = build_model(model_config(name, prec="f16f6", max_batch=int(w.get("max_batch", 41)), n_streams=3))
-    model.load_state_dict(W.synth_state_dict(state_spec(name), seed=0), strict=True)
+    from patchrefinerv2_amd.tester import UnrealStereo4kDataset
+    w, model = EB.workload_model()
     ds = UnrealStereo4kDataset("infer", root, split, dict(network_process_size=[384, 512]), MIN_DEPTH, MAX_DEPTH, image_raw_shape=w["raw"])
-    out = {}
-    for tag, data in (("with_gt", ds), ("without_gt", _NoGroundTruth(ds))):
-        t = Tester(None, RunnerInfo(), data, model)
-        run = lambda: t.run(cai_mode=w["mode"], image_raw_shape=w["raw"], patch_split_num=w["split"], seed=621)  # noqa: E731
-        run()  # warm-up (kernels, allocator, hipGraphs, page cache)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        res = run()
-        torch.cuda.synchronize()
-        out[tag] = round(n_maps / (time.perf_counter() - t0), 3)
-        assert ("metrics" in res[0]) == (tag == "with_gt")
+    out, _keys = EB.gt_pair_maps_s(model, ds, w, n_maps)
     ds.close()
-    return dict(workload=name, maps=n_maps, overhead_pct=round(100 * (out["without_gt"] / out["with_gt"] - 1), 2), **out)
+    return dict(workload=EB.WORKLOAD, maps=n_maps, **out)
 
 
 def main():
@@ -160,21 +114,14 @@ def main():
     ap.add_argument("--skip-tester", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "u4k_eval_bench.json"))
     a = ap.parse_args()
-    torch.set_grad_enabled(False)
-    from patchrefinerv2_amd import lib
-    lib.load()
+    EB.begin_step()
     with tempfile.TemporaryDirectory() as root:
         split = write_tree(root, 1 if a.skip_tester else a.maps)
         fused, parent, agree = routes_ms(root, a.reps)
         out = dict(frame=list(RAW), fused_ms=fused, parent_ms=parent, max_rel_diff_fused_vs_parent=float(f"{agree:.3e}"))
         if not a.skip_tester:
             out["tester_maps_s"] = tester_maps_s(root, split, a.maps)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    EB.report(out, a.out)
 
 
 if __name__ == "__main__":

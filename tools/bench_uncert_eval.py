@@ -24,19 +24,19 @@ exit with status 0 ends the run (nothing more is started on the GPU) and the too
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import re
-import statistics
-import subprocess
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))  # (the package's tree is chosen per step, in main)
+import evalbench as EB  # noqa: E402
+from evalbench import alloc_bytes, wall_ms  # noqa: E402
+
 MIN_DEPTH, MAX_DEPTH, LEVELS = 1e-3, 80, 20
 SIZES = {"4k": (2160, 3840), "cityscapes": (1024, 2048)}
 STEPS = ("deviation", "4k", "cityscapes", "tester")
@@ -56,30 +56,6 @@ def maps(shape, seed=0, kind="continuous"):
         uncert = (np.floor(uncert * 4 / float(uncert.max())).clip(0, 3) / 4).astype(np.float32)
     count = (1.0 + np.floor(8.0 * np.abs(np.sin(x / 200.0) * np.cos(y / 150.0)))).astype(np.float32)
     return gt, pred, uncert, count
-
-
-def wall_ms(fn, reps, warm=2):
-    for _ in range(warm):
-        fn()
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return round(statistics.median(ts), 3)
-
-
-def alloc_bytes(fn):
-    """device bytes the caching allocator hands out during one call"""
-    torch.cuda.synchronize()
-    key = "allocated_bytes.all.allocated"
-    b0 = torch.cuda.memory_stats()[key]
-    out = fn()
-    torch.cuda.synchronize()
-    del out
-    return int(torch.cuda.memory_stats()[key] - b0)
 
 
 def uncert_torch(gt, pred, uncert, count, min_count, mn, mx, levels):
@@ -177,34 +153,21 @@ def write_u4k_tree(root, n, shape):
 
 
 def step_tester(n_maps):
-    from patchrefinerv2_amd import models, weights as W  # noqa: F401  (registers the model classes)
-    from patchrefinerv2_amd.registry import DATASETS, build_model
-    from patchrefinerv2_amd.tester import RunnerInfo, Tester
-    from patchrefinerv2_amd.workloads import WORKLOADS, model_config, state_spec
-    name = "v2_zoe_4k_r32"
-    w = WORKLOADS[name]
+    from patchrefinerv2_amd import tester  # noqa: F401  (registers the datasets)
+    from patchrefinerv2_amd.registry import DATASETS
+    w, model = EB.workload_model()
     with tempfile.TemporaryDirectory() as root:
         split = write_u4k_tree(root, n_maps, tuple(w["raw"]))
-        model = build_model(model_config(name, prec="f16f6", max_batch=int(w.get("max_batch", 41)), n_streams=3))
-        model.load_state_dict(W.synth_state_dict(state_spec(name), seed=0), strict=True)
         ds = DATASETS.build(dict(type="UnrealStereo4kDataset", mode="infer", data_root=root, split=split, min_depth=MIN_DEPTH, max_depth=MAX_DEPTH,
                                  transform_cfg=dict(network_process_size=[384, 512]), image_raw_shape=list(w["raw"])))
         out = {}
         for tag, flag in (("uncert_off", False), ("uncert_on", True)):
-            t = Tester(None, RunnerInfo(rank=0, world_size=1), ds, model)
-            run = lambda: t.generate_pl(cai_mode=w["mode"], image_raw_shape=w["raw"], patch_split_num=w["split"], seed=621,  # noqa: E731
-                                        uncert_metrics=flag)
-            run()  # warm-up (kernels, allocator, hipGraphs, page cache)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = run()
-            torch.cuda.synchronize()
-            out[tag] = round(n_maps / (time.perf_counter() - t0), 3)
+            out[tag], res, t = EB.timed_maps_s(model, ds, w, n_maps, method="generate_pl", uncert_metrics=flag)
             if flag:
                 out["last_eval"] = {k: float(f"{v:.6g}") for k, v in t.last_eval.items()}
                 assert all("uncert_metrics" in r for r in res)
         ds.close()
-    return dict(workload=name, maps=n_maps, mode=w["mode"], **out)
+    return dict(workload=EB.WORKLOAD, maps=n_maps, mode=w["mode"], **out)
 
 
 def main():
@@ -212,32 +175,20 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--maps", type=int, default=3)
     ap.add_argument("--skip-tester", action="store_true")
-    ap.add_argument("--step-timeout", type=int, default=280, help="seconds each GPU step may take")
-    ap.add_argument("--step", choices=STEPS, default=None, help="(internal) run one step in this process and print its JSON")
+    EB.add_step_arguments(ap, STEPS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "uncert_eval.json"))
     a = ap.parse_args()
     if a.step:
         sys.path.insert(0, ROOT)
-        torch.set_grad_enabled(False)
-        from patchrefinerv2_amd import lib
-        lib.load()
+        EB.begin_step()
         if a.step == "deviation":
             res = step_deviation()
         elif a.step == "tester":
             res = step_tester(a.maps)
         else:
             res = step_size(a.step, a.reps)
-        print("RESULT " + json.dumps(res))
-        return 0
-    out = {}
-    for step in (s for s in STEPS if not (a.skip_tester and s == "tester")):
-        cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--step", step, "--reps", str(a.reps),
-               "--maps", str(a.maps)]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:  # a fault, an abort or the time limit: start nothing more on the GPU
-            sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:] + f"\nstep {step} exited with status {r.returncode}: stopping\n")
-            return r.returncode
-        out[step] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+        return EB.end_step(res)
+    out = EB.run_steps(__file__, [s for s in STEPS if not (a.skip_tester and s == "tester")], a.step_timeout, ["--reps", a.reps, "--maps", a.maps])
     if "tester" in out:
         t = out["tester"]
         t["uncert_overhead_pct"] = round(100 * (t["uncert_off"] / t["uncert_on"] - 1), 2)
@@ -245,13 +196,7 @@ def main():
     m = re.search(r"^MEASURED = ([0-9.e+-]+)", open(os.path.join(ROOT, "tests", "test_uncert_eval_gpu.py")).read(), flags=re.M)
     if m:
         out["tests"] = dict(measured_rel_deviation=float(m.group(1)), asserted_rtol=4 * float(m.group(1)), cap=1e-9)
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
-    return 0
+    return EB.report(out, a.out)
 
 
 if __name__ == "__main__":
