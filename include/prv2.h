@@ -860,6 +860,55 @@ int prv2_sparsify(const float* gt, const float* pred, const float* uncert, const
                   int32_t w, float min_depth, float max_depth, int32_t levels, double* out, void* workspace, int64_t workspace_bytes,
                   void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Geometry export (csrc/pointcloud.hip): the depth map as geometry -- the vertex records of a binary PLY point cloud and the
+ * scanlines of a surface-normal map, made from B >= 1 dense frames [n, h, w] where they are (h, w >= 1; n * h * w < 2^29).  Not in
+ * the reference.  Fixed launch counts, no host synchronisation, no atomics: the same input gives the same bytes on every call.
+ * Added without an ABI bump (additive).  The host specification is the numpy float32 restatement pointcloud_host /
+ * normal_map_host of patchrefinerv2_amd/output.py, which the kernels equal bit for bit: fp32, one rounding per operation in the
+ * order written, correctly rounded division and square root.
+ *   camera     pinhole, x right, y down, z forward: Z = D[y, x], X = (((float)x + 0.5) - cx) * Z / fx, Y = (((float)y + 0.5) - cy) * Z / fy;
+ *              fx, fy, cx, cy in pixels of the [h, w] grid (fx, fy > 0, all finite), the same for every frame of a call
+ *   valid      Z finite and lo < Z < hi
+ *   flying     edge_thr > 0 and one of the four in-frame neighbours is valid with |Z - Zn| > edge_thr * min(Z, Zn)
+ *   kept       valid, not flying, y % stride == 0 and x % stride == 0 (the neighbours are the full-resolution ones)
+ *   byte       clamp(rint(v * 255), 0, 255), ties to even, NaN -> 0
+ * ------------------------------------------------------------------------------------------ */
+
+/* bytes of workspace prv2_pointcloud_count / _pack need for n frames of h x w: one int32 per run of pixels a block owns (-1 for
+ * bad arguments) */
+int64_t prv2_pointcloud_workspace_bytes(int32_t n, int32_t h, int32_t w);
+
+/* 15 * ceil(h / stride) * ceil(w / stride): the bytes of a frame's vertex records when every strided pixel is kept (-1 for bad
+ * arguments) */
+int64_t prv2_pointcloud_bound(int32_t h, int32_t w, int32_t stride);
+
+/* depth: fp32 [n, h, w].  counts: DEVICE int64 [n] = N, the kept pixels of each frame.  workspace: DEVICE, 4-byte aligned,
+ * prv2_pointcloud_workspace_bytes(n, h, w); it leaves with the exclusive offsets of every block's run of pixels, in block order
+ * (a block counts its run, a one-block scan per frame adds the counts up) -- what prv2_pointcloud_pack reads. */
+int prv2_pointcloud_count(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float fy, float cx, float cy, float lo, float hi,
+                          float edge_thr, int32_t stride, int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* the vertex records of the kept pixels in row-major pixel order: float x, y, z (little endian) + uchar red, green, blue, 15 bytes
+ * each, frame f's at vertices[f * vertices_fstride + 15 * k], k < N.  Same depth, camera, range, edge_thr and stride as the
+ * prv2_pointcloud_count call that filled ``workspace``.  image: fp32 [n, 3, ih, iw] (any size), sampled nearest with integer
+ * arithmetic: sy = ((2 y + 1) * ih) / (2 h), sx = ((2 x + 1) * iw) / (2 w); colour = byte(image[c, sy, sx]).  vertices: DEVICE uint8,
+ * no alignment asked of the pointer or of vertices_fstride >= prv2_pointcloud_bound(h, w, stride).  Exactly the 15 * N bytes of a
+ * frame are written and nothing else is touched: a block stores the ragged ends of its byte range with byte stores and the
+ * 16-byte-aligned interior with 16-byte stores; no byte is read back. */
+int prv2_pointcloud_pack(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx, float fy,
+                         float cx, float cy, float lo, float hi, float edge_thr, int32_t stride, const void* workspace,
+                         int64_t workspace_bytes, uint8_t* vertices, int64_t vertices_fstride, void* stream);
+
+/* the surface normals as RGB scanlines (bpp 3; a scanline buffer of the output stage).  P = (X, Y, Z) of a valid pixel;
+ * Px = P[y, x + 1] - P[y, x - 1] where both neighbours are valid and in frame, else P[y, x + 1] - P or P - P[y, x - 1] with the one
+ * that is, else the pixel has no normal; Py likewise along y.  n = cross(Px, Py) / |cross(Px, Py)| (|v| = sqrt((vx vx + vy vy) + vz vz)),
+ * negated where (n.x X + n.y Y) + n.z Z > 0 (it faces the camera); a length that is zero or not finite, or a component that is not
+ * finite, gives no normal.  RGB = byte(n * 0.5 + 0.5); (0, 0, 0) for invalid pixels and pixels without a normal.  The flying-pixel
+ * filter and the stride do not apply. */
+int prv2_normal_rows(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float fy, float cx, float cy, float lo, float hi,
+                     uint8_t* rows, int64_t rows_fstride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,344 @@
+// Geometry export (include/prv2.h "Geometry export"): a metric depth map turned into geometry where it already is.  The vertex records
+// of a binary PLY point cloud (float x, y, z + uchar red, green, blue: 15 bytes, kept pixels in row-major order) and the PNG scanlines
+// of a surface-normal map, of B >= 1 frames [n, h, w].  Fixed launch counts, no host synchronisation, no atomics: the same input gives
+// the same bytes on every call.  All three kernels are streaming passes (one read of the depth map and, for the cloud, one nearest
+// sample of the image per kept pixel).
+//
+// Arithmetic contract (the numpy float32 restatement is output.py: pointcloud_host / normal_map_host; bit for bit):
+//   - the file is built with -ffp-contract=off; every fp32 operation is written with __f*_rn (IEEE, one rounding each, in the order
+//     of the restatement); division and square root are the correctly rounded ones (sqrtf: HIP's __fsqrt_rn is the native,
+//     1-ulp instruction);
+//   - camera: Z = D[y, x], X = (((float)x + 0.5) - cx) * Z / fx, Y likewise with cy, fy;
+//   - valid: Z finite and lo < Z < hi; flying: a valid in-frame 4-neighbour Zn with |Z - Zn| > thr * min(Z, Zn) (thr > 0);
+//   - kept: valid, not flying, y % stride == 0 and x % stride == 0.
+#include "rows.h"
+
+namespace prv2 {
+namespace {
+
+constexpr int kRun = 2048;     // pixels of a frame one block owns: kRounds steps of 256 lanes, lane t of step r has pixel r * 256 + t of the run
+constexpr int kRounds = kRun / 256;
+constexpr int kSegs = kRounds * 4;  // (step, wave) segments of 64 consecutive pixels
+constexpr int kRecord = 15;    // bytes of a vertex
+
+struct Camera {
+  float fx, fy, cx, cy;  // in pixels of the depth map's grid
+  float lo, hi;          // valid: lo < Z < hi
+};
+
+struct CloudArgs {
+  const float* depth;  // [n, h, w]
+  Camera cam;
+  float thr;           // flying-pixel threshold (<= 0: off)
+  int32_t h, w, stride;
+  int32_t nblk;        // blocks (runs) per frame
+};
+
+__device__ __forceinline__ bool valid_z(const Camera& c, float z) { return fabsf(z) < __builtin_inff() && z > c.lo && z < c.hi; }
+
+__device__ __forceinline__ bool flying(const Camera& c, float thr, float z, float zn) {
+  return valid_z(c, zn) && fabsf(__fsub_rn(z, zn)) > __fmul_rn(thr, fminf(z, zn));
+}
+
+// the keep predicate of pixel (y, x) of frame ``d``; z = d[y * w + x]
+__device__ __forceinline__ bool keep_pixel(const CloudArgs& a, const float* __restrict__ d, int y, int x, float z) {
+  if (!valid_z(a.cam, z) || y % a.stride != 0 || x % a.stride != 0) return false;
+  if (!(a.thr > 0.0f)) return true;
+  const int64_t i = (int64_t)y * a.w + x;
+  bool fly = false;
+  if (x > 0) fly = fly || flying(a.cam, a.thr, z, d[i - 1]);
+  if (x + 1 < a.w) fly = fly || flying(a.cam, a.thr, z, d[i + 1]);
+  if (y > 0) fly = fly || flying(a.cam, a.thr, z, d[i - a.w]);
+  if (y + 1 < a.h) fly = fly || flying(a.cam, a.thr, z, d[i + a.w]);
+  return !fly;
+}
+
+__device__ __forceinline__ float cam_x(const Camera& c, int x, float z) {
+  return __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)x, 0.5f), c.cx), z), c.fx);
+}
+__device__ __forceinline__ float cam_y(const Camera& c, int y, float z) {
+  return __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)y, 0.5f), c.cy), z), c.fy);
+}
+
+// clamp(rint(v), 0, 255), ties to even, NaN -> 0
+__device__ __forceinline__ uint32_t byte_of(float v) {
+  const float r = rintf(v);
+  return !(r > 0.0f) ? 0u : r >= 255.0f ? 255u : (uint32_t)r;
+}
+
+// One step of a block over its run: lane t evaluates pixel p0 + t (p0 a multiple of 64 inside the frame's pixel range or behind it).
+// Returns the pixel's keep flag; ``below``: kept pixels of lower lanes of this wave, ``total``: of the whole wave.
+__device__ __forceinline__ bool step_keep(const CloudArgs& a, const float* __restrict__ d, int64_t p, int64_t hw, float& z, int& y, int& x,
+                                          int& below, int& total) {
+  bool k = false;
+  z = 0.0f, y = 0, x = 0;
+  if (p < hw) {
+    y = (int)(p / a.w);
+    x = (int)(p - (int64_t)y * a.w);
+    z = d[p];
+    k = keep_pixel(a, d, y, x, z);
+  }
+  const unsigned long long b = __ballot(k);
+  const int lane = threadIdx.x & 63;
+  below = __popcll(b & ((1ull << lane) - 1ull));
+  total = __popcll(b);
+  return k;
+}
+
+// kept pixels of every run: counts[f][blk]
+__global__ void __launch_bounds__(256) cloud_count_kernel(CloudArgs a, int32_t* __restrict__ counts) {
+  __shared__ int32_t seg[kSegs];
+  const int tid = threadIdx.x, wave = tid >> 6, f = blockIdx.y;
+  const int64_t hw = (int64_t)a.h * a.w, p0 = (int64_t)blockIdx.x * kRun;
+  const float* d = a.depth + (int64_t)f * hw;
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    float z;
+    int y, x, below, total;
+    step_keep(a, d, p0 + r * 256 + tid, hw, z, y, x, below, total);
+    if ((tid & 63) == 0) seg[r * 4 + wave] = total;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int32_t c = 0;
+    for (int s = 0; s < kSegs; ++s) c += seg[s];
+    counts[(int64_t)f * a.nblk + blockIdx.x] = c;
+  }
+}
+
+// one block per frame: counts[f][0 .. nblk) -> their exclusive prefix sums in block order (in place), totals[f] = the frame's N
+__global__ void __launch_bounds__(256) cloud_scan_kernel(int32_t* __restrict__ counts, int32_t nblk, int64_t* __restrict__ totals) {
+  __shared__ int32_t part[256];
+  const int tid = threadIdx.x, f = blockIdx.x;
+  int32_t* c = counts + (int64_t)f * nblk;
+  const int per = (nblk + 255) / 256;  // a lane's contiguous chunk
+  const int i0 = tid * per < nblk ? tid * per : nblk, i1 = i0 + per < nblk ? i0 + per : nblk;
+  int32_t sum = 0;
+  for (int i = i0; i < i1; ++i) sum += c[i];
+  part[tid] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    int32_t run = 0;
+    for (int t = 0; t < 256; ++t) {
+      const int32_t v = part[t];
+      part[t] = run;
+      run += v;
+    }
+    totals[f] = (int64_t)run;
+  }
+  __syncthreads();
+  int32_t run = part[tid];
+  for (int i = i0; i < i1; ++i) {
+    const int32_t v = c[i];
+    c[i] = run;
+    run += v;
+  }
+}
+
+// The records of every run.  The block ranks its kept pixels in pixel order (ballot + popcount inside a wave, the (step, wave) segment
+// totals through LDS), builds the records in LDS and stores its byte range [15 off, 15 (off + cnt)) of the frame's vertex buffer.  That
+// range starts and ends at any byte alignment and the dwords at its two ends may belong to the neighbouring runs as well: the LDS image
+// is shifted so that LDS offset == global address (mod 16), the bytes up to the first and from the last 16-byte boundary are stored one
+// by one and only the aligned interior with 16-byte stores.  Nothing outside the range is written (or read).
+__global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, const float* __restrict__ image, int32_t ih, int32_t iw,
+                                                         const int32_t* __restrict__ offsets, uint8_t* __restrict__ out, int64_t out_fstride) {
+  __shared__ uint4 buf4[(kRun * kRecord + 16 + 15) / 16];
+  __shared__ int32_t seg[kSegs + 1];
+  uint8_t* buf = (uint8_t*)buf4;
+  const int tid = threadIdx.x, wave = tid >> 6, f = blockIdx.y;
+  const int64_t hw = (int64_t)a.h * a.w, p0 = (int64_t)blockIdx.x * kRun;
+  const float* d = a.depth + (int64_t)f * hw;
+  float z[kRounds];
+  int32_t rank[kRounds];  // rank inside the wave's segment, -1: not kept
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    int y, x, below, total;
+    const bool k = step_keep(a, d, p0 + r * 256 + tid, hw, z[r], y, x, below, total);
+    rank[r] = k ? below : -1;
+    if ((tid & 63) == 0) seg[r * 4 + wave] = total;
+  }
+  __syncthreads();
+  if (tid == 0) {  // exclusive prefix of the segment totals; seg[kSegs] = the run's count
+    int32_t run = 0;
+    for (int s = 0; s < kSegs; ++s) {
+      const int32_t v = seg[s];
+      seg[s] = run;
+      run += v;
+    }
+    seg[kSegs] = run;
+  }
+  __syncthreads();
+  const int32_t cnt = seg[kSegs];
+  if (cnt == 0) return;
+  uint8_t* dst = out + (int64_t)f * out_fstride + (int64_t)kRecord * offsets[(int64_t)f * a.nblk + blockIdx.x];
+  const int shift = (int)((uintptr_t)dst & 15);
+  const float* img = image + (int64_t)f * 3 * ih * iw;
+  const int64_t plane = (int64_t)ih * iw;
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    if (rank[r] < 0) continue;
+    const int64_t p = p0 + r * 256 + tid;
+    const int y = (int)(p / a.w), x = (int)(p - (int64_t)y * a.w);
+    const int sy = (int)(((int64_t)(2 * y + 1) * ih) / (2 * (int64_t)a.h)), sx = (int)(((int64_t)(2 * x + 1) * iw) / (2 * (int64_t)a.w));
+    const float* c = img + (int64_t)sy * iw + sx;
+    const uint32_t w0 = __float_as_uint(cam_x(a.cam, x, z[r])), w1 = __float_as_uint(cam_y(a.cam, y, z[r])), w2 = __float_as_uint(z[r]);
+    uint8_t* rec = buf + shift + kRecord * (seg[r * 4 + wave] + rank[r]);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      rec[b] = (uint8_t)(w0 >> (8 * b));
+      rec[4 + b] = (uint8_t)(w1 >> (8 * b));
+      rec[8 + b] = (uint8_t)(w2 >> (8 * b));
+    }
+    rec[12] = (uint8_t)byte_of(__fmul_rn(c[0], 255.0f));
+    rec[13] = (uint8_t)byte_of(__fmul_rn(c[plane], 255.0f));
+    rec[14] = (uint8_t)byte_of(__fmul_rn(c[2 * plane], 255.0f));
+  }
+  __syncthreads();
+  // buf[shift + i] <-> dst[i], i in [0, nb); dst - shift is 16-byte aligned
+  const int nb = kRecord * cnt;
+  const int head = (16 - shift) & 15;              // bytes before the first 16-byte boundary
+  const int h_end = head < nb ? head : nb;
+  const int wide = (nb - h_end) / 16;              // aligned 16-byte words of the interior
+  const int t_beg = h_end + 16 * wide;
+  if (tid < h_end) dst[tid] = buf[shift + tid];
+  uint4* dst4 = (uint4*)(dst + h_end);
+  const uint4* src4 = buf4 + (shift + h_end) / 16;
+  for (int i = tid; i < wide; i += 256) dst4[i] = src4[i];
+  if (tid < nb - t_beg) dst[t_beg + tid] = buf[shift + t_beg + tid];
+}
+
+// the surface normal of a pixel as RGB scanline bytes; pixels without a normal are (0, 0, 0)
+struct NormalOp {
+  static constexpr int bpp = 3;
+  static constexpr bool lut = false;
+  const float* depth;
+  Camera cam;
+  int32_t h, w;
+  __device__ __forceinline__ bool point(const float* d, int y, int x, float& px, float& py, float& pz) const {
+    if (y < 0 || y >= h || x < 0 || x >= w) return false;
+    pz = d[(int64_t)y * w + x];
+    if (!valid_z(cam, pz)) return false;
+    px = cam_x(cam, x, pz);
+    py = cam_y(cam, y, pz);
+    return true;
+  }
+  // central difference of two valid neighbours, else the one-sided difference with the valid one
+  __device__ __forceinline__ bool diff(const float* d, int y, int x, int dy, int dx, float cx_, float cy_, float cz_, float& gx, float& gy,
+                                       float& gz) const {
+    float ax, ay, az, bx, by, bz;
+    const bool fwd = point(d, y + dy, x + dx, ax, ay, az), bwd = point(d, y - dy, x - dx, bx, by, bz);
+    if (!fwd && !bwd) return false;
+    if (!fwd) ax = cx_, ay = cy_, az = cz_;
+    if (!bwd) bx = cx_, by = cy_, bz = cz_;
+    gx = __fsub_rn(ax, bx), gy = __fsub_rn(ay, by), gz = __fsub_rn(az, bz);
+    return true;
+  }
+  __device__ __forceinline__ uint32_t pixel(int f, int64_t i, const uint32_t*) const {
+    const int64_t hw = (int64_t)h * w, local = i - (int64_t)f * hw;
+    const int y = (int)(local / w), x = (int)(local - (int64_t)y * w);
+    const float* d = depth + (int64_t)f * hw;
+    float X, Y, Z, ux, uy, uz, vx, vy, vz;
+    if (!point(d, y, x, X, Y, Z)) return 0u;
+    if (!diff(d, y, x, 0, 1, X, Y, Z, ux, uy, uz) || !diff(d, y, x, 1, 0, X, Y, Z, vx, vy, vz)) return 0u;
+    float nx = __fsub_rn(__fmul_rn(uy, vz), __fmul_rn(uz, vy));
+    float ny = __fsub_rn(__fmul_rn(uz, vx), __fmul_rn(ux, vz));
+    float nz = __fsub_rn(__fmul_rn(ux, vy), __fmul_rn(uy, vx));
+    const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
+    if (!(len > 0.0f) || !(len < __builtin_inff())) return 0u;
+    nx = __fdiv_rn(nx, len), ny = __fdiv_rn(ny, len), nz = __fdiv_rn(nz, len);
+    const float inf = __builtin_inff();
+    if (!(fabsf(nx) < inf && fabsf(ny) < inf && fabsf(nz) < inf)) return 0u;
+    const float dot = __fadd_rn(__fadd_rn(__fmul_rn(nx, X), __fmul_rn(ny, Y)), __fmul_rn(nz, Z));
+    if (dot > 0.0f) nx = -nx, ny = -ny, nz = -nz;
+    const uint32_t r = byte_of(__fmul_rn(__fadd_rn(__fmul_rn(nx, 0.5f), 0.5f), 255.0f));
+    const uint32_t g = byte_of(__fmul_rn(__fadd_rn(__fmul_rn(ny, 0.5f), 0.5f), 255.0f));
+    const uint32_t b = byte_of(__fmul_rn(__fadd_rn(__fmul_rn(nz, 0.5f), 0.5f), 255.0f));
+    return r | g << 8 | b << 16;
+  }
+};
+
+static int64_t cloud_blocks(int h, int w) { return cdiv((int64_t)h * w, kRun); }
+
+static int check_camera(const char* name, float fx, float fy, float cx, float cy) {
+  PRV2_REQUIRE(fx > 0.0f && fy > 0.0f && fx < __builtin_inff() && fy < __builtin_inff(), "%s: focal lengths %g, %g: finite and positive", name,
+               (double)fx, (double)fy);
+  PRV2_REQUIRE(cx == cx && cy == cy && fabsf(cx) < __builtin_inff() && fabsf(cy) < __builtin_inff(), "%s: principal point %g, %g: finite", name,
+               (double)cx, (double)cy);
+  return 0;
+}
+
+static int check_cloud(const char* name, const float* depth, int n, int h, int w, float fx, float fy, float cx, float cy, int stride,
+                       const void* workspace, int64_t workspace_bytes) {
+  PRV2_REQUIRE(depth != nullptr, "%s: null pointer (depth)", name);
+  if (check_map(name, n, h, w) || check_camera(name, fx, fy, cx, cy)) return 1;
+  PRV2_REQUIRE(stride >= 1, "%s: stride %d < 1", name, stride);
+  PRV2_REQUIRE(workspace != nullptr, "%s: null workspace", name);
+  PRV2_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: the workspace must be 4-byte aligned", name);
+  PRV2_REQUIRE(workspace_bytes >= prv2_pointcloud_workspace_bytes(n, h, w), "%s: workspace of %lld bytes < %lld (prv2_pointcloud_workspace_bytes)",
+               name, (long long)workspace_bytes, (long long)prv2_pointcloud_workspace_bytes(n, h, w));
+  return 0;
+}
+
+static CloudArgs cloud_args(const float* depth, int h, int w, float fx, float fy, float cx, float cy, float lo, float hi, float thr, int stride) {
+  CloudArgs a{};
+  a.depth = depth;
+  a.cam = Camera{fx, fy, cx, cy, lo, hi};
+  a.thr = thr;
+  a.h = h, a.w = w, a.stride = stride;
+  a.nblk = (int32_t)cloud_blocks(h, w);
+  return a;
+}
+
+}  // namespace
+}  // namespace prv2
+
+using namespace prv2;
+
+extern "C" int64_t prv2_pointcloud_workspace_bytes(int32_t n, int32_t h, int32_t w) {
+  if (n < 1 || n > 65535 || h < 1 || w < 1 || (int64_t)n * h * w >= (int64_t)INT_MAX / 4) return -1;
+  return (int64_t)n * cloud_blocks(h, w) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int64_t prv2_pointcloud_bound(int32_t h, int32_t w, int32_t stride) {
+  if (h < 1 || w < 1 || stride < 1) return -1;
+  return cdiv(h, stride) * cdiv(w, stride) * kRecord;
+}
+
+extern "C" int prv2_pointcloud_count(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float fy, float cx, float cy, float lo, float hi,
+                                     float edge_thr, int32_t stride, int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* name = "pointcloud_count";
+  PRV2_REQUIRE(counts != nullptr, "%s: null pointer (counts)", name);
+  if (check_cloud(name, depth, n, h, w, fx, fy, cx, cy, stride, workspace, workspace_bytes)) return 1;
+  const CloudArgs a = cloud_args(depth, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride);
+  hipLaunchKernelGGL(cloud_count_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, (int32_t*)workspace);
+  hipLaunchKernelGGL(cloud_scan_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (int32_t*)workspace, a.nblk, counts);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_pointcloud_pack(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx,
+                                    float fy, float cx, float cy, float lo, float hi, float edge_thr, int32_t stride, const void* workspace,
+                                    int64_t workspace_bytes, uint8_t* vertices, int64_t vertices_fstride, void* stream) {
+  const char* name = "pointcloud_pack";
+  PRV2_REQUIRE(image && vertices, "%s: null pointer", name);
+  if (check_cloud(name, depth, n, h, w, fx, fy, cx, cy, stride, workspace, workspace_bytes)) return 1;
+  PRV2_REQUIRE(ih >= 1 && iw >= 1 && (int64_t)n * 3 * ih * iw < (int64_t)INT_MAX, "%s: bad image shape %d x %d", name, ih, iw);
+  PRV2_REQUIRE(vertices_fstride >= prv2_pointcloud_bound(h, w, stride), "%s: frame stride %lld of the vertex buffer < %lld (prv2_pointcloud_bound)",
+               name, (long long)vertices_fstride, (long long)prv2_pointcloud_bound(h, w, stride));
+  const CloudArgs a = cloud_args(depth, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride);
+  hipLaunchKernelGGL(cloud_pack_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, image, ih, iw,
+                     (const int32_t*)workspace, vertices, vertices_fstride);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_normal_rows(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float fy, float cx, float cy, float lo, float hi,
+                                uint8_t* rows, int64_t rows_fstride, void* stream) {
+  const char* name = "normal_rows";
+  PRV2_REQUIRE(depth != nullptr, "%s: null pointer (depth)", name);
+  if (check_map(name, n, h, w) || check_camera(name, fx, fy, cx, cy) || check_rows(name, rows, rows_fstride, n, h, w, 3)) return 1;
+  NormalOp op{depth, Camera{fx, fy, cx, cy, lo, hi}, h, w};
+  launch_rows(op, nullptr, 0, n, h, w, rows, rows_fstride, (hipStream_t)stream);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}

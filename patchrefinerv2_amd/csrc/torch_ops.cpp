@@ -1249,6 +1249,45 @@ Tensor sparsify(const Tensor& gt, const Tensor& pred, const Tensor& uncert, cons
   return out;
 }
 
+// geometry export (include/prv2.h "Geometry export"): PLY vertex records and surface-normal scanlines of B frames [n, h, w]
+const double* camera4(at::ArrayRef<double> k, const char* op) {
+  TORCH_CHECK(k.size() == 4, "prv2::", op, ": intrinsics are fx, fy, cx, cy (got ", k.size(), " values)");
+  return k.data();
+}
+// counts int64 [n]; frame f's records are vertices[f, :15 * counts[f]] (the rest of ``vertices`` is left as it is)
+Tensor pointcloud_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, double lo, double hi, double edge_thr,
+                       int64_t stride, Tensor vertices) {
+  dev_frames(depth, "depth", at::kFloat);
+  const double* k = camera4(intrinsics, "pointcloud_pack");
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
+                  image.size(1) == 3 && image.device() == depth.device(), "prv2::pointcloud_pack: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+  const int n = (int)depth.size(0), h = (int)depth.size(1), w = (int)depth.size(2);
+  const int64_t bytes = prv2_pointcloud_workspace_bytes(n, h, w), bound = prv2_pointcloud_bound(h, w, (int)stride);
+  TORCH_CHECK(bytes > 0, "prv2::pointcloud_pack: bad frame shape ", depth.sizes());
+  TORCH_CHECK(stride >= 1 && stride <= INT_MAX && bound > 0, "prv2::pointcloud_pack: stride ", stride, " < 1");
+  TORCH_CHECK(vertices.is_cuda() && vertices.scalar_type() == at::kByte && vertices.dim() == 2 && vertices.is_contiguous() && vertices.size(0) == n &&
+                  vertices.size(1) >= bound && vertices.device() == depth.device(),
+              "prv2::pointcloud_pack: vertices must be a contiguous GPU uint8 [n, >= ", bound, "] tensor");
+  Tensor ws = at::empty({bytes}, depth.options().dtype(at::kByte));
+  Tensor counts = at::empty({depth.size(0)}, depth.options().dtype(at::kLong));
+  Launch L(depth);
+  ok(prv2_pointcloud_count(depth.data_ptr<float>(), n, h, w, (float)k[0], (float)k[1], (float)k[2], (float)k[3], (float)lo, (float)hi, (float)edge_thr,
+                           (int)stride, counts.data_ptr<int64_t>(), ws.data_ptr(), ws.numel(), L.stream), "pointcloud_count");
+  ok(prv2_pointcloud_pack(depth.data_ptr<float>(), image.data_ptr<float>(), n, h, w, (int)image.size(2), (int)image.size(3), (float)k[0], (float)k[1],
+                          (float)k[2], (float)k[3], (float)lo, (float)hi, (float)edge_thr, (int)stride, ws.data_ptr(), ws.numel(),
+                          (uint8_t*)vertices.data_ptr(), vertices.size(1), L.stream), "pointcloud_pack");
+  return counts;
+}
+Tensor normal_rows(const Tensor& depth, at::ArrayRef<double> intrinsics, double lo, double hi) {
+  dev_frames(depth, "depth", at::kFloat);
+  const double* k = camera4(intrinsics, "normal_rows");
+  Tensor rows = alloc_rows(depth, 3);
+  Launch L(depth);
+  ok(prv2_normal_rows(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2), (float)k[0], (float)k[1], (float)k[2],
+                      (float)k[3], (float)lo, (float)hi, (uint8_t*)rows.data_ptr(), rows.size(1), L.stream), "normal_rows");
+  return rows;
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1399,6 +1438,9 @@ TORCH_LIBRARY(prv2, m) {
         "int x0, int x1) -> Tensor");
   m.def("ssi_metrics(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1) -> Tensor");
   m.def("sparsify(Tensor gt, Tensor pred, Tensor uncert, Tensor? count, float min_count, float min_depth, float max_depth, int levels) -> Tensor");
+  // geometry export: PLY vertex records (written into ``vertices``; returns the per-frame counts) and surface-normal scanlines
+  m.def("pointcloud_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices) -> Tensor");
+  m.def("normal_rows(Tensor depth, float[] intrinsics, float lo, float hi) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1486,4 +1528,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("image_edge_region", &image_edge_region);
   m.impl("ssi_metrics", &ssi_metrics);
   m.impl("sparsify", &sparsify);
+  m.impl("pointcloud_pack", &pointcloud_pack);
+  m.impl("normal_rows", &normal_rows);
 }

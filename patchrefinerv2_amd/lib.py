@@ -175,6 +175,12 @@ SIGNATURES = {
     # sparsification curves of a per-pixel uncertainty (csrc/sparsify.hip): thresholds by the radix select, bucket sums, suffix sums
     "prv2_sparsify_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "prv2_sparsify": (_I, [_P, _P, _P, _P, _D, _I, _I, _I, _F, _F, _I, _P, _P, _L, _P]),
+    # geometry export (csrc/pointcloud.hip): PLY vertex records and surface-normal scanlines of B frames
+    "prv2_pointcloud_workspace_bytes": (_L, [_I, _I, _I]),
+    "prv2_pointcloud_bound": (_L, [_I, _I, _I]),
+    "prv2_pointcloud_count": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _L, _P]),
+    "prv2_pointcloud_pack": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _L, _P, _L, _P]),
+    "prv2_normal_rows": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _L, _P]),
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
 SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS

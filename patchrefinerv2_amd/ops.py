@@ -1718,6 +1718,72 @@ def deflate_rows(rows, length):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Geometry export (csrc/pointcloud.hip): PLY vertex records and surface-normal scanlines of frames [B, H, W], both dispatch
+# routes.  The host specification is output.pointcloud_host / output.normal_map_host.
+# ------------------------------------------------------------------------------------------------------------------
+def _camera(intrinsics, depth_range, what):
+    """(fx, fy, cx, cy), (lo, hi) as Python floats that hold float32 values (the kernels' arithmetic is fp32)"""
+    k = [float(np.float32(v)) for v in np.asarray(intrinsics, dtype=np.float64).reshape(-1)]
+    if len(k) != 4 or not all(math.isfinite(v) for v in k) or k[0] <= 0 or k[1] <= 0:
+        raise ValueError(f"{what}: intrinsics are finite fx, fy, cx, cy with fx, fy > 0 (got {intrinsics})")
+    lo, hi = (float(np.float32(v)) for v in depth_range)
+    if math.isnan(lo) or math.isnan(hi):
+        raise ValueError(f"{what}: the depth range (lo, hi) must not be NaN")
+    return k, (lo, hi)
+
+
+def pointcloud_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, out=None):
+    """the PLY vertex records of fp32 depth frames [B, H, W] -> (vertex bytes uint8 [B, bound], counts int64 [B]), both on the
+    device: frame f's cloud is the first 15 * counts[f] bytes of row f (float x, y, z + uchar r, g, b per kept pixel, row-major
+    pixel order), bound = 15 * ceil(H / stride) * ceil(W / stride); the bytes behind a frame's records are not written.
+    ``image``: fp32 [B, 3, Hi, Wi] ([3, Hi, Wi] for one frame), any size, sampled nearest.  ``intrinsics``: fx, fy, cx, cy in
+    pixels of the [H, W] grid; ``depth_range``: (lo, hi), valid is lo < Z < hi; ``edge_thr``: the flying-pixel threshold
+    (<= 0: off).  ``out``: a uint8 [B, >= bound] buffer to write into (include/prv2.h prv2_pointcloud_count / _pack)."""
+    d = _edge_frames(depth, torch.float32)
+    k, (lo, hi) = _camera(intrinsics, depth_range, "pointcloud_pack")
+    stride, thr = int(stride), float(np.float32(edge_thr))
+    if stride < 1:
+        raise ValueError(f"pointcloud_pack: stride {stride} < 1")
+    if math.isnan(thr):
+        raise ValueError("pointcloud_pack: edge_thr must not be NaN")
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
+        raise ValueError("pointcloud_pack: image is a GPU tensor on the depth map's device")
+    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"pointcloud_pack: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    lib = L.load()
+    bound = lib.prv2_pointcloud_bound(d.shape[1], d.shape[2], stride)
+    if out is None:
+        out = torch.empty((d.shape[0], bound), dtype=torch.uint8, device=d.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != d.device or out.dim() != 2 or not out.is_contiguous()
+          or out.shape[0] != d.shape[0] or out.shape[1] < bound):
+        raise ValueError(f"pointcloud_pack: out is a contiguous GPU uint8 [{d.shape[0]}, >= {bound}] tensor")
+    if DISPATCH == "torch":
+        return out, _tops().pointcloud_pack(d, img, k, lo, hi, thr, stride, out)
+    wsb = lib.prv2_pointcloud_workspace_bytes(*d.shape)
+    if wsb < 0:
+        raise ValueError(f"pointcloud_pack: bad frame shape {tuple(d.shape)}")
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=d.device)
+    counts = torch.empty((d.shape[0],), dtype=torch.int64, device=d.device)
+    _c("pointcloud_count", d.data_ptr(), *d.shape, *k, lo, hi, thr, stride, counts.data_ptr(), ws.data_ptr(), wsb)
+    _c("pointcloud_pack", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], *k, lo, hi, thr, stride, ws.data_ptr(), wsb,
+       out.data_ptr(), out.shape[1])
+    return out, counts
+
+
+def normal_rows(depth, intrinsics, depth_range=(0.0, math.inf)):
+    """the camera-facing surface normals of fp32 depth frames [B, H, W] as RGB scanlines (n * 0.5 + 0.5 in bytes; (0, 0, 0)
+    where there is no normal) -> scanline buffer (include/prv2.h prv2_normal_rows)"""
+    d = _edge_frames(depth, torch.float32)
+    k, (lo, hi) = _camera(intrinsics, depth_range, "normal_rows")
+    if DISPATCH == "torch":
+        return _tops().normal_rows(d, k, lo, hi)
+    rows = _rows(d, 3)
+    _c("normal_rows", d.data_ptr(), *d.shape, *k, lo, hi, rows.data_ptr(), rows.shape[1])
+    return rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Ground-truth evaluation (csrc/evalgt.hip): the device half of UnrealStereo4kDataset and the sums behind compute_metrics, both
 # dispatch routes.
 # ------------------------------------------------------------------------------------------------------------------

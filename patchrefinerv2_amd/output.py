@@ -17,10 +17,18 @@ percentile_device        np.percentile(value[mask], q) of a device map (exact or
 colorize_device          metrics.colorize of a device map -> device uint8 [H, W, 3] view + its scanline buffer
 png_bytes_from_stream    the PNG container around a given IDAT payload
 write_png16 / write_png8 a host array as a PNG file (the host route's dependency-free encoder)
+camera_intrinsics        fx, fy, cx, cy of a result map's grid from --intrinsics / --fov (host)
+pointcloud_host / normal_map_host / ply_bytes
+                         the host specification of the geometry export (csrc/pointcloud.hip equals it bit for bit) and the PLY file
 OutputStage              side stream, ring of pinned staging slots, writer pool
+
+Geometry export (``runner_info.save_ply`` / ``save_normals``; tools/test.py --save-ply / --save-normals): <name>.ply, a binary
+little-endian point cloud of the result map (float x, y, z + uchar red, green, blue per kept pixel, row-major pixel order), and
+<name>_normal.png, its camera-facing surface normals.  Pinhole camera, x right, y down, z forward.
 """
 from __future__ import annotations
 
+import math
 import os
 import struct
 import threading
@@ -134,6 +142,156 @@ def write_png8(path: str, arr_u8: np.ndarray):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# geometry export: the host specification (numpy float32, one rounding per operation in the order written; csrc/pointcloud.hip
+# equals it bit for bit) and the PLY container
+# ------------------------------------------------------------------------------------------------------------------
+PLY_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])  # 15 bytes, packed
+
+
+def camera_intrinsics(raw_shape, result_shape, intrinsics=None, fov=60.0) -> np.ndarray:
+    """float32 [4] = fx, fy, cx, cy in pixels of the result map's grid.  ``intrinsics`` (fx, fy, cx, cy) are given in pixels of the
+    ``raw_shape`` (H_raw, W_raw) grid; without them they come from ``fov``, a horizontal field of view in degrees:
+    fx = fy = (W_raw / 2) / tan(fov / 2), cx = W_raw / 2, cy = H_raw / 2.  They are scaled in float64 to ``result_shape`` (H, W) --
+    the m-modes return the re-ensemble shape, not the raw one: fx, cx by W / W_raw and fy, cy by H / H_raw -- and cast once."""
+    hr, wr = (float(v) for v in raw_shape)
+    h, w = (float(v) for v in result_shape)
+    if intrinsics is None:
+        if not 0.0 < float(fov) < 180.0:
+            raise ValueError(f"fov {fov}: a horizontal field of view in degrees, inside (0, 180)")
+        f = (wr / 2.0) / math.tan(math.radians(float(fov)) / 2.0)
+        intrinsics = (f, f, wr / 2.0, hr / 2.0)
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    return np.array([fx * (w / wr), fy * (h / hr), cx * (w / wr), cy * (h / hr)], dtype=np.float64).astype(F32)
+
+
+def _valid_depth(d, depth_range):
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(d) & (d > F32(depth_range[0])) & (d < F32(depth_range[1]))
+
+
+def backproject_host(depth, intrinsics):
+    """-> X, Y, Z float32 [h, w]: Z = D[y, x], u = (float(x) + 0.5) - cx, X = (u * Z) / fx; Y likewise with cy, fy"""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    h, w = d.shape
+    fx, fy, cx, cy = (F32(v) for v in intrinsics)
+    u = (np.arange(w, dtype=F32) + F32(0.5)) - cx
+    v = (np.arange(h, dtype=F32) + F32(0.5)) - cy
+    with np.errstate(all="ignore"):
+        return (u[None, :] * d) / fx, (v[:, None] * d) / fy, d
+
+
+def color_bytes(v) -> np.ndarray:
+    """clamp(rint(v), 0, 255) as uint8: ties to even, NaN gives 0"""
+    with np.errstate(invalid="ignore"):
+        r = np.rint(np.asarray(v, dtype=F32))
+        return np.clip(np.where(np.isnan(r), F32(0), r), 0, 255).astype(np.uint8)
+
+
+def sample_indices(n_out: int, n_in: int) -> np.ndarray:
+    """the nearest sample of an axis of n_in values for each of n_out positions: ((2 i + 1) * n_in) // (2 * n_out)"""
+    return ((2 * np.arange(n_out, dtype=np.int64) + 1) * n_in) // (2 * n_out)
+
+
+def keep_mask_host(depth, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1) -> np.ndarray:
+    """the pixels of a depth map the point cloud keeps: valid (finite, lo < Z < hi), not a flying pixel (no valid in-frame
+    4-neighbour Zn with |Z - Zn| > edge_thr * min(Z, Zn); edge_thr <= 0: no filter; neighbours at full resolution) and on the
+    stride grid (y % stride == 0 and x % stride == 0)"""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    valid = _valid_depth(d, depth_range)
+    keep = valid.copy()
+    thr = F32(edge_thr)
+    if thr > 0:
+        for a, b in (((slice(None), slice(None, -1)), (slice(None), slice(1, None))), ((slice(None, -1), slice(None)), (slice(1, None), slice(None)))):
+            with np.errstate(all="ignore"):
+                edge = valid[a] & valid[b] & (np.abs(d[a] - d[b]) > thr * np.minimum(d[a], d[b]))
+            keep[a] &= ~edge
+            keep[b] &= ~edge
+    grid = np.zeros_like(keep)
+    grid[::int(stride), ::int(stride)] = True
+    return keep & grid
+
+
+def pointcloud_host(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1) -> np.ndarray:
+    """The specification of ``ops.pointcloud_pack`` for one frame: depth [h, w], image [3, hi, wi] (any size; nearest sample by
+    ``sample_indices``, byte = ``color_bytes(v * 255)``), intrinsics fx, fy, cx, cy of the depth map's grid -> the kept pixels'
+    vertices in row-major pixel order, a ``PLY_VERTEX`` array [N] (``.tobytes()``: the 15 N bytes of the cloud)"""
+    if int(stride) < 1:
+        raise ValueError(f"stride {stride} < 1")
+    X, Y, Z = backproject_host(depth, intrinsics)
+    img = np.asarray(image, dtype=F32)
+    h, w = Z.shape
+    keep = keep_mask_host(Z, depth_range, edge_thr, stride)
+    ys, xs = np.nonzero(keep)  # row-major
+    sy, sx = sample_indices(h, img.shape[1])[ys], sample_indices(w, img.shape[2])[xs]
+    out = np.empty((ys.size,), dtype=PLY_VERTEX)
+    out["x"], out["y"], out["z"] = X[ys, xs], Y[ys, xs], Z[ys, xs]
+    for c, name in enumerate(("red", "green", "blue")):
+        with np.errstate(all="ignore"):
+            out[name] = color_bytes(img[c, sy, sx] * F32(255))
+    return out
+
+
+def normal_map_host(depth, intrinsics, depth_range=(0.0, math.inf)) -> np.ndarray:
+    """The specification of ``ops.normal_rows`` for one frame -> uint8 [h, w, 3].  P = (X, Y, Z); Px = P[y, x + 1] - P[y, x - 1]
+    where both neighbours are valid and in frame, else the one-sided difference with the one that is (P[y, x + 1] - P or
+    P - P[y, x - 1]), else no normal; Py likewise along y.  n = cross(Px, Py) / sqrt((nx nx + ny ny) + nz nz), negated where
+    (nx X + ny Y) + nz Z > 0; a zero or non-finite length or a non-finite component gives no normal.  RGB =
+    ``color_bytes((n * 0.5 + 0.5) * 255)``, (0, 0, 0) for invalid pixels and pixels without a normal."""
+    X, Y, Z = backproject_host(depth, intrinsics)
+    P = np.stack([X, Y, Z])  # [3, h, w]
+    valid = _valid_depth(Z, depth_range)
+
+    def diff(axis):
+        nxt, prv = np.roll(P, -1, axis=axis), np.roll(P, 1, axis=axis)  # (the wrapped border is masked below)
+        v_nxt, v_prv = np.roll(valid, -1, axis=axis - 1), np.roll(valid, 1, axis=axis - 1)
+        edge = [slice(None), slice(None)]
+        edge[axis - 1] = -1
+        v_nxt[tuple(edge)] = False
+        edge[axis - 1] = 0
+        v_prv[tuple(edge)] = False
+        with np.errstate(all="ignore"):
+            g = np.where(v_nxt & v_prv, nxt - prv, np.where(v_nxt, nxt - P, P - prv))
+        return g, v_nxt | v_prv
+
+    (ux, uy, uz), has_x = diff(2)
+    (vx, vy, vz), has_y = diff(1)
+    with np.errstate(all="ignore"):
+        nx, ny, nz = uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx
+        length = np.sqrt((nx * nx + ny * ny) + nz * nz)
+        ok = valid & has_x & has_y & np.isfinite(length) & (length > 0)
+        nx, ny, nz = nx / length, ny / length, nz / length
+        ok &= np.isfinite(nx) & np.isfinite(ny) & np.isfinite(nz)
+        flip = ((nx * X + ny * Y) + nz * Z) > 0
+        rgb = np.stack([color_bytes((np.where(flip, -c, c) * F32(0.5) + F32(0.5)) * F32(255)) for c in (nx, ny, nz)], axis=-1)
+    rgb[~ok] = 0
+    return rgb
+
+
+def ply_header(n: int) -> bytes:
+    """the fixed header of a cloud of n vertices"""
+    return (f"ply\nformat binary_little_endian 1.0\nelement vertex {int(n)}\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n").encode("ascii")
+
+
+def ply_bytes(n: int, vertex_bytes) -> bytes:
+    """the PLY file of n vertices: the header, then the first 15 n bytes of ``vertex_bytes`` (``PLY_VERTEX`` records)"""
+    body = memoryview(vertex_bytes).cast("B")[:PLY_VERTEX.itemsize * int(n)]
+    if len(body) != PLY_VERTEX.itemsize * int(n):
+        raise ValueError(f"ply_bytes: {n} vertices need {PLY_VERTEX.itemsize * int(n)} bytes, got {len(body)}")
+    return ply_header(n) + bytes(body)
+
+
+def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True):
+    """the host route of ``OutputStage.submit_geometry``: <base>.ply and <base>_normal.png from the host specification"""
+    if ply:
+        v = pointcloud_host(depth, image, intrinsics, depth_range, edge_thr, stride)
+        with open(base + ".ply", "wb") as f:
+            f.write(ply_bytes(v.size, v.tobytes()))
+    if normals:
+        write_png8(base + "_normal.png", normal_map_host(depth, intrinsics, depth_range))
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # device functions
 # ------------------------------------------------------------------------------------------------------------------
 _LUTS = {}
@@ -236,13 +394,13 @@ class OutputStage:
         self.pool = ThreadPoolExecutor(max_workers=self.workers, thread_name_prefix="prv2-png")
         self.device_deflate = bool(device_deflate)
         self.stream = None
-        self.copy_stream = None  # device_deflate: the writer threads' D2H copies
-        self._slots = [dict(buf=None, sizes=None, futures=[]) for _ in range(self.depth)]
+        self.copy_stream = None  # device_deflate / point clouds: the writer threads' D2H copies
+        self._slots = [dict(buf=None, sizes=None, ply=None, ply_n=None, futures=[]) for _ in range(self.depth)]
         self._loose = []  # files queued from host rows (write_rows)
         self._next = 0
         self._error = None
         self._lock = threading.Lock()
-        self.bytes_d2h = 0  # bytes copied to the host so far: packed scanlines, or compressed streams and their sizes
+        self.bytes_d2h = 0  # bytes copied to the host so far: packed scanlines, or compressed streams and their sizes; vertex records and their counts
         self.files = 0
         os.makedirs(work_dir, exist_ok=True)
 
@@ -275,6 +433,30 @@ class OutputStage:
             data = png_bytes_from_stream(header, memoryview(host.numpy())[:nb])
             with open(path, "wb") as f:
                 f.write(data)
+        except BaseException as e:  # kept for flush()
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
+    def _write_ply(self, path, verts, count, event, host):
+        """wait for the frame's vertex count, copy exactly its 15 N bytes of ``verts`` (device uint8 [bound]) into the pinned
+        ``host`` on the copy stream, prepend the header, write"""
+        try:
+            event.synchronize()  # the count and pack kernels and the copy of the count
+            n = int(count[0])
+            nb = PLY_VERTEX.itemsize * n
+            if nb:
+                with torch.cuda.device(verts.device), torch.cuda.stream(self.copy_stream):
+                    verts.record_stream(self.copy_stream)
+                    host[:nb].copy_(verts[:nb], non_blocking=True)
+                    done = torch.cuda.Event()
+                    done.record(self.copy_stream)
+                done.synchronize()
+            with self._lock:
+                self.bytes_d2h += nb
+            with open(path, "wb") as f:
+                f.write(ply_header(n))
+                f.write(memoryview(host.numpy())[:nb])
         except BaseException as e:  # kept for flush()
             with self._lock:
                 if self._error is None:
@@ -382,6 +564,46 @@ class OutputStage:
             for t in (result, coarse):
                 if t is not None:
                     t.record_stream(self.stream)
+
+    @torch.no_grad()
+    def submit_geometry(self, base: str, result: torch.Tensor, image_hr, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1,
+                        ply=True, normals=True):
+        """the geometry of one frame, from the device map: <base>.ply (``ply``: the point cloud of ``pointcloud_host``, coloured
+        from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size) and <base>_normal.png (``normals``: the map of
+        ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``).
+        ``intrinsics``: fx, fy, cx, cy of the RESULT's grid (``camera_intrinsics``).  The vertex buffer is sized for the bound
+        (15 bytes per strided pixel); only the frame's count goes to pinned memory with an event, and the file's writer thread
+        copies exactly 15 N bytes on the copy stream."""
+        from . import ops
+        dev = result.device
+        slot = self._begin(dev)
+        if ply and self.copy_stream is None:
+            self.copy_stream = torch.cuda.Stream(dev)
+        with torch.cuda.device(dev), torch.cuda.stream(self.stream):
+            d = _frames(result)
+            h, w = d.shape[1:]
+            if normals:
+                self._stage(slot, [(base + "_normal.png", w, h, 3, ops.normal_rows(d, intrinsics, depth_range))])
+            if ply:
+                img = torch.as_tensor(image_hr)
+                if img.dim() == 4 and img.shape[0] == 1:
+                    img = img[0]
+                img = img.to(dev, torch.float32, non_blocking=True)
+                verts, counts = ops.pointcloud_pack(d, img, intrinsics, depth_range, edge_thr, stride)
+                if slot["ply"] is None or slot["ply"].numel() < verts.shape[1]:
+                    slot["ply"] = torch.empty((int(verts.shape[1]),), dtype=torch.uint8, pin_memory=True)
+                if slot["ply_n"] is None:
+                    slot["ply_n"] = torch.empty((1,), dtype=torch.int64, pin_memory=True)
+                slot["ply_n"].copy_(counts, non_blocking=True)
+                with self._lock:
+                    self.bytes_d2h += 8
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                self.files += 1
+                slot["futures"].append(self.pool.submit(self._write_ply, base + ".ply", verts[0], slot["ply_n"], ev, slot["ply"]))
+            result.record_stream(self.stream)
+            if isinstance(image_hr, torch.Tensor) and image_hr.is_cuda:
+                image_hr.record_stream(self.stream)
 
     @torch.no_grad()
     def submit_pseudo_label(self, base: str, depth, uncertainty, count_map, n_tiles: int, count_thr: float, cmap="magma_r"):

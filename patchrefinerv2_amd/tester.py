@@ -6,6 +6,9 @@ Tester.generate_pl  estimator/tester/tester.py:132-181 (pseudo labels: depth, un
 the GPU, deflate on a writer pool; the default is the host route below.  ``runner_info.device_deflate`` (--device-deflate, needs
 device_output) makes the zlib streams on the GPU as well: the files hold the device route's pixels, but not its bytes (the deflate
 stream differs from zlib's).
+``runner_info.save_ply`` / ``save_normals`` (--save-ply / --save-normals, with ``save``) add the frame's geometry: <name>.ply (a
+binary point cloud of the result map, coloured from the image) and <name>_normal.png (its surface normals) -- from the device map
+with the output stage, from output.py's host specification otherwise; the same files either way.
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) and <name>_edge.png (Canny edges of the log depth, widened by one pixel,
 :98-106; metrics.depth_edges) -- colour maps and metrics in metrics.py, PNGs through a dependency-free encoder (output.py).
@@ -165,6 +168,19 @@ class Tester:
         cityscapes = getattr(self.dataloader, "dataset_name", "") == "cityscapes"
         return ("magma_r" if pseudo_label or cityscapes else "Spectral"), (0, 100)
 
+    def _geometry(self, result, image_raw_shape):
+        """the keyword arguments of ``submit_geometry`` / ``write_geometry_host`` for a result map, None without ``save_ply`` /
+        ``save_normals``: the camera of ``runner_info.intrinsics`` (fx fy cx cy in pixels of the raw grid) or ``runner_info.fov``
+        (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``"""
+        info = self.runner_info
+        ply, normals = bool(getattr(info, "save_ply", False)), bool(getattr(info, "save_normals", False))
+        if not (info.save and (ply or normals)):
+            return None
+        from .output import camera_intrinsics
+        k = camera_intrinsics(image_raw_shape, result.shape[-2:], getattr(info, "intrinsics", None), getattr(info, "fov", None) or 60.0)
+        return dict(intrinsics=k, depth_range=tuple(getattr(info, "ply_depth_range", None) or (0.0, float("inf"))),
+                    edge_thr=float(getattr(info, "ply_edge_thr", 0.05)), stride=int(getattr(info, "ply_stride", 1)), ply=ply, normals=normals)
+
     def _entry(self, item, result, score=None, **extra):
         """one frame's result entry.  ``mean``: a host map's fp32 mean, a device map's float64 sum on the device (equal within that
         sum's rounding).  ``score``: the map the dataset scores when the item carries ground truth"""
@@ -184,6 +200,9 @@ class Tester:
             if not result.is_cuda:
                 raise ValueError("device_output: the model returned a host map")
             stage.submit_frame(base, result, coarse, image_raw_shape, cmap=cmap, percentiles=(lo, hi))
+            geo = self._geometry(result, image_raw_shape)
+            if geo is not None:
+                stage.submit_geometry(base, result, item["image_hr"], **geo)
             results.append(self._entry(item, result, score=result))
             return
         score = result  # (a device map is scored where it is)
@@ -198,6 +217,11 @@ class Tester:
             if coarse is not None:  # absent for BaselinePretrain
                 coarse_map = F.interpolate(coarse.cpu(), tuple(image_raw_shape), mode="bilinear")
                 write_png8(base + "_coarse.png", np.ascontiguousarray(colorize(coarse_map, cmap="Spectral", vminp=0, vmaxp=100)[:, :, :3]))
+            geo = self._geometry(result, image_raw_shape)
+            if geo is not None:  # the host route of the geometry export: the host specification itself
+                from .output import write_geometry_host
+                image = torch.as_tensor(item["image_hr"]).cpu().float().numpy()
+                write_geometry_host(base, result.squeeze().numpy(), image.reshape(3, *image.shape[-2:]), geo.pop("intrinsics"), **geo)
         results.append(self._entry(item, result, score=score))
 
     @torch.no_grad()

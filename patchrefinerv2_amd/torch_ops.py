@@ -48,7 +48,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # scale-and-shift-invariant evaluation: the fits, the SSI scores and the error sums of the aligned prediction
        "ssi_metrics",
        # sparsification curves (AUSE / AURG) of a per-pixel uncertainty
-       "sparsify")
+       "sparsify",
+       # geometry export: PLY vertex records and surface-normal scanlines
+       "pointcloud_pack", "normal_rows")
 _loaded = False
 
 

@@ -1,4 +1,4 @@
-"""What the evaluation benches share (bench_u4k_eval, bench_general_gt, bench_eth_eval, bench_ssi_eval, bench_uncert_eval): the two
+"""What the evaluation benches share (bench_u4k_eval, bench_general_gt, bench_eth_eval, bench_ssi_eval, bench_uncert_eval, bench_geometry): the two
 per-call measurements, the timed Tester run on the flagship workload, and the runner that gives every GPU step a process of its own.
 The package is imported inside the functions: a tool decides first which tree's package it measures (``sys.path``)."""
 from __future__ import annotations
@@ -67,11 +67,11 @@ def workload_model():
     return w, model
 
 
-def timed_maps_s(model, ds, w, n_maps, method="run", **kw):
+def timed_maps_s(model, ds, w, n_maps, method="run", info=None, **kw):
     """``Tester.<method>`` over ``ds`` with the workload's arguments, once to warm up (kernels, allocator, hipGraphs, page cache) and once
-    timed -> (maps/s, the timed call's results, the Tester)"""
+    timed -> (maps/s, the timed call's results, the Tester).  ``info``: the RunnerInfo (default: one process, nothing saved)"""
     from patchrefinerv2_amd.tester import RunnerInfo, Tester
-    t = Tester(None, RunnerInfo(rank=0, world_size=1), ds, model)
+    t = Tester(None, info or RunnerInfo(rank=0, world_size=1), ds, model)
 
     def run():
         return getattr(t, method)(cai_mode=w["mode"], image_raw_shape=w["raw"], patch_split_num=w["split"], seed=621, **kw)

@@ -10,6 +10,9 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--generate-pl [--count-thr T]``: Tester.generate_pl instead of run -- pseudo labels with per-pixel uncertainty and tile counts.
 ``--device-output [--output-workers N]``: with ``--save``, the output files' pixels are produced on the GPU and written by a thread pool.
 ``--device-deflate``: with ``--device-output``, the files' zlib streams are made on the GPU too (same pixels, different file bytes).
+``--save-ply`` / ``--save-normals``: with ``--save``, <name>.ply (binary little-endian point cloud of the result map, coloured from the image)
+and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`` (pixels of the --image-raw-shape grid) or ``--fov DEG``
+(horizontal, default 60); ``--ply-stride S``, ``--ply-edge-thr T`` (flying-pixel filter, <= 0 off), ``--ply-depth-range LO HI``.
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
 ``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
@@ -131,10 +134,30 @@ def main():
                     help="with --device-output: deflate the scanlines on the GPU as well (csrc/deflate.hip): only compressed bytes are copied "
                          "to the host; the files hold the same pixels as --device-output's, their bytes differ (another deflate stream)")
     ap.add_argument("--output-workers", type=int, default=8, metavar="N", help="--device-output: writer threads (at most 16)")
+    ap.add_argument("--save-ply", action="store_true",
+                    help="with --save: <name>.ply, a binary little-endian point cloud of the result map (float x y z, uchar red green blue per "
+                         "kept pixel, row-major; pinhole camera, x right, y down, z forward), made on the GPU with --device-output")
+    ap.add_argument("--save-normals", action="store_true", help="with --save: <name>_normal.png, the camera-facing surface normals as 8-bit RGB (n * 0.5 + 0.5)")
+    ap.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("FX", "FY", "CX", "CY"),
+                    help="--save-ply / --save-normals: the camera in pixels of the --image-raw-shape grid (scaled to the result's shape)")
+    ap.add_argument("--fov", type=float, default=None, metavar="DEG",
+                    help="--save-ply / --save-normals without --intrinsics: horizontal field of view (default 60): fx = fy = (W / 2) / tan(fov / 2), "
+                         "principal point at the centre")
+    ap.add_argument("--ply-stride", type=int, default=1, metavar="S", help="--save-ply: keep the pixels with y %% S == 0 and x %% S == 0")
+    ap.add_argument("--ply-edge-thr", type=float, default=0.05, metavar="T",
+                    help="--save-ply: drop a pixel when a valid 4-neighbour differs by more than T x the nearer depth (flying pixels); <= 0: off")
+    ap.add_argument("--ply-depth-range", nargs=2, type=float, default=[0.0, float("inf")], metavar=("LO", "HI"),
+                    help="--save-ply / --save-normals: a pixel is valid when its depth is finite and LO < depth < HI")
     ap.add_argument("--benchmark-iters", nargs=2, type=int, default=[20, 50], metavar=("WARMUP", "TOTAL"))
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
+    if (args.save_ply or args.save_normals) and not args.save:
+        ap.error("--save-ply / --save-normals need --save (they add files to the frames it writes)")
+    if args.ply_stride < 1:
+        ap.error(f"--ply-stride {args.ply_stride}: at least 1")
+    if args.intrinsics is not None and args.fov is not None:
+        ap.error("--intrinsics and --fov both given: the camera comes from one of them")
     if args.uncert_metrics and not args.generate_pl:
         ap.error("--uncert-metrics needs --generate-pl (it scores the pseudo label's uncertainty)")
 
@@ -167,7 +190,9 @@ def main():
 
     dataset = DATASETS.build(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
-                        device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate)
+                        device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate,
+                        save_ply=args.save_ply, save_normals=args.save_normals, intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
+                        ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range))
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
         for r in tester.run_consistency(image_raw_shape=args.image_raw_shape, patch_split_num=args.patch_split_num, overlap=args.consistency):
