@@ -24,7 +24,7 @@ from . import lib as L
 from .lib import ACT_GELU, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, ACT_SOFTPLUS, PREC_F32  # noqa: F401
 
 
-# How the host mirror reaches the kernels: "torch" = through the PyTorch-ROCm custom ops torch.ops.prv2.* (csrc/torch_ops.cpp ->
+# How the host mirror (frame.py's drivers, the networks under models.py) reaches the kernels: "torch" = through the PyTorch-ROCm custom ops torch.ops.prv2.* (csrc/torch_ops.cpp ->
 # libprv2_torch.so: at::Tensor in / out on torch's current stream; ``_tops()``), "ctypes" = straight through the C ABI (lib.py;
 # ``_c``).  Every entry point a frame uses exists on both routes; same kernels, same results bit for bit (tests/test_hip_models.py::
 # test_models_through_torch_custom_ops) and the same profiler records (tests/test_ops_routes_gpu.py).  The wrappers read DISPATCH when

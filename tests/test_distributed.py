@@ -1,4 +1,4 @@
-"""CPU, world_size 2 over gloo: the patch-sharded mode's host / exchange logic -- the tile-to-rank layout with its gather
+"""CPU, world_size 2 over gloo: the patch-sharded mode's host / exchange logic (patchrefinerv2_amd/frame.py) -- the tile-to-rank layout with its gather
 groups, the asynchronous exchange of the per-rank prediction stacks (all-gather or gather-to-rank-0) and the permutation back
 to tile order reproduce the single-process ordering; the tile plan tensor is rank 0's on every rank; Tester's cross-rank
 result collection keeps the dataset order.  (The sharded FORWARD itself is emulated on one GPU in tests/test_hip_models.py
