@@ -909,6 +909,53 @@ int prv2_pointcloud_pack(const float* depth, const float* image, int32_t n, int3
 int prv2_normal_rows(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float fy, float cx, float cy, float lo, float hi,
                      uint8_t* rows, int64_t rows_fstride, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh export (csrc/pointcloud.hip): the faces of a triangle mesh over the point cloud's vertices, from the connectivity the pixel
+ * grid already holds.  Not in the reference.  Fixed launch counts, no host synchronisation, no atomics: the same input gives the
+ * same bytes on every call.  Added without an ABI bump (additive).  The host specification is mesh_faces_host of
+ * patchrefinerv2_amd/output.py, which the kernels equal byte for byte.
+ *   vertices   the kept pixels of "Geometry export" in row-major order; a face index is a vertex's rank in that order
+ *   grid       node (gy, gx) is pixel (gy * stride, gx * stride), gh = ceil(h / stride), gw = ceil(w / stride)
+ *   cell       (gy, gx) with gy + 1 < gh and gx + 1 < gw; corners a = (gy, gx), b = (gy, gx + 1), c = (gy + 1, gx), d = (gy + 1, gx + 1)
+ *   joined     two kept corners p, q: edge_thr <= 0, or not (|Zp - Zq| > edge_thr * min(Zp, Zq)) (the fp32 operations of "flying")
+ *   diagonal   four corners kept: a-d if |Za - Zd| <= |Zb - Zc|, else b-c; three kept: the diagonal whose two ends are kept;
+ *              fewer: the cell has no face
+ *   candidates a-d: (a, c, d) then (a, d, b); b-c: (a, c, b) then (b, c, d); a candidate is a face when its three corners are kept
+ *              and its three edges are joined
+ *   order      cells row-major, inside a cell the first candidate first; with x right, y down, z forward every face looks at the
+ *              camera (cross(P1 - P0, P2 - P0) has negative z on a fronto-parallel plane)
+ *   record     uchar 3, then the three vertex indices as little-endian int32: 13 bytes
+ * ------------------------------------------------------------------------------------------ */
+
+/* bytes of workspace prv2_mesh_index / _count / _pack need for n frames of h x w at a stride: the index map int32 [n, gh, gw], then
+ * one int32 per run of cells a block owns (-1 for bad arguments) */
+int64_t prv2_mesh_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t stride);
+
+/* 26 * (gh - 1) * (gw - 1): the bytes of a frame's face records when every cell has two faces; 0 for a grid of one row or one
+ * column (-1 for bad arguments).  Past 2^31 for the largest frames: every byte offset is an int64. */
+int64_t prv2_mesh_bound(int32_t h, int32_t w, int32_t stride);
+
+/* the index map: workspace[f][gy][gx] (int32, at the start of ``workspace``) = the rank of pixel (gy * stride, gx * stride) among
+ * frame f's kept pixels in row-major order -- the vertex prv2_pointcloud_pack writes for it -- or -1 where it is not kept.  Same
+ * depth, range, edge_thr and stride as the prv2_pointcloud_count call that filled ``cloud_workspace`` (its exclusive offsets are
+ * read; the camera is not needed).  workspace: DEVICE, 4-byte aligned, prv2_mesh_workspace_bytes(n, h, w, stride). */
+int prv2_mesh_index(const float* depth, int32_t n, int32_t h, int32_t w, float lo, float hi, float edge_thr, int32_t stride,
+                    const void* cloud_workspace, int64_t cloud_workspace_bytes, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* counts: DEVICE int64 [n] = M, the faces of each frame, by the rule above.  ``workspace`` holds prv2_mesh_index's map and leaves
+ * with the exclusive offsets of every block's run of cells as well, in block order (a block counts its run, the one-block scan of
+ * prv2_pointcloud_count adds the counts up) -- what prv2_mesh_pack reads.  Same depth, edge_thr and stride as that call. */
+int prv2_mesh_count(const float* depth, int32_t n, int32_t h, int32_t w, float edge_thr, int32_t stride, int64_t* counts, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
+/* the face records in cell order, frame f's at faces[f * faces_fstride + 13 * k], k < M (the offset computed in int64).  Same
+ * arguments as the prv2_mesh_count call that filled ``workspace``.  faces: DEVICE uint8, no alignment asked of the pointer or of
+ * faces_fstride >= prv2_mesh_bound(h, w, stride).  Exactly the 13 * M bytes of a frame are written and nothing else is touched: a
+ * block stores the ragged ends of its byte range with byte stores and the 16-byte-aligned interior with 16-byte stores; no byte is
+ * read back. */
+int prv2_mesh_pack(const float* depth, int32_t n, int32_t h, int32_t w, float edge_thr, int32_t stride, const void* workspace,
+                   int64_t workspace_bytes, uint8_t* faces, int64_t faces_fstride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

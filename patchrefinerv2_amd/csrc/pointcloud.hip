@@ -2,7 +2,8 @@
 // of a binary PLY point cloud (float x, y, z + uchar red, green, blue: 15 bytes, kept pixels in row-major order) and the PNG scanlines
 // of a surface-normal map, of B >= 1 frames [n, h, w].  Fixed launch counts, no host synchronisation, no atomics: the same input gives
 // the same bytes on every call.  All three kernels are streaming passes (one read of the depth map and, for the cloud, one nearest
-// sample of the image per kept pixel).
+// sample of the image per kept pixel).  The faces of a triangle mesh over the cloud's vertices (include/prv2.h "Mesh export") are made the
+// same way from the grid's cells: an index map, a count and a pack pass.
 //
 // Arithmetic contract (the numpy float32 restatement is output.py: pointcloud_host / normal_map_host; bit for bit):
 //   - the file is built with -ffp-contract=off; every fp32 operation is written with __f*_rn (IEEE, one rounding each, in the order
@@ -135,6 +136,21 @@ __global__ void __launch_bounds__(256) cloud_scan_kernel(int32_t* __restrict__ c
   }
 }
 
+// A block's store of the LDS image buf[shift + i] to dst[i], i in [0, nb), where shift = dst mod 16 (so dst - shift is 16-byte aligned):
+// the bytes before the first and from the last 16-byte boundary one by one, the aligned interior as 16-byte words
+__device__ __forceinline__ void store_ragged(uint8_t* __restrict__ dst, const uint4* buf4, int shift, int nb, int tid) {
+  const uint8_t* buf = (const uint8_t*)buf4;
+  const int head = (16 - shift) & 15;              // bytes before the first 16-byte boundary
+  const int h_end = head < nb ? head : nb;
+  const int wide = (nb - h_end) / 16;              // aligned 16-byte words of the interior
+  const int t_beg = h_end + 16 * wide;
+  if (tid < h_end) dst[tid] = buf[shift + tid];
+  uint4* dst4 = (uint4*)(dst + h_end);
+  const uint4* src4 = buf4 + (shift + h_end) / 16;
+  for (int i = tid; i < wide; i += 256) dst4[i] = src4[i];
+  if (tid < nb - t_beg) dst[t_beg + tid] = buf[shift + t_beg + tid];
+}
+
 // The records of every run.  The block ranks its kept pixels in pixel order (ballot + popcount inside a wave, the (step, wave) segment
 // totals through LDS), builds the records in LDS and stores its byte range [15 off, 15 (off + cnt)) of the frame's vertex buffer.  That
 // range starts and ends at any byte alignment and the dwords at its two ends may belong to the neighbouring runs as well: the LDS image
@@ -194,17 +210,177 @@ __global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, const floa
     rec[14] = (uint8_t)byte_of(__fmul_rn(c[2 * plane], 255.0f));
   }
   __syncthreads();
-  // buf[shift + i] <-> dst[i], i in [0, nb); dst - shift is 16-byte aligned
-  const int nb = kRecord * cnt;
-  const int head = (16 - shift) & 15;              // bytes before the first 16-byte boundary
-  const int h_end = head < nb ? head : nb;
-  const int wide = (nb - h_end) / 16;              // aligned 16-byte words of the interior
-  const int t_beg = h_end + 16 * wide;
-  if (tid < h_end) dst[tid] = buf[shift + tid];
-  uint4* dst4 = (uint4*)(dst + h_end);
-  const uint4* src4 = buf4 + (shift + h_end) / 16;
-  for (int i = tid; i < wide; i += 256) dst4[i] = src4[i];
-  if (tid < nb - t_beg) dst[t_beg + tid] = buf[shift + t_beg + tid];
+  store_ragged(dst, buf4, shift, kRecord * cnt, tid);
+}
+
+// ---- triangle mesh (include/prv2.h "Mesh export"; the numpy restatement is output.py: mesh_faces_host) -------------------------------
+// The vertices are the cloud's.  Grid node (gy, gx) is pixel (gy * stride, gx * stride); cell (gy, gx), gy + 1 < gh, gx + 1 < gw, has the
+// corners a = (gy, gx), b = (gy, gx + 1), c = (gy + 1, gx), d = (gy + 1, gx + 1) and emits up to two faces.  Cells are ranked like pixels:
+// a block owns a run of kRun cells in row-major order, a lane has 0, 1 or 2 faces (two ballots).
+constexpr int kFace = 13;  // bytes of a face record: uchar 3 + three int32
+
+struct MeshArgs {
+  const float* depth;    // [n, h, w]
+  const int32_t* index;  // [n, gh, gw]: the vertex of a node, -1: not kept
+  float thr;             // an edge is joined unless |Zp - Zq| > thr * min(Zp, Zq) (<= 0: always joined)
+  int32_t h, w, stride, gh, gw;
+  int32_t ncell;         // (gh - 1) * (gw - 1)
+  int32_t nrun;          // blocks (runs of cells) per frame
+};
+
+// index[f][gy][gx] of every node: the rank of its pixel among the frame's kept pixels (cloud_pack_kernel's order), -1 where not kept
+__global__ void __launch_bounds__(256) mesh_index_kernel(CloudArgs a, const int32_t* __restrict__ offsets, int32_t* __restrict__ index, int32_t gh,
+                                                         int32_t gw) {
+  __shared__ int32_t seg[kSegs];
+  const int tid = threadIdx.x, wave = tid >> 6, f = blockIdx.y;
+  const int64_t hw = (int64_t)a.h * a.w, p0 = (int64_t)blockIdx.x * kRun;
+  const float* d = a.depth + (int64_t)f * hw;
+  int32_t rank[kRounds];  // rank inside the wave's segment, -1: not kept
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    float z;
+    int y, x, below, total;
+    const bool k = step_keep(a, d, p0 + r * 256 + tid, hw, z, y, x, below, total);
+    rank[r] = k ? below : -1;
+    if ((tid & 63) == 0) seg[r * 4 + wave] = total;
+  }
+  __syncthreads();
+  if (tid == 0) {  // exclusive prefix of the segment totals
+    int32_t run = 0;
+    for (int s = 0; s < kSegs; ++s) {
+      const int32_t v = seg[s];
+      seg[s] = run;
+      run += v;
+    }
+  }
+  __syncthreads();
+  const int32_t base = offsets[(int64_t)f * a.nblk + blockIdx.x];
+  int32_t* idx = index + (int64_t)f * gh * gw;
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    const int64_t p = p0 + r * 256 + tid;
+    if (p >= hw) continue;
+    const int y = (int)(p / a.w), x = (int)(p - (int64_t)y * a.w);
+    if (y % a.stride != 0 || x % a.stride != 0) continue;
+    idx[(int64_t)(y / a.stride) * gw + x / a.stride] = rank[r] < 0 ? -1 : base + seg[r * 4 + wave] + rank[r];
+  }
+}
+
+__device__ __forceinline__ bool joined(float thr, float zp, float zq) {
+  return !(thr > 0.0f) || !(fabsf(__fsub_rn(zp, zq)) > __fmul_rn(thr, fminf(zp, zq)));
+}
+
+// the faces of cell c of a frame (idx, d: the frame's index map and depth) -> their number; tri: their vertices, first candidate first.
+// Four corners kept: the diagonal a-d if |Za - Zd| <= |Zb - Zc|, else b-c; three: the diagonal whose ends are kept; fewer: no face.
+// a-d: (a, c, d) then (a, d, b); b-c: (a, c, b) then (b, c, d); a candidate needs its three corners kept and its three edges joined.
+__device__ __forceinline__ int cell_faces(const MeshArgs& m, const float* __restrict__ d, const int32_t* __restrict__ idx, int c, int32_t (&tri)[6]) {
+  const int gy = c / (m.gw - 1), gx = c - gy * (m.gw - 1);
+  const int32_t* i0 = idx + (int64_t)gy * m.gw + gx;
+  const int32_t ia = i0[0], ib = i0[1], ic = i0[m.gw], id = i0[m.gw + 1];
+  const int kept = (ia >= 0) + (ib >= 0) + (ic >= 0) + (id >= 0);
+  if (kept < 3) return 0;
+  const int64_t down = (int64_t)m.stride * m.w;
+  const float* z0 = d + gy * down + (int64_t)gx * m.stride;
+  const float za = z0[0], zb = z0[m.stride], zc = z0[down], zd = z0[down + m.stride];  // (a corner's Z counts only where it is kept)
+  const bool ad = kept == 4 ? fabsf(__fsub_rn(za, zd)) <= fabsf(__fsub_rn(zb, zc)) : (ia >= 0 && id >= 0);
+  const bool ac = ia >= 0 && ic >= 0 && joined(m.thr, za, zc), cd = ic >= 0 && id >= 0 && joined(m.thr, zc, zd);
+  const bool ab = ia >= 0 && ib >= 0 && joined(m.thr, za, zb), bd = ib >= 0 && id >= 0 && joined(m.thr, zb, zd);
+  const bool dg = ad ? joined(m.thr, za, zd) : joined(m.thr, zb, zc);  // (both ends of the chosen diagonal are kept)
+  const bool first = dg && ac && (ad ? cd : ab), second = dg && bd && (ad ? ab : cd);
+  const int32_t f0[3] = {ia, ic, ad ? id : ib}, f1[3] = {ad ? ia : ib, ad ? id : ic, ad ? ib : id};
+#pragma unroll
+  for (int v = 0; v < 3; ++v) {
+    tri[v] = first ? f0[v] : f1[v];
+    tri[3 + v] = f1[v];
+  }
+  return (int)first + (int)second;
+}
+
+// One step of a block over its run of cells: lane t evaluates cell c.  Returns the cell's faces; ``below``: faces of lower lanes of this
+// wave, ``total``: of the whole wave.
+__device__ __forceinline__ int step_faces(const MeshArgs& m, const float* __restrict__ d, const int32_t* __restrict__ idx, int64_t c,
+                                          int32_t (&tri)[6], int& below, int& total) {
+  const int k = c < m.ncell ? cell_faces(m, d, idx, (int)c, tri) : 0;
+  const unsigned long long b1 = __ballot(k >= 1), b2 = __ballot(k >= 2), lower = (1ull << (threadIdx.x & 63)) - 1ull;
+  below = __popcll(b1 & lower) + __popcll(b2 & lower);
+  total = __popcll(b1) + __popcll(b2);
+  return k;
+}
+
+// faces of every run of cells: counts[f][run]
+__global__ void __launch_bounds__(256) mesh_count_kernel(MeshArgs m, int32_t* __restrict__ counts) {
+  __shared__ int32_t seg[kSegs];
+  const int tid = threadIdx.x, wave = tid >> 6, f = blockIdx.y;
+  const int64_t c0 = (int64_t)blockIdx.x * kRun;
+  const float* d = m.depth + (int64_t)f * m.h * m.w;
+  const int32_t* idx = m.index + (int64_t)f * m.gh * m.gw;
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    int32_t tri[6];
+    int below, total;
+    step_faces(m, d, idx, c0 + r * 256 + tid, tri, below, total);
+    if ((tid & 63) == 0) seg[r * 4 + wave] = total;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int32_t c = 0;
+    for (int s = 0; s < kSegs; ++s) c += seg[s];
+    counts[(int64_t)f * m.nrun + blockIdx.x] = c;
+  }
+}
+
+// The face records of every run of cells, as cloud_pack_kernel makes the vertex records: ranked in cell order, built in LDS at
+// LDS offset == global address (mod 16), stored as the byte range [13 off, 13 (off + cnt)) of the frame's face buffer.  Byte offsets
+// are int64: 13 * M passes 2^31 for the largest frames.
+__global__ void __launch_bounds__(256) mesh_pack_kernel(MeshArgs m, const int32_t* __restrict__ offsets, uint8_t* __restrict__ out,
+                                                        int64_t out_fstride) {
+  __shared__ uint4 buf4[(kRun * 2 * kFace + 16 + 15) / 16];
+  __shared__ int32_t seg[kSegs + 1];
+  uint8_t* buf = (uint8_t*)buf4;
+  const int tid = threadIdx.x, wave = tid >> 6, f = blockIdx.y;
+  const int64_t c0 = (int64_t)blockIdx.x * kRun;
+  const float* d = m.depth + (int64_t)f * m.h * m.w;
+  const int32_t* idx = m.index + (int64_t)f * m.gh * m.gw;
+  int32_t tri[kRounds][6];
+  int32_t faces[kRounds], rank[kRounds];  // the cell's faces and the rank of its first one inside the wave's segment
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+    int total;
+    faces[r] = step_faces(m, d, idx, c0 + r * 256 + tid, tri[r], rank[r], total);
+    if ((tid & 63) == 0) seg[r * 4 + wave] = total;
+  }
+  __syncthreads();
+  if (tid == 0) {  // exclusive prefix of the segment totals; seg[kSegs] = the run's count
+    int32_t run = 0;
+    for (int s = 0; s < kSegs; ++s) {
+      const int32_t v = seg[s];
+      seg[s] = run;
+      run += v;
+    }
+    seg[kSegs] = run;
+  }
+  __syncthreads();
+  const int32_t cnt = seg[kSegs];
+  if (cnt == 0) return;
+  uint8_t* dst = out + (int64_t)f * out_fstride + (int64_t)kFace * offsets[(int64_t)f * m.nrun + blockIdx.x];
+  const int shift = (int)((uintptr_t)dst & 15);
+#pragma unroll
+  for (int r = 0; r < kRounds; ++r) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (j >= faces[r]) continue;
+      uint8_t* rec = buf + shift + kFace * (seg[r * 4 + wave] + rank[r] + j);
+      rec[0] = 3;
+#pragma unroll
+      for (int v = 0; v < 3; ++v) {
+        const uint32_t word = (uint32_t)tri[r][3 * j + v];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) rec[1 + 4 * v + b] = (uint8_t)(word >> (8 * b));
+      }
+    }
+  }
+  __syncthreads();
+  store_ragged(dst, buf4, shift, kFace * cnt, tid);
 }
 
 // the surface normal of a pixel as RGB scanline bytes; pixels without a normal are (0, 0, 0)
@@ -289,6 +465,33 @@ static CloudArgs cloud_args(const float* depth, int h, int w, float fx, float fy
   return a;
 }
 
+static int64_t mesh_cells(int h, int w, int stride) { return (cdiv(h, stride) - 1) * (cdiv(w, stride) - 1); }
+
+static int check_mesh(const char* name, const float* depth, int n, int h, int w, int stride, const void* workspace, int64_t workspace_bytes) {
+  PRV2_REQUIRE(depth != nullptr, "%s: null pointer (depth)", name);
+  if (check_map(name, n, h, w)) return 1;
+  PRV2_REQUIRE(stride >= 1, "%s: stride %d < 1", name, stride);
+  PRV2_REQUIRE(workspace != nullptr, "%s: null workspace", name);
+  PRV2_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: the workspace must be 4-byte aligned", name);
+  PRV2_REQUIRE(workspace_bytes >= prv2_mesh_workspace_bytes(n, h, w, stride), "%s: workspace of %lld bytes < %lld (prv2_mesh_workspace_bytes)", name,
+               (long long)workspace_bytes, (long long)prv2_mesh_workspace_bytes(n, h, w, stride));
+  return 0;
+}
+
+// the mesh workspace: the index map int32 [n, gh, gw], then the face counts / offsets of the runs of cells int32 [n, nrun]
+static MeshArgs mesh_args(const float* depth, int n, int h, int w, float thr, int stride, void* workspace, int32_t** runs) {
+  MeshArgs m{};
+  m.depth = depth;
+  m.index = (const int32_t*)workspace;
+  m.thr = thr;
+  m.h = h, m.w = w, m.stride = stride;
+  m.gh = (int32_t)cdiv(h, stride), m.gw = (int32_t)cdiv(w, stride);
+  m.ncell = (int32_t)mesh_cells(h, w, stride);
+  m.nrun = (int32_t)cdiv(m.ncell, kRun);
+  *runs = (int32_t*)workspace + (int64_t)n * m.gh * m.gw;
+  return m;
+}
+
 }  // namespace
 }  // namespace prv2
 
@@ -328,6 +531,58 @@ extern "C" int prv2_pointcloud_pack(const float* depth, const float* image, int3
   const CloudArgs a = cloud_args(depth, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride);
   hipLaunchKernelGGL(cloud_pack_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, image, ih, iw,
                      (const int32_t*)workspace, vertices, vertices_fstride);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int64_t prv2_mesh_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t stride) {
+  if (prv2_pointcloud_workspace_bytes(n, h, w) < 0 || stride < 1) return -1;
+  return (int64_t)n * (cdiv(h, stride) * cdiv(w, stride) + cdiv(mesh_cells(h, w, stride), kRun)) * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int64_t prv2_mesh_bound(int32_t h, int32_t w, int32_t stride) {
+  if (h < 1 || w < 1 || stride < 1) return -1;
+  return 2 * kFace * mesh_cells(h, w, stride);
+}
+
+extern "C" int prv2_mesh_index(const float* depth, int32_t n, int32_t h, int32_t w, float lo, float hi, float edge_thr, int32_t stride,
+                               const void* cloud_workspace, int64_t cloud_workspace_bytes, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* name = "mesh_index";
+  if (check_mesh(name, depth, n, h, w, stride, workspace, workspace_bytes)) return 1;
+  PRV2_REQUIRE(cloud_workspace != nullptr && ((uintptr_t)cloud_workspace & 3) == 0, "%s: the cloud's workspace: null or not 4-byte aligned", name);
+  PRV2_REQUIRE(cloud_workspace_bytes >= prv2_pointcloud_workspace_bytes(n, h, w), "%s: cloud workspace of %lld bytes < %lld (prv2_pointcloud_workspace_bytes)",
+               name, (long long)cloud_workspace_bytes, (long long)prv2_pointcloud_workspace_bytes(n, h, w));
+  const CloudArgs a = cloud_args(depth, h, w, 1.0f, 1.0f, 0.0f, 0.0f, lo, hi, edge_thr, stride);  // (the keep predicate does not read the camera)
+  hipLaunchKernelGGL(mesh_index_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, (const int32_t*)cloud_workspace,
+                     (int32_t*)workspace, (int32_t)cdiv(h, stride), (int32_t)cdiv(w, stride));
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_mesh_count(const float* depth, int32_t n, int32_t h, int32_t w, float edge_thr, int32_t stride, int64_t* counts, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  const char* name = "mesh_count";
+  PRV2_REQUIRE(counts != nullptr, "%s: null pointer (counts)", name);
+  if (check_mesh(name, depth, n, h, w, stride, workspace, workspace_bytes)) return 1;
+  int32_t* runs;
+  const MeshArgs m = mesh_args(depth, n, h, w, edge_thr, stride, workspace, &runs);
+  if (m.nrun > 0) hipLaunchKernelGGL(mesh_count_kernel, dim3((unsigned)m.nrun, n), dim3(256), 0, (hipStream_t)stream, m, runs);
+  hipLaunchKernelGGL(cloud_scan_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, runs, m.nrun, counts);  // (no runs: M = 0)
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_mesh_pack(const float* depth, int32_t n, int32_t h, int32_t w, float edge_thr, int32_t stride, const void* workspace,
+                              int64_t workspace_bytes, uint8_t* faces, int64_t faces_fstride, void* stream) {
+  const char* name = "mesh_pack";
+  if (check_mesh(name, depth, n, h, w, stride, workspace, workspace_bytes)) return 1;
+  PRV2_REQUIRE(faces != nullptr || prv2_mesh_bound(h, w, stride) == 0, "%s: null pointer (faces)", name);
+  PRV2_REQUIRE(faces_fstride >= prv2_mesh_bound(h, w, stride), "%s: frame stride %lld of the face buffer < %lld (prv2_mesh_bound)", name,
+               (long long)faces_fstride, (long long)prv2_mesh_bound(h, w, stride));
+  int32_t* runs;
+  const MeshArgs m = mesh_args(depth, n, h, w, edge_thr, stride, (void*)workspace, &runs);
+  if (m.nrun > 0)
+    hipLaunchKernelGGL(mesh_pack_kernel, dim3((unsigned)m.nrun, n), dim3(256), 0, (hipStream_t)stream, m, (const int32_t*)runs, faces, faces_fstride);
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }

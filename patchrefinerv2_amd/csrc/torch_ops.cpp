@@ -1278,6 +1278,41 @@ Tensor pointcloud_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<do
                           (uint8_t*)vertices.data_ptr(), vertices.size(1), L.stream), "pointcloud_pack");
   return counts;
 }
+// mesh export (include/prv2.h "Mesh export"): pointcloud_pack plus the face records over its vertices, from one count of the kept
+// pixels.  -> (N, M) int64 [n]; frame f's faces are faces[f, :13 * M[f]] (the rest of ``faces`` is left as it is)
+std::tuple<Tensor, Tensor> mesh_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, double lo, double hi, double edge_thr,
+                                     int64_t stride, Tensor vertices, Tensor faces) {
+  dev_frames(depth, "depth", at::kFloat);
+  const double* k = camera4(intrinsics, "mesh_pack");
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
+                  image.size(1) == 3 && image.device() == depth.device(), "prv2::mesh_pack: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+  const int n = (int)depth.size(0), h = (int)depth.size(1), w = (int)depth.size(2);
+  TORCH_CHECK(stride >= 1 && stride <= INT_MAX, "prv2::mesh_pack: stride ", stride, " < 1");
+  const int64_t cloud_bytes = prv2_pointcloud_workspace_bytes(n, h, w), bytes = prv2_mesh_workspace_bytes(n, h, w, (int)stride);
+  const int64_t vbound = prv2_pointcloud_bound(h, w, (int)stride), fbound = prv2_mesh_bound(h, w, (int)stride);
+  TORCH_CHECK(cloud_bytes > 0 && bytes > 0 && vbound > 0 && fbound >= 0, "prv2::mesh_pack: bad frame shape ", depth.sizes());
+  TORCH_CHECK(vertices.is_cuda() && vertices.scalar_type() == at::kByte && vertices.dim() == 2 && vertices.is_contiguous() && vertices.size(0) == n &&
+                  vertices.size(1) >= vbound && vertices.device() == depth.device(),
+              "prv2::mesh_pack: vertices must be a contiguous GPU uint8 [n, >= ", vbound, "] tensor");
+  TORCH_CHECK(faces.is_cuda() && faces.scalar_type() == at::kByte && faces.dim() == 2 && faces.is_contiguous() && faces.size(0) == n &&
+                  faces.size(1) >= fbound && faces.device() == depth.device(),
+              "prv2::mesh_pack: faces must be a contiguous GPU uint8 [n, >= ", fbound, "] tensor");
+  Tensor cloud_ws = at::empty({cloud_bytes}, depth.options().dtype(at::kByte)), ws = at::empty({bytes}, depth.options().dtype(at::kByte));
+  Tensor nv = at::empty({depth.size(0)}, depth.options().dtype(at::kLong)), nf = at::empty({depth.size(0)}, depth.options().dtype(at::kLong));
+  Launch L(depth);
+  const float* d = depth.data_ptr<float>();
+  ok(prv2_pointcloud_count(d, n, h, w, (float)k[0], (float)k[1], (float)k[2], (float)k[3], (float)lo, (float)hi, (float)edge_thr, (int)stride,
+                           nv.data_ptr<int64_t>(), cloud_ws.data_ptr(), cloud_ws.numel(), L.stream), "pointcloud_count");
+  ok(prv2_pointcloud_pack(d, image.data_ptr<float>(), n, h, w, (int)image.size(2), (int)image.size(3), (float)k[0], (float)k[1], (float)k[2],
+                          (float)k[3], (float)lo, (float)hi, (float)edge_thr, (int)stride, cloud_ws.data_ptr(), cloud_ws.numel(),
+                          (uint8_t*)vertices.data_ptr(), vertices.size(1), L.stream), "pointcloud_pack");
+  ok(prv2_mesh_index(d, n, h, w, (float)lo, (float)hi, (float)edge_thr, (int)stride, cloud_ws.data_ptr(), cloud_ws.numel(), ws.data_ptr(), ws.numel(),
+                     L.stream), "mesh_index");
+  ok(prv2_mesh_count(d, n, h, w, (float)edge_thr, (int)stride, nf.data_ptr<int64_t>(), ws.data_ptr(), ws.numel(), L.stream), "mesh_count");
+  ok(prv2_mesh_pack(d, n, h, w, (float)edge_thr, (int)stride, ws.data_ptr(), ws.numel(), (uint8_t*)faces.data_ptr(), faces.size(1), L.stream),
+     "mesh_pack");
+  return {nv, nf};
+}
 Tensor normal_rows(const Tensor& depth, at::ArrayRef<double> intrinsics, double lo, double hi) {
   dev_frames(depth, "depth", at::kFloat);
   const double* k = camera4(intrinsics, "normal_rows");
@@ -1441,6 +1476,7 @@ TORCH_LIBRARY(prv2, m) {
   // geometry export: PLY vertex records (written into ``vertices``; returns the per-frame counts) and surface-normal scanlines
   m.def("pointcloud_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices) -> Tensor");
   m.def("normal_rows(Tensor depth, float[] intrinsics, float lo, float hi) -> Tensor");
+  m.def("mesh_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices, Tensor(b!) faces) -> (Tensor, Tensor)");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1530,4 +1566,5 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("sparsify", &sparsify);
   m.impl("pointcloud_pack", &pointcloud_pack);
   m.impl("normal_rows", &normal_rows);
+  m.impl("mesh_pack", &mesh_pack);
 }

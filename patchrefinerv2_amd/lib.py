@@ -181,6 +181,12 @@ SIGNATURES = {
     "prv2_pointcloud_count": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _L, _P]),
     "prv2_pointcloud_pack": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _I, _P, _L, _P, _L, _P]),
     "prv2_normal_rows": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _L, _P]),
+    # mesh export (csrc/pointcloud.hip): the face records of a triangle mesh over the cloud's vertices
+    "prv2_mesh_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "prv2_mesh_bound": (_L, [_I, _I, _I]),
+    "prv2_mesh_index": (_I, [_P, _I, _I, _I, _F, _F, _F, _I, _P, _L, _P, _L, _P]),
+    "prv2_mesh_count": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _L, _P]),
+    "prv2_mesh_pack": (_I, [_P, _I, _I, _I, _F, _I, _P, _L, _P, _L, _P]),
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
 SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS

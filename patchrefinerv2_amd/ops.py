@@ -1732,6 +1732,34 @@ def _camera(intrinsics, depth_range, what):
     return k, (lo, hi)
 
 
+def _cloud_inputs(what, depth, image, intrinsics, depth_range, edge_thr, stride):
+    """the arguments pointcloud_pack and mesh_pack share, checked -> (frames fp32 [B, H, W], image fp32 [B, 3, Hi, Wi], k, lo, hi,
+    edge_thr, stride)"""
+    d = _edge_frames(depth, torch.float32)
+    k, (lo, hi) = _camera(intrinsics, depth_range, what)
+    stride, thr = int(stride), float(np.float32(edge_thr))
+    if stride < 1:
+        raise ValueError(f"{what}: stride {stride} < 1")
+    if math.isnan(thr):
+        raise ValueError(f"{what}: edge_thr must not be NaN")
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
+        raise ValueError(f"{what}: image is a GPU tensor on the depth map's device")
+    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"{what}: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    return d, img, k, lo, hi, thr, stride
+
+
+def _record_buffer(what, out, d, bound):
+    """``out``, or a new uint8 [B, bound] buffer on the device of the frames ``d``; ``out`` must be a contiguous uint8 [B, >= bound]"""
+    if out is None:
+        return torch.empty((d.shape[0], bound), dtype=torch.uint8, device=d.device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != d.device or out.dim() != 2 or not out.is_contiguous()
+            or out.shape[0] != d.shape[0] or out.shape[1] < bound):
+        raise ValueError(f"{what} is a contiguous GPU uint8 [{d.shape[0]}, >= {bound}] tensor")
+    return out
+
+
 def pointcloud_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, out=None):
     """the PLY vertex records of fp32 depth frames [B, H, W] -> (vertex bytes uint8 [B, bound], counts int64 [B]), both on the
     device: frame f's cloud is the first 15 * counts[f] bytes of row f (float x, y, z + uchar r, g, b per kept pixel, row-major
@@ -1739,25 +1767,9 @@ def pointcloud_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_
     ``image``: fp32 [B, 3, Hi, Wi] ([3, Hi, Wi] for one frame), any size, sampled nearest.  ``intrinsics``: fx, fy, cx, cy in
     pixels of the [H, W] grid; ``depth_range``: (lo, hi), valid is lo < Z < hi; ``edge_thr``: the flying-pixel threshold
     (<= 0: off).  ``out``: a uint8 [B, >= bound] buffer to write into (include/prv2.h prv2_pointcloud_count / _pack)."""
-    d = _edge_frames(depth, torch.float32)
-    k, (lo, hi) = _camera(intrinsics, depth_range, "pointcloud_pack")
-    stride, thr = int(stride), float(np.float32(edge_thr))
-    if stride < 1:
-        raise ValueError(f"pointcloud_pack: stride {stride} < 1")
-    if math.isnan(thr):
-        raise ValueError("pointcloud_pack: edge_thr must not be NaN")
-    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
-        raise ValueError("pointcloud_pack: image is a GPU tensor on the depth map's device")
-    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
-    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
-        raise ValueError(f"pointcloud_pack: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    d, img, k, lo, hi, thr, stride = _cloud_inputs("pointcloud_pack", depth, image, intrinsics, depth_range, edge_thr, stride)
     lib = L.load()
-    bound = lib.prv2_pointcloud_bound(d.shape[1], d.shape[2], stride)
-    if out is None:
-        out = torch.empty((d.shape[0], bound), dtype=torch.uint8, device=d.device)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != d.device or out.dim() != 2 or not out.is_contiguous()
-          or out.shape[0] != d.shape[0] or out.shape[1] < bound):
-        raise ValueError(f"pointcloud_pack: out is a contiguous GPU uint8 [{d.shape[0]}, >= {bound}] tensor")
+    out = _record_buffer("pointcloud_pack: out", out, d, lib.prv2_pointcloud_bound(d.shape[1], d.shape[2], stride))
     if DISPATCH == "torch":
         return out, _tops().pointcloud_pack(d, img, k, lo, hi, thr, stride, out)
     wsb = lib.prv2_pointcloud_workspace_bytes(*d.shape)
@@ -1769,6 +1781,37 @@ def pointcloud_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_
     _c("pointcloud_pack", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], *k, lo, hi, thr, stride, ws.data_ptr(), wsb,
        out.data_ptr(), out.shape[1])
     return out, counts
+
+
+def mesh_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, out_vertices=None, out_faces=None):
+    """the triangle mesh of fp32 depth frames [B, H, W] -> (vertex bytes uint8 [B, vbound], N int64 [B], face bytes uint8
+    [B, fbound], M int64 [B]), all on the device.  The vertices are ``pointcloud_pack``'s (same arguments, same bytes); frame f's
+    faces are the first 13 * M[f] bytes of row f (uchar 3 + three little-endian int32 vertex indices per face, cells in row-major
+    order; the rule is output.mesh_faces_host), fbound = 26 * (ceil(H / stride) - 1) * (ceil(W / stride) - 1); the bytes behind
+    a frame's records are not written.  The kept pixels are counted once: the vertex records and the index map of the faces read
+    the same offsets.  ``out_vertices`` / ``out_faces``: uint8 [B, >= bound] buffers to write into (include/prv2.h "Mesh
+    export")."""
+    d, img, k, lo, hi, thr, stride = _cloud_inputs("mesh_pack", depth, image, intrinsics, depth_range, edge_thr, stride)
+    lib = L.load()
+    cwsb, wsb = lib.prv2_pointcloud_workspace_bytes(*d.shape), lib.prv2_mesh_workspace_bytes(*d.shape, stride)
+    if cwsb < 0 or wsb < 0:
+        raise ValueError(f"mesh_pack: bad frame shape {tuple(d.shape)}")
+    verts = _record_buffer("mesh_pack: out_vertices", out_vertices, d, lib.prv2_pointcloud_bound(d.shape[1], d.shape[2], stride))
+    faces = _record_buffer("mesh_pack: out_faces", out_faces, d, lib.prv2_mesh_bound(d.shape[1], d.shape[2], stride))
+    if DISPATCH == "torch":
+        n, m = _tops().mesh_pack(d, img, k, lo, hi, thr, stride, verts, faces)
+        return verts, n, faces, m
+    cws = torch.empty((cwsb,), dtype=torch.uint8, device=d.device)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=d.device)
+    n = torch.empty((d.shape[0],), dtype=torch.int64, device=d.device)
+    m = torch.empty((d.shape[0],), dtype=torch.int64, device=d.device)
+    _c("pointcloud_count", d.data_ptr(), *d.shape, *k, lo, hi, thr, stride, n.data_ptr(), cws.data_ptr(), cwsb)
+    _c("pointcloud_pack", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], *k, lo, hi, thr, stride, cws.data_ptr(), cwsb,
+       verts.data_ptr(), verts.shape[1])
+    _c("mesh_index", d.data_ptr(), *d.shape, lo, hi, thr, stride, cws.data_ptr(), cwsb, ws.data_ptr(), wsb)
+    _c("mesh_count", d.data_ptr(), *d.shape, thr, stride, m.data_ptr(), ws.data_ptr(), wsb)
+    _c("mesh_pack", d.data_ptr(), *d.shape, thr, stride, ws.data_ptr(), wsb, faces.data_ptr(), faces.shape[1])
+    return verts, n, faces, m
 
 
 def normal_rows(depth, intrinsics, depth_range=(0.0, math.inf)):

@@ -20,11 +20,15 @@ write_png16 / write_png8 a host array as a PNG file (the host route's dependency
 camera_intrinsics        fx, fy, cx, cy of a result map's grid from --intrinsics / --fov (host)
 pointcloud_host / normal_map_host / ply_bytes
                          the host specification of the geometry export (csrc/pointcloud.hip equals it bit for bit) and the PLY file
+mesh_faces_host / mesh_ply_bytes
+                         the host specification of the mesh's faces (likewise) and the PLY file of vertices and faces
 OutputStage              side stream, ring of pinned staging slots, writer pool
 
 Geometry export (``runner_info.save_ply`` / ``save_normals``; tools/test.py --save-ply / --save-normals): <name>.ply, a binary
 little-endian point cloud of the result map (float x, y, z + uchar red, green, blue per kept pixel, row-major pixel order), and
-<name>_normal.png, its camera-facing surface normals.  Pinhole camera, x right, y down, z forward.
+<name>_normal.png, its camera-facing surface normals.  Pinhole camera, x right, y down, z forward.  ``runner_info.save_mesh``
+(--save-mesh) adds <name>_mesh.ply: the same vertices joined into camera-facing triangles along the pixel grid, two per cell of
+four kept neighbours at most, none across a depth discontinuity (``mesh_faces_host``).
 """
 from __future__ import annotations
 
@@ -281,14 +285,98 @@ def ply_bytes(n: int, vertex_bytes) -> bytes:
     return ply_header(n) + bytes(body)
 
 
-def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True):
-    """the host route of ``OutputStage.submit_geometry``: <base>.ply and <base>_normal.png from the host specification"""
-    if ply:
+def mesh_faces_host(depth, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1) -> np.ndarray:
+    """The specification of the faces of ``ops.mesh_pack`` for one frame -> '<i4' [M, 3], indices into the vertices of
+    ``pointcloud_host`` (the rank of a kept pixel in row-major order).  Grid node (gy, gx) is pixel (gy * stride, gx * stride);
+    cell (gy, gx), gy + 1 < gh and gx + 1 < gw, has the corners a = (gy, gx), b = (gy, gx + 1), c = (gy + 1, gx), d = (gy + 1, gx + 1).
+    Two kept corners are joined when edge_thr <= 0 or not (|Zp - Zq| > edge_thr * min(Zp, Zq)) -- the flying-pixel test's fp32
+    operations.  Four corners kept: the diagonal a-d if |Za - Zd| <= |Zb - Zc|, else b-c; three: the diagonal whose two ends are
+    kept; fewer: no face.  With a-d the candidates are (a, c, d) then (a, d, b), with b-c (a, c, b) then (b, c, d); a candidate is
+    a face when its three corners are kept and its three edges are joined.  Cells in row-major order, the first candidate first.
+    With x right, y down, z forward every face looks at the camera: cross(P1 - P0, P2 - P0) has negative z on a fronto-parallel
+    plane."""
+    s = int(stride)
+    if s < 1:
+        raise ValueError(f"stride {stride} < 1")
+    d = np.ascontiguousarray(depth, dtype=F32)
+    keep = keep_mask_host(d, depth_range, edge_thr, s)
+    index = np.where(keep, np.cumsum(keep.reshape(-1), dtype=np.int64).reshape(keep.shape) - 1, -1)[::s, ::s]
+    z = d[::s, ::s]
+    if min(index.shape) < 2:
+        return np.zeros((0, 3), dtype="<i4")
+    corner = dict(a=(slice(None, -1), slice(None, -1)), b=(slice(None, -1), slice(1, None)), c=(slice(1, None), slice(None, -1)),
+                  d=(slice(1, None), slice(1, None)))
+    i = {n: index[c] for n, c in corner.items()}
+    zc = {n: z[c] for n, c in corner.items()}
+    kept = {n: v >= 0 for n, v in i.items()}
+    thr = F32(edge_thr)
+
+    def joined(p, q):
+        if not thr > 0:
+            return kept[p] & kept[q]
+        with np.errstate(all="ignore"):
+            return kept[p] & kept[q] & ~(np.abs(zc[p] - zc[q]) > thr * np.minimum(zc[p], zc[q]))
+
+    def face(p, q, r):
+        return joined(p, q) & joined(q, r) & joined(p, r), np.stack([i[p], i[q], i[r]], axis=-1)
+
+    with np.errstate(all="ignore"):
+        four = kept["a"] & kept["b"] & kept["c"] & kept["d"]
+        ad = np.where(four, np.abs(zc["a"] - zc["d"]) <= np.abs(zc["b"] - zc["c"]), kept["a"] & kept["d"])
+    emit, faces = [], []
+    for with_ad, with_bc in (("acd", "acb"), ("adb", "bcd")):  # the first and the second candidate of a cell
+        (ok_ad, tri_ad), (ok_bc, tri_bc) = face(*with_ad), face(*with_bc)
+        emit.append(np.where(ad, ok_ad, ok_bc))
+        faces.append(np.where(ad[..., None], tri_ad, tri_bc))
+    emit, faces = np.stack(emit, axis=-1), np.stack(faces, axis=-2)  # [gh - 1, gw - 1, 2], [gh - 1, gw - 1, 2, 3]
+    return np.ascontiguousarray(faces[emit], dtype="<i4")  # (boolean indexing walks cells row-major, then the candidates)
+
+
+PLY_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])  # 13 bytes, packed: the list length (3), then the vertex indices
+
+
+def mesh_face_records(faces) -> np.ndarray:
+    """'<i4' [M, 3] -> the ``PLY_FACE`` records [M] (``.tobytes()``: the 13 M bytes of the face element)"""
+    f = np.asarray(faces, dtype="<i4").reshape(-1, 3)
+    out = np.empty((f.shape[0],), dtype=PLY_FACE)
+    out["n"], out["v"] = 3, f
+    return out
+
+
+def mesh_ply_header(n: int, m: int) -> bytes:
+    """the fixed header of a mesh of n vertices and m faces: the cloud's up to its last property, then the face element"""
+    head = ply_header(n)
+    end = b"end_header\n"
+    assert head.endswith(end)
+    return head[:-len(end)] + f"element face {int(m)}\nproperty list uchar int vertex_indices\n".encode("ascii") + end
+
+
+def mesh_ply_bytes(n: int, vertex_bytes, m: int, face_bytes) -> bytes:
+    """the PLY file of a mesh: the header, the first 15 n bytes of ``vertex_bytes`` (``PLY_VERTEX`` records: the body of the
+    cloud's file), then the first 13 m bytes of ``face_bytes`` (``PLY_FACE`` records)"""
+    verts = memoryview(vertex_bytes).cast("B")[:PLY_VERTEX.itemsize * int(n)]
+    faces = memoryview(face_bytes).cast("B")[:PLY_FACE.itemsize * int(m)]
+    if len(verts) != PLY_VERTEX.itemsize * int(n) or len(faces) != PLY_FACE.itemsize * int(m):
+        raise ValueError(f"mesh_ply_bytes: {n} vertices and {m} faces need {PLY_VERTEX.itemsize * int(n)} + {PLY_FACE.itemsize * int(m)} bytes, "
+                         f"got {len(verts)} + {len(faces)}")
+    return mesh_ply_header(n, m) + bytes(verts) + bytes(faces)
+
+
+def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True,
+                        mesh=False):
+    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png and <base>_mesh.ply from the host
+    specification"""
+    if ply or mesh:
         v = pointcloud_host(depth, image, intrinsics, depth_range, edge_thr, stride)
+    if ply:
         with open(base + ".ply", "wb") as f:
             f.write(ply_bytes(v.size, v.tobytes()))
     if normals:
         write_png8(base + "_normal.png", normal_map_host(depth, intrinsics, depth_range))
+    if mesh:
+        faces = mesh_face_records(mesh_faces_host(depth, depth_range, edge_thr, stride))
+        with open(base + "_mesh.ply", "wb") as f:
+            f.write(mesh_ply_bytes(v.size, v.tobytes(), faces.size, faces.tobytes()))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -395,12 +483,12 @@ class OutputStage:
         self.device_deflate = bool(device_deflate)
         self.stream = None
         self.copy_stream = None  # device_deflate / point clouds: the writer threads' D2H copies
-        self._slots = [dict(buf=None, sizes=None, ply=None, ply_n=None, futures=[]) for _ in range(self.depth)]
+        self._slots = [dict(buf=None, sizes=None, ply=None, ply_n=None, mesh=None, mesh_n=None, futures=[]) for _ in range(self.depth)]
         self._loose = []  # files queued from host rows (write_rows)
         self._next = 0
         self._error = None
         self._lock = threading.Lock()
-        self.bytes_d2h = 0  # bytes copied to the host so far: packed scanlines, or compressed streams and their sizes; vertex records and their counts
+        self.bytes_d2h = 0  # bytes copied to the host so far: packed scanlines, or compressed streams and their sizes; vertex and face records and their counts
         self.files = 0
         os.makedirs(work_dir, exist_ok=True)
 
@@ -438,24 +526,29 @@ class OutputStage:
                 if self._error is None:
                     self._error = e
 
-    def _write_ply(self, path, verts, count, event, host):
-        """wait for the frame's vertex count, copy exactly its 15 N bytes of ``verts`` (device uint8 [bound]) into the pinned
-        ``host`` on the copy stream, prepend the header, write"""
+    def _write_ply(self, path, header, parts, counts, event, host):
+        """a PLY file of one or two elements.  ``parts``: per element (records: device uint8 [bound], bytes per record);
+        ``counts``: pinned int64, element k's record count at [k].  Wait for the counts, copy exactly each element's bytes into the
+        pinned ``host`` on the copy stream, prepend ``header(*counts)``, write"""
         try:
-            event.synchronize()  # the count and pack kernels and the copy of the count
-            n = int(count[0])
-            nb = PLY_VERTEX.itemsize * n
+            event.synchronize()  # the count and pack kernels and the copy of the counts
+            nums = [int(counts[k]) for k in range(len(parts))]
+            sizes = [size * n for (_, size), n in zip(parts, nums)]
+            nb = sum(sizes)
             if nb:
-                with torch.cuda.device(verts.device), torch.cuda.stream(self.copy_stream):
-                    verts.record_stream(self.copy_stream)
-                    host[:nb].copy_(verts[:nb], non_blocking=True)
+                with torch.cuda.device(parts[0][0].device), torch.cuda.stream(self.copy_stream):
+                    off = 0
+                    for (records, _), size in zip(parts, sizes):
+                        records.record_stream(self.copy_stream)
+                        host[off:off + size].copy_(records[:size], non_blocking=True)
+                        off += size
                     done = torch.cuda.Event()
                     done.record(self.copy_stream)
                 done.synchronize()
             with self._lock:
                 self.bytes_d2h += nb
             with open(path, "wb") as f:
-                f.write(ply_header(n))
+                f.write(header(*nums))
                 f.write(memoryview(host.numpy())[:nb])
         except BaseException as e:  # kept for flush()
             with self._lock:
@@ -567,29 +660,34 @@ class OutputStage:
 
     @torch.no_grad()
     def submit_geometry(self, base: str, result: torch.Tensor, image_hr, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1,
-                        ply=True, normals=True):
+                        ply=True, normals=True, mesh=False):
         """the geometry of one frame, from the device map: <base>.ply (``ply``: the point cloud of ``pointcloud_host``, coloured
-        from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size) and <base>_normal.png (``normals``: the map of
-        ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``).
-        ``intrinsics``: fx, fy, cx, cy of the RESULT's grid (``camera_intrinsics``).  The vertex buffer is sized for the bound
-        (15 bytes per strided pixel); only the frame's count goes to pinned memory with an event, and the file's writer thread
-        copies exactly 15 N bytes on the copy stream."""
+        from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size), <base>_normal.png (``normals``: the map of
+        ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``) and
+        <base>_mesh.ply (``mesh``: the cloud's vertices and the faces of ``mesh_faces_host``; with ``ply`` as well the vertex
+        records are made once and feed both files).  ``intrinsics``: fx, fy, cx, cy of the RESULT's grid (``camera_intrinsics``).
+        The vertex and face buffers are sized for their bounds (15 bytes per strided pixel, 26 per cell); only the frame's counts
+        go to pinned memory with an event, and a file's writer thread copies exactly its 15 N (+ 13 M) bytes on the copy stream."""
         from . import ops
         dev = result.device
         slot = self._begin(dev)
-        if ply and self.copy_stream is None:
+        if (ply or mesh) and self.copy_stream is None:
             self.copy_stream = torch.cuda.Stream(dev)
         with torch.cuda.device(dev), torch.cuda.stream(self.stream):
             d = _frames(result)
             h, w = d.shape[1:]
             if normals:
                 self._stage(slot, [(base + "_normal.png", w, h, 3, ops.normal_rows(d, intrinsics, depth_range))])
-            if ply:
+            if ply or mesh:
                 img = torch.as_tensor(image_hr)
                 if img.dim() == 4 and img.shape[0] == 1:
                     img = img[0]
                 img = img.to(dev, torch.float32, non_blocking=True)
-                verts, counts = ops.pointcloud_pack(d, img, intrinsics, depth_range, edge_thr, stride)
+                if mesh:
+                    verts, counts, faces, n_faces = ops.mesh_pack(d, img, intrinsics, depth_range, edge_thr, stride)
+                else:
+                    verts, counts = ops.pointcloud_pack(d, img, intrinsics, depth_range, edge_thr, stride)
+            if ply:
                 if slot["ply"] is None or slot["ply"].numel() < verts.shape[1]:
                     slot["ply"] = torch.empty((int(verts.shape[1]),), dtype=torch.uint8, pin_memory=True)
                 if slot["ply_n"] is None:
@@ -600,7 +698,22 @@ class OutputStage:
                 ev = torch.cuda.Event()
                 ev.record(self.stream)
                 self.files += 1
-                slot["futures"].append(self.pool.submit(self._write_ply, base + ".ply", verts[0], slot["ply_n"], ev, slot["ply"]))
+                slot["futures"].append(self.pool.submit(self._write_ply, base + ".ply", ply_header, [(verts[0], PLY_VERTEX.itemsize)], slot["ply_n"], ev,
+                                                      slot["ply"]))
+            if mesh:
+                room = int(verts.shape[1]) + int(faces.shape[1])
+                if slot["mesh"] is None or slot["mesh"].numel() < room:
+                    slot["mesh"] = torch.empty((room,), dtype=torch.uint8, pin_memory=True)
+                    slot["mesh_n"] = torch.empty((2,), dtype=torch.int64, pin_memory=True)
+                slot["mesh_n"][:1].copy_(counts, non_blocking=True)
+                slot["mesh_n"][1:].copy_(n_faces, non_blocking=True)
+                with self._lock:
+                    self.bytes_d2h += 16
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                self.files += 1
+                slot["futures"].append(self.pool.submit(self._write_ply, base + "_mesh.ply", mesh_ply_header,
+                                                      [(verts[0], PLY_VERTEX.itemsize), (faces[0], PLY_FACE.itemsize)], slot["mesh_n"], ev, slot["mesh"]))
             result.record_stream(self.stream)
             if isinstance(image_hr, torch.Tensor) and image_hr.is_cuda:
                 image_hr.record_stream(self.stream)

@@ -50,7 +50,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # sparsification curves (AUSE / AURG) of a per-pixel uncertainty
        "sparsify",
        # geometry export: PLY vertex records and surface-normal scanlines
-       "pointcloud_pack", "normal_rows")
+       "pointcloud_pack", "normal_rows",
+       # mesh export: the cloud's vertex records and the face records over them
+       "mesh_pack")
 _loaded = False
 
 

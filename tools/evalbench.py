@@ -122,6 +122,7 @@ def run_steps(script, steps, timeout, args):
             sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:] + f"\nstep {step} exited with status {r.returncode}: stopping\n")
             sys.exit(r.returncode)
         out[step] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+        sys.stderr.write(f"step {step}: done\n")  # (a sign of life between steps; the result is the one JSON line at the end)
     return out
 
 

@@ -13,6 +13,7 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 ``--save-ply`` / ``--save-normals``: with ``--save``, <name>.ply (binary little-endian point cloud of the result map, coloured from the image)
 and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`` (pixels of the --image-raw-shape grid) or ``--fov DEG``
 (horizontal, default 60); ``--ply-stride S``, ``--ply-edge-thr T`` (flying-pixel filter, <= 0 off), ``--ply-depth-range LO HI``.
+``--save-mesh``: with ``--save``, <name>_mesh.ply: the same vertices plus a face element, triangles along the pixel grid (same camera and --ply-* options).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
 ``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
@@ -138,6 +139,9 @@ def main():
                     help="with --save: <name>.ply, a binary little-endian point cloud of the result map (float x y z, uchar red green blue per "
                          "kept pixel, row-major; pinhole camera, x right, y down, z forward), made on the GPU with --device-output")
     ap.add_argument("--save-normals", action="store_true", help="with --save: <name>_normal.png, the camera-facing surface normals as 8-bit RGB (n * 0.5 + 0.5)")
+    ap.add_argument("--save-mesh", action="store_true",
+                    help="with --save: <name>_mesh.ply, the vertices of --save-ply joined into camera-facing triangles along the pixel grid (binary "
+                         "little-endian PLY with a face element; no triangle across an edge --ply-edge-thr splits), made on the GPU with --device-output")
     ap.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="--save-ply / --save-normals: the camera in pixels of the --image-raw-shape grid (scaled to the result's shape)")
     ap.add_argument("--fov", type=float, default=None, metavar="DEG",
@@ -152,8 +156,8 @@ def main():
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
-    if (args.save_ply or args.save_normals) and not args.save:
-        ap.error("--save-ply / --save-normals need --save (they add files to the frames it writes)")
+    if (args.save_ply or args.save_normals or args.save_mesh) and not args.save:
+        ap.error("--save-ply / --save-normals / --save-mesh need --save (they add files to the frames it writes)")
     if args.ply_stride < 1:
         ap.error(f"--ply-stride {args.ply_stride}: at least 1")
     if args.intrinsics is not None and args.fov is not None:
@@ -191,7 +195,7 @@ def main():
     dataset = DATASETS.build(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
                         device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate,
-                        save_ply=args.save_ply, save_normals=args.save_normals, intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
+                        save_ply=args.save_ply, save_normals=args.save_normals, save_mesh=args.save_mesh, intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
                         ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range))
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
