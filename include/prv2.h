@@ -956,6 +956,43 @@ int prv2_mesh_count(const float* depth, int32_t n, int32_t h, int32_t w, float e
 int prv2_mesh_pack(const float* depth, int32_t n, int32_t h, int32_t w, float edge_thr, int32_t stride, const void* workspace,
                    int64_t workspace_bytes, uint8_t* faces, int64_t faces_fstride, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stereo export (csrc/stereo.hip): the frame re-rendered from a second eye a baseline to the right of the camera, from its metric
+ * depth map: B >= 1 dense frames [n, h, w] (h, w >= 1; n * h * w < 2^29; w <= prv2_stereo_max_width()).  Not in the reference.  One
+ * workgroup per (frame, row) keeps the row in LDS; one launch, no host synchronisation; the depth test is an integer minimum, so the
+ * same input gives the same bytes on every call.  Added without an ABI bump (additive).  The host specification is
+ * stereo_source_host / stereo_image_host of patchrefinerv2_amd/output.py, which the kernel equals byte for byte.
+ *   valid      Z finite and lo < Z < hi ("Geometry export")
+ *   target     k = fx * baseline, c = k / convergence (0 for an infinite convergence; both fp32, rounded once), s = k / Z - c,
+ *              t(x) = (int)clip((float)x - rint(s), -1, w), ties of rint to even, NaN -> -1
+ *   span       a valid pixel x covers the columns [t(x), e]: e = max(t(x), t(x + 1) - 1) when x + 1 is in the frame, valid and joined
+ *              to x ("Mesh export": edge_thr <= 0, or not |Z - Zn| > edge_thr * min(Z, Zn)), else e = t(x); cut to [0, w - 1]
+ *   depth test a column shows the covering source of the smallest Z, between equal Z the smaller x; no source: a hole (-1)
+ *   fill       a hole takes the source of the nearest shown column to its left, l, or right, r, of its row: r's when r's winner has
+ *              the larger Z, else l's; the one that exists at a border; -1 in a row that shows nothing
+ *   colour     image fp32 [n, 3, ih, iw] sampled as prv2_pointcloud_pack does, at (y, source column); byte = "Geometry export";
+ *              (0, 0, 0) for -1
+ * ------------------------------------------------------------------------------------------ */
+#define PRV2_STEREO_RIGHT 0    /* the right-eye view, w columns */
+#define PRV2_STEREO_SBS 1      /* left | right, 2 w columns; left = the image sampled to the [h, w] grid */
+#define PRV2_STEREO_ANAGLYPH 2 /* red of the left eye, green and blue of the right eye, w columns */
+
+/* the widest row prv2_stereo_rows / _source take: the columns of depth-test keys a workgroup keeps in LDS (8192) */
+int32_t prv2_stereo_max_width(void);
+
+/* src, filled: DEVICE int32 [n, h, w]: the winning source column of every column of the view (-1: hole), and the same with the holes
+ * filled by the rule above.  fx > 0 finite, baseline finite (metres, positive: the eye moves right), convergence != 0 (the depth
+ * that keeps its column; +/-inf: parallel axes). */
+int prv2_stereo_source(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float baseline, float convergence, float lo, float hi,
+                       float edge_thr, int32_t* src, int32_t* filled, void* stream);
+
+/* the view as RGB scanlines (bpp 3; a scanline buffer of the output stage: [h][1 + 3 wout] bytes per frame, wout = 2 w for
+ * PRV2_STEREO_SBS, else w; rows 16-byte aligned, rows_fstride a multiple of 16 and >= prv2_rows_bytes(h, wout, 3); the tail up to the
+ * next multiple of 16 is zero).  A workgroup assembles its scanline in LDS and stores it once: byte stores at the ragged ends,
+ * 16-byte stores inside; no byte is read back. */
+int prv2_stereo_rows(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx, float baseline,
+                     float convergence, float lo, float hi, float edge_thr, int32_t layout, uint8_t* rows, int64_t rows_fstride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,21 +136,6 @@ __global__ void __launch_bounds__(256) cloud_scan_kernel(int32_t* __restrict__ c
   }
 }
 
-// A block's store of the LDS image buf[shift + i] to dst[i], i in [0, nb), where shift = dst mod 16 (so dst - shift is 16-byte aligned):
-// the bytes before the first and from the last 16-byte boundary one by one, the aligned interior as 16-byte words
-__device__ __forceinline__ void store_ragged(uint8_t* __restrict__ dst, const uint4* buf4, int shift, int nb, int tid) {
-  const uint8_t* buf = (const uint8_t*)buf4;
-  const int head = (16 - shift) & 15;              // bytes before the first 16-byte boundary
-  const int h_end = head < nb ? head : nb;
-  const int wide = (nb - h_end) / 16;              // aligned 16-byte words of the interior
-  const int t_beg = h_end + 16 * wide;
-  if (tid < h_end) dst[tid] = buf[shift + tid];
-  uint4* dst4 = (uint4*)(dst + h_end);
-  const uint4* src4 = buf4 + (shift + h_end) / 16;
-  for (int i = tid; i < wide; i += 256) dst4[i] = src4[i];
-  if (tid < nb - t_beg) dst[t_beg + tid] = buf[shift + t_beg + tid];
-}
-
 // The records of every run.  The block ranks its kept pixels in pixel order (ballot + popcount inside a wave, the (step, wave) segment
 // totals through LDS), builds the records in LDS and stores its byte range [15 off, 15 (off + cnt)) of the frame's vertex buffer.  That
 // range starts and ends at any byte alignment and the dwords at its two ends may belong to the neighbouring runs as well: the LDS image

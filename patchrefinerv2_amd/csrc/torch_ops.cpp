@@ -1323,6 +1323,39 @@ Tensor normal_rows(const Tensor& depth, at::ArrayRef<double> intrinsics, double 
   return rows;
 }
 
+// stereo export (include/prv2.h "Stereo export"): the right-eye view of B frames as scanlines, or its source-column maps
+void stereo_width(const Tensor& depth, const char* op) {
+  TORCH_CHECK(depth.size(2) <= prv2_stereo_max_width(), "prv2::", op, ": a row of ", depth.size(2), " columns is wider than the ",
+              prv2_stereo_max_width(), " the kernel keeps in LDS");
+}
+std::tuple<Tensor, Tensor> stereo_source(const Tensor& depth, double fx, double baseline, double convergence, double lo, double hi, double edge_thr) {
+  dev_frames(depth, "depth", at::kFloat);
+  stereo_width(depth, "stereo_source");
+  Tensor src = at::empty(depth.sizes(), depth.options().dtype(at::kInt)), filled = at::empty(depth.sizes(), depth.options().dtype(at::kInt));
+  Launch L(depth);
+  ok(prv2_stereo_source(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2), (float)fx, (float)baseline,
+                        (float)convergence, (float)lo, (float)hi, (float)edge_thr, src.data_ptr<int32_t>(), filled.data_ptr<int32_t>(), L.stream),
+     "stereo_source");
+  return {src, filled};
+}
+Tensor stereo_rows(const Tensor& depth, const Tensor& image, double fx, double baseline, double convergence, double lo, double hi, double edge_thr,
+                   int64_t layout) {
+  dev_frames(depth, "depth", at::kFloat);
+  stereo_width(depth, "stereo_rows");
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
+                  image.size(1) == 3 && image.device() == depth.device(), "prv2::stereo_rows: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+  TORCH_CHECK(layout == PRV2_STEREO_RIGHT || layout == PRV2_STEREO_SBS || layout == PRV2_STEREO_ANAGLYPH, "prv2::stereo_rows: layout ", layout);
+  const int64_t wout = depth.size(2) * (layout == PRV2_STEREO_SBS ? 2 : 1);
+  const int64_t bytes = prv2_rows_bytes((int)depth.size(1), (int)wout, 3);
+  TORCH_CHECK(bytes > 0, "prv2::stereo_rows: bad frame shape ", depth.sizes());
+  Tensor rows = at::empty({depth.size(0), bytes}, depth.options().dtype(at::kByte));
+  Launch L(depth);
+  ok(prv2_stereo_rows(depth.data_ptr<float>(), image.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2), (int)image.size(2),
+                      (int)image.size(3), (float)fx, (float)baseline, (float)convergence, (float)lo, (float)hi, (float)edge_thr, (int)layout,
+                      (uint8_t*)rows.data_ptr(), rows.size(1), L.stream), "stereo_rows");
+  return rows;
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1477,6 +1510,8 @@ TORCH_LIBRARY(prv2, m) {
   m.def("pointcloud_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices) -> Tensor");
   m.def("normal_rows(Tensor depth, float[] intrinsics, float lo, float hi) -> Tensor");
   m.def("mesh_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices, Tensor(b!) faces) -> (Tensor, Tensor)");
+  m.def("stereo_source(Tensor depth, float fx, float baseline, float convergence, float lo, float hi, float edge_thr) -> (Tensor, Tensor)");
+  m.def("stereo_rows(Tensor depth, Tensor image, float fx, float baseline, float convergence, float lo, float hi, float edge_thr, int layout) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1567,4 +1602,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("pointcloud_pack", &pointcloud_pack);
   m.impl("normal_rows", &normal_rows);
   m.impl("mesh_pack", &mesh_pack);
+  m.impl("stereo_source", &stereo_source);
+  m.impl("stereo_rows", &stereo_rows);
 }

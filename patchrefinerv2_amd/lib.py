@@ -187,6 +187,10 @@ SIGNATURES = {
     "prv2_mesh_index": (_I, [_P, _I, _I, _I, _F, _F, _F, _I, _P, _L, _P, _L, _P]),
     "prv2_mesh_count": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _L, _P]),
     "prv2_mesh_pack": (_I, [_P, _I, _I, _I, _F, _I, _P, _L, _P, _L, _P]),
+    # stereo export (csrc/stereo.hip): the right-eye view of B frames as scanlines, or its source-column maps
+    "prv2_stereo_max_width": (_I, []),
+    "prv2_stereo_source": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
+    "prv2_stereo_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _L, _P]),
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
 SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS

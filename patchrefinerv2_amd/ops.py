@@ -1827,6 +1827,68 @@ def normal_rows(depth, intrinsics, depth_range=(0.0, math.inf)):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Stereo export (csrc/stereo.hip): the right-eye view of frames [B, H, W] as scanlines, or its source-column maps, both dispatch
+# routes.  The host specification is output.stereo_source_host / output.stereo_image_host.
+# ------------------------------------------------------------------------------------------------------------------
+STEREO_LAYOUTS = {"right": 0, "sbs": 1, "anaglyph": 2}  # PRV2_STEREO_RIGHT / _SBS / _ANAGLYPH
+
+
+def _stereo_inputs(what, depth, intrinsics, baseline, convergence, depth_range, edge_thr):
+    """the arguments stereo_rows and stereo_source share, checked -> (frames fp32 [B, H, W], fx, baseline, convergence, lo, hi,
+    edge_thr) with the scalars as Python floats that hold float32 values"""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
+        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
+    d = _edge_frames(depth, torch.float32)
+    k, (lo, hi) = _camera(intrinsics, depth_range, what)
+    base, conv, thr = (float(np.float32(v)) for v in (baseline, convergence, edge_thr))
+    if not math.isfinite(base):
+        raise ValueError(f"{what}: baseline {baseline} must be finite")
+    if math.isnan(conv) or conv == 0.0:
+        raise ValueError(f"{what}: convergence {convergence}: a distance other than 0 (inf: parallel axes)")
+    if math.isnan(thr):
+        raise ValueError(f"{what}: edge_thr must not be NaN")
+    limit = L.load().prv2_stereo_max_width()
+    if d.shape[2] > limit:
+        raise ValueError(f"{what}: a row of {d.shape[2]} columns is wider than the {limit} the kernel keeps in LDS (prv2_stereo_max_width)")
+    return d, k[0], base, conv, lo, hi, thr
+
+
+def stereo_source(depth, intrinsics, baseline, convergence=math.inf, depth_range=(0.0, math.inf), edge_thr=0.05):
+    """the source columns of the right-eye view of fp32 depth frames [B, H, W] -> (src, filled), int32 [B, H, W] on the device: the
+    source column every column of the view shows (-1: a hole), and the same with the holes filled from the farther side
+    (output.stereo_source_host; include/prv2.h prv2_stereo_source).  ``intrinsics``: fx, fy, cx, cy of the [H, W] grid (fx is used);
+    ``baseline``: metres to the right; ``convergence``: the depth that keeps its column (inf: parallel axes)."""
+    d, fx, base, conv, lo, hi, thr = _stereo_inputs("stereo_source", depth, intrinsics, baseline, convergence, depth_range, edge_thr)
+    if DISPATCH == "torch":
+        return tuple(_tops().stereo_source(d, fx, base, conv, lo, hi, thr))
+    src, filled = torch.empty(d.shape, dtype=torch.int32, device=d.device), torch.empty(d.shape, dtype=torch.int32, device=d.device)
+    _c("stereo_source", d.data_ptr(), *d.shape, fx, base, conv, lo, hi, thr, src.data_ptr(), filled.data_ptr())
+    return src, filled
+
+
+def stereo_rows(depth, image, intrinsics, baseline, convergence=math.inf, depth_range=(0.0, math.inf), edge_thr=0.05, layout="right"):
+    """the right-eye view of fp32 depth frames [B, H, W] as RGB scanlines -> scanline buffer uint8 [B, prv2_rows_bytes(H, Wout, 3)],
+    Wout = 2 W for ``layout`` 'sbs' (left | right), W for 'right' and 'anaglyph' (red of the left eye, green and blue of the right);
+    output.stereo_image_host is the specification (include/prv2.h prv2_stereo_rows).  ``image``: fp32 [B, 3, Hi, Wi] ([3, Hi, Wi]
+    for one frame), any size, sampled nearest; the other arguments as ``stereo_source``."""
+    if layout not in STEREO_LAYOUTS:
+        raise ValueError(f"stereo_rows: layout {layout!r}: one of {tuple(STEREO_LAYOUTS)}")
+    d, fx, base, conv, lo, hi, thr = _stereo_inputs("stereo_rows", depth, intrinsics, baseline, convergence, depth_range, edge_thr)
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
+        raise ValueError("stereo_rows: image is a GPU tensor on the depth map's device")
+    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"stereo_rows: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    if DISPATCH == "torch":
+        return _tops().stereo_rows(d, img, fx, base, conv, lo, hi, thr, STEREO_LAYOUTS[layout])
+    wout = d.shape[2] * (2 if layout == "sbs" else 1)
+    rows = torch.empty((d.shape[0], L.load().prv2_rows_bytes(d.shape[1], wout, 3)), dtype=torch.uint8, device=d.device)
+    _c("stereo_rows", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], fx, base, conv, lo, hi, thr, STEREO_LAYOUTS[layout],
+       rows.data_ptr(), rows.shape[1])
+    return rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Ground-truth evaluation (csrc/evalgt.hip): the device half of UnrealStereo4kDataset and the sums behind compute_metrics, both
 # dispatch routes.
 # ------------------------------------------------------------------------------------------------------------------

@@ -22,13 +22,17 @@ pointcloud_host / normal_map_host / ply_bytes
                          the host specification of the geometry export (csrc/pointcloud.hip equals it bit for bit) and the PLY file
 mesh_faces_host / mesh_ply_bytes
                          the host specification of the mesh's faces (likewise) and the PLY file of vertices and faces
+stereo_source_host / stereo_view_host / stereo_image_host
+                         the host specification of the right-eye view (csrc/stereo.hip equals it byte for byte)
 OutputStage              side stream, ring of pinned staging slots, writer pool
 
 Geometry export (``runner_info.save_ply`` / ``save_normals``; tools/test.py --save-ply / --save-normals): <name>.ply, a binary
 little-endian point cloud of the result map (float x, y, z + uchar red, green, blue per kept pixel, row-major pixel order), and
 <name>_normal.png, its camera-facing surface normals.  Pinhole camera, x right, y down, z forward.  ``runner_info.save_mesh``
 (--save-mesh) adds <name>_mesh.ply: the same vertices joined into camera-facing triangles along the pixel grid, two per cell of
-four kept neighbours at most, none across a depth discontinuity (``mesh_faces_host``).
+four kept neighbours at most, none across a depth discontinuity (``mesh_faces_host``).  ``runner_info.save_stereo`` (--save-stereo)
+adds <name>_right.png (or _sbs / _anaglyph): the frame seen from a second eye ``stereo_baseline`` metres to the right
+(``stereo_source_host``: a per-row forward warp with a depth test, disocclusions filled from the farther side).
 """
 from __future__ import annotations
 
@@ -362,10 +366,124 @@ def mesh_ply_bytes(n: int, vertex_bytes, m: int, face_bytes) -> bytes:
     return mesh_ply_header(n, m) + bytes(verts) + bytes(faces)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# stereo export: the host specification of the right-eye view (numpy float32 for the two rounded operations, integers after them;
+# csrc/stereo.hip equals it byte for byte)
+# ------------------------------------------------------------------------------------------------------------------
+STEREO_LAYOUTS = ("right", "sbs", "anaglyph")
+
+
+def _stereo_targets(d, fx, baseline, convergence):
+    """t [h, w] int64: the target column of every source pixel, in [-1, w] (-1 and w: off the frame; NaN: -1).  k = fx * baseline,
+    c = k / convergence (0 for inf), s = k / Z - c, tf = float32(x) - rint(s)"""
+    h, w = d.shape
+    with np.errstate(all="ignore"):
+        k = F32(F32(fx) * F32(baseline))
+        c = F32(0) if math.isinf(float(convergence)) else F32(k / F32(convergence))
+        s = (k / d).astype(F32) - c
+        tf = np.arange(w, dtype=F32)[None, :] - np.rint(s)
+        return np.where(np.isnan(tf), F32(-1), np.clip(tf, F32(-1), F32(w))).astype(np.int64)
+
+
+def stereo_source_host(depth, intrinsics, baseline, convergence=math.inf, depth_range=(0.0, math.inf), edge_thr=0.05):
+    """The specification of ``ops.stereo_source`` for one frame -> (src, filled), int32 [h, w]: the source column every column of the
+    view of a second eye ``baseline`` to the right shows (same row; the camera moves along x only).  A valid pixel x (the cloud's
+    rule) lands at column t(x) = x - rint(fx * baseline / Z - fx * baseline / convergence) and covers [t(x), e], e = max(t(x),
+    t(x + 1) - 1) when x + 1 is in the frame, valid and joined to x (the mesh's rule: edge_thr <= 0, or not |Z - Zn| > edge_thr *
+    min(Z, Zn)), else t(x): a surface that stretches in the new view has no one-pixel cracks.  Columns outside [0, w - 1] are
+    dropped.  A target column keeps the source of the smallest Z, between equal Z the smaller x: ``src``, -1 for a hole.
+    ``filled``: every hole of a row takes the source of the nearest non-hole column to its left or right -- the right one when its
+    winner has the larger Z (the background), the left one otherwise, the one that exists at the frame's border; a row without a
+    valid pixel stays -1."""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    h, w = d.shape
+    if not float(convergence) != 0.0:  # (0 and NaN)
+        raise ValueError(f"convergence {convergence}: a distance other than 0 (inf: parallel axes)")
+    valid = _valid_depth(d, depth_range)
+    t = _stereo_targets(d, intrinsics[0], baseline, convergence)
+    thr = F32(edge_thr)
+    link = valid[:, :-1] & valid[:, 1:]
+    if thr > 0:
+        with np.errstate(all="ignore"):
+            link &= ~(np.abs(d[:, :-1] - d[:, 1:]) > thr * np.minimum(d[:, :-1], d[:, 1:]))
+    e = t.copy()
+    e[:, :-1] = np.where(link, np.maximum(t[:, :-1], t[:, 1:] - 1), t[:, :-1])
+    q0, q1 = np.maximum(t, 0), np.minimum(e, w - 1)
+    n = np.where(valid, np.maximum(q1 - q0 + 1, 0), 0).reshape(-1)  # columns every source pixel covers
+    who = np.repeat(np.arange(h * w, dtype=np.int64), n)             # the source pixel of every (source, target) pair
+    first = np.cumsum(n) - n
+    col = q0.reshape(-1)[who] + (np.arange(who.size, dtype=np.int64) - first[who])
+    tgt = (who // w) * w + col
+    order = np.lexsort((who % w, d.reshape(-1)[who], tgt))           # by target, then Z, then source x
+    tgt, who = tgt[order], who[order]
+    win = np.ones(tgt.shape, dtype=bool)
+    win[1:] = tgt[1:] != tgt[:-1]
+    src = np.full((h, w), -1, dtype=np.int64)
+    src.reshape(-1)[tgt[win]] = who[win] % w
+    # the fill: nearest non-hole column on either side
+    cols = np.arange(w, dtype=np.int64)[None, :]
+    shown = src >= 0
+    left = np.maximum.accumulate(np.where(shown, cols, -1), axis=1)
+    right = np.minimum.accumulate(np.where(shown, cols, w)[:, ::-1], axis=1)[:, ::-1]
+    has_l, has_r = left >= 0, right < w
+    rows = np.arange(h)[:, None]
+    src_l, src_r = src[rows, np.maximum(left, 0)], src[rows, np.minimum(right, w - 1)]
+    z_l, z_r = d[rows, np.maximum(src_l, 0)], d[rows, np.maximum(src_r, 0)]
+    take_r = has_r & (~has_l | (z_r > z_l))
+    filled = np.where(shown, src, np.where(take_r, src_r, np.where(has_l, src_l, -1)))
+    return src.astype(np.int32), filled.astype(np.int32)
+
+
+def _sampled_bytes(image, h, w, ys, xs):
+    """uint8 [..., 3]: ``color_bytes(img[c, sy, sx] * 255)`` of the [h, w] grid's pixels (ys, xs), the cloud's colour rule"""
+    img = np.asarray(image, dtype=F32)
+    sy, sx = sample_indices(h, img.shape[1])[ys], sample_indices(w, img.shape[2])[xs]
+    with np.errstate(all="ignore"):
+        return np.stack([color_bytes(img[c, sy, sx] * F32(255)) for c in range(3)], axis=-1)
+
+
+def stereo_view_host(depth, image, intrinsics, baseline, convergence=math.inf, depth_range=(0.0, math.inf), edge_thr=0.05) -> np.ndarray:
+    """the right-eye view of one frame -> uint8 [h, w, 3]: column q of row y shows the image (image [3, hi, wi], any size, the
+    cloud's nearest sample and byte rule) at (y, filled[y, q]) of ``stereo_source_host``, (0, 0, 0) where that is -1"""
+    _, filled = stereo_source_host(depth, intrinsics, baseline, convergence, depth_range, edge_thr)
+    h, w = filled.shape
+    view = _sampled_bytes(image, h, w, np.arange(h)[:, None], np.maximum(filled, 0))
+    view[filled < 0] = 0
+    return view
+
+
+def stereo_image_host(depth, image, intrinsics, baseline, convergence=math.inf, depth_range=(0.0, math.inf), edge_thr=0.05,
+                      layout="right") -> np.ndarray:
+    """The specification of ``ops.stereo_rows`` for one frame.  ``layout``: 'right' -> the view [h, w, 3]; 'sbs' -> left | right
+    [h, 2 w, 3], left = the image sampled to the depth map's grid with the same byte rule; 'anaglyph' -> red from left, green and
+    blue from right [h, w, 3]"""
+    if layout not in STEREO_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: one of {STEREO_LAYOUTS}")
+    right = stereo_view_host(depth, image, intrinsics, baseline, convergence, depth_range, edge_thr)
+    if layout == "right":
+        return right
+    h, w = right.shape[:2]
+    left = _sampled_bytes(image, h, w, np.arange(h)[:, None], np.arange(w)[None, :])
+    if layout == "sbs":
+        return np.ascontiguousarray(np.concatenate([left, right], axis=1))
+    return np.ascontiguousarray(np.stack([left[..., 0], right[..., 1], right[..., 2]], axis=-1))
+
+
+def _stereo_options(stereo):
+    """the ``stereo`` dict of ``submit_geometry`` / ``write_geometry_host`` -> (baseline, convergence, layout)"""
+    unknown = set(stereo) - {"baseline", "convergence", "layout"}
+    if unknown:
+        raise ValueError(f"stereo: unknown keys {sorted(unknown)} (baseline, convergence, layout)")
+    layout = stereo.get("layout", "right")
+    if layout not in STEREO_LAYOUTS:
+        raise ValueError(f"stereo layout {layout!r}: one of {STEREO_LAYOUTS}")
+    return float(stereo.get("baseline", 0.065)), float(stereo.get("convergence", math.inf)), layout
+
+
 def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True,
-                        mesh=False):
-    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png and <base>_mesh.ply from the host
-    specification"""
+                        mesh=False, stereo=None):
+    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png, <base>_mesh.ply and (``stereo``: a dict of
+    baseline, convergence, layout) <base>_right.png / _sbs.png / _anaglyph.png from the host specification"""
     if ply or mesh:
         v = pointcloud_host(depth, image, intrinsics, depth_range, edge_thr, stride)
     if ply:
@@ -377,6 +495,9 @@ def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, m
         faces = mesh_face_records(mesh_faces_host(depth, depth_range, edge_thr, stride))
         with open(base + "_mesh.ply", "wb") as f:
             f.write(mesh_ply_bytes(v.size, v.tobytes(), faces.size, faces.tobytes()))
+    if stereo is not None:
+        baseline, convergence, layout = _stereo_options(stereo)
+        write_png8(f"{base}_{layout}.png", stereo_image_host(depth, image, intrinsics, baseline, convergence, depth_range, edge_thr, layout))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -660,14 +781,16 @@ class OutputStage:
 
     @torch.no_grad()
     def submit_geometry(self, base: str, result: torch.Tensor, image_hr, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1,
-                        ply=True, normals=True, mesh=False):
+                        ply=True, normals=True, mesh=False, stereo=None):
         """the geometry of one frame, from the device map: <base>.ply (``ply``: the point cloud of ``pointcloud_host``, coloured
         from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size), <base>_normal.png (``normals``: the map of
         ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``) and
         <base>_mesh.ply (``mesh``: the cloud's vertices and the faces of ``mesh_faces_host``; with ``ply`` as well the vertex
         records are made once and feed both files).  ``intrinsics``: fx, fy, cx, cy of the RESULT's grid (``camera_intrinsics``).
         The vertex and face buffers are sized for their bounds (15 bytes per strided pixel, 26 per cell); only the frame's counts
-        go to pinned memory with an event, and a file's writer thread copies exactly its 15 N (+ 13 M) bytes on the copy stream."""
+        go to pinned memory with an event, and a file's writer thread copies exactly its 15 N (+ 13 M) bytes on the copy stream.
+        ``stereo`` (a dict of baseline, convergence, layout; default 0.065, inf, 'right') adds <base>_right.png, <base>_sbs.png or
+        <base>_anaglyph.png: the view of ``stereo_image_host`` coloured from ``image_hr``, through the PNG path as the normal map."""
         from . import ops
         dev = result.device
         slot = self._begin(dev)
@@ -676,13 +799,21 @@ class OutputStage:
         with torch.cuda.device(dev), torch.cuda.stream(self.stream):
             d = _frames(result)
             h, w = d.shape[1:]
+            jobs = []
             if normals:
-                self._stage(slot, [(base + "_normal.png", w, h, 3, ops.normal_rows(d, intrinsics, depth_range))])
-            if ply or mesh:
+                jobs.append((base + "_normal.png", w, h, 3, ops.normal_rows(d, intrinsics, depth_range)))
+            if ply or mesh or stereo is not None:
                 img = torch.as_tensor(image_hr)
                 if img.dim() == 4 and img.shape[0] == 1:
                     img = img[0]
                 img = img.to(dev, torch.float32, non_blocking=True)
+            if stereo is not None:
+                baseline, convergence, layout = _stereo_options(stereo)
+                jobs.append((f"{base}_{layout}.png", w * (2 if layout == "sbs" else 1), h, 3,
+                             ops.stereo_rows(d, img, intrinsics, baseline, convergence, depth_range, edge_thr, layout)))
+            if jobs:
+                self._stage(slot, jobs)
+            if ply or mesh:
                 if mesh:
                     verts, counts, faces, n_faces = ops.mesh_pack(d, img, intrinsics, depth_range, edge_thr, stride)
                 else:

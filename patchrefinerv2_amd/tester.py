@@ -8,7 +8,8 @@ device_output) makes the zlib streams on the GPU as well: the files hold the dev
 stream differs from zlib's).
 ``runner_info.save_ply`` / ``save_normals`` (--save-ply / --save-normals, with ``save``) add the frame's geometry: <name>.ply (a
 binary point cloud of the result map, coloured from the image) and <name>_normal.png (its surface normals);
-``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles) -- from the device map
+``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles) and
+``runner_info.save_stereo`` (--save-stereo) <name>_right.png / _sbs.png / _anaglyph.png (the right-eye view) -- from the device map
 with the output stage, from output.py's host specification otherwise; the same files either way.
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) and <name>_edge.png (Canny edges of the log depth, widened by one pixel,
@@ -171,16 +172,20 @@ class Tester:
 
     def _geometry(self, result, image_raw_shape):
         """the keyword arguments of ``submit_geometry`` / ``write_geometry_host`` for a result map, None without ``save_ply`` /
-        ``save_normals`` / ``save_mesh``: the camera of ``runner_info.intrinsics`` (fx fy cx cy in pixels of the raw grid) or ``runner_info.fov``
-        (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``"""
+        ``save_normals`` / ``save_mesh`` / ``save_stereo``: the camera of ``runner_info.intrinsics`` (fx fy cx cy in pixels of the raw grid) or ``runner_info.fov``
+        (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``; with ``save_stereo`` the
+        ``stereo`` dict of ``stereo_baseline`` (default 0.065), ``stereo_convergence`` (inf) and ``stereo_layout`` ('right')"""
         info = self.runner_info
-        ply, normals, mesh = (bool(getattr(info, k, False)) for k in ("save_ply", "save_normals", "save_mesh"))
-        if not (info.save and (ply or normals or mesh)):
+        ply, normals, mesh, stereo = (bool(getattr(info, k, False)) for k in ("save_ply", "save_normals", "save_mesh", "save_stereo"))
+        if not (info.save and (ply or normals or mesh or stereo)):
             return None
         from .output import camera_intrinsics
         k = camera_intrinsics(image_raw_shape, result.shape[-2:], getattr(info, "intrinsics", None), getattr(info, "fov", None) or 60.0)
         return dict(intrinsics=k, depth_range=tuple(getattr(info, "ply_depth_range", None) or (0.0, float("inf"))),
-                    edge_thr=float(getattr(info, "ply_edge_thr", 0.05)), stride=int(getattr(info, "ply_stride", 1)), ply=ply, normals=normals, mesh=mesh)
+                    edge_thr=float(getattr(info, "ply_edge_thr", 0.05)), stride=int(getattr(info, "ply_stride", 1)), ply=ply, normals=normals, mesh=mesh,
+                    **(dict(stereo=dict(baseline=float(getattr(info, "stereo_baseline", 0.065)),
+                                        convergence=float(getattr(info, "stereo_convergence", float("inf"))),
+                                        layout=getattr(info, "stereo_layout", "right"))) if stereo else {}))
 
     def _entry(self, item, result, score=None, **extra):
         """one frame's result entry.  ``mean``: a host map's fp32 mean, a device map's float64 sum on the device (equal within that

@@ -52,7 +52,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # geometry export: PLY vertex records and surface-normal scanlines
        "pointcloud_pack", "normal_rows",
        # mesh export: the cloud's vertex records and the face records over them
-       "mesh_pack")
+       "mesh_pack",
+       # stereo export: the right-eye view as scanlines, and its source-column maps
+       "stereo_rows", "stereo_source")
 _loaded = False
 
 

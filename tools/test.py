@@ -142,6 +142,16 @@ def main():
     ap.add_argument("--save-mesh", action="store_true",
                     help="with --save: <name>_mesh.ply, the vertices of --save-ply joined into camera-facing triangles along the pixel grid (binary "
                          "little-endian PLY with a face element; no triangle across an edge --ply-edge-thr splits), made on the GPU with --device-output")
+    ap.add_argument("--save-stereo", action="store_true",
+                    help="with --save: <name>_right.png (--stereo-layout: _sbs / _anaglyph), the frame seen from a second eye to the right: "
+                         "a per-row forward warp of the image by the result map's disparity with a depth test, disocclusions filled from "
+                         "the farther side (camera of --intrinsics / --fov, validity of --ply-depth-range, surfaces split by "
+                         "--ply-edge-thr); made on the GPU with --device-output")
+    ap.add_argument("--stereo-baseline", type=float, default=0.065, metavar="M", help="--save-stereo: the distance between the eyes in metres")
+    ap.add_argument("--stereo-convergence", type=float, default=float("inf"), metavar="Z",
+                    help="--save-stereo: the depth that keeps its column (nearer pops out, farther recedes); inf: parallel axes")
+    ap.add_argument("--stereo-layout", default="right", choices=["right", "sbs", "anaglyph"],
+                    help="--save-stereo: right = the view, sbs = left | right (twice the width), anaglyph = red of left, green and blue of right")
     ap.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="--save-ply / --save-normals: the camera in pixels of the --image-raw-shape grid (scaled to the result's shape)")
     ap.add_argument("--fov", type=float, default=None, metavar="DEG",
@@ -156,8 +166,10 @@ def main():
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
-    if (args.save_ply or args.save_normals or args.save_mesh) and not args.save:
-        ap.error("--save-ply / --save-normals / --save-mesh need --save (they add files to the frames it writes)")
+    if (args.save_ply or args.save_normals or args.save_mesh or args.save_stereo) and not args.save:
+        ap.error("--save-ply / --save-normals / --save-mesh / --save-stereo need --save (they add files to the frames it writes)")
+    if args.stereo_convergence == 0 or args.stereo_convergence != args.stereo_convergence:
+        ap.error(f"--stereo-convergence {args.stereo_convergence}: a depth other than 0")
     if args.ply_stride < 1:
         ap.error(f"--ply-stride {args.ply_stride}: at least 1")
     if args.intrinsics is not None and args.fov is not None:
@@ -195,7 +207,9 @@ def main():
     dataset = DATASETS.build(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
                         device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate,
-                        save_ply=args.save_ply, save_normals=args.save_normals, save_mesh=args.save_mesh, intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
+                        save_ply=args.save_ply, save_normals=args.save_normals, save_mesh=args.save_mesh, save_stereo=args.save_stereo,
+                        stereo_baseline=args.stereo_baseline, stereo_convergence=args.stereo_convergence, stereo_layout=args.stereo_layout,
+                        intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
                         ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range))
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
