@@ -294,6 +294,32 @@ int prv2_conv3x3_ln_gate_f6(const prv2_conv_desc* d, const float* x, const void*
                             const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias, const float* mul,
                             const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream);
 
+/* prv2_conv3x3_ln_gate_pre / prv2_conv3x3_ln_gate_f6 with the addend GATHERED INSIDE the kernel: instead of ``pre`` they take the tables
+ * prv2_coarse_tap_gather would have read (v, g of prv2_coarse_tap_knots[_frames] for cout = 256 channels) and the tiles' boxes, and the
+ * epilogue of the 256-column gate kernels runs the gather's column walk (csrc/coarse_taps_walk.h) for its 8 x 16 pixels -- the addend is
+ * never written to or read from HBM.  Image i of the conv is tile i of ``boxes`` ([d->n, 4] (x1, y1, x2, y2), or [d->n, 5] with the frame
+ * index in front when n_frames >= 1; n_frames = 0: single-frame tables), gathered at the conv's own d->h x d->w.  Bit-identical to the
+ * same call with pre = prv2_coarse_tap_gather[_frames](...).  Contract: that of the entry point it stands for, with gate weights,
+ * d->cout = 256 (prv2_conv3x3_ln_gate_taps_supported(d) != 0); the tables' contract is prv2_coarse_tap_gather's.  (Additive: the ABI stays at 20.) */
+typedef struct prv2_tap_tables {
+  const float* v;        /* [B, 3h, 3w, ldv] knots (prv2_coarse_tap_knots)                 */
+  const float* g;        /* [B, h, w, ldg >= 9 * 256] tap-major                            */
+  const float* boxes;    /* device fp32 [d->n, 4 or 5]                                     */
+  int32_t n_frames;      /* 0: single-frame tables and 4-column boxes                      */
+  int32_t h, w;          /* coarse size                                                    */
+  int32_t ldv, ldg;
+  float knot_bh, knot_bw;
+  float spatial_scale;
+} prv2_tap_tables;
+int prv2_conv3x3_ln_gate_taps_supported(const prv2_conv_desc* d);
+int prv2_conv3x3_ln_gate_taps(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const prv2_tap_tables* taps,
+                              const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                              const float* mul, const float* res, float* y, void* stream);
+int prv2_conv3x3_ln_gate_f6_taps(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const prv2_tap_tables* taps,
+                                 const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                                 const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y,
+                                 void* stream);
+
 /* Convolution with ONE output channel (direct, HBM-bound):
  *   final_conv 3x3 -> 1 + clamp(update_base + offset, 0)   bi_directional_fusion_model.py:438-442, fusion_model.py:113-118
  *   output_conv2.2 1x1 32->1 + Sigmoid * max_depth          external/depth_anything_v2/dpt.py:111-113,190

@@ -32,15 +32,9 @@
 
 PRV2_NO_PACKED_FP32_BEGIN  // (common.h)
 
-namespace prv2 {
+#include "coarse_taps_walk.h"  // fma4, knot_cell, roi_axis and the gather's column walk (shared with the gate kernels' epilogue)
 
-__device__ __forceinline__ void fma4(float4& a, float w, const float4& v) {
-  a.x = fmaf(w, v.x, a.x);
-  a.y = fmaf(w, v.y, a.y);
-  a.z = fmaf(w, v.z, a.z);
-  a.w = fmaf(w, v.w, a.w);
-}
-__device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+namespace prv2 {
 
 // weights of the rows (k - 1, k, k + 1) for the position k + o * b, o in -2 .. 2, b <= 1/2 (clamped rows replicate: roi_align's
 // ``x <= 0 -> 0`` / ``lo >= size - 1 -> lo = hi = size - 1`` rules)
@@ -116,35 +110,8 @@ __global__ void __launch_bounds__(256) tap_knots_kernel(const float* __restrict_
     for (int c = 0; c < 3; ++c) *reinterpret_cast<float4*>(V + ((int64_t)(3 * k + a) * (3 * W) + 3 * m + c) * ldv + ch) = acc[a][c];
 }
 
-// the cell of the knot grid {k - b, k, k + b} (index 3k, 3k + 1, 3k + 2; n coarse samples) that holds position v, and the weight of
-// its upper knot.  Below the first / above the last knot U is constant (every shifted sample is clamped there).
-struct KnotCell {
-  int i0, i1;
-  float t;
-};
-__device__ __forceinline__ KnotCell knot_cell(float v, int n, float b) {
-  const float kf = floorf(v), f = v - kf;
-  const int k = (int)kf;
-  KnotCell c;
-  if (f < b) { c.i0 = 3 * k + 1; c.t = f / b; }
-  else if (f < 1.0f - b) { c.i0 = 3 * k + 2; c.t = (f - b) / (1.0f - 2.0f * b); }
-  else { c.i0 = 3 * k + 3; c.t = (f - (1.0f - b)) / b; }
-  c.i1 = c.i0 + 1;
-  if (c.i0 < 0) { c.i0 = 0; c.i1 = 0; }
-  if (c.i1 > 3 * n - 1) { c.i1 = 3 * n - 1; c.i0 = min(c.i0, 3 * n - 1); }
-  return c;
-}
-
-// roi_align's clamped axis sample: (lo, hi, weight of hi)
-__device__ __forceinline__ void roi_axis(float v, int n, int& lo, int& hi, float& l) {
-  float vv = v <= 0.f ? 0.f : v;
-  lo = (int)vv;
-  if (lo >= n - 1) { hi = lo = n - 1; vv = (float)lo; } else hi = lo + 1;
-  l = vv - (float)lo;
-}
-
 // B[k, i, j, ch] = U(ys(i), xs(j)) - (taps hidden by the zero padding at the tile border).  Thread = (column j, 4 channels) x R
-// output rows; the x-interpolated knot rows of the previous output row are kept (consecutive rows share one knot row).
+// output rows: coarse_taps_walk (coarse_taps_walk.h) with a sink that stores each row to HBM.
 template <int R, bool NT = false, bool FR = false>
 __global__ void __launch_bounds__(256) tap_gather_kernel(const float* __restrict__ V, const float* __restrict__ G, int H, int W, int C, int ldv,
                                                          int ldg, float kbh, float kbw, const float* __restrict__ boxes, float scale, int oh,
@@ -154,79 +121,10 @@ __global__ void __launch_bounds__(256) tap_gather_kernel(const float* __restrict
   if (t >= (unsigned)ow * cg) return;
   const int px = (int)(t / cg), ch = (int)(t - (unsigned)px * cg) * 4;
   const int py0 = blockIdx.y * R, k = blockIdx.z;
-  const float* b;
-  if constexpr (FR) {
-    b = boxes + 5 * k;
-    const int64_t f = min(max((int)b[0], 0), B - 1);
-    G += f * H * W * ldg;
-    V += f * 9 * H * W * ldv;
-    ++b;
-  } else {
-    b = boxes + 4 * k;
-  }
-  // torchvision roi_align_forward_kernel_impl, aligned=True (as gather.hip::roi_align_kernel)
-  const float rsw = b[0] * scale - 0.5f, rsh = b[1] * scale - 0.5f;
-  const float rew = b[2] * scale - 0.5f, reh = b[3] * scale - 0.5f;
-  const float bin_h = (reh - rsh) / (float)oh, bin_w = (rew - rsw) / (float)ow;
-  const float x = rsw + (float)px * bin_w + .5f * bin_w;
-  const KnotCell cx = knot_cell(x, W, kbw);
-  const int W3 = 3 * W;
-  const bool xedge = px == 0 || px == ow - 1;
-  int c0 = -1, c1 = -1;  // knot rows whose x-interpolated values are in registers
-  float4 h0 = zero4(), h1 = zero4();
-  auto hrow = [&](int i) {
-    const float4 a = *reinterpret_cast<const float4*>(V + ((int64_t)i * W3 + cx.i0) * ldv + ch);
-    const float4 c = *reinterpret_cast<const float4*>(V + ((int64_t)i * W3 + cx.i1) * ldv + ch);
-    float4 r = zero4();
-    fma4(r, 1.0f - cx.t, a);
-    fma4(r, cx.t, c);
-    return r;
-  };
-  auto tap_sample = [&](int tap, float yy, float xx) {  // Bil(G_tap; yy, xx)
-    int yl, yh, xl, xh;
-    float ly, lx;
-    roi_axis(yy, H, yl, yh, ly);
-    roi_axis(xx, W, xl, xh, lx);
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    const float* g = G + tap * C + ch;
-    float4 r = zero4();
-    const float4 a0 = *reinterpret_cast<const float4*>(g + ((int64_t)yl * W + xl) * ldg);
-    const float4 a1 = *reinterpret_cast<const float4*>(g + ((int64_t)yl * W + xh) * ldg);
-    const float4 a2 = *reinterpret_cast<const float4*>(g + ((int64_t)yh * W + xl) * ldg);
-    const float4 a3 = *reinterpret_cast<const float4*>(g + ((int64_t)yh * W + xh) * ldg);
-    fma4(r, hy * hx, a0);
-    fma4(r, hy * lx, a1);
-    fma4(r, ly * hx, a2);
-    fma4(r, ly * lx, a3);
-    return r;
-  };
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int py = py0 + r;
-    if (py >= oh) break;
-    const float y = rsh + (float)py * bin_h + .5f * bin_h;
-    const KnotCell cy = knot_cell(y, H, kbh);
-    float4 lo, hi;
-    if (cy.i0 == c0) lo = h0; else if (cy.i0 == c1) lo = h1; else lo = hrow(cy.i0);
-    if (cy.i1 == cy.i0) hi = lo; else if (cy.i1 == c1) hi = h1; else if (cy.i1 == c0) hi = h0; else hi = hrow(cy.i1);
-    c0 = cy.i0; h0 = lo; c1 = cy.i1; h1 = hi;
-    float4 acc = zero4();
-    fma4(acc, 1.0f - cy.t, lo);
-    fma4(acc, cy.t, hi);
-    const bool top = py == 0, bot = py == oh - 1;
-    if (top || bot || xedge) {  // (xedge is wave-uniform: a wave is one pixel column; top / bot are block-uniform)
-      const bool left = px == 0, right = px == ow - 1;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const bool hidden = (ky == 0 && top) || (ky == 2 && bot) || (kx == 0 && left) || (kx == 2 && right);
-          if (hidden) {
-            const float4 s = tap_sample(ky * 3 + kx, y + (float)(ky - 1) * kbh, x + (float)(kx - 1) * kbw);
-            acc.x -= s.x; acc.y -= s.y; acc.z -= s.z; acc.w -= s.w;
-          }
-        }
-    }
+  TapTables tt = {V, G, H, W, C, ldv, ldg, kbh, kbw};
+  const float* b = tap_tile_box(tt, boxes, k, FR ? B : 0);
+  const int pxs[1] = {px};
+  coarse_taps_walk<R, 1>(tt, b, scale, oh, ow, pxs, ch, py0, [&](int, int, int py, const float4& acc) {
     float4* dst = reinterpret_cast<float4*>(out + (((int64_t)k * oh + py) * ow + px) * ldo + ch);
     if constexpr (NT) {
       typedef float f32x4n __attribute__((ext_vector_type(4)));
@@ -234,7 +132,7 @@ __global__ void __launch_bounds__(256) tap_gather_kernel(const float* __restrict
     } else {
       *dst = acc;
     }
-  }
+  });
 }
 
 static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }

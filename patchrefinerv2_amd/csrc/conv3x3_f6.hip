@@ -33,6 +33,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+// BUILD NOTE: this file is compiled with packed fp32 math OFF for the whole device pass (Makefile: NO_PK_FLAGS): the gate kernels' epilogue runs
+// the coarse-tap walk (coarse_taps_walk.h; BUILD NOTE in coarse_taps.hip).  A function attribute on the kernels (common.h) does not do here: the
+// runtime's and the device library's helpers (threadIdx, __shfl_xor, ...) lack it and are then CALLED instead of inlined.
 #include "igemm.h"
 #include "conv3x3_gate_epi.h"
 
@@ -668,9 +671,29 @@ extern "C" int prv2_conv3x3_f6(const prv2_conv_desc* d, const float* x, const vo
   return 0;
 }
 
+static int ln_gate_f6_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
+                           const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                           const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream);
+
 extern "C" int prv2_conv3x3_ln_gate_f6(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
                                        const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias, const float* mul,
                                        const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream) {
+  return ln_gate_f6_impl(d, x, w_packed, bias, pre, ld_pre, nullptr, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, x_scale, out_scale, range_word, y,
+                         stream);
+}
+
+extern "C" int prv2_conv3x3_ln_gate_f6_taps(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const prv2_tap_tables* taps,
+                                            const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                                            const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y,
+                                            void* stream) {
+  PRV2_REQUIRE(taps, "conv3x3_ln_gate_f6_taps: null tap tables");
+  return ln_gate_f6_impl(d, x, w_packed, bias, nullptr, 0, taps, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, x_scale, out_scale, range_word, y,
+                         stream);
+}
+
+static int ln_gate_f6_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
+                           const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                           const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream) {
   PRV2_REQUIRE(d && x && w_packed && y && ln_weight && ln_bias && gate_w_packed, "conv3x3_ln_gate_f6: null pointer (the LayerNorm and the gate stage are part of the kernel)");
   PRV2_REQUIRE(f6_shape_ok(d), "conv3x3_ln_gate_f6: 3x3 s1 p1, cout 256, cin %% 64 == 0, width >= 16 (got %dx%d %d->%d k%d s%d)", d->h, d->w, d->cin, d->cout, d->kh,
                d->stride);
@@ -699,6 +722,7 @@ extern "C" int prv2_conv3x3_ln_gate_f6(const prv2_conv_desc* d, const float* x, 
   PRV2_REQUIRE(!res || (d->ld_res >= d->cout && d->ld_res % 4 == 0 && aligned16(res) && px * d->ld_res < (1LL << 29)), "conv3x3_ln_gate_f6: res layout");
   PRV2_REQUIRE(!bias || aligned16(bias), "conv3x3_ln_gate_f6: bias alignment");
   gp.gate_w = gate_w_packed; gp.gate_bias = gate_bias; gp.pre = pre; gp.ld_pre = ld_pre;
+  if (taps && gate_taps_fill(gp, taps, d, "conv3x3_ln_gate_f6_taps")) return 1;
   gp.x_x2 = x2; gp.mul_x2 = mul && x2 ? 1 : 0; gp.y_x2 = 0;
   gp.f6_x_scale = x_scale; gp.f6_out_scale = out_scale; gp.f6_range = range_word;
 #ifdef PRV2_GATE_STAMPS

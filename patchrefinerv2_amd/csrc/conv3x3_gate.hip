@@ -23,6 +23,9 @@
 #include <cstdlib>
 #include <type_traits>
 
+// BUILD NOTE: this file is compiled with packed fp32 math OFF for the whole device pass (Makefile: NO_PK_FLAGS): the gate kernels' epilogue runs
+// the coarse-tap walk (coarse_taps_walk.h; BUILD NOTE in coarse_taps.hip).  A function attribute on the kernels (common.h) does not do here: the
+// runtime's and the device library's helpers (threadIdx, __shfl_xor, ...) lack it and are then CALLED instead of inlined.
 #include "igemm.h"
 #include "conv3x3_gate_epi.h"
 
@@ -388,9 +391,29 @@ extern "C" int prv2_conv3x3_ln_gate(const prv2_conv_desc* d, const float* x, con
   return prv2_conv3x3_ln_gate_pre(d, x, w_packed, bias, nullptr, 0, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
 }
 
+static int ln_gate_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
+                        const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed,
+                        const float* gate_bias, const float* mul, const float* res, float* y, void* stream);
+
 extern "C" int prv2_conv3x3_ln_gate_pre(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre,
                                         int32_t ld_pre, const float* ln_weight, const float* ln_bias, const void* gate_w_packed,
                                         const float* gate_bias, const float* mul, const float* res, float* y, void* stream) {
+  return ln_gate_impl(d, x, w_packed, bias, pre, ld_pre, nullptr, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
+}
+
+extern "C" int prv2_conv3x3_ln_gate_taps_supported(const prv2_conv_desc* d) { return d && gate_conv_shape_ok(d) ? 1 : 0; }
+
+extern "C" int prv2_conv3x3_ln_gate_taps(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const prv2_tap_tables* taps,
+                                         const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                                         const float* mul, const float* res, float* y, void* stream) {
+  PRV2_REQUIRE(d && taps && gate_w_packed && ln_weight && d->cout == g256::BN,
+               "conv3x3_ln_gate_taps: the in-kernel gather belongs to the 256-column gate kernels (tables, LayerNorm and gate weights required)");
+  return ln_gate_impl(d, x, w_packed, bias, nullptr, 0, taps, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
+}
+
+static int ln_gate_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
+                        const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed,
+                        const float* gate_bias, const float* mul, const float* res, float* y, void* stream) {
   PRV2_REQUIRE(d && x && w_packed && y && (ln_weight != nullptr) == (ln_bias != nullptr), "conv3x3_ln_gate: null pointer");
   PRV2_REQUIRE(!pre || (ln_weight && ld_pre >= d->cout && ld_pre % 4 == 0 && aligned16(pre) && (long long)d->h * d->w * ld_pre < (1LL << 29)),
                "conv3x3_ln_gate_pre: the addend goes in front of a LayerNorm; [n, h, w, ld_pre >= cout], ld_pre %% 4 == 0, 16-byte aligned");
@@ -429,6 +452,7 @@ extern "C" int prv2_conv3x3_ln_gate_pre(const prv2_conv_desc* d, const float* x,
   gp.gate_bias = gate_bias;
   gp.pre = pre;
   gp.ld_pre = ld_pre;
+  if (taps && gate_taps_fill(gp, taps, d, "conv3x3_ln_gate_taps")) return 1;
   gp.x_x2 = (d->fmt & PRV2_FMT_X_X2) != 0;
   gp.mul_x2 = (d->fmt & PRV2_FMT_MUL_X2) != 0;
   gp.y_x2 = (d->fmt & PRV2_FMT_Y_X2) != 0;

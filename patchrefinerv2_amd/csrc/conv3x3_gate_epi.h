@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "coarse_taps_walk.h"
 #include "igemm.h"
 
 namespace prv2 {
@@ -38,10 +39,33 @@ struct GateConvParams {
   int x_x2, mul_x2, y_x2;  // operand formats (X2 = pre-split, see the head of this file); y_x2: the no-gate, no-LayerNorm kernel
   const float* pre;        // pre-LayerNorm addend [n, h, w, ld_pre] (prv2_conv3x3_ln_gate_pre: the conv's coarse half, coarse_taps.hip), or null
   int ld_pre;
+  // ... or, instead of ``pre``, the tables it would have been gathered from (taps.V set; prv2_conv3x3_ln_gate_taps / _f6_taps): the epilogue
+  // runs the gather's column walk itself and the addend never exists in HBM.  Image n of the conv is tile n of ``tap_boxes``
+  // ([n, 4], or [n, 5] with the frame in front when tap_frames >= 1); the tile is the conv's h x w map.
+  TapTables taps;
+  const float* tap_boxes;
+  float tap_scale;
+  int tap_frames;
   float f6_x_scale, f6_out_scale;  // conv3x3_c256_gate_f6_kernel (conv3x3_f6.hip): the power-of-two operand scales of the fp16 + fp6 main loop
   unsigned* f6_range;              // ... and its range word (or null)
   long long* stamps;       // -DPRV2_GATE_STAMPS builds (tools/probes/gate_phase_stamps.sh): 10 s_memtime stamps per wave
 };
+
+// host: the tap tables of prv2_conv3x3_ln_gate_taps / _f6_taps -> gp (the checks of coarse_taps.hip's gather for 256 channels, tile = the conv's map)
+static inline int gate_taps_fill(GateConvParams& gp, const prv2_tap_tables* t, const prv2_conv_desc* d, const char* name) {
+  PRV2_REQUIRE(t && t->v && t->g && t->boxes, "%s: null tap tables", name);
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  PRV2_REQUIRE(d->cout == g256::BN && t->h > 0 && t->w > 0 && t->n_frames >= 0 && t->ldg >= 9 * g256::BN && t->ldg % 4 == 0 && t->ldv >= g256::BN &&
+                   t->ldv % 4 == 0 && al16(t->g) && al16(t->v),
+               "%s: tables of 256 channels, ldg >= 9 * 256, 16-byte aligned rows (ldg=%d ldv=%d)", name, t->ldg, t->ldv);
+  PRV2_REQUIRE(t->knot_bh > 0.f && t->knot_bh <= 0.5f && t->knot_bw > 0.f && t->knot_bw <= 0.5f, "%s: the knot offsets must be in (0, 1/2] (got %g, %g)", name,
+               (double)t->knot_bh, (double)t->knot_bw);
+  gp.taps = TapTables{t->v, t->g, t->h, t->w, g256::BN, t->ldv, t->ldg, t->knot_bh, t->knot_bw};
+  gp.tap_boxes = t->boxes;
+  gp.tap_scale = t->spatial_scale;
+  gp.tap_frames = t->n_frames;
+  return 0;
+}
 
 #ifdef PRV2_GATE_STAMPS
 #define PRV2_STAMP(i)                                                                                      \
@@ -89,6 +113,7 @@ __device__ __forceinline__ void c256_epilogue(const GateConvParams& gp, float* s
   // row, 16 rows per thread, all requested here -- they land while the C tile is written -- and added to the C tile in LDS
   constexpr int PC4 = BN / 4, PRPP = 512 / PC4, PNR = ROWS / PRPP;
   const bool has_pre = gp.pre != nullptr;  // block-uniform
+  const bool has_taps = gp.taps.V != nullptr;  // block-uniform (host: never both)
   f32x4 pv[PNR];
   if (has_pre) {
     const __amdgpu_buffer_rsrc_t pre_rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -116,6 +141,21 @@ __device__ __forceinline__ void c256_epilogue(const GateConvParams& gp, float* s
       f32x4* q = reinterpret_cast<f32x4*>(&csm[(tid / PC4 + i * PRPP) * CLD + (tid % PC4) * 4]);
       *q = *q + pv[i];
     }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+  if (has_taps) {
+    // the same rows from the tap tables: wave w owns the tile's columns w and w + 8 for all 8 rows (rr = w + 8 i above), lane = 4 channels --
+    // tap_gather_kernel's walk, both columns at once (they share the rows' knot cells: 4 loads in flight per new knot row, from
+    // tables that neighbouring tiles share in L2).  Column, row and hence the border branch are wave-uniform.  Columns beyond the image:
+    // clamped like the addresses above; rows beyond it are left alone (neither is stored).
+    TapTables tt = gp.taps;
+    const float* const box = tap_tile_box(tt, gp.tap_boxes, n_img, gp.tap_frames);
+    const int wv = __builtin_amdgcn_readfirstlane(wave);
+    const int cols[2] = {min(x0 + wv, p.W - 1), min(x0 + wv + 8, p.W - 1)};
+    coarse_taps_walk<TH, 2>(tt, box, gp.tap_scale, p.H, p.W, cols, lane * 4, y0, [&](int r, int c, int, const float4& a) {
+      f32x4* q = reinterpret_cast<f32x4*>(&csm[(r * TW + wv + 8 * c) * CLD + lane * 4]);
+      *q = *q + f32x4{a.x, a.y, a.z, a.w};
+    });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
   PRV2_STAMP(3);

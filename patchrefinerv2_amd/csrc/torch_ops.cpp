@@ -210,10 +210,11 @@ Tensor pack_gate_weight(const Tensor& w) {
   return packed;
 }
 
-Tensor conv3x3_ln_gate(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const Tensor& ln_weight, const Tensor& ln_bias,
-                       const optional<Tensor>& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul,
-                       const optional<Tensor>& res, int64_t act, bool relu_in, int64_t prec, double ln_eps, const optional<Tensor>& out,
-                       const optional<Tensor>& pre, int64_t fmt) {
+// (taps: the tables of conv3x3_ln_gate_taps below instead of ``pre``, or null)
+Tensor conv3x3_ln_gate_any(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const Tensor& ln_weight, const Tensor& ln_bias,
+                           const optional<Tensor>& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul,
+                           const optional<Tensor>& res, int64_t act, bool relu_in, int64_t prec, double ln_eps, const optional<Tensor>& out,
+                           const optional<Tensor>& pre, int64_t fmt, const prv2_tap_tables* taps) {
   const int64_t ldx = nhwc_ld(x, "x");
   dev_f32(w_packed, "w_packed");
   const int64_t n = x.size(0), h = x.size(1), w = x.size(2), cin = x.size(3), cout = ln_weight.numel();
@@ -240,10 +241,24 @@ Tensor conv3x3_ln_gate(const Tensor& x, const Tensor& w_packed, const optional<T
   int32_t ld_pre = 0;
   const float* pp = aux(pre, "pre", ld_pre);
   Launch L(x);
+  if (taps) {
+    TORCH_CHECK(prv2_conv3x3_ln_gate_taps_supported(&d) && gate_w_packed.has_value(), "prv2::conv3x3_ln_gate_taps: the in-kernel gather belongs to the 256-column gate kernels");
+    ok(prv2_conv3x3_ln_gate_taps(&d, x.data_ptr<float>(), w_packed.data_ptr(), opt_ptr(bias, "bias", cout), taps, opt_ptr(ln_weight, "ln_weight", cout),
+                                 opt_ptr(ln_bias, "ln_bias", cout), gate_w_packed->data_ptr(), opt_ptr(gate_bias, "gate_bias", cout), pm, pr,
+                                 y.data_ptr<float>(), L.stream), "conv3x3_ln_gate_taps");
+    return y;
+  }
   ok(prv2_conv3x3_ln_gate_pre(&d, x.data_ptr<float>(), w_packed.data_ptr(), opt_ptr(bias, "bias", cout), pp, ld_pre, opt_ptr(ln_weight, "ln_weight", cout),
                               opt_ptr(ln_bias, "ln_bias", cout), gate_w_packed.has_value() ? gate_w_packed->data_ptr() : nullptr,
                               opt_ptr(gate_bias, "gate_bias", cout), pm, pr, y.data_ptr<float>(), L.stream), "conv3x3_ln_gate");
   return y;
+}
+
+Tensor conv3x3_ln_gate(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const Tensor& ln_weight, const Tensor& ln_bias,
+                       const optional<Tensor>& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul,
+                       const optional<Tensor>& res, int64_t act, bool relu_in, int64_t prec, double ln_eps, const optional<Tensor>& out,
+                       const optional<Tensor>& pre, int64_t fmt) {
+  return conv3x3_ln_gate_any(x, w_packed, bias, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, act, relu_in, prec, ln_eps, out, pre, fmt, nullptr);
 }
 
 // shared by conv3x3_tail / conv3x3_pre: the descriptor of a 3x3 s1 p1 conv over x -> y
@@ -323,10 +338,10 @@ void conv3x3_f6(const Tensor& x, const Tensor& w_packed, const optional<Tensor>&
 }
 
 // include/prv2.h::prv2_conv3x3_ln_gate_f6: the GatedConvUnit tail with its 3x3 conv in the fp16 + fp6 arithmetic; x / mul: the unit's pre-split ``out`` (raw buffers)
-void conv3x3_ln_gate_f6(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const optional<Tensor>& pre, const Tensor& ln_weight,
-                        const Tensor& ln_bias, const Tensor& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul,
-                        const optional<Tensor>& res, int64_t act, double ln_eps, double x_scale, double out_scale, const optional<Tensor>& range, Tensor out,
-                        int64_t fmt) {
+void conv3x3_ln_gate_f6_any(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const optional<Tensor>& pre, const Tensor& ln_weight,
+                            const Tensor& ln_bias, const Tensor& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul,
+                            const optional<Tensor>& res, int64_t act, double ln_eps, double x_scale, double out_scale, const optional<Tensor>& range, Tensor out,
+                            int64_t fmt, const prv2_tap_tables* taps) {
   dev_f32(w_packed, "w_packed");
   const int64_t cout = ln_weight.numel();
   TORCH_CHECK(w_packed.numel() * 4 == prv2_conv3x3_f6_weight_bytes((int)cout, (int)x.size(3)), "prv2::conv3x3_ln_gate_f6: w_packed does not match a 3x3 ", x.size(3), " -> ", cout, " conv");
@@ -345,9 +360,22 @@ void conv3x3_ln_gate_f6(const Tensor& x, const Tensor& w_packed, const optional<
   }
   TORCH_CHECK(prv2_conv3x3_f6_supported(&d), "prv2::conv3x3_ln_gate_f6: layer not covered (3x3 s1 p1, cout 256, cin % 64 == 0, width >= 16)");
   Launch L(x);
+  if (taps) {
+    ok(prv2_conv3x3_ln_gate_f6_taps(&d, x.data_ptr<float>(), w_packed.data_ptr(), opt_ptr(bias, "bias", cout), taps, opt_ptr(ln_weight, "ln_weight", cout),
+                                    opt_ptr(ln_bias, "ln_bias", cout), gate_w_packed.data_ptr(), opt_ptr(gate_bias, "gate_bias", cout), pm, pr, (float)x_scale,
+                                    (float)out_scale, rw, out.data_ptr<float>(), L.stream), "conv3x3_ln_gate_f6_taps");
+    return;
+  }
   ok(prv2_conv3x3_ln_gate_f6(&d, x.data_ptr<float>(), w_packed.data_ptr(), opt_ptr(bias, "bias", cout), pp, ld_pre, opt_ptr(ln_weight, "ln_weight", cout),
                              opt_ptr(ln_bias, "ln_bias", cout), gate_w_packed.data_ptr(), opt_ptr(gate_bias, "gate_bias", cout), pm, pr, (float)x_scale,
                              (float)out_scale, rw, out.data_ptr<float>(), L.stream), "conv3x3_ln_gate_f6");
+}
+
+void conv3x3_ln_gate_f6(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const optional<Tensor>& pre, const Tensor& ln_weight,
+                        const Tensor& ln_bias, const Tensor& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul,
+                        const optional<Tensor>& res, int64_t act, double ln_eps, double x_scale, double out_scale, const optional<Tensor>& range, Tensor out,
+                        int64_t fmt) {
+  conv3x3_ln_gate_f6_any(x, w_packed, bias, pre, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, act, ln_eps, x_scale, out_scale, range, out, fmt, nullptr);
 }
 
 // include/prv2.h::prv2_upconv5x5*: output_conv2[0] o output_conv1 o interpolate as one 5x5 conv at u's resolution (csrc/upconv5.hip)
@@ -852,6 +880,40 @@ Tensor coarse_tap_gather_frames(const Tensor& v, const Tensor& g, double knot_bh
                                    y.data_ptr<float>(), (int)nhwc_ld(y, "out"), L.stream),
      "coarse_tap_gather_frames");
   return y;
+}
+
+// include/prv2.h::prv2_conv3x3_ln_gate_taps / _f6_taps: the gate kernels gather their coarse addend from the tap tables themselves.
+// v [B, 3h, 3w, 256], g [B, h, w, 9 * 256]; boxes [n, 4], or [n, 5] (frame in front) with ``frames`` set -- one row per image of x
+prv2_tap_tables tap_tables_of(const Tensor& v, const Tensor& g, const Tensor& boxes, bool frames, double knot_bh, double knot_bw, double spatial_scale,
+                              int64_t n, const char* name) {
+  const int64_t ldv = nhwc_ld(v, "v"), ldg = nhwc_ld(g, "g"), cout = v.size(3);
+  if (frames) frame_tiles(boxes, 5, at::kFloat, name);
+  else dev_f32(boxes, "boxes");
+  TORCH_CHECK(boxes.dim() == 2 && boxes.size(0) == n && boxes.size(1) == (frames ? 5 : 4) && boxes.is_contiguous(), "prv2::", name, ": boxes [n, ", frames ? 5 : 4,
+              "], one row per image of x");
+  TORCH_CHECK(cout == 256 && g.size(3) == 9 * cout && v.size(0) == g.size(0) && (frames || g.size(0) == 1) && v.size(1) == 3 * g.size(1) && v.size(2) == 3 * g.size(2),
+              "prv2::", name, ": v [B, 3h, 3w, 256], g [B, h, w, 9 * 256]");
+  prv2_tap_tables t = {};
+  t.v = v.data_ptr<float>(); t.g = g.data_ptr<float>(); t.boxes = boxes.data_ptr<float>();
+  t.n_frames = frames ? (int32_t)g.size(0) : 0; t.h = (int32_t)g.size(1); t.w = (int32_t)g.size(2); t.ldv = (int32_t)ldv; t.ldg = (int32_t)ldg;
+  t.knot_bh = (float)knot_bh; t.knot_bw = (float)knot_bw; t.spatial_scale = (float)spatial_scale;
+  return t;
+}
+
+Tensor conv3x3_ln_gate_taps(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const Tensor& ln_weight, const Tensor& ln_bias,
+                            const Tensor& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul, const optional<Tensor>& res,
+                            int64_t act, bool relu_in, int64_t prec, double ln_eps, const optional<Tensor>& out, int64_t fmt, const Tensor& v, const Tensor& g,
+                            const Tensor& boxes, bool frames, double knot_bh, double knot_bw, double spatial_scale) {
+  const prv2_tap_tables t = tap_tables_of(v, g, boxes, frames, knot_bh, knot_bw, spatial_scale, x.size(0), "conv3x3_ln_gate_taps");
+  return conv3x3_ln_gate_any(x, w_packed, bias, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, act, relu_in, prec, ln_eps, out, c10::nullopt, fmt, &t);
+}
+
+void conv3x3_ln_gate_f6_taps(const Tensor& x, const Tensor& w_packed, const optional<Tensor>& bias, const Tensor& ln_weight, const Tensor& ln_bias,
+                             const Tensor& gate_w_packed, const optional<Tensor>& gate_bias, const optional<Tensor>& mul, const optional<Tensor>& res,
+                             int64_t act, double ln_eps, double x_scale, double out_scale, const optional<Tensor>& range, Tensor out, int64_t fmt,
+                             const Tensor& v, const Tensor& g, const Tensor& boxes, bool frames, double knot_bh, double knot_bw, double spatial_scale) {
+  const prv2_tap_tables t = tap_tables_of(v, g, boxes, frames, knot_bh, knot_bw, spatial_scale, x.size(0), "conv3x3_ln_gate_f6_taps");
+  conv3x3_ln_gate_f6_any(x, w_packed, bias, c10::nullopt, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, act, ln_eps, x_scale, out_scale, range, out, fmt, &t);
 }
 
 // pred [B, k, ph, pw] and tiles [B, k, 2]: frame f's slice of a frame-major list (any frame stride, dense inside a frame -- e.g.
@@ -1472,6 +1534,12 @@ TORCH_LIBRARY(prv2, m) {
   m.def("coarse_tap_knots_frames(Tensor g, int cout, float knot_bh, float knot_bw) -> Tensor");
   m.def("coarse_tap_gather_frames(Tensor v, Tensor g, float knot_bh, float knot_bw, Tensor boxes, float spatial_scale, int oh, int ow, "
         "Tensor(a!)? out=None) -> Tensor");
+  m.def("conv3x3_ln_gate_taps(Tensor x, Tensor w_packed, Tensor? bias, Tensor ln_weight, Tensor ln_bias, Tensor gate_w_packed, Tensor? gate_bias, "
+        "Tensor? mul, Tensor? res, int act, bool relu_in, int prec, float ln_eps, Tensor(a!)? out, int fmt, Tensor v, Tensor g, Tensor boxes, bool frames, "
+        "float knot_bh, float knot_bw, float spatial_scale) -> Tensor");
+  m.def("conv3x3_ln_gate_f6_taps(Tensor x, Tensor w_packed, Tensor? bias, Tensor ln_weight, Tensor ln_bias, Tensor gate_w_packed, Tensor? gate_bias, "
+        "Tensor? mul, Tensor? res, int act, float ln_eps, float x_scale, float out_scale, Tensor(a!)? range, Tensor(b!) out, int fmt, Tensor v, Tensor g, "
+        "Tensor boxes, bool frames, float knot_bh, float knot_bw, float spatial_scale) -> ()");
   m.def("blend_init_frames(Tensor(a!) avg, Tensor(b!) cnt, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
   m.def("blend_update_frames(Tensor(a!) avg, Tensor(b!) cnt, Tensor pred, Tensor mask, Tensor tiles, int th, int tw) -> ()");
   m.def("blend_resize_frames(Tensor avg, Tensor cnt, int oh, int ow) -> (Tensor, Tensor)");
@@ -1572,6 +1640,8 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("roi_align_frames", &roi_align_frames);
   m.impl("coarse_tap_knots_frames", &coarse_tap_knots_frames);
   m.impl("coarse_tap_gather_frames", &coarse_tap_gather_frames);
+  m.impl("conv3x3_ln_gate_taps", &conv3x3_ln_gate_taps);
+  m.impl("conv3x3_ln_gate_f6_taps", &conv3x3_ln_gate_f6_taps);
   m.impl("blend_init_frames", &blend_init_frames);
   m.impl("blend_update_frames", &blend_update_frames);
   m.impl("blend_resize_frames", &blend_resize_frames);

@@ -486,12 +486,15 @@ class BiDirectionalFusion(_EncDec):
         ``out`` only (K = F instead of 2F), ``c_feat`` is never gathered."""
         out = Feat(torch.empty((x.n, x.h, x.w, F_), device=x.device, dtype=torch.float32), x2=F_ == 256)  # (256: the gate kernel's operand format)
         BiDirectionalFusion._unit_conv(u, x, out, x)                                                # conv(relu(x)) + x
-        pre = taps.gather(coarse.boxes, coarse.scale, x.h, x.w)                                      # conv3x3(c_feat; W[:, F:]) per tile
+        # conv3x3(c_feat; W[:, F:]) per tile: gathered inside the 256-column gate kernels, materialised for the narrower ones
+        if ops.conv3x3_ln_gate_taps_supported(out, u["f0a"]):
+            pre = dict(taps=taps, boxes=coarse.boxes, spatial_scale=coarse.scale)
+        else:
+            pre = dict(pre=taps.gather(coarse.boxes, coarse.scale, x.h, x.w))
         cw6 = u.get("f0a_f6")
         if cw6 is not None and out.x2 and ops.conv3x3_f6_supported(x, cw6.cout, cw6.cin):
-            return ops.conv3x3_ln_gate_f6(out, cw6, (u["lnw"], u["lnb"]), u["f3g"], u["f3"].bias, act=ACT_RELU, mul=out, res=res, pre=pre, pre_cin=F_)
-        return ops.conv3x3_ln_gate(out, u["f0a"], (u["lnw"], u["lnb"]), u["f3g"], u["f3"].bias, act=ACT_RELU, mul=out, res=res, pre=pre,
-                                   pre_cin=F_)
+            return ops.conv3x3_ln_gate_f6(out, cw6, (u["lnw"], u["lnb"]), u["f3g"], u["f3"].bias, act=ACT_RELU, mul=out, res=res, pre_cin=F_, **pre)
+        return ops.conv3x3_ln_gate(out, u["f0a"], (u["lnw"], u["lnb"]), u["f3g"], u["f3"].bias, act=ACT_RELU, mul=out, res=res, pre_cin=F_, **pre)
 
     @staticmethod
     def _plain_unit(u, x: Feat, res: Optional[Feat] = None) -> Feat:

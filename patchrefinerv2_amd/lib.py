@@ -50,6 +50,11 @@ class Chain32Desc(C.Structure):  # prv2_chain32_desc
                 ("ldx", C.c_int32), ("ldy", C.c_int32), ("ld_pre", C.c_int32), ("b3", C.c_float), ("ln_eps", C.c_float)]
 
 
+class TapTables(C.Structure):  # prv2_tap_tables
+    _fields_ = [("v", C.c_void_p), ("g", C.c_void_p), ("boxes", C.c_void_p), ("n_frames", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("ldv", C.c_int32), ("ldg", C.c_int32), ("knot_bh", C.c_float), ("knot_bw", C.c_float), ("spatial_scale", C.c_float)]
+
+
 _P, _I, _L, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol include/prv2.h declares
@@ -116,6 +121,9 @@ SIGNATURES = {
     "prv2_pack_conv3x3_f6_weight": (_I, [_P, _F, _P, _I, _I, _P]),
     "prv2_conv3x3_f6": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _F, _F, _P, _P, _P]),
     "prv2_conv3x3_ln_gate_f6": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P]),
+    "prv2_conv3x3_ln_gate_taps_supported": (_I, [C.POINTER(ConvDesc)]),
+    "prv2_conv3x3_ln_gate_taps": (_I, [C.POINTER(ConvDesc), _P, _P, _P, C.POINTER(TapTables), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "prv2_conv3x3_ln_gate_f6_taps": (_I, [C.POINTER(ConvDesc), _P, _P, _P, C.POINTER(TapTables), _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P]),
     "prv2_coarse_tap_knots": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _P]),
     "prv2_coarse_tap_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _I, _F, _I, _I, _P, _I, _P]),
     "prv2_conv_border_bias": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),

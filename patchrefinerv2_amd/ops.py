@@ -744,12 +744,32 @@ def conv3x3_ln_gate_supported(x: Feat, cw: ConvW) -> bool:
     return bool(L.load().prv2_conv3x3_ln_gate_supported(C.byref(_conv_desc(x, cw, roundup(cw.cout, 4), fmt=_gate_fmt(x)))))
 
 
+TAPS_FOLD = os.environ.get("PRV2_TAPS_FOLD", "1") != "0"  # A/B switch: the 256-column gate kernels gather their coarse addend themselves
+
+
+def conv3x3_ln_gate_taps_supported(x: Feat, cw) -> bool:
+    """can the gate kernel that runs this layer take ``CoarseTaps`` tables instead of a gathered ``pre``? (the 256-column kernels)"""
+    if not TAPS_FOLD or cw.cout != 256 or x.c != cw.cin or x.ld % 4:
+        return False
+    return bool(L.load().prv2_conv3x3_ln_gate_taps_supported(C.byref(_conv_desc(x, cw, 256, fmt=_gate_fmt(x)))))
+
+
+def _tap_tables(taps: "CoarseTaps", boxes: torch.Tensor, spatial_scale: float, n: int) -> "L.TapTables":
+    """prv2_tap_tables of ``taps`` for the n tiles ``boxes`` (the checks of ``CoarseTaps.gather``)"""
+    assert boxes.dtype == torch.float32 and boxes.is_cuda and boxes.is_contiguous() and tuple(boxes.shape) == (n, 5 if taps.nf else 4)
+    assert taps.cout == 256 and not taps.v.x2 and not taps.g.x2
+    return L.TapTables(v=taps.v.ptr, g=taps.g.ptr, boxes=boxes.data_ptr(), n_frames=taps.g.n if taps.nf else 0, h=taps.g.h, w=taps.g.w, ldv=taps.v.ld,
+                       ldg=taps.g.ld, knot_bh=taps.kb[0], knot_bw=taps.kb[1], spatial_scale=spatial_scale)
+
+
 def conv3x3_ln_gate(x: Feat, cw: ConvW, ln, gate_w: Optional[torch.Tensor], gate_bias: Optional[torch.Tensor], out: Optional[Feat] = None,
                     *, act: int = ACT_RELU, mul: Optional[Feat] = None, res: Optional[Feat] = None, relu_in: bool = False,
-                    ln_eps: float = 1e-6, pre: Optional[Feat] = None, pre_cin: int = 0) -> Feat:
+                    ln_eps: float = 1e-6, pre: Optional[Feat] = None, pre_cin: int = 0, taps: Optional["CoarseTaps"] = None,
+                    boxes: Optional[torch.Tensor] = None, spatial_scale: float = 1.0) -> Feat:
     """y = mul * sigmoid(conv1x1(act(LN(conv3x3(x) + b))) + gate_bias) (+ res) in one kernel (include/prv2.h::prv2_conv3x3_ln_gate);
     ``gate_w`` None: y = act(LN(conv3x3(x) + b)).  ``pre``: pre-LayerNorm addend [n, h, w, cout] -- the conv's coarse half from
-    ``CoarseTaps.gather`` (prv2_conv3x3_ln_gate_pre), standing for ``pre_cin`` further input channels of the reference's conv."""
+    ``CoarseTaps.gather`` (prv2_conv3x3_ln_gate_pre), standing for ``pre_cin`` further input channels of the reference's conv.
+    ``taps`` + ``boxes`` + ``spatial_scale`` instead of ``pre``: the kernel gathers that addend itself (prv2_conv3x3_ln_gate_taps; same bits)."""
     if out is None:
         out = Feat.alloc(x.n, x.h, x.w, cw.cout, x.device)
     assert (out.n, out.h, out.w, out.c) == (x.n, x.h, x.w, cw.cout) and x.c == cw.cin
@@ -759,29 +779,40 @@ def conv3x3_ln_gate(x: Feat, cw: ConvW, ln, gate_w: Optional[torch.Tensor], gate
     assert not out.x2 and (res is None or not res.x2)
     flops = 2.0 * x.n * x.h * x.w * cw.cout * (cw.cin * 9 + (cw.cout if gate_w is not None else 0))
     if pre is not None:
-        assert (pre.n, pre.h, pre.w, pre.c) == (out.n, out.h, out.w, out.c) and not pre.x2
+        assert taps is None and (pre.n, pre.h, pre.w, pre.c) == (out.n, out.h, out.w, out.c) and not pre.x2
+    boxes = boxes.contiguous() if taps is not None else None
+    tt = _tap_tables(taps, boxes, spatial_scale, x.n) if taps is not None else None
 
     def call():
-        if DISPATCH == "torch":
-            r = lambda f: None if f is None else f.raw()  # noqa: E731
+        r = lambda f: None if f is None else f.raw()  # noqa: E731
+        if tt is not None and DISPATCH == "torch":
+            _tops().conv3x3_ln_gate_taps(x.raw(), cw.w, cw.bias, ln[0], ln[1], gate_w, gate_bias, r(mul), r(res), act, relu_in, cw.prec, ln_eps, out.view(),
+                                         d.fmt, taps.v.view(), taps.g.view(), boxes, bool(taps.nf), *taps.kb, float(spatial_scale))
+        elif tt is not None:
+            _c("conv3x3_ln_gate_taps", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), C.byref(tt), _ptr(ln[0]), _ptr(ln[1]), _ptr(gate_w),
+               _ptr(gate_bias), _ptr(mul), _ptr(res), out.ptr)
+        elif DISPATCH == "torch":
             _tops().conv3x3_ln_gate(x.raw(), cw.w, cw.bias, ln[0], ln[1], gate_w, gate_bias, r(mul), r(res), act, relu_in, cw.prec, ln_eps, out.view(),
                                     r(pre), d.fmt)
         else:
             _c("conv3x3_ln_gate_pre", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(pre), _ld(pre), _ptr(ln[0]), _ptr(ln[1]), _ptr(gate_w),
                _ptr(gate_bias), _ptr(mul), _ptr(res), out.ptr, what="conv3x3_ln_gate")
 
-    coarse = f"(+{pre_cin} coarse)" if pre is not None else ""
+    has_pre = pre is not None or tt is not None
+    coarse = f"(+{pre_cin} coarse)" if has_pre else ""
     PROFILER.launch(_last_kernel, flops, call,
                     shape=f"{cw.cin}{coarse}->{cw.cout}{'->' + str(cw.cout) + ' gate' if gate_w is not None else ''} k3s1 {x.n}x{x.h}x{x.w}",
-                    algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9 if pre is not None else None)
+                    algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9 if has_pre else None)
     return out
 
 
 def conv3x3_ln_gate_f6(x: Feat, cw: ConvWF6, ln, gate_w: torch.Tensor, gate_bias: Optional[torch.Tensor], out: Optional[Feat] = None, *,
                        act: int = ACT_RELU, mul: Optional[Feat] = None, res: Optional[Feat] = None, ln_eps: float = 1e-6,
-                       pre: Optional[Feat] = None, pre_cin: int = 0) -> Feat:
+                       pre: Optional[Feat] = None, pre_cin: int = 0, taps: Optional["CoarseTaps"] = None, boxes: Optional[torch.Tensor] = None,
+                       spatial_scale: float = 1.0) -> Feat:
     """``conv3x3_ln_gate`` with the 3x3 conv in the fp16 + fp6 arithmetic (include/prv2.h::prv2_conv3x3_ln_gate_f6): x and mul in one format -- the unit's
-    pre-split (X2) ``out`` / concat, or the fp32 concat; LayerNorm, gate GEMM (bf16x3) and final stage are the bf16x3 kernel's."""
+    pre-split (X2) ``out`` / concat, or the fp32 concat; LayerNorm, gate GEMM (bf16x3) and final stage are the bf16x3 kernel's.  ``taps`` + ``boxes`` +
+    ``spatial_scale`` instead of ``pre``: prv2_conv3x3_ln_gate_f6_taps."""
     x2 = bool(getattr(x, "x2", False))
     assert x.c == cw.cin and (mul is None or bool(mul.x2) == x2)
     if out is None:
@@ -792,19 +823,29 @@ def conv3x3_ln_gate_f6(x: Feat, cw: ConvWF6, ln, gate_w: torch.Tensor, gate_bias
     d = _conv_desc(x, cw, out.ld, act=act, ld_mul=_ld(mul), ld_res=_ld(res), ln_eps=ln_eps, fmt=_gate_fmt(x, mul))
     out_scale = 1.0 / (cw.x_scale * cw.w_scale)
     flops = 2.0 * x.n * x.h * x.w * cw.cout * (cw.cin * 9 + cw.cout)
+    assert pre is None or taps is None
+    boxes = boxes.contiguous() if taps is not None else None
+    tt = _tap_tables(taps, boxes, spatial_scale, x.n) if taps is not None else None
 
     def call():
-        if DISPATCH == "torch":
-            r = lambda f: None if f is None else f.raw()  # noqa: E731
+        r = lambda f: None if f is None else f.raw()  # noqa: E731
+        if tt is not None and DISPATCH == "torch":
+            _tops().conv3x3_ln_gate_f6_taps(x.raw(), cw.w, cw.bias, ln[0], ln[1], gate_w, gate_bias, r(mul), r(res), act, ln_eps, cw.x_scale, out_scale,
+                                            cw.range, out.view(), d.fmt, taps.v.view(), taps.g.view(), boxes, bool(taps.nf), *taps.kb, float(spatial_scale))
+        elif tt is not None:
+            _c("conv3x3_ln_gate_f6_taps", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), C.byref(tt), _ptr(ln[0]), _ptr(ln[1]), _ptr(gate_w),
+               _ptr(gate_bias), _ptr(mul), _ptr(res), cw.x_scale, out_scale, _ptr(cw.range), out.ptr)
+        elif DISPATCH == "torch":
             _tops().conv3x3_ln_gate_f6(x.raw(), cw.w, cw.bias, r(pre), ln[0], ln[1], gate_w, gate_bias, r(mul), r(res), act, ln_eps, cw.x_scale, out_scale,
                                        cw.range, out.view(), d.fmt)
         else:
             _c("conv3x3_ln_gate_f6", C.byref(d), x.ptr, cw.w.data_ptr(), _ptr(cw.bias), _ptr(pre), _ld(pre), _ptr(ln[0]), _ptr(ln[1]), _ptr(gate_w),
                _ptr(gate_bias), _ptr(mul), _ptr(res), cw.x_scale, out_scale, _ptr(cw.range), out.ptr)
 
-    coarse = f"(+{pre_cin} coarse)" if pre is not None else ""
+    has_pre = pre is not None or tt is not None
+    coarse = f"(+{pre_cin} coarse)" if has_pre else ""
     PROFILER.launch(_last_kernel, flops, call, shape=f"{cw.cin}{coarse}->{cw.cout}->{cw.cout} gate k3s1 {x.n}x{x.h}x{x.w}",
-                    algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9 if pre is not None else None)
+                    algo=flops + 2.0 * x.n * x.h * x.w * cw.cout * pre_cin * 9 if has_pre else None)
     return out
 
 

@@ -54,7 +54,9 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        # mesh export: the cloud's vertex records and the face records over them
        "mesh_pack",
        # stereo export: the right-eye view as scanlines, and its source-column maps
-       "stereo_rows", "stereo_source")
+       "stereo_rows", "stereo_source",
+       # the gate kernels with the coarse-tap gather inside (tables instead of ``pre``)
+       "conv3x3_ln_gate_taps", "conv3x3_ln_gate_f6_taps")
 _loaded = False
 
 

@@ -23,6 +23,9 @@ if which == "pk":
     assert len(others) >= 10, "the in-tree objects of the other sources are needed (make -C patchrefinerv2_amd/csrc)"
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, *others, obj], check=True, capture_output=True)
     os.environ["PRV2_HIP_LIB"] = so
+    # the control is about tap_gather_kernel's packed code: every coarse addend of the frame goes through it, as before the 256-column gate
+    # kernels learnt to gather theirs themselves (their copy of the walk is built without packed fp32 in the other objects)
+    os.environ["PRV2_TAPS_FOLD"] = "0"
 os.environ["PRV2_DISPATCH"] = "ctypes"
 
 import torch  # noqa: E402
