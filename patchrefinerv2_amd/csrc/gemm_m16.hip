@@ -315,7 +315,8 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) gemm16_kernel(const 
     for (int rr = tid / C4; rr < TM && rr < rows_here; rr += RPP) {
       const f32x4 cv = *reinterpret_cast<const f32x4*>(&smem[rr * CLD + col4 * 4]);
       const long long m = row0 + rr;
-      epi_store<decltype(act_c)::value>(p, ec, cv, m, m * p.ldy + ec.co, ln_stats[rr], ln_stats[TM + rr]);
+      // (act_apply_bf, as the lean loop above and gemm_ss.hip: GELU with gamma / res2 / LN must give the bits the size-selected twin gives)
+      epi_store<decltype(act_c)::value, true>(p, ec, cv, m, m * p.ldy + ec.co, ln_stats[rr], ln_stats[TM + rr]);
     }
   });
 }

@@ -246,8 +246,10 @@ __device__ __forceinline__ void dispatch_act(int act, F&& f) {
   }
 }
 
-// m = dense output pixel index (for mul/res/res2), o = element offset of y[m, co]; ACT >= 0: compile-time activation
-template <int ACT = -1>
+// m = dense output pixel index (for mul/res/res2), o = element offset of y[m, co]; ACT >= 0: compile-time activation;
+// BF_ACT: the activation formulas of the bf16-mode store loops (act_apply_bf: gelu_fast) -- for a kernel whose other store path, or whose
+// size-selected twin, uses them (gemm16_kernel / gemm_ss.hip): a layer's bits must not depend on which of them ran
+template <int ACT = -1, bool BF_ACT = false>
 __device__ __forceinline__ void epi_store(const IgemmParams& p, const EpiCols& c, const f32x4 cv, long long m, long long o,
                                           float ln_mean = 0.f, float ln_rstd = 1.f) {
   float v[4] = {cv.x, cv.y, cv.z, cv.w};
@@ -268,7 +270,7 @@ __device__ __forceinline__ void epi_store(const IgemmParams& p, const EpiCols& c
   for (int e = 0; e < 4; ++e) {
     float t = v[e] + c.bias[e];
     if (p.ln_w) t = (t - ln_mean) * ln_rstd * c.lnw[e] + c.lnb[e];
-    t = act_apply(t, ACT >= 0 ? ACT : p.act);
+    t = BF_ACT ? act_apply_bf(t, ACT >= 0 ? ACT : p.act) : act_apply(t, ACT >= 0 ? ACT : p.act);
     if (p.gamma) t *= c.gam[e];
     if (p.mul) t = mulv[e] * t;
     if (p.res) t += resv[e];

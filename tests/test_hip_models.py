@@ -552,6 +552,28 @@ def test_batching_independence(P):
     for _ in range(3):
         d, _ = _run(m, c, "r8")
         assert torch.equal(a, d)
+    # the headline path: PatchRefinerPlus with the tap tables and the fused 32-channel chains, in bf16x3 and in fp16 + fp6 (the V1 model above
+    # crosses none of the size-dependent kernel choices of DESIGN.md's table except by luck)
+    from patchrefinerv2_amd import ops
+    c = E2E_V2
+    for prec in ("bf16x3", "f16f6"):
+        m = _build("PatchRefinerPlus", c, e2e_v2_sd(), prec=prec)
+        a, _ = _run(m, c, "r4")
+        if prec == "f16f6":
+            # forward runs ops.F6Range.check behind every frame; a frame that moved a layer's power-of-two input scale EARLY (no recompute) was
+            # computed under the old one: the frame to compare against is the first one after which the calibrated scales stand
+            assert m.refiner_fusion_model.f16f6 and m.f6_guarded_frames == 1
+            for _ in range(3):
+                if not ops.F6Range.moved:
+                    break
+                a, _ = _run(m, c, "r4")
+            assert not ops.F6Range.moved
+        for max_batch, n_streams in ((1, 1), (3, 1), (7, 1), (3, 3)):
+            m.max_batch, m.n_streams = max_batch, n_streams
+            d, _ = _run(m, c, "r4")
+            assert prec != "f16f6" or not ops.F6Range.moved  # (every compared frame ran under the same scales)
+            nd = int((a != d).sum())
+            assert torch.equal(a, d), f"{prec} max_batch={max_batch} n_streams={n_streams}: {nd} pixels differ, max |d| = {float((a - d).abs().max()):.3e}"
 
 
 @pytest.mark.parametrize("kind", ["PatchRefiner", "PatchRefinerPlus"])

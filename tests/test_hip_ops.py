@@ -731,6 +731,32 @@ def test_gemm_ss_bit_equal_to_gemm16(P, M, K, N, tile, monkeypatch):
         y16 = P.linear(xd, cw, **kw)
         yss = P.gemm_ss(xs, cw, **kw)
         assert torch.equal(y16, yss), kw.keys()
+    # the whole epilogue cross product, on every gemm_ss variant the switches select (256-row tiles: persistent and one-tile workgroups): gemm16_kernel
+    # leaves its lean store loop for the general epilogue with gamma, so GELU must be the same formula (gelu_fast) in both of them and in gemm_ss
+    differ = []  # every combination is run before the assertion: the message names all that diverge
+    for persist in (("1", "0") if tile == "256" else (None,)):
+        if persist is not None:
+            monkeypatch.setenv("PRV2_GSS_PERSIST", persist)
+        for act in (P.ACT_NONE, P.ACT_GELU):
+            for with_gamma in (False, True):
+                for with_res in (False, True):
+                    kw = dict(act=act, gamma=gd if with_gamma else None, res=rd if with_res else None)
+                    y16, yss_ = P.linear(xd, cw, **kw), P.gemm_ss(xs, cw, **kw)
+                    assert P.L.load().prv2_last_kernel().decode().startswith("gemm_ss_kernel<"), P.L.load().prv2_last_kernel().decode()
+                    if not torch.equal(y16, yss_):
+                        differ.append(f"{'GELU' if act else 'none'}{'+gamma' if with_gamma else ''}{'+res' if with_res else ''} (persist={persist}): "
+                                      f"{int((y16 != yss_).sum())} of {y16.numel()} elements, max |d| = {float((y16 - yss_).abs().max()):.3e}")
+            # split-swizzled rows: what the kernel writes == the split of the fp32 rows of the other kernel
+            if not torch.equal(P.split_ss(P.linear(xd, cw, act=act)), P.gemm_ss(xs, cw, act=act, out_ss=True)):
+                differ.append(f"{'GELU' if act else 'none'}, out_ss (persist={persist})")
+    monkeypatch.delenv("PRV2_GSS_PERSIST", raising=False)
+    assert not differ, "gemm_ss != gemm16 in: " + "; ".join(differ)
+    # what gemm_ss does not take it refuses (a split output has neither gamma nor a residual): no silent other formula
+    for bad in (dict(gamma=gd), dict(res=rd), dict(act=P.ACT_GELU, gamma=gd, res=rd)):
+        with pytest.raises(RuntimeError):
+            P.gemm_ss(xs, cw, out_ss=True, **bad)
+    with pytest.raises(RuntimeError):
+        P.gemm_ss(xs, cw, act=P.ACT_RELU)
     ref = x @ w.t() + b
     assert float((yss.cpu() - (ref * gam + res)).abs().max()) < 2e-4 * float(ref.abs().max())
     # chain with a split-swizzled intermediate (fc1 -> GELU -> fc2): the producer's split == the consumer's in-kernel split
