@@ -1019,6 +1019,51 @@ int prv2_stereo_source(const float* depth, int32_t n, int32_t h, int32_t w, floa
 int prv2_stereo_rows(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx, float baseline,
                      float convergence, float lo, float hi, float edge_thr, int32_t layout, uint8_t* rows, int64_t rows_fstride, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Temporal stabilisation (csrc/temporal.hip): the metric maps of consecutive video frames with the frame-to-frame jitter of their
+ * global scale and shift taken out.  Not in the reference.  Every frame is aligned to the previous OUTPUT by a gated least-squares
+ * scale and shift and blended with it where the image has not changed.  Four launches per frame, chained on the stream: the
+ * coefficients go from the fit to the apply pass through device memory, nothing is synchronised, nothing is allocated (graph-capture
+ * safe).  Every sum is an int64 sum of integers, so the same input gives the same bits on every call and however a sequence is cut
+ * into calls.  Added without an ABI bump (additive).  The host specification is temporal_step_host of
+ * patchrefinerv2_amd/temporal.py, which the kernels equal bit for bit.
+ *   state      the previous output y (fp32 [h, w]) and the previous luma Lp (uint8 [h, w]), or nothing
+ *   valid(v)   v finite and > 0
+ *   luma       R, G, B = the bytes prv2_pointcloud_pack gives pixel (r, c) from image fp32 [3, ih, iw] ("Geometry export": its nearest
+ *              sample and its byte rule); L = (77 R + 150 G + 29 B + 128) >> 8
+ *   gate       g = |L - Lp| <= tau and valid(x) and valid(y); without a state no pixel is gated
+ *   fit mask   m = g and 1 <= qx < 2^18 and 1 <= qy < 2^18 and |x - y| <= 0.5 y (float64), qx = rint(x * 256), qy = rint(y * 256) in
+ *              fp32, ties to even
+ *   sums       over m, int64: n, sum qx, sum qx^2, sum qx qy, sum qy ((2^18)^2 * 2^25 < 2^63: frames of at most 2^25 pixels)
+ *   reset      n < max(64, h w / 100) (no state, or a scene cut): out = x
+ *   fit        float64 from the sums, one IEEE operation per step: a00 = sum qx^2, a01 = sum qx, a11 = n, b0 = sum qx qy, b1 = sum qy,
+ *              det = a00 a11 - a01 a01; det > 0: s = (a11 b0 - a01 b1) / det, b = ((a00 b1 - a01 b0) / det) / 256; det <= 0 or NaN,
+ *              s outside [0.5, 2] or b not finite: identity (s = 1, b = 0).  Then s = 1 + anchor (s - 1), b = anchor b
+ *   apply      a = fp32(s x + b) where x and that value are valid, else a = x; where g: r = (a - y) / min(a, y),
+ *              w = alpha / (1 + (r / rho)(r / rho)), out = fp32(a + w (y - a)); elsewhere out = a (an invalid x leaves as it came)
+ *   change     sum over g of rint(65536 min(1, |v - y| / y)), v = x ("before") and v = out ("after"); a NaN ratio counts as 1
+ *   then       state = (out, L)
+ * ------------------------------------------------------------------------------------------ */
+#define PRV2_TEMPORAL_STATS 12 /* 8-byte words per frame of prv2_temporal_step's stats */
+
+/* bytes of workspace prv2_temporal_step needs for frames of h x w, whatever their count: the int64 partials of one frame's blocks
+ * (-1 for bad arguments: h, w < 1 or more than 2^25 pixels) */
+int64_t prv2_temporal_workspace_bytes(int32_t h, int32_t w);
+
+/* n >= 1 frames in sequence order.  depth: fp32 [n, h, w]; image: fp32 [n, 3, ih, iw] (any size); out: fp32 [n, h, w] (not the
+ * input).  alpha in [0, 1), tau in 0 .. 255, rho > 0 finite, anchor in [0, 1].  state_depth: fp32 [h, w], read by the first frame when
+ * state_present is 1 and left holding the last frame's output.  luma0, luma1: two distinct uint8 [h, w] buffers; frame f reads the
+ * previous luma from luma[f & 1] and writes its own into luma[(f + 1) & 1], so the caller passes the buffer that holds the state
+ * first and the state leaves in luma[n & 1].  The maps are read and written with 16-byte accesses when w % 4 == 0 and depth, out
+ * and state_depth are 16-byte, the luma buffers 4-byte aligned; element by element otherwise.  stats: DEVICE, 8-byte aligned,
+ * [n][PRV2_TEMPORAL_STATS] 8-byte words per frame: int64 0 reset, 1 n, 2 n_gate (pixels of g), 3 sum qx, 4 sum qx^2, 5 sum qx qy,
+ * 6 sum qy, 7 change before, 8 change after, 11 fitted (1: the fit was taken, 0: reset or identity); float64 9 s, 10 b (after the
+ * anchor).  workspace: DEVICE, 8-byte aligned, prv2_temporal_workspace_bytes(h, w).  Every argument is checked before anything is
+ * launched (prv2_last_error). */
+int prv2_temporal_step(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, double alpha,
+                       int32_t tau, double rho, double anchor, float* state_depth, uint8_t* luma0, uint8_t* luma1, int32_t state_present,
+                       float* out, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

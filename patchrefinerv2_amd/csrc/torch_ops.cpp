@@ -1418,6 +1418,32 @@ Tensor stereo_rows(const Tensor& depth, const Tensor& image, double fx, double b
   return rows;
 }
 
+// temporal stabilisation (include/prv2.h "Temporal stabilisation"): n frames in sequence order; the state (its map and the two luma
+// buffers, the previous luma in luma0) is updated in place -> (out [n, h, w], stats int64 [n, PRV2_TEMPORAL_STATS] on the device)
+std::tuple<Tensor, Tensor> temporal_step_(const Tensor& depth, const Tensor& image, double alpha, int64_t tau, double rho, double anchor,
+                                          Tensor state_depth, Tensor luma0, Tensor luma1, bool state_present) {
+  dev_frames(depth, "depth", at::kFloat);
+  const int64_t n = depth.size(0), h = depth.size(1), w = depth.size(2);
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == n &&
+                  image.size(1) == 3 && image.device() == depth.device(), "prv2::temporal_step_: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+  TORCH_CHECK(state_depth.is_cuda() && state_depth.scalar_type() == at::kFloat && state_depth.is_contiguous() && state_depth.dim() == 2 &&
+                  state_depth.size(0) == h && state_depth.size(1) == w && state_depth.device() == depth.device(),
+              "prv2::temporal_step_: state_depth must be a contiguous GPU fp32 [h, w] tensor of the frames' shape");
+  for (const Tensor* l : {&luma0, &luma1})
+    TORCH_CHECK(l->is_cuda() && l->scalar_type() == at::kByte && l->is_contiguous() && l->dim() == 2 && l->size(0) == h && l->size(1) == w &&
+                    l->device() == depth.device(), "prv2::temporal_step_: a luma buffer must be a contiguous GPU uint8 [h, w] tensor of the frames' shape");
+  const int64_t bytes = prv2_temporal_workspace_bytes((int)h, (int)w);
+  TORCH_CHECK(bytes > 0, "prv2::temporal_step_: bad frame shape ", depth.sizes(), " (at most 2^25 pixels)");
+  Tensor ws = at::empty({bytes}, depth.options().dtype(at::kByte));
+  Tensor out = at::empty_like(depth), stats = at::empty({n, PRV2_TEMPORAL_STATS}, depth.options().dtype(at::kLong));
+  Launch L(depth);
+  ok(prv2_temporal_step(depth.data_ptr<float>(), image.data_ptr<float>(), (int)n, (int)h, (int)w, (int)image.size(2), (int)image.size(3), alpha,
+                        (int)std::min<int64_t>(std::max<int64_t>(tau, -1), 256), rho, anchor, state_depth.data_ptr<float>(),
+                        (uint8_t*)luma0.data_ptr(), (uint8_t*)luma1.data_ptr(), state_present ? 1 : 0, out.data_ptr<float>(),
+                        stats.data_ptr<int64_t>(), ws.data_ptr(), ws.numel(), L.stream), "temporal_step");
+  return {out, stats};
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1580,6 +1606,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("mesh_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices, Tensor(b!) faces) -> (Tensor, Tensor)");
   m.def("stereo_source(Tensor depth, float fx, float baseline, float convergence, float lo, float hi, float edge_thr) -> (Tensor, Tensor)");
   m.def("stereo_rows(Tensor depth, Tensor image, float fx, float baseline, float convergence, float lo, float hi, float edge_thr, int layout) -> Tensor");
+  m.def("temporal_step_(Tensor depth, Tensor image, float alpha, int tau, float rho, float anchor, Tensor(a!) state_depth, Tensor(b!) luma0, Tensor(c!) luma1, bool state_present) -> (Tensor, Tensor)");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1674,4 +1701,5 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("mesh_pack", &mesh_pack);
   m.impl("stereo_source", &stereo_source);
   m.impl("stereo_rows", &stereo_rows);
+  m.impl("temporal_step_", &temporal_step_);
 }

@@ -199,8 +199,12 @@ SIGNATURES = {
     "prv2_stereo_max_width": (_I, []),
     "prv2_stereo_source": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "prv2_stereo_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P, _L, _P]),
+    # temporal stabilisation (csrc/temporal.hip): n frames of a sequence aligned to and blended with the previous output
+    "prv2_temporal_workspace_bytes": (_L, [_I, _I]),
+    "prv2_temporal_step": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _D, _D, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
+TEMPORAL_STATS = 12  # PRV2_TEMPORAL_STATS: 8-byte words per frame of prv2_temporal_step's stats
 SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS
 
 

@@ -1930,6 +1930,61 @@ def stereo_rows(depth, image, intrinsics, baseline, convergence=math.inf, depth_
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Temporal stabilisation (csrc/temporal.hip): the frames of a sequence aligned to and blended with the previous output, both dispatch
+# routes.  The host specification is temporal.temporal_step_host; temporal.TemporalStabilizer keeps the state.
+# ------------------------------------------------------------------------------------------------------------------
+TEMPORAL_STATS = L.TEMPORAL_STATS
+
+
+def temporal_step(depth, image, state_depth, luma_prev, luma_next, state_present, alpha=0.5, tau=6, rho=0.05, anchor=0.9):
+    """n frames of a sequence, in order: ``depth`` fp32 [n, H, W] and ``image`` fp32 [n, 3, Hi, Wi] on the GPU -> (out fp32 [n, H, W],
+    stats int64 [n, 12] on the device: the rows ``temporal.stats_dict`` names; include/prv2.h prv2_temporal_step).  The state is
+    updated in place: ``state_depth`` fp32 [H, W] (read when ``state_present``; leaves with the last output), ``luma_prev`` /
+    ``luma_next`` two distinct uint8 [H, W] buffers (frame f reads the previous luma from the first when f is even and writes its own
+    into the other; the state leaves in ``luma_prev`` for an even n, in ``luma_next`` for an odd one).  Four launches per frame on the
+    current stream, no host synchronisation; the same bits however a sequence is cut into calls."""
+    from .temporal import MAX_PIXELS, check_params
+    alpha, tau, rho, anchor = check_params(alpha, tau, rho, anchor)
+    tensors = dict(depth=depth, image=image, state_depth=state_depth, luma_prev=luma_prev, luma_next=luma_next)
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != depth.device:
+            raise ValueError(f"temporal_step: {name} is a GPU tensor on the maps' device (temporal.temporal_step_host is the host's)")
+        want = torch.uint8 if name.startswith("luma") else torch.float32
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError(f"temporal_step: {name} must be a contiguous {want} tensor (got {t.dtype}, strides {t.stride()})")
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError(f"temporal_step: depth is [n, H, W] (got {tuple(depth.shape)})")
+    n, h, w = depth.shape
+    if h * w > MAX_PIXELS:
+        raise ValueError(f"temporal_step: a frame of {h} x {w} exceeds 2^25 pixels (the bound of the exact int64 sums)")
+    if image.dim() != 4 or image.shape[0] != n or image.shape[1] != 3 or image.shape[2] < 1 or image.shape[3] < 1:
+        raise ValueError(f"temporal_step: image is [n, 3, Hi, Wi] with the maps' n = {n} (got {tuple(image.shape)})")
+    for name in ("state_depth", "luma_prev", "luma_next"):
+        if tuple(tensors[name].shape) != (h, w):
+            raise ValueError(f"temporal_step: {name} {tuple(tensors[name].shape)} is not the frames' [{h}, {w}]")
+    if luma_prev.data_ptr() == luma_next.data_ptr():
+        raise ValueError("temporal_step: the two luma buffers must differ")
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().temporal_step_(depth, image, alpha, tau, rho, anchor, state_depth, luma_prev, luma_next,  # noqa: E731
+                                                         bool(state_present)))
+    else:
+        wsb = L.load().prv2_temporal_workspace_bytes(h, w)
+        if wsb < 0:
+            raise ValueError(f"temporal_step: bad frame shape {tuple(depth.shape)}")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=depth.device)
+        out = torch.empty_like(depth)
+        stats = torch.empty((n, TEMPORAL_STATS), dtype=torch.int64, device=depth.device)
+        box.extend((out, stats))
+        call = lambda: _c("temporal_step", depth.data_ptr(), image.data_ptr(), n, h, w, image.shape[2], image.shape[3], alpha, tau, rho,  # noqa: E731
+                          anchor, state_depth.data_ptr(), luma_prev.data_ptr(), luma_next.data_ptr(), int(bool(state_present)), out.data_ptr(),
+                          stats.data_ptr(), ws.data_ptr(), wsb)
+    # per pixel: the fit reads x, y, Lp and the image's three samples and writes L; the apply reads x, y, L, Lp and writes out
+    PROFILER.launch_aux("temporal_step", n * h * w * 39.0, call, f"{n}x{h}x{w}")
+    return box[0], box[1]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Ground-truth evaluation (csrc/evalgt.hip): the device half of UnrealStereo4kDataset and the sums behind compute_metrics, both
 # dispatch routes.
 # ------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@ binary point cloud of the result map, coloured from the image) and <name>_normal
 ``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles) and
 ``runner_info.save_stereo`` (--save-stereo) <name>_right.png / _sbs.png / _anaglyph.png (the right-eye view) -- from the device map
 with the output stage, from output.py's host specification otherwise; the same files either way.
+``runner_info.temporal_stabilize`` (--temporal-stabilize; ``temporal_alpha`` / ``_tau`` / ``_rho`` / ``_anchor``) treats the dataset as
+one video: every result map goes through temporal.TemporalStabilizer before it is saved, exported or scored.
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) and <name>_edge.png (Canny edges of the log depth, widened by one pixel,
 :98-106; metrics.depth_edges) -- colour maps and metrics in metrics.py, PNGs through a dependency-free encoder (output.py).
@@ -83,17 +85,22 @@ class Tester:
         patches = shard == "patches" and world > 1
         if max(1, int(frame_batch)) > 1 and patches:
             raise ValueError("frame_batch > 1 with shard='patches': the patch-sharded mode takes one frame per call")
+        stab = self._stabilizer()
         stage = self.last_output_stage = self._output_stage()  # (kept: its bytes_d2h / files counters)
         # with ground truth the frame is scored on the device (metrics.compute_metrics_device): ask for the device map
-        for items, result, log in self._frames(stage, cai_mode, process_num, image_raw_shape, patch_split_num, seed, frame_batch,
-                                               device_scoring=True, patches=patches):
+        for items, hr, result, log in self._frames(stage, cai_mode, process_num, image_raw_shape, patch_split_num, seed, frame_batch,
+                                                   device_scoring=True, patches=patches, want_device=stab is not None):
             if result is None:  # patch-sharded: only rank 0 holds the map
                 continue
+            temporal = None
+            if stab is not None:  # the group's frames in dataset order; the coarse prediction is left alone
+                result, temporal = stab.step(result, hr)
             coarse = log.get("coarse_prediction")
             for f, item in enumerate(items):
                 one = len(items) == 1
                 self._emit(results, item, result if one else result[f:f + 1], coarse if one or coarse is None else coarse[f:f + 1],
-                           image_raw_shape, stage)
+                           image_raw_shape, stage,
+                           **({} if temporal is None else dict(temporal={k: temporal[f][k] for k in self.TEMPORAL_KEYS})))
         if stage is not None:
             stage.close()  # every file is on disk (or its error raised) before run returns
         if not patches:
@@ -104,16 +111,41 @@ class Tester:
             from .metrics import evaluate
             own = getattr(self.dataloader, "evaluate", None)  # a dataset's own aggregation (ETHDataset: nanmean)
             self.last_eval = (own or evaluate)([r["metrics"] for r in results])
+        if stab is not None:  # the flicker of the sequence before / after, over the frames that had a predecessor
+            import warnings
+            rows = [r["temporal"] for r in results if not r["temporal"]["reset"]]
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                means = {"temporal_" + k: float(np.mean([t[k] for t in rows])) if rows else float("nan") for k in ("change_before", "change_after")}
+            scored = bool(results) and "metrics" in results[0]
+            self.last_eval = {**(self.last_eval if scored else {}), **means}
         return results
 
+    TEMPORAL_KEYS = ("reset", "static_fraction", "scale", "shift", "change_before", "change_after")  # of a result entry's ``temporal``
+
+    def _stabilizer(self):
+        """the run's ``temporal.TemporalStabilizer`` when ``runner_info.temporal_stabilize`` is set (``temporal_alpha``, ``temporal_tau``,
+        ``temporal_rho``, ``temporal_anchor``: its parameters), else None.  The frames are one sequence in dataset order: a run over
+        several ranks is rejected (frame sharding breaks the order; the patch-sharded mode is not built)."""
+        info = self.runner_info
+        if not getattr(info, "temporal_stabilize", False):
+            return None
+        if getattr(info, "world_size", 1) > 1:
+            raise ValueError("temporal_stabilize: one process only -- the frames of a sequence are stabilised in dataset order, which a "
+                             f"run over {info.world_size} ranks does not keep")
+        from .temporal import DEFAULTS, TemporalStabilizer
+        return TemporalStabilizer(**{k: getattr(info, "temporal_" + k, None) if getattr(info, "temporal_" + k, None) is not None else v
+                                     for k, v in DEFAULTS.items()})
+
     def _frames(self, stage, cai_mode, process_num, image_raw_shape, patch_split_num, seed, frame_batch, device_scoring, patches=False,
-                **model_kw):
-        """The frame loop of ``run`` and ``generate_pl`` -> (items, result, log) per model call.  Frame f is dealt to rank f mod world
+                want_device=False, **model_kw):
+        """The frame loop of ``run`` and ``generate_pl`` -> (items, image_hr on the device, result, log) per model call.  Frame f is dealt to rank f mod world
         (``patches``: every frame to every rank, the call sharded over them) and ``frame_batch`` of a rank's frames make one call.  The
         next group is loaded BEFORE the model call, so that its decode and uploads overlap the current frames' tiles, and its
         low-resolution images are announced to a model that runs a coarse forward (``next_image_lr``).  ``seed``: every frame's plan
         from that seed.  The maps stay on the device (``return_device``) for the output stage, and with ``device_scoring`` for a
-        group with ground truth when the model can return them there.  ``model_kw`` goes to the model as it is."""
+        group with ground truth -- with ``want_device`` for every group -- when the model can return them there.  ``model_kw`` goes to the
+        model as it is."""
         import random
         rank, world = self.runner_info.rank, getattr(self.runner_info, "world_size", 1)
         fb = max(1, int(frame_batch))
@@ -138,7 +170,7 @@ class Tester:
                 else:  # (every frame's plan from the same seed, as one frame per call does)
                     kw["frame_seeds"] = [seed] * len(idxs)
             scored = device_scoring and any(item.get("depth_gt") is not None for item in items)
-            if stage is not None or (scored and getattr(self.model, "supports_return_device", False)):
+            if stage is not None or ((scored or want_device) and getattr(self.model, "supports_return_device", False)):
                 kw.update(return_device=True)
             if patches:
                 kw.update(shard=(rank, world), gather_dst=0)
@@ -147,7 +179,7 @@ class Tester:
             tile_cfg = dict(image_raw_shape=list(image_raw_shape), patch_split_num=list(patch_split_num))
             result, log = self.model(mode="infer", cai_mode=cai_mode, process_num=process_num, tile_cfg=tile_cfg,
                                      image_lr=lr, image_hr=hr, **kw)
-            yield items, result, log
+            yield items, hr, result, log
 
     def _output_stage(self):
         """the run's ``output.OutputStage`` when ``runner_info.device_output`` and ``save`` are set (``output_workers`` threads,
@@ -197,9 +229,9 @@ class Tester:
                                                            image_hr=item["image_hr"])
         return entry
 
-    def _emit(self, results, item, result, coarse, image_raw_shape, stage=None):
-        """one frame's outputs: PNGs (--save), its metrics and its result entry.  With ``stage`` the same files come from scanlines
-        produced on the GPU (the device output stage)"""
+    def _emit(self, results, item, result, coarse, image_raw_shape, stage=None, **extra):
+        """one frame's outputs: PNGs (--save), its metrics and its result entry (``extra``: further keys of the entry).  With ``stage``
+        the same files come from scanlines produced on the GPU (the device output stage)"""
         base = os.path.join(self.runner_info.work_dir, item["img_file_basename"])
         cmap, (lo, hi) = self._colour()
         if stage is not None:
@@ -209,7 +241,7 @@ class Tester:
             geo = self._geometry(result, image_raw_shape)
             if geo is not None:
                 stage.submit_geometry(base, result, item["image_hr"], **geo)
-            results.append(self._entry(item, result, score=result))
+            results.append(self._entry(item, result, score=result, **extra))
             return
         score = result  # (a device map is scored where it is)
         result = result.cpu()  # BaselinePretrain(target='coarse') hands back the device tensor (baseline_pretrain.py:464)
@@ -228,7 +260,7 @@ class Tester:
                 from .output import write_geometry_host
                 image = torch.as_tensor(item["image_hr"]).cpu().float().numpy()
                 write_geometry_host(base, result.squeeze().numpy(), image.reshape(3, *image.shape[-2:]), geo.pop("intrinsics"), **geo)
-        results.append(self._entry(item, result, score=score))
+        results.append(self._entry(item, result, score=score, **extra))
 
     @torch.no_grad()
     def generate_pl(self, cai_mode="r32", process_num=4, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), count_thr=0.05, seed=None,
@@ -251,11 +283,13 @@ class Tester:
         ``uncert_metrics``; ``self.last_eval`` becomes their per-key nanmean over the scored frames.  Items without ground truth are
         skipped; a result of another shape than the ground truth (an m-mode at the re-ensemble shape) is an error.  The files and
         the rest of the dicts do not change."""
+        if getattr(self.runner_info, "temporal_stabilize", False):
+            raise ValueError("temporal_stabilize with generate_pl: pseudo labels are per-image (the stabiliser carries one frame into the next)")
         results = []
         stage = self.last_output_stage = self._output_stage()  # (kept: its bytes_d2h / files counters)
         # (with uncert_metrics the maps stay where they are scored)
-        for items, result, log in self._frames(stage, cai_mode, process_num, image_raw_shape, patch_split_num, seed, frame_batch,
-                                               device_scoring=bool(uncert_metrics), return_uncertainty=True):
+        for items, _, result, log in self._frames(stage, cai_mode, process_num, image_raw_shape, patch_split_num, seed, frame_batch,
+                                                  device_scoring=bool(uncert_metrics), return_uncertainty=True):
             # the plan's tile count (every frame of a call has the same passes; only random positions differ)
             n_tiles = sum(len(p["raw"]) for p in self.model.last_plan)
             for f, item in enumerate(items):

@@ -152,6 +152,15 @@ def main():
                     help="--save-stereo: the depth that keeps its column (nearer pops out, farther recedes); inf: parallel axes")
     ap.add_argument("--stereo-layout", default="right", choices=["right", "sbs", "anaglyph"],
                     help="--save-stereo: right = the view, sbs = left | right (twice the width), anaglyph = red of left, green and blue of right")
+    ap.add_argument("--temporal-stabilize", action="store_true",
+                    help="treat the frames as one video, in dataset order: every result map is aligned to the previous output by a gated "
+                         "least-squares scale and shift and blended with it where the image has not changed (patchrefinerv2_amd/temporal.py; "
+                         "on the GPU when the model returns device maps); saved files, exports and metrics see the stabilised map.  One process")
+    ap.add_argument("--temporal-alpha", type=float, default=0.5, metavar="A", help="--temporal-stabilize: the weight of the previous output in [0, 1)")
+    ap.add_argument("--temporal-tau", type=int, default=6, metavar="T", help="--temporal-stabilize: a pixel is static when its luma moved by at most T (0 .. 255)")
+    ap.add_argument("--temporal-rho", type=float, default=0.05, metavar="R", help="--temporal-stabilize: the relative depth change that halves the blend weight (> 0)")
+    ap.add_argument("--temporal-anchor", type=float, default=0.9, metavar="K",
+                    help="--temporal-stabilize: how much of the fitted scale and shift is applied, in [0, 1] (below 1 the sequence leaks back to the model's own scale)")
     ap.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="--save-ply / --save-normals: the camera in pixels of the --image-raw-shape grid (scaled to the result's shape)")
     ap.add_argument("--fov", type=float, default=None, metavar="DEG",
@@ -174,6 +183,18 @@ def main():
         ap.error(f"--ply-stride {args.ply_stride}: at least 1")
     if args.intrinsics is not None and args.fov is not None:
         ap.error("--intrinsics and --fov both given: the camera comes from one of them")
+    if not 0.0 <= args.temporal_alpha < 1.0:
+        ap.error(f"--temporal-alpha {args.temporal_alpha}: in [0, 1)")
+    if not 0 <= args.temporal_tau <= 255:
+        ap.error(f"--temporal-tau {args.temporal_tau}: an integer in 0 .. 255")
+    if not (args.temporal_rho > 0.0 and args.temporal_rho != float("inf")):
+        ap.error(f"--temporal-rho {args.temporal_rho}: positive and finite")
+    if not 0.0 <= args.temporal_anchor <= 1.0:
+        ap.error(f"--temporal-anchor {args.temporal_anchor}: in [0, 1]")
+    if args.temporal_stabilize and args.generate_pl:
+        ap.error("--temporal-stabilize with --generate-pl: pseudo labels are per-image")
+    if args.temporal_stabilize and int(os.environ.get("WORLD_SIZE", 1)) > 1:
+        ap.error("--temporal-stabilize: one process only (the frames of a sequence are stabilised in dataset order)")
     if args.uncert_metrics and not args.generate_pl:
         ap.error("--uncert-metrics needs --generate-pl (it scores the pseudo label's uncertainty)")
 
@@ -210,7 +231,9 @@ def main():
                         save_ply=args.save_ply, save_normals=args.save_normals, save_mesh=args.save_mesh, save_stereo=args.save_stereo,
                         stereo_baseline=args.stereo_baseline, stereo_convergence=args.stereo_convergence, stereo_layout=args.stereo_layout,
                         intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
-                        ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range))
+                        ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range),
+                        temporal_stabilize=args.temporal_stabilize, temporal_alpha=args.temporal_alpha, temporal_tau=args.temporal_tau,
+                        temporal_rho=args.temporal_rho, temporal_anchor=args.temporal_anchor)
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
         for r in tester.run_consistency(image_raw_shape=args.image_raw_shape, patch_split_num=args.patch_split_num, overlap=args.consistency):
@@ -246,6 +269,10 @@ def main():
     if rank == 0 or world == 1:  # (frame-sharded runs: rank 0 holds every rank's results, collected like collect_results_gpu)
         for r in results:
             print(f"[rank {rank}] {r['name']}: depth {r['shape']} mean {r['mean']:.4f}")
+            if "temporal" in r:
+                t = r["temporal"]
+                print(f"[rank {rank}] {r['name']}: temporal " + ("reset" if t["reset"] else f"scale {t['scale']:.6f} shift {t['shift']:.6f} static "
+                      f"{t['static_fraction']:.3f} change {t['change_before']:.6f} -> {t['change_after']:.6f}"))
             if args.test_type != "general" and "metrics" in r:  # a dataset evaluation: the frame's own row
                 print(f"[rank {rank}] {r['name']}: " + ", ".join(f"{k} {float(v):.6f}" for k, v in r["metrics"].items()))
         if getattr(tester, "last_eval", None):  # frames that came with ground truth (dataset gt_dir, or a dataset with its own)
