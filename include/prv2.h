@@ -43,7 +43,10 @@ const char* prv2_last_error(void);
 /* Name of the device kernel the calling thread's last successful prv2_conv2d dispatched to, as "name<BN,prec>"
  * (e.g. "conv3x3_halo16_kernel<128,bf16x3>", "gemm16_kernel<64,bf16x3>"): what bench.py's roofline attributes time to.
  * Which kernel runs a layer depends on the layer's shape PER IMAGE, never on the batch size (so results do not depend on
- * how tiles are batched).  When a call issues two kernels (f32 mode: 3x3 tiles + remainder strip) it names the last. */
+ * how tiles are batched).  When a call issues two kernels (f32 mode: 3x3 tiles + remainder strip) it names the last.
+ * prv2_dwconv2d_ex (and prv2_dwconv2d through it) and prv2_conv2d_cout1 report theirs the same way, with the kernel size in the
+ * first slot: "dwconv_strip_kernel<K,f32>" (stride 1, 8 pixels per thread) / "dwconv_kernel<K,f32>", and
+ * "conv_cout1_k3_kernel<32,f32>" (32-channel slabs) / "conv_cout1_k1_kernel<0,f32>". */
 const char* prv2_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------------

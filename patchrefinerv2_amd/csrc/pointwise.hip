@@ -17,7 +17,7 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-// the kernel the calling thread's last prv2_conv2d dispatched to (prv2_last_kernel): "name<BN,prec>"
+// the kernel the calling thread's last prv2_conv2d / prv2_dwconv2d_ex / prv2_conv2d_cout1 dispatched to (prv2_last_kernel): "name<BN,prec>"
 static thread_local char g_kernel[96] = "";
 void set_kernel(const char* name, int bn, int prec) {
   static const char* const pn[4] = {"f32", "bf16x3", "bf16", "f16f6"};
@@ -634,10 +634,12 @@ extern "C" int prv2_conv2d_cout1(const float* x, int32_t n, int32_t h, int32_t w
     PRV2_REQUIRE((size_t)cin * 4 <= 64 * 1024, "conv2d_cout1: cin too large");
     hipLaunchKernelGGL(conv_cout1_k1_kernel, dim3(flat_grid(total, 256)), dim3(256), (size_t)cin * 4, (hipStream_t)stream,
                        x, total, cin, ldx, wgt, bias, act, scale, res, clamp0, y);
+    set_kernel("conv_cout1_k1_kernel", 0, PRV2_PREC_F32);
   } else {
     const int tiles = n * (int)cdiv(h, C1_TH) * (int)cdiv(w, C1_TW);
     hipLaunchKernelGGL(conv_cout1_k3_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, x, n, h, w, cin, ldx, wgt,
                        act, scale, bias, res, clamp0, y);
+    set_kernel("conv_cout1_k3_kernel", 32, PRV2_PREC_F32);
   }
   PRV2_LAUNCH_CHECK("conv2d_cout1");
   return 0;
@@ -671,11 +673,13 @@ extern "C" int prv2_dwconv2d_ex(const float* x, int32_t n, int32_t h, int32_t w,
     if (k == 3) hipLaunchKernelGGL((dwconv_strip_kernel<3, PX>), grid, dim3(256), 0, (hipStream_t)stream, x, n, h, w, c, ldx, wgt, bias, act, y, ldy);
     else if (k == 5) hipLaunchKernelGGL((dwconv_strip_kernel<5, PX>), grid, dim3(256), 0, (hipStream_t)stream, x, n, h, w, c, ldx, wgt, bias, act, y, ldy);
     else hipLaunchKernelGGL((dwconv_strip_kernel<7, PX>), grid, dim3(256), 0, (hipStream_t)stream, x, n, h, w, c, ldx, wgt, bias, act, y, ldy);
+    set_kernel("dwconv_strip_kernel", k, PRV2_PREC_F32);
     PRV2_LAUNCH_CHECK("dwconv2d");
     return 0;
   }
   hipLaunchKernelGGL(dwconv_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, n, h, w, c, ldx, wgt,
                      bias, k, stride, act, pad_y, pad_x, oh, ow, y, ldy);
+  set_kernel("dwconv_kernel", k, PRV2_PREC_F32);
   PRV2_LAUNCH_CHECK("dwconv2d");
   return 0;
 }
