@@ -135,8 +135,6 @@ __global__ void __launch_bounds__(256) tap_gather_kernel(const float* __restrict
   });
 }
 
-static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace prv2
 
 using namespace prv2;

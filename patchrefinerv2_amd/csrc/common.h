@@ -45,6 +45,7 @@ void set_kernel(const char* name, int bn, int prec);  // what prv2_last_kernel()
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t roundup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
+static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // memory-bound grids: cap at 256 CUs x 8 blocks and grid-stride the rest
 static inline int flat_grid(int64_t work_items, int block) {

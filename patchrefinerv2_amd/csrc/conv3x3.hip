@@ -304,37 +304,29 @@ void launch_conv3x3_halo16(IgemmParams& p, int prec, hipStream_t s);  // conv3x3
 
 // bf16 modes run on the 16x16x32 MFMA shape (conv3x3_m16.hip; its buffer-addressed halo loads need the image extent
 // below 2^31 bytes); PRV2_HALO_MFMA32=1 keeps them on this file's 32x32x16 kernel (A/B knob for tools/ab_conv.sh)
-bool conv3x3_halo16_usable(const IgemmParams& p, int prec) {
+bool halo_mfma32_forced() {
   static const bool force32 = [] { const char* e = getenv("PRV2_HALO_MFMA32"); return e && e[0] == '1'; }();
-  return prec != PRV2_PREC_F32 && !force32 && (long long)p.H * p.W * p.ldx < (1LL << 29);
+  return force32;
+}
+bool conv3x3_halo16_usable(const IgemmParams& p, int prec) {
+  return prec != PRV2_PREC_F32 && !halo_mfma32_forced() && (long long)p.H * p.W * p.ldx < (1LL << 29);
 }
 
 void launch_conv3x3_halo(IgemmParams& p, int prec, hipStream_t s) {
   if (conv3x3_halo16_usable(p, prec)) return launch_conv3x3_halo16(p, prec, s);  // (with its strip, if any)
   const int tiles = p.N * ((p.H + TH - 1) / TH) * p.tiles_x;
-#define PRV2_LAUNCH_HALO(BN_, PREC_) \
-  hipLaunchKernelGGL((conv3x3_halo_kernel<BN_, PREC_>), dim3(tiles * p.tiles_n), dim3(512), 0, s, p)
   set_kernel("conv3x3_halo_kernel", p.Ncols > 64 ? 128 : (p.Ncols > 32 ? 64 : 32), prec);
-  if (p.Ncols > 64) {
-    p.tiles_n = (int)cdiv(p.Ncols, 128);
-    if (prec == PRV2_PREC_F32) PRV2_LAUNCH_HALO(128, PRV2_PREC_F32);
-    else if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_HALO(128, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_HALO(128, PRV2_PREC_BF16);
+  p.tiles_n = p.Ncols > 64 ? (int)cdiv(p.Ncols, 128) : 1;
+  // (one with_prec per tile width, widest first: the order in which the kernels are instantiated is the order of the code object)
+#define PRV2_LAUNCH_HALO(BN_) \
+  with_prec(prec, [&](auto pr) { hipLaunchKernelGGL((conv3x3_halo_kernel<BN_, decltype(pr)::value>), dim3(tiles * p.tiles_n), dim3(512), 0, s, p); })
+  if (p.Ncols > 64) PRV2_LAUNCH_HALO(128);
 #ifdef PRV2_NO_BN32
-  } else if (true) {
+  else if (true) PRV2_LAUNCH_HALO(64);
 #else
-  } else if (p.Ncols > 32) {
+  else if (p.Ncols > 32) PRV2_LAUNCH_HALO(64);
 #endif
-    p.tiles_n = 1;
-    if (prec == PRV2_PREC_F32) PRV2_LAUNCH_HALO(64, PRV2_PREC_F32);
-    else if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_HALO(64, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_HALO(64, PRV2_PREC_BF16);
-  } else {
-    p.tiles_n = 1;
-    if (prec == PRV2_PREC_F32) PRV2_LAUNCH_HALO(32, PRV2_PREC_F32);
-    else if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_HALO(32, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_HALO(32, PRV2_PREC_BF16);
-  }
+  else PRV2_LAUNCH_HALO(32);
 #undef PRV2_LAUNCH_HALO
 }
 

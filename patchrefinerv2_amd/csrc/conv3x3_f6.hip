@@ -610,11 +610,10 @@ __global__ void __launch_bounds__(256) f6_pack_weight_kernel(const float* __rest
   *reinterpret_cast<u32x4*>(o + 3 * 1024) = u32x4{q[4], q[5], (unsigned)e, 0u};
 }
 
-static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
+// the 256-column contract (conv3x3_gate_epi.h) + this file's main loop: 64-channel steps, y addressed like x
 static bool f6_shape_ok(const prv2_conv_desc* d) {
-  return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && d->cout == 256 && d->cin >= 64 &&
-         d->cin % 64 == 0 && d->w >= f6::TW && (long long)d->h * d->w * d->ldx < (1LL << 29) && (long long)d->h * d->w * d->ldy < (1LL << 29);
+  static_assert(f6::TW == g256::TW, "one tile width");
+  return c256_shape_ok(d) && d->cin >= 64 && d->cin % 64 == 0 && (long long)d->h * d->w * d->ldy < (1LL << 29);
 }
 
 }  // namespace prv2
@@ -671,60 +670,22 @@ extern "C" int prv2_conv3x3_f6(const prv2_conv_desc* d, const float* x, const vo
   return 0;
 }
 
-static int ln_gate_f6_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
-                           const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
-                           const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream);
-
-extern "C" int prv2_conv3x3_ln_gate_f6(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
-                                       const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias, const float* mul,
-                                       const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream) {
-  return ln_gate_f6_impl(d, x, w_packed, bias, pre, ld_pre, nullptr, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, x_scale, out_scale, range_word, y,
-                         stream);
-}
-
-extern "C" int prv2_conv3x3_ln_gate_f6_taps(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const prv2_tap_tables* taps,
-                                            const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
-                                            const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y,
-                                            void* stream) {
-  PRV2_REQUIRE(taps, "conv3x3_ln_gate_f6_taps: null tap tables");
-  return ln_gate_f6_impl(d, x, w_packed, bias, nullptr, 0, taps, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, x_scale, out_scale, range_word, y,
-                         stream);
-}
-
-static int ln_gate_f6_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
-                           const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
-                           const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream) {
-  PRV2_REQUIRE(d && x && w_packed && y && ln_weight && ln_bias && gate_w_packed, "conv3x3_ln_gate_f6: null pointer (the LayerNorm and the gate stage are part of the kernel)");
+static int ln_gate_f6_impl(const prv2_conv_desc* d, const ConvOperands& o, void* stream) {
+  PRV2_REQUIRE(d && o.x && o.w && o.y && o.ln_w && o.ln_b && o.gate_w, "conv3x3_ln_gate_f6: null pointer (the LayerNorm and the gate stage are part of the kernel)");
   PRV2_REQUIRE(f6_shape_ok(d), "conv3x3_ln_gate_f6: 3x3 s1 p1, cout 256, cin %% 64 == 0, width >= 16 (got %dx%d %d->%d k%d s%d)", d->h, d->w, d->cin, d->cout, d->kh,
                d->stride);
   const bool x2 = (d->fmt & PRV2_FMT_X_X2) != 0;
-  PRV2_REQUIRE(!(d->fmt & ~(PRV2_FMT_X_X2 | PRV2_FMT_MUL_X2)) && (!mul || x2 == ((d->fmt & PRV2_FMT_MUL_X2) != 0)) && (mul || !(d->fmt & PRV2_FMT_MUL_X2)) && !d->relu_in,
+  PRV2_REQUIRE(!(d->fmt & ~(PRV2_FMT_X_X2 | PRV2_FMT_MUL_X2)) && (!o.mul || x2 == ((d->fmt & PRV2_FMT_MUL_X2) != 0)) && (o.mul || !(d->fmt & PRV2_FMT_MUL_X2)) && !d->relu_in,
                "conv3x3_ln_gate_f6: x and mul in the same format (fp32, or PRV2_FMT_X_X2 | PRV2_FMT_MUL_X2), no input ReLU, fp32 output");
   PRV2_REQUIRE(d->act == PRV2_ACT_RELU || d->act == PRV2_ACT_NONE, "conv3x3_ln_gate_f6: ReLU or no activation in front of the gate (act %d)", d->act);
-  PRV2_REQUIRE(x_scale > 0.f && (__builtin_bit_cast(unsigned, x_scale) & 0x7fffffu) == 0 && out_scale > 0.f, "conv3x3_ln_gate_f6: x_scale is a power of two");
-  const long long px = (long long)d->h * d->w;
-  PRV2_REQUIRE(!pre || (ld_pre >= d->cout && ld_pre % 4 == 0 && aligned16(pre) && px * ld_pre < (1LL << 29)), "conv3x3_ln_gate_f6: pre layout");
+  PRV2_REQUIRE(o.f6_x_scale > 0.f && (__builtin_bit_cast(unsigned, o.f6_x_scale) & 0x7fffffu) == 0 && o.f6_out_scale > 0.f, "conv3x3_ln_gate_f6: x_scale is a power of two");
+  PRV2_REQUIRE(!o.pre || (o.ld_pre >= d->cout && o.ld_pre % 4 == 0 && aligned16(o.pre) && (long long)d->h * d->w * o.ld_pre < (1LL << 29)), "conv3x3_ln_gate_f6: pre layout");
   GateConvParams gp;
-  memset(&gp, 0, sizeof(gp));
-  IgemmParams& p = gp.c;
-  p.x = x; p.w = w_packed; p.bias = bias; p.ln_w = ln_weight; p.ln_b = ln_bias; p.ln_eps = d->ln_eps; p.mul = mul; p.res = res; p.y = y;
-  p.N = d->n; p.H = d->h; p.W = d->w; p.OH = d->h; p.OW = d->w;
-  p.Cin = d->cin; p.Cin_pad = d->cin; p.Cout = d->cout; p.Ncols = d->cout;
-  p.KH = 3; p.KW = 3; p.stride = 1; p.pad = 1; p.pad_x = 1;
-  p.ldx = d->ldx; p.ldy = d->ldy; p.ld_mul = d->ld_mul; p.ld_res = d->ld_res;
-  p.x_bstride = d->x_bstride ? d->x_bstride : px * d->ldx;
-  p.y_bstride = d->y_bstride ? d->y_bstride : px * d->ldy;
-  p.M = (long long)d->n * px;
-  p.relu_in = 0; p.act = d->act; p.vec_ok = 1; p.vec_epi = 1;
-  PRV2_REQUIRE(d->n > 0 && d->h > 0 && d->ldx >= d->cin && d->ldx % 4 == 0 && aligned16(x) && p.x_bstride % 4 == 0, "conv3x3_ln_gate_f6: x layout");
-  PRV2_REQUIRE(d->ldy >= d->cout && d->ldy % 4 == 0 && aligned16(y) && p.y_bstride % 4 == 0, "conv3x3_ln_gate_f6: y layout");
-  PRV2_REQUIRE(!mul || (d->ld_mul >= d->cout && d->ld_mul % 4 == 0 && aligned16(mul) && px * d->ld_mul < (1LL << 29)), "conv3x3_ln_gate_f6: mul layout");
-  PRV2_REQUIRE(!res || (d->ld_res >= d->cout && d->ld_res % 4 == 0 && aligned16(res) && px * d->ld_res < (1LL << 29)), "conv3x3_ln_gate_f6: res layout");
-  PRV2_REQUIRE(!bias || aligned16(bias), "conv3x3_ln_gate_f6: bias alignment");
-  gp.gate_w = gate_w_packed; gp.gate_bias = gate_bias; gp.pre = pre; gp.ld_pre = ld_pre;
-  if (taps && gate_taps_fill(gp, taps, d, "conv3x3_ln_gate_f6_taps")) return 1;
-  gp.x_x2 = x2; gp.mul_x2 = mul && x2 ? 1 : 0; gp.y_x2 = 0;
-  gp.f6_x_scale = x_scale; gp.f6_out_scale = out_scale; gp.f6_range = range_word;
+  if (int rc = c256_fill(gp, d, o, "conv3x3_ln_gate_f6")) return rc;
+  PRV2_REQUIRE(!o.bias || aligned16(o.bias), "conv3x3_ln_gate_f6: bias alignment");
+  if (o.taps && gate_taps_fill(gp, o.taps, d, "conv3x3_ln_gate_f6_taps")) return 1;
+  gp.x_x2 = x2; gp.mul_x2 = o.mul && x2 ? 1 : 0; gp.y_x2 = 0;
+  gp.f6_x_scale = o.f6_x_scale; gp.f6_out_scale = o.f6_out_scale; gp.f6_range = o.f6_range;
 #ifdef PRV2_GATE_STAMPS
   gp.stamps = getenv("PRV2_STAMP_PTR") ? (long long*)strtoull(getenv("PRV2_STAMP_PTR"), nullptr, 16) : nullptr;
 #endif
@@ -736,3 +697,26 @@ static int ln_gate_f6_impl(const prv2_conv_desc* d, const float* x, const void* 
   PRV2_LAUNCH_CHECK("conv3x3_ln_gate_f6");
   return 0;
 }
+
+extern "C" int prv2_conv3x3_ln_gate_f6(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
+                                       const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias, const float* mul,
+                                       const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y, void* stream) {
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.pre = pre; o.ld_pre = ld_pre; o.ln_w = ln_weight; o.ln_b = ln_bias;
+  o.gate_w = gate_w_packed; o.gate_bias = gate_bias; o.mul = mul; o.res = res; o.y = y;
+  o.f6_x_scale = x_scale; o.f6_out_scale = out_scale; o.f6_range = range_word;
+  return ln_gate_f6_impl(d, o, stream);
+}
+
+extern "C" int prv2_conv3x3_ln_gate_f6_taps(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const prv2_tap_tables* taps,
+                                            const float* ln_weight, const float* ln_bias, const void* gate_w_packed, const float* gate_bias,
+                                            const float* mul, const float* res, float x_scale, float out_scale, uint32_t* range_word, float* y,
+                                            void* stream) {
+  PRV2_REQUIRE(taps, "conv3x3_ln_gate_f6_taps: null tap tables");
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.taps = taps; o.ln_w = ln_weight; o.ln_b = ln_bias;
+  o.gate_w = gate_w_packed; o.gate_bias = gate_bias; o.mul = mul; o.res = res; o.y = y;
+  o.f6_x_scale = x_scale; o.f6_out_scale = out_scale; o.f6_range = range_word;
+  return ln_gate_f6_impl(d, o, stream);
+}
+

@@ -343,12 +343,8 @@ __global__ void __launch_bounds__(256) pack_gate_weight_kernel(const float* __re
   o[0] = cc.x; o[1] = cc.y; o[2] = d.x; o[3] = d.y;
 }
 
-static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
-static bool gate_conv_shape_ok(const prv2_conv_desc* d) {
-  return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && d->cout == g256::BN && d->cin >= 32 &&
-         d->cin % 32 == 0 && d->w >= g256::TW && d->prec != PRV2_PREC_F32 && (long long)d->h * d->w * d->ldx < (1LL << 29);
-}
+// the 256-column contract (conv3x3_gate_epi.h) + this file's main loop: 32-channel slabs, bf16 modes
+static bool gate_conv_shape_ok(const prv2_conv_desc* d) { return c256_shape_ok(d) && d->cin >= 32 && d->cin % 32 == 0 && d->prec != PRV2_PREC_F32; }
 
 // prv2_conv2d's dispatch: 3x3 convs with 256 output channels whose epilogue is bias, [LayerNorm,] activation, [+ res]
 bool conv3x3_c256_eligible(const prv2_conv_desc* d, const float* x, const float* res, const float* y) {
@@ -364,11 +360,9 @@ using namespace prv2;
 
 static bool gate_channels_ok(int c) { return c == 32 || c == 128 || c == 256; }
 
-// 32 / 128 channels: the layer runs on the 8 x 32-pixel kernels of conv3x3_m16.hip (their shape contract), gate stage in the epilogue
+// 32 / 128 channels: the layer runs on the 8 x 32-pixel kernels of conv3x3_m16.hip (their shape contract, igemm.h), gate stage in the epilogue
 static bool gate_narrow_shape_ok(const prv2_conv_desc* d) {
-  return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && (d->cout == 32 || d->cout == 128) &&
-         d->cin >= 32 && d->cin % 32 == 0 && d->w >= 24 && d->h >= 4 && d->prec != PRV2_PREC_F32 && (long long)d->h * d->w * d->ldx < (1LL << 29) &&
-         (long long)d->h * d->w * d->ldy < (1LL << 29);
+  return halo16_shape_ok(d) && (d->cout == 32 || d->cout == 128) && d->cin >= 32 && d->cin % 32 == 0 && (long long)d->h * d->w * d->ldy < (1LL << 29);
 }
 
 extern "C" int prv2_conv3x3_ln_gate_supported(const prv2_conv_desc* d) { return d && (gate_conv_shape_ok(d) || gate_narrow_shape_ok(d)) ? 1 : 0; }
@@ -385,20 +379,19 @@ extern "C" int prv2_pack_gate_weight(const float* w_src, void* w_packed, int32_t
   return 0;
 }
 
-extern "C" int prv2_conv3x3_ln_gate(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* ln_weight,
-                                    const float* ln_bias, const void* gate_w_packed, const float* gate_bias, const float* mul, const float* res,
-                                    float* y, void* stream) {
-  return prv2_conv3x3_ln_gate_pre(d, x, w_packed, bias, nullptr, 0, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
-}
-
-static int ln_gate_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
-                        const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed,
-                        const float* gate_bias, const float* mul, const float* res, float* y, void* stream);
-
 extern "C" int prv2_conv3x3_ln_gate_pre(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre,
                                         int32_t ld_pre, const float* ln_weight, const float* ln_bias, const void* gate_w_packed,
                                         const float* gate_bias, const float* mul, const float* res, float* y, void* stream) {
-  return ln_gate_impl(d, x, w_packed, bias, pre, ld_pre, nullptr, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.pre = pre; o.ld_pre = ld_pre; o.ln_w = ln_weight; o.ln_b = ln_bias;
+  o.gate_w = gate_w_packed; o.gate_bias = gate_bias; o.mul = mul; o.res = res; o.y = y;
+  return ln_gate_impl(d, o, stream);
+}
+
+extern "C" int prv2_conv3x3_ln_gate(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* ln_weight,
+                                    const float* ln_bias, const void* gate_w_packed, const float* gate_bias, const float* mul, const float* res,
+                                    float* y, void* stream) {
+  return prv2_conv3x3_ln_gate_pre(d, x, w_packed, bias, /*pre=*/nullptr, /*ld_pre=*/0, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
 }
 
 extern "C" int prv2_conv3x3_ln_gate_taps_supported(const prv2_conv_desc* d) { return d && gate_conv_shape_ok(d) ? 1 : 0; }
@@ -408,81 +401,54 @@ extern "C" int prv2_conv3x3_ln_gate_taps(const prv2_conv_desc* d, const float* x
                                          const float* mul, const float* res, float* y, void* stream) {
   PRV2_REQUIRE(d && taps && gate_w_packed && ln_weight && d->cout == g256::BN,
                "conv3x3_ln_gate_taps: the in-kernel gather belongs to the 256-column gate kernels (tables, LayerNorm and gate weights required)");
-  return ln_gate_impl(d, x, w_packed, bias, nullptr, 0, taps, ln_weight, ln_bias, gate_w_packed, gate_bias, mul, res, y, stream);
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.taps = taps; o.ln_w = ln_weight; o.ln_b = ln_bias;
+  o.gate_w = gate_w_packed; o.gate_bias = gate_bias; o.mul = mul; o.res = res; o.y = y;
+  return ln_gate_impl(d, o, stream);
 }
 
-static int ln_gate_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* pre, int32_t ld_pre,
-                        const prv2_tap_tables* taps, const float* ln_weight, const float* ln_bias, const void* gate_w_packed,
-                        const float* gate_bias, const float* mul, const float* res, float* y, void* stream) {
-  PRV2_REQUIRE(d && x && w_packed && y && (ln_weight != nullptr) == (ln_bias != nullptr), "conv3x3_ln_gate: null pointer");
-  PRV2_REQUIRE(!pre || (ln_weight && ld_pre >= d->cout && ld_pre % 4 == 0 && aligned16(pre) && (long long)d->h * d->w * ld_pre < (1LL << 29)),
+int prv2::ln_gate_impl(const prv2_conv_desc* d, const ConvOperands& o, void* stream) {
+  PRV2_REQUIRE(d && o.x && o.w && o.y && (o.ln_w != nullptr) == (o.ln_b != nullptr), "conv3x3_ln_gate: null pointer");
+  PRV2_REQUIRE(!o.pre || (o.ln_w && o.ld_pre >= d->cout && o.ld_pre % 4 == 0 && aligned16(o.pre) && (long long)d->h * d->w * o.ld_pre < (1LL << 29)),
                "conv3x3_ln_gate_pre: the addend goes in front of a LayerNorm; [n, h, w, ld_pre >= cout], ld_pre %% 4 == 0, 16-byte aligned");
-  if (gate_w_packed && d->cout != g256::BN) {  // 32 / 128 channels: conv3x3_m16.hip's kernels with the gate stage in their epilogue
+  if (o.gate_w && d->cout != g256::BN) {  // 32 / 128 channels: conv3x3_m16.hip's kernels with the gate stage in their epilogue
     PRV2_REQUIRE(d->fmt == 0, "conv3x3_ln_gate: pre-split (X2) operands are taken at 256 channels only");
-    PRV2_REQUIRE(gate_narrow_shape_ok(d) && ln_weight, "conv3x3_ln_gate: 3x3 s1 p1, cout 32 / 128 / 256, cin %% 32 == 0, bf16 modes (got %dx%d %d->%d k%d s%d prec %d)",
+    PRV2_REQUIRE(gate_narrow_shape_ok(d) && o.ln_w, "conv3x3_ln_gate: 3x3 s1 p1, cout 32 / 128 / 256, cin %% 32 == 0, bf16 modes (got %dx%d %d->%d k%d s%d prec %d)",
                  d->h, d->w, d->cin, d->cout, d->kh, d->stride, d->prec);
     PRV2_REQUIRE(d->act == PRV2_ACT_RELU || d->act == PRV2_ACT_NONE, "conv3x3_ln_gate: ReLU or no activation in front of the gate (act %d)", d->act);
-    return conv2d_impl(d, x, w_packed, bias, ln_weight, ln_bias, nullptr, mul, res, nullptr, y, stream, gate_w_packed, gate_bias, nullptr, nullptr, nullptr, 0, 0,
-                       pre, ld_pre);
+    return conv2d_impl(d, o, stream);
   }
-  PRV2_REQUIRE(ln_weight || !gate_w_packed, "conv3x3_ln_gate: the gate stage sits behind the LayerNorm");
+  PRV2_REQUIRE(o.ln_w || !o.gate_w, "conv3x3_ln_gate: the gate stage sits behind the LayerNorm");
   PRV2_REQUIRE(gate_conv_shape_ok(d), "conv3x3_ln_gate: 3x3 s1 p1, cout 256, cin %% 32 == 0, width >= 16, bf16 modes (got %dx%d %d->%d k%d s%d prec %d)",
                d->h, d->w, d->cin, d->cout, d->kh, d->stride, d->prec);
-  PRV2_REQUIRE(gate_w_packed || (!mul && !gate_bias), "conv3x3_ln_gate: mul / gate_bias belong to the gate stage");
-  PRV2_REQUIRE(!gate_w_packed || d->act == PRV2_ACT_RELU || d->act == PRV2_ACT_NONE, "conv3x3_ln_gate: ReLU or no activation in front of the gate (act %d)", d->act);
+  PRV2_REQUIRE(o.gate_w || (!o.mul && !o.gate_bias), "conv3x3_ln_gate: mul / gate_bias belong to the gate stage");
+  PRV2_REQUIRE(!o.gate_w || d->act == PRV2_ACT_RELU || d->act == PRV2_ACT_NONE, "conv3x3_ln_gate: ReLU or no activation in front of the gate (act %d)", d->act);
   GateConvParams gp;
-  memset(&gp, 0, sizeof(gp));
-  IgemmParams& p = gp.c;
-  p.x = x; p.w = w_packed; p.bias = bias; p.ln_w = ln_weight; p.ln_b = ln_bias; p.ln_eps = d->ln_eps; p.mul = mul; p.res = res; p.y = y;
-  p.N = d->n; p.H = d->h; p.W = d->w; p.OH = d->h; p.OW = d->w;
-  p.Cin = d->cin; p.Cin_pad = d->cin; p.Cout = d->cout; p.Ncols = d->cout;
-  p.KH = 3; p.KW = 3; p.stride = 1; p.pad = 1; p.pad_x = 1;
-  p.ldx = d->ldx; p.ldy = d->ldy; p.ld_mul = d->ld_mul; p.ld_res = d->ld_res;
-  p.x_bstride = d->x_bstride ? d->x_bstride : (long long)d->h * d->w * d->ldx;
-  p.y_bstride = d->y_bstride ? d->y_bstride : (long long)d->h * d->w * d->ldy;
-  p.M = (long long)d->n * d->h * d->w;
-  p.relu_in = d->relu_in; p.act = d->act;
-  PRV2_REQUIRE(d->n > 0 && d->h > 0 && d->ldx >= d->cin && d->ldx % 4 == 0 && aligned16(x) && p.x_bstride % 4 == 0, "conv3x3_ln_gate: x layout");
-  PRV2_REQUIRE(d->ldy >= d->cout && d->ldy % 4 == 0 && aligned16(y) && p.y_bstride % 4 == 0, "conv3x3_ln_gate: y layout");
-  const long long px = (long long)d->h * d->w;
-  PRV2_REQUIRE(!mul || (d->ld_mul >= d->cout && d->ld_mul % 4 == 0 && aligned16(mul) && px * d->ld_mul < (1LL << 29)), "conv3x3_ln_gate: mul layout");
-  PRV2_REQUIRE(!res || (d->ld_res >= d->cout && d->ld_res % 4 == 0 && aligned16(res) && px * d->ld_res < (1LL << 29)), "conv3x3_ln_gate: res layout");
-  p.vec_ok = 1; p.vec_epi = 1;
-  gp.gate_w = gate_w_packed;
-  gp.gate_bias = gate_bias;
-  gp.pre = pre;
-  gp.ld_pre = ld_pre;
-  if (taps && gate_taps_fill(gp, taps, d, "conv3x3_ln_gate_taps")) return 1;
+  if (int rc = c256_fill(gp, d, o, "conv3x3_ln_gate")) return rc;
+  if (o.taps && gate_taps_fill(gp, o.taps, d, "conv3x3_ln_gate_taps")) return 1;
   gp.x_x2 = (d->fmt & PRV2_FMT_X_X2) != 0;
   gp.mul_x2 = (d->fmt & PRV2_FMT_MUL_X2) != 0;
   gp.y_x2 = (d->fmt & PRV2_FMT_Y_X2) != 0;
   PRV2_REQUIRE(!(d->fmt & ~(PRV2_FMT_X_X2 | PRV2_FMT_MUL_X2 | PRV2_FMT_Y_X2)), "conv3x3_ln_gate: unknown format bits %d", d->fmt);
-  PRV2_REQUIRE(!gp.x_x2 || (gate_w_packed && d->cin % 8 == 0 && !d->relu_in), "conv3x3_ln_gate: a pre-split (X2) input is taken by the gate kernel only (no input ReLU)");
-  PRV2_REQUIRE(!gate_w_packed || !mul || gp.mul_x2 == gp.x_x2, "conv3x3_ln_gate: the gate kernel takes mul in the format of x (PRV2_FMT_X_X2 and PRV2_FMT_MUL_X2 go together)");
-  PRV2_REQUIRE(!gp.mul_x2 || (gate_w_packed && mul), "conv3x3_ln_gate: PRV2_FMT_MUL_X2 without a gate stage / mul operand");
-  PRV2_REQUIRE(!gp.y_x2 || (!gate_w_packed && !ln_weight), "conv3x3_ln_gate: a pre-split (X2) output is written by the plain 256-column conv (no LayerNorm, no gate)");
+  PRV2_REQUIRE(!gp.x_x2 || (o.gate_w && d->cin % 8 == 0 && !d->relu_in), "conv3x3_ln_gate: a pre-split (X2) input is taken by the gate kernel only (no input ReLU)");
+  PRV2_REQUIRE(!o.gate_w || !o.mul || gp.mul_x2 == gp.x_x2, "conv3x3_ln_gate: the gate kernel takes mul in the format of x (PRV2_FMT_X_X2 and PRV2_FMT_MUL_X2 go together)");
+  PRV2_REQUIRE(!gp.mul_x2 || (o.gate_w && o.mul), "conv3x3_ln_gate: PRV2_FMT_MUL_X2 without a gate stage / mul operand");
+  PRV2_REQUIRE(!gp.y_x2 || (!o.gate_w && !o.ln_w), "conv3x3_ln_gate: a pre-split (X2) output is written by the plain 256-column conv (no LayerNorm, no gate)");
 #ifdef PRV2_GATE_STAMPS
   gp.stamps = getenv("PRV2_STAMP_PTR") ? (long long*)strtoull(getenv("PRV2_STAMP_PTR"), nullptr, 16) : nullptr;
 #endif
   const int64_t blocks = (int64_t)d->n * cdiv(d->h, g256::TH) * cdiv(d->w, g256::TW);
   PRV2_REQUIRE(blocks < (1LL << 31), "conv3x3_ln_gate: grid too large");
   hipStream_t s = (hipStream_t)stream;
-  const bool x3 = d->prec == PRV2_PREC_BF16X3;
-  if (gate_w_packed && gp.x_x2) {
-    if (x3) hipLaunchKernelGGL((conv3x3_c256_gate_x2_kernel<256, PRV2_PREC_BF16X3>), dim3((unsigned)blocks), dim3(512), 0, s, gp);
-    else hipLaunchKernelGGL((conv3x3_c256_gate_x2_kernel<256, PRV2_PREC_BF16>), dim3((unsigned)blocks), dim3(512), 0, s, gp);
-    set_kernel("conv3x3_c256_gate_x2_kernel", 256, d->prec);
-    PRV2_LAUNCH_CHECK("conv3x3_ln_gate");
-    return 0;
-  }
-  if (gate_w_packed) {
-    if (x3) hipLaunchKernelGGL((conv3x3_c256_gate_kernel<256, PRV2_PREC_BF16X3>), dim3((unsigned)blocks), dim3(512), 0, s, gp);
-    else hipLaunchKernelGGL((conv3x3_c256_gate_kernel<256, PRV2_PREC_BF16>), dim3((unsigned)blocks), dim3(512), 0, s, gp);
-  } else {
-    if (x3) hipLaunchKernelGGL((conv3x3_c256_kernel<256, PRV2_PREC_BF16X3>), dim3((unsigned)blocks), dim3(512), 0, s, gp);
-    else hipLaunchKernelGGL((conv3x3_c256_kernel<256, PRV2_PREC_BF16>), dim3((unsigned)blocks), dim3(512), 0, s, gp);
-  }
-  set_kernel(gate_w_packed ? "conv3x3_c256_gate_kernel" : "conv3x3_c256_kernel", 256, d->prec);
+  // (one with_prec per kernel: the order in which the kernels are instantiated is the order of the code object)
+#define PRV2_LAUNCH_C256(KERNEL_) \
+  with_prec<false>(d->prec, [&](auto pr) { hipLaunchKernelGGL((KERNEL_<256, decltype(pr)::value>), dim3((unsigned)blocks), dim3(512), 0, s, gp); })
+  if (o.gate_w && gp.x_x2) PRV2_LAUNCH_C256(conv3x3_c256_gate_x2_kernel);
+  else if (o.gate_w) PRV2_LAUNCH_C256(conv3x3_c256_gate_kernel);
+  else PRV2_LAUNCH_C256(conv3x3_c256_kernel);
+#undef PRV2_LAUNCH_C256
+  set_kernel(!o.gate_w ? "conv3x3_c256_kernel" : (gp.x_x2 ? "conv3x3_c256_gate_x2_kernel" : "conv3x3_c256_gate_kernel"), 256, d->prec);
   PRV2_LAUNCH_CHECK("conv3x3_ln_gate");
   return 0;
 }
+

@@ -51,12 +51,37 @@ struct GateConvParams {
   long long* stamps;       // -DPRV2_GATE_STAMPS builds (tools/probes/gate_phase_stamps.sh): 10 s_memtime stamps per wave
 };
 
+// host: the shape contract of the 256-column kernels (8 x 16-pixel tiles x all channels), on the descriptor alone; the bf16x3 and the fp16 + fp6
+// main loops add their own terms (gate_conv_shape_ok, f6_shape_ok)
+static inline bool c256_shape_ok(const prv2_conv_desc* d) { return conv3x3_s1p1_shape_ok(d) && d->cout == g256::BN && d->w >= g256::TW; }
+
+// host: descriptor + operands -> gp, with the layout checks the 256-column kernels share (name: the entry point, for the messages)
+static inline int c256_fill(GateConvParams& gp, const prv2_conv_desc* d, const ConvOperands& o, const char* name) {
+  memset(&gp, 0, sizeof(gp));
+  IgemmParams& p = gp.c;
+  const long long px = (long long)d->h * d->w;
+  p.x = o.x; p.w = o.w; p.bias = o.bias; p.ln_w = o.ln_w; p.ln_b = o.ln_b; p.ln_eps = d->ln_eps; p.mul = o.mul; p.res = o.res; p.y = o.y;
+  p.N = d->n; p.H = d->h; p.W = d->w; p.OH = d->h; p.OW = d->w;
+  p.Cin = d->cin; p.Cin_pad = d->cin; p.Cout = d->cout; p.Ncols = d->cout;
+  p.KH = 3; p.KW = 3; p.stride = 1; p.pad = 1; p.pad_x = 1;
+  p.ldx = d->ldx; p.ldy = d->ldy; p.ld_mul = d->ld_mul; p.ld_res = d->ld_res;
+  p.x_bstride = d->x_bstride ? d->x_bstride : px * d->ldx;
+  p.y_bstride = d->y_bstride ? d->y_bstride : px * d->ldy;
+  p.M = (long long)d->n * px;
+  p.relu_in = d->relu_in; p.act = d->act; p.vec_ok = 1; p.vec_epi = 1;
+  PRV2_REQUIRE(d->n > 0 && d->h > 0 && d->ldx >= d->cin && d->ldx % 4 == 0 && aligned16(o.x) && p.x_bstride % 4 == 0, "%s: x layout", name);
+  PRV2_REQUIRE(d->ldy >= d->cout && d->ldy % 4 == 0 && aligned16(o.y) && p.y_bstride % 4 == 0, "%s: y layout", name);
+  PRV2_REQUIRE(!o.mul || (d->ld_mul >= d->cout && d->ld_mul % 4 == 0 && aligned16(o.mul) && px * d->ld_mul < (1LL << 29)), "%s: mul layout", name);
+  PRV2_REQUIRE(!o.res || (d->ld_res >= d->cout && d->ld_res % 4 == 0 && aligned16(o.res) && px * d->ld_res < (1LL << 29)), "%s: res layout", name);
+  gp.gate_w = o.gate_w; gp.gate_bias = o.gate_bias; gp.pre = o.pre; gp.ld_pre = o.ld_pre;
+  return 0;
+}
+
 // host: the tap tables of prv2_conv3x3_ln_gate_taps / _f6_taps -> gp (the checks of coarse_taps.hip's gather for 256 channels, tile = the conv's map)
 static inline int gate_taps_fill(GateConvParams& gp, const prv2_tap_tables* t, const prv2_conv_desc* d, const char* name) {
   PRV2_REQUIRE(t && t->v && t->g && t->boxes, "%s: null tap tables", name);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   PRV2_REQUIRE(d->cout == g256::BN && t->h > 0 && t->w > 0 && t->n_frames >= 0 && t->ldg >= 9 * g256::BN && t->ldg % 4 == 0 && t->ldv >= g256::BN &&
-                   t->ldv % 4 == 0 && al16(t->g) && al16(t->v),
+                   t->ldv % 4 == 0 && aligned16(t->g) && aligned16(t->v),
                "%s: tables of 256 channels, ldg >= 9 * 256, 16-byte aligned rows (ldg=%d ldv=%d)", name, t->ldg, t->ldv);
   PRV2_REQUIRE(t->knot_bh > 0.f && t->knot_bh <= 0.5f && t->knot_bw > 0.f && t->knot_bw <= 0.5f, "%s: the knot offsets must be in (0, 1/2] (got %g, %g)", name,
                (double)t->knot_bh, (double)t->knot_bw);

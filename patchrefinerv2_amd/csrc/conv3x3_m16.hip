@@ -884,13 +884,9 @@ void launch_conv3x3_halo16_gate(IgemmParams& p, int prec, hipStream_t s) {
   p.strip_blocks = p.rw > 0 ? p.N * (int)cdiv(p.H, 32) : 0;
   const int blocks = p.N * (int)cdiv(p.H, 8) * p.tiles_x + p.strip_blocks;
   set_kernel("conv3x3_halo16_gate_kernel", p.Cout, prec);
-  if (p.Cout == 128) {
-    if (prec == PRV2_PREC_BF16X3) hipLaunchKernelGGL((conv3x3_halo16_gate_kernel<128, PRV2_PREC_BF16X3>), dim3(blocks), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((conv3x3_halo16_gate_kernel<128, PRV2_PREC_BF16>), dim3(blocks), dim3(512), 0, s, p);
-  } else {
-    if (prec == PRV2_PREC_BF16X3) hipLaunchKernelGGL((conv3x3_halo16_gate_kernel<32, PRV2_PREC_BF16X3>), dim3(blocks), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((conv3x3_halo16_gate_kernel<32, PRV2_PREC_BF16>), dim3(blocks), dim3(512), 0, s, p);
-  }
+  // (one with_prec per kernel and tile width, here and below: the order in which the kernels are instantiated is the order of the code object)
+  if (p.Cout == 128) with_prec<false>(prec, [&](auto pr) { hipLaunchKernelGGL((conv3x3_halo16_gate_kernel<128, decltype(pr)::value>), dim3(blocks), dim3(512), 0, s, p); });
+  else with_prec<false>(prec, [&](auto pr) { hipLaunchKernelGGL((conv3x3_halo16_gate_kernel<32, decltype(pr)::value>), dim3(blocks), dim3(512), 0, s, p); });
 }
 
 static int persist_workgroups() {  // one persistent workgroup per CU of the CURRENT device (cached per device ordinal)
@@ -913,62 +909,38 @@ void launch_conv3x3_halo16(IgemmParams& p, int prec, hipStream_t s) {
   p.tiles_n = p.Ncols > 64 ? (int)cdiv(p.Ncols, 128) : 1;
   p.strip_blocks = p.rw > 0 ? p.N * (int)cdiv(p.H, 32) * p.tiles_n : 0;
   const int blocks = p.N * (int)cdiv(p.H, 8) * p.tiles_x * p.tiles_n + p.strip_blocks;
-  if (p.xu) {  // fused-upsample loader: the 128-column kernel (conv2d_impl checked conv3x3_halo16_ups_usable)
-    set_kernel("conv3x3_halo16_ups_kernel", 128, prec);
-#define PRV2_LAUNCH_UPS(PREC_)                                                                                             \
-  do {                                                                                                                   \
-    if (p.w_tail) hipLaunchKernelGGL((conv3x3_halo16_ups_kernel<128, PREC_, true>), dim3(blocks), dim3(512), 0, s, p);   \
-    else hipLaunchKernelGGL((conv3x3_halo16_ups_kernel<128, PREC_, false>), dim3(blocks), dim3(512), 0, s, p);           \
-  } while (0)
-    if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_UPS(PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_UPS(PRV2_PREC_BF16);
-#undef PRV2_LAUNCH_UPS
-    return;
-  }
   static const bool no_persist = getenv("PRV2_HALO_NO_PERSIST") != nullptr;  // A/B switches
   static const int n32_mode = getenv("PRV2_HALO_N32") ? atoi(getenv("PRV2_HALO_N32")) : 1;  // 1: two single-halo workgroups per CU; 0: round-1 paths
-  set_kernel("conv3x3_halo16_kernel", p.Ncols > 64 ? 128 : (p.Ncols > 32 ? 64 : 32), prec);
-#define PRV2_LAUNCH_NARROW(BN_, PREC_)                                                                                       \
-  do {                                                                                                                       \
-    if (p.w_tail) hipLaunchKernelGGL((conv3x3_halo16_narrow_kernel<BN_, PREC_, true>), dim3(blocks), dim3(512), 0, s, p);    \
-    else hipLaunchKernelGGL((conv3x3_halo16_narrow_kernel<BN_, PREC_, false>), dim3(blocks), dim3(512), 0, s, p);            \
-  } while (0)
-  if (p.Ncols <= 32 && n32_mode == 1) {
-    if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_NARROW(32, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_NARROW(32, PRV2_PREC_BF16);
-    return;
-  }
   static const int n64_mode = getenv("PRV2_HALO_N64") ? atoi(getenv("PRV2_HALO_N64")) : 1;
-  if (p.Ncols > 32 && p.Ncols <= 64 && n64_mode == 1) {
-    if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_NARROW(64, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_NARROW(64, PRV2_PREC_BF16);
+  // KERNEL_<BN_, precision, has a tail tile>
+#define PRV2_LAUNCH_TAIL(KERNEL_, BN_)                                                                                     \
+  with_prec<false>(prec, [&](auto pr) {                                                                                    \
+    if (p.w_tail) hipLaunchKernelGGL((KERNEL_<BN_, decltype(pr)::value, true>), dim3(blocks), dim3(512), 0, s, p);         \
+    else hipLaunchKernelGGL((KERNEL_<BN_, decltype(pr)::value, false>), dim3(blocks), dim3(512), 0, s, p);                 \
+  })
+  if (p.xu) {  // fused-upsample loader: the 128-column kernel (conv2d_impl's plan checked conv3x3_halo16_ups_usable)
+    set_kernel("conv3x3_halo16_ups_kernel", 128, prec);
+    PRV2_LAUNCH_TAIL(conv3x3_halo16_ups_kernel, 128);
     return;
   }
-  // (wider layers as N-tiles of 64 on this kernel -- two workgroups per CU, the halo staged once per N-tile -- are no faster than one
-  //  workgroup with 128 columns: 98->98 272 vs 283 TF, 194->194 336 vs 335, 322->322 376 vs 397)
-#undef PRV2_LAUNCH_NARROW
-  if (p.Ncols <= 32 && !p.w_tail && !no_persist) {
+  set_kernel("conv3x3_halo16_kernel", p.Ncols > 64 ? 128 : (p.Ncols > 32 ? 64 : 32), prec);
+  if (p.Ncols <= 32 && n32_mode == 1) {
+    PRV2_LAUNCH_TAIL(conv3x3_halo16_narrow_kernel, 32);
+  } else if (p.Ncols > 32 && p.Ncols <= 64 && n64_mode == 1) {
+    // (wider layers as N-tiles of 64 on this kernel -- two workgroups per CU, the halo staged once per N-tile -- are no faster than one
+    //  workgroup with 128 columns: 98->98 272 vs 283 TF, 194->194 336 vs 335, 322->322 376 vs 397)
+    PRV2_LAUNCH_TAIL(conv3x3_halo16_narrow_kernel, 64);
+  } else if (p.Ncols <= 32 && !p.w_tail && !no_persist) {
     const int tiles = blocks - p.strip_blocks, wgs = tiles < persist_workgroups() ? tiles : persist_workgroups();
-    if (prec == PRV2_PREC_BF16X3) hipLaunchKernelGGL((conv3x3_halo16_persist_kernel<PRV2_PREC_BF16X3>), dim3(wgs + p.strip_blocks), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL((conv3x3_halo16_persist_kernel<PRV2_PREC_BF16>), dim3(wgs + p.strip_blocks), dim3(512), 0, s, p);
-    return;
-  }
-#define PRV2_LAUNCH_HALO16(BN_, PREC_)                                                                                 \
-  do {                                                                                                                 \
-    if (p.w_tail) hipLaunchKernelGGL((conv3x3_halo16_kernel<BN_, PREC_, true>), dim3(blocks), dim3(512), 0, s, p);     \
-    else hipLaunchKernelGGL((conv3x3_halo16_kernel<BN_, PREC_, false>), dim3(blocks), dim3(512), 0, s, p);             \
-  } while (0)
-  if (p.Ncols > 64) {
-    if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_HALO16(128, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_HALO16(128, PRV2_PREC_BF16);
+    with_prec<false>(prec, [&](auto pr) { hipLaunchKernelGGL((conv3x3_halo16_persist_kernel<decltype(pr)::value>), dim3(wgs + p.strip_blocks), dim3(512), 0, s, p); });
+  } else if (p.Ncols > 64) {
+    PRV2_LAUNCH_TAIL(conv3x3_halo16_kernel, 128);
   } else if (p.Ncols > 32) {
-    if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_HALO16(64, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_HALO16(64, PRV2_PREC_BF16);
+    PRV2_LAUNCH_TAIL(conv3x3_halo16_kernel, 64);
   } else {
-    if (prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_HALO16(32, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_HALO16(32, PRV2_PREC_BF16);
+    PRV2_LAUNCH_TAIL(conv3x3_halo16_kernel, 32);
   }
-#undef PRV2_LAUNCH_HALO16
+#undef PRV2_LAUNCH_TAIL
 }
 
 }  // namespace prv2

@@ -495,8 +495,6 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const float* __restri
   }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace prv2
 
 using namespace prv2;

@@ -352,16 +352,54 @@ __device__ __forceinline__ void ln_row_stats(const IgemmParams& p, const float* 
   }
 }
 
+// ---- host: what a conv entry point takes beside the descriptor and the stream (null / 0: not given) ----------
+struct ConvOperands {
+  const float* x = nullptr;
+  const void* w = nullptr;  // packed weights (prv2_pack_conv_weight / prv2_pack_conv3x3_f6_weight)
+  const float *bias = nullptr, *ln_w = nullptr, *ln_b = nullptr, *gamma = nullptr, *mul = nullptr, *res = nullptr, *res2 = nullptr;
+  float* y = nullptr;
+  const void* gate_w = nullptr;  // GatedConvUnit tail: mul / res then belong to y = mul * sigmoid(W_g act(LN(conv + bias)) + gate_bias) (+ res)
+  const float* gate_bias = nullptr;
+  const prv2_ups_src* ups = nullptr;                 // fused-upsample loader (prv2_conv2d_ups)
+  const float *tail1 = nullptr, *tail2 = nullptr;    // depth-pair tail (prv2_conv2d_tail), maps of tail_h x tail_w
+  int tail_h = 0, tail_w = 0;
+  const float* pre = nullptr;                        // pre-stage addend (prv2_conv2d_pre / prv2_conv3x3_ln_gate_pre), pixel stride ld_pre
+  int ld_pre = 0;
+  const prv2_tap_tables* taps = nullptr;             // ... or the tables it is gathered from (256-column gate kernels)
+  float f6_x_scale = 0.f, f6_out_scale = 0.f;        // fp16 + fp6 gate kernel: operand scales and range word
+  uint32_t* f6_range = nullptr;
+};
+
+// The shape contracts, on the descriptor alone.  3x3 / stride 1 / pad 1 with the image below 2^29 elements is common to the two kernel families ...
+static inline bool conv3x3_s1p1_shape_ok(const prv2_conv_desc* d) {
+  return d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && (long long)d->h * d->w * d->ldx < (1LL << 29);
+}
+bool halo_mfma32_forced();  // conv3x3.hip: PRV2_HALO_MFMA32=1 (A/B knob) keeps the bf16 modes off the 16x16x32 halo kernels
+// ... the 8 x 32-pixel halo kernels on the 16x16x32 MFMA shape (conv3x3_m16.hip): what the ups / tail / pre / 32- and 128-channel gate layers need
+static inline bool halo16_shape_ok(const prv2_conv_desc* d) {
+  return conv3x3_s1p1_shape_ok(d) && d->prec != PRV2_PREC_F32 && d->w >= 24 && d->h >= 4 && !halo_mfma32_forced();
+}
+// (the 256-column kernels' contract, c256_shape_ok, is in conv3x3_gate_epi.h beside their tile constants)
+
+// Runs f(integral_constant<int, prec>) for the layer's precision mode, so that a launcher names its kernel once.  F32 = false: the bf16-only
+// kernels, which have no f32 instance.
+template <bool F32 = true, class F>
+static inline void with_prec(int prec, F&& f) {
+  if constexpr (F32)
+    if (prec == PRV2_PREC_F32) return f(std::integral_constant<int, PRV2_PREC_F32>{});
+  if (prec == PRV2_PREC_BF16X3) return f(std::integral_constant<int, PRV2_PREC_BF16X3>{});
+  return f(std::integral_constant<int, PRV2_PREC_BF16>{});
+}
+
 // conv3x3.hip: LDS-halo kernel for 3x3 / stride 1 / pad 1; returns false when the shape is not covered
 bool conv3x3_halo_supported(const IgemmParams& p);
 void launch_conv3x3_halo(IgemmParams& p, int prec, hipStream_t stream);
 bool conv3x3_halo16_usable(const IgemmParams& p, int prec);
 void launch_conv3x3_halo16(IgemmParams& p, int prec, hipStream_t stream);  // tiles [0, tiles_x) + strip [rx0, rx0 + rw)
-int conv2d_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* ln_weight, const float* ln_bias,
-                const float* gamma, const float* mul, const float* res, const float* res2, float* y, void* stream, const void* gate_w,
-                const float* gate_bias, const prv2_ups_src* ups = nullptr, const float* tail1 = nullptr, const float* tail2 = nullptr,
-                int tail_h = 0, int tail_w = 0, const float* pre = nullptr, int ld_pre = 0);  // igemm.hip: prv2_conv2d, with the optional gate stage of the 32 / 128-channel layers /
-                                                  // the fused-upsample loader / the depth-pair tail
+// igemm.hip: prv2_conv2d, with the optional gate stage of the 32 / 128-channel layers / the fused-upsample loader / the depth-pair tail / the addend
+int conv2d_impl(const prv2_conv_desc* d, const ConvOperands& o, void* stream);
+// conv3x3_gate.hip: the 256-column kernels (and, with gate weights at 32 / 128 channels, back to conv2d_impl)
+int ln_gate_impl(const prv2_conv_desc* d, const ConvOperands& o, void* stream);
 bool conv3x3_halo16_ups_usable(const IgemmParams& p, int prec);  // p.xu layers (prv2_conv2d_ups): the 128-column 16x16x32 halo kernel
 bool conv3x3_halo16_gate_usable(const IgemmParams& p, int prec);                 // p.gate_w layers: Cout == 32 or 128, Cin % 32 == 0
 void launch_conv3x3_halo16_gate(IgemmParams& p, int prec, hipStream_t stream);

@@ -261,8 +261,6 @@ __global__ void __launch_bounds__(256) pack_tail_kernel(const float* __restrict_
   d16[((((e >> 3) + 4) ^ key) << 3) + (e & 7)] = prec == PRV2_PREC_BF16X3 ? lo : (__bf16)0.0f;
 }
 
-static inline bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 // ---------------------------------------------------------------------------------------------
 // small 1x1 convs (Cin, Cout <= 64: the 32->32 gates / out_convs at full resolution).  A GEMM tile would be 3/4
 // padding and the layer is HBM-bound anyway: one thread = one pixel x 8 output channels on the fp32 VALU, the
@@ -431,27 +429,21 @@ extern "C" int prv2_pack_conv_weight(const float* w_src, const float* bn_scale, 
   return 0;
 }
 
-namespace prv2 {
-int conv2d_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* ln_weight, const float* ln_bias,
-                const float* gamma, const float* mul, const float* res, const float* res2, float* y, void* stream, const void* gate_w,
-                const float* gate_bias, const prv2_ups_src* ups, const float* tail1, const float* tail2, int tail_h, int tail_w, const float* pre,
-                int ld_pre);
-}
-
 extern "C" int prv2_conv2d(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias,
                            const float* ln_weight, const float* ln_bias, const float* gamma, const float* mul,
                            const float* res, const float* res2, float* y, void* stream) {
-  return conv2d_impl(d, x, w_packed, bias, ln_weight, ln_bias, gamma, mul, res, res2, y, stream, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0);
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.ln_w = ln_weight; o.ln_b = ln_bias; o.gamma = gamma; o.mul = mul; o.res = res; o.res2 = res2; o.y = y;
+  return conv2d_impl(d, o, stream);
 }
 
-// gate_w != null: the GatedConvUnit tail at 32 / 128 channels (prv2_conv3x3_ln_gate routes here; conv3x3_m16.hip GATE): mul / res then
-// belong to the final stage y = mul * sigmoid(W_g act(LN(conv + bias)) + gate_bias) (+ res)
+// the layers that must end on the 8 x 32-pixel halo kernels, whole (no f32-mode part, no generic route): the shared contract (igemm.h) + own terms
+static bool halo16_whole_ok(const prv2_conv_desc* d) { return halo16_shape_ok(d) && !d->force_generic && d->part == 0; }
+
 // fused-upsample loader (prv2.h): the layer's shape contract, checked on the descriptor alone
 static bool ups_shape_ok(const prv2_conv_desc* d, const prv2_ups_src* u) {
-  return d && u && u->x && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && d->prec != PRV2_PREC_F32 &&
-         !d->force_generic && d->part == 0 && d->cout > 64 && d->w >= 24 && d->h >= 4 && !d->relu_in && u->channels > 0 && u->channels % 32 == 0 &&
-         u->channels <= d->cin && u->ld % 4 == 0 && u->ld >= u->channels && u->h >= 1 && u->w >= 1 && (long long)u->h * u->w * u->ld < (1LL << 29) &&
-         (long long)d->h * d->w * d->ldx < (1LL << 29) && !(getenv("PRV2_HALO_MFMA32") && getenv("PRV2_HALO_MFMA32")[0] == '1');
+  return d && u && u->x && halo16_whole_ok(d) && d->cout > 64 && !d->relu_in && u->channels > 0 && u->channels % 32 == 0 && u->channels <= d->cin &&
+         u->ld % 4 == 0 && u->ld >= u->channels && u->h >= 1 && u->w >= 1 && (long long)u->h * u->w * u->ld < (1LL << 29);
 }
 
 extern "C" int prv2_conv2d_ups_supported(const prv2_conv_desc* d, const prv2_ups_src* u) { return ups_shape_ok(d, u) ? 1 : 0; }
@@ -460,15 +452,15 @@ extern "C" int prv2_conv2d_ups(const prv2_conv_desc* d, const float* x, const pr
                                const float* ln_weight, const float* ln_bias, const float* res, float* y, void* stream) {
   PRV2_REQUIRE(ups_shape_ok(d, u), "conv2d_ups: layer / source not covered (3x3 s1 p1, bf16 modes, cout > 64, width >= 24, channels %% 32 == 0, no input ReLU)");
   PRV2_REQUIRE(aligned16(u->x) && (u->bstride % 4 == 0), "conv2d_ups: source must be 16-byte aligned");
-  return conv2d_impl(d, x, w_packed, bias, ln_weight, ln_bias, nullptr, nullptr, res, nullptr, y, stream, nullptr, nullptr, u, nullptr, nullptr, 0, 0);
+  ConvOperands o;
+  o.x = x; o.ups = u; o.w = w_packed; o.bias = bias; o.ln_w = ln_weight; o.ln_b = ln_bias; o.res = res; o.y = y;
+  return conv2d_impl(d, o, stream);
 }
 
 // depth-pair tail (prv2.h): the layer must end in the lean store loop of the 16x16x32 halo kernels
 static bool tail_shape_ok(const prv2_conv_desc* d) {
-  return d && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && d->prec != PRV2_PREC_F32 &&
-         !d->force_generic && d->part == 0 && d->w >= 24 && d->h >= 4 && d->cout % 4 == 0 && d->ldy >= d->cout + 4 && d->ldy % 4 == 0 &&
-         d->cout <= 128 && (long long)d->h * d->w * d->ldx < (1LL << 29) && (long long)d->h * d->w * d->ldy < (1LL << 31) &&
-         !(getenv("PRV2_HALO_MFMA32") && getenv("PRV2_HALO_MFMA32")[0] == '1');
+  return d && halo16_whole_ok(d) && d->cout % 4 == 0 && d->ldy >= d->cout + 4 && d->ldy % 4 == 0 && d->cout <= 128 &&
+         (long long)d->h * d->w * d->ldy < (1LL << 31);
 }
 
 extern "C" int prv2_conv2d_tail_supported(const prv2_conv_desc* d) { return tail_shape_ok(d) ? 1 : 0; }
@@ -478,15 +470,15 @@ extern "C" int prv2_conv2d_tail(const prv2_conv_desc* d, const float* x, const v
                                 void* stream) {
   PRV2_REQUIRE(tail_shape_ok(d) && p1 && p2 && ph > 0 && pw > 0 && !(ln_weight && res),
                "conv2d_tail: layer not covered (3x3 s1 p1, bf16 modes, width >= 24, cout %% 4 == 0 and <= 128, ldy >= cout + 4, LayerNorm or residual but not both)");
-  return conv2d_impl(d, x, w_packed, bias, ln_weight, ln_bias, nullptr, nullptr, res, nullptr, y, stream, nullptr, nullptr, nullptr, p1, p2, ph, pw);
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.ln_w = ln_weight; o.ln_b = ln_bias; o.res = res; o.y = y;
+  o.tail1 = p1; o.tail2 = p2; o.tail_h = ph; o.tail_w = pw;
+  return conv2d_impl(d, o, stream);
 }
 
 // pre-stage addend (prv2.h prv2_conv2d_pre): the layer must run on the 16x16x32 halo kernels or on the 256-column kernel
 static bool pre_shape_ok(const prv2_conv_desc* d) {
-  return d && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->convt_k == 0 && !d->same_pad && d->prec != PRV2_PREC_F32 &&
-         !d->force_generic && d->part == 0 && d->w >= 24 && d->h >= 4 && d->cout % 4 == 0 && d->fmt == 0 &&
-         (long long)d->h * d->w * d->ldx < (1LL << 29) && (long long)d->h * d->w * d->ldy < (1LL << 29) &&
-         !(getenv("PRV2_HALO_MFMA32") && getenv("PRV2_HALO_MFMA32")[0] == '1');
+  return d && halo16_whole_ok(d) && d->cout % 4 == 0 && d->fmt == 0 && (long long)d->h * d->w * d->ldy < (1LL << 29);
 }
 
 extern "C" int prv2_conv2d_pre_supported(const prv2_conv_desc* d) { return pre_shape_ok(d) ? 1 : 0; }
@@ -496,43 +488,44 @@ extern "C" int prv2_conv2d_pre(const prv2_conv_desc* d, const float* x, const vo
   PRV2_REQUIRE(pre_shape_ok(d) && pre, "conv2d_pre: layer not covered (3x3 s1 p1, bf16 modes, width >= 24, height >= 4, cout %% 4 == 0)");
   PRV2_REQUIRE(ld_pre >= d->cout && ld_pre % 4 == 0 && aligned16(pre) && (long long)d->h * d->w * ld_pre < (1LL << 29), "conv2d_pre: addend layout");
   PRV2_REQUIRE(!ln_weight || d->cout <= 128 || d->cout == 256, "conv2d_pre: fused LayerNorm needs cout <= 128 or == 256 (got %d)", d->cout);
-  return conv2d_impl(d, x, w_packed, bias, ln_weight, ln_bias, nullptr, nullptr, res, nullptr, y, stream, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                     pre, ld_pre);
+  ConvOperands o;
+  o.x = x; o.w = w_packed; o.bias = bias; o.pre = pre; o.ld_pre = ld_pre; o.ln_w = ln_weight; o.ln_b = ln_bias; o.res = res; o.y = y;
+  return conv2d_impl(d, o, stream);
 }
 
-int prv2::conv2d_impl(const prv2_conv_desc* d, const float* x, const void* w_packed, const float* bias, const float* ln_weight,
-                      const float* ln_bias, const float* gamma, const float* mul, const float* res, const float* res2, float* y, void* stream,
-                      const void* gate_w, const float* gate_bias, const prv2_ups_src* ups, const float* tail1, const float* tail2, int tail_h,
-                      int tail_w, const float* pre, int ld_pre) {
-  PRV2_REQUIRE(d && x && w_packed && y, "conv2d: null pointer");
+// ---- prv2_conv2d and its variants in three steps: (a) check the arguments and fill IgemmParams, (b) name the kernel(s), (c) launch ----------
+
+// (a) ... what must hold for every route
+static int conv_check_args(const prv2_conv_desc* d, const ConvOperands& o) {
+  PRV2_REQUIRE(d && o.x && o.w && o.y, "conv2d: null pointer");
   PRV2_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "conv2d: bad sizes");
   PRV2_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->pad >= 0, "conv2d: bad kernel geometry");
   PRV2_REQUIRE(d->ldx >= d->cin, "conv2d: ldx %d < cin %d", d->ldx, d->cin);
   PRV2_REQUIRE(d->prec >= PRV2_PREC_F32 && d->prec <= PRV2_PREC_BF16, "conv2d: unknown precision mode %d", d->prec);
   PRV2_REQUIRE(d->act >= PRV2_ACT_NONE && d->act <= PRV2_ACT_SILU, "conv2d: unknown activation %d", d->act);
-  PRV2_REQUIRE(aligned16(w_packed), "conv2d: packed weights must be 16-byte aligned");
-  PRV2_REQUIRE((ln_weight == nullptr) == (ln_bias == nullptr), "conv2d: ln_weight and ln_bias go together");
-  // 3x3 convs with 256 output channels (a layer property: the choice never depends on the batch): the workgroup holds the whole
-  // channel row, so the LayerNorm is fused for this width too
-  if (!ups && !gate_w && !d->force_generic && !gamma && !mul && !res2 && d->part == 0 && conv3x3_c256_eligible(d, x, res, y) && (!pre || ln_weight))
-    return prv2_conv3x3_ln_gate_pre(d, x, w_packed, bias, pre, ld_pre, ln_weight, ln_bias, nullptr, nullptr, nullptr, res, y, stream);
+  PRV2_REQUIRE(aligned16(o.w), "conv2d: packed weights must be 16-byte aligned");
+  PRV2_REQUIRE((o.ln_w == nullptr) == (o.ln_b == nullptr), "conv2d: ln_weight and ln_bias go together");
+  return 0;
+}
+
+// (a) ... and the parameters of every kernel but the 256-column one (which has its own fill, c256_fill)
+static int conv_fill_params(const prv2_conv_desc* d, const ConvOperands& o, IgemmParams& p) {
   PRV2_REQUIRE(d->fmt == 0, "conv2d: pre-split (X2) operands are only taken by the 256-column 3x3 kernels (fmt %d, %d->%d k%d)", d->fmt, d->cin, d->cout, d->kh);
-  IgemmParams p;
   memset(&p, 0, sizeof(p));
-  p.x = x; p.w = w_packed; p.bias = bias; p.gamma = gamma; p.mul = mul; p.res = res; p.res2 = res2; p.y = y;
-  p.ln_w = ln_weight; p.ln_b = ln_bias; p.ln_eps = d->ln_eps;
-  p.gate_w = gate_w; p.gate_bias = gate_bias;
-  p.pre = pre; p.ld_pre = ld_pre;
-  if (tail1) {
-    p.tail1 = tail1; p.tail2 = tail2; p.tH = tail_h; p.tW = tail_w;
-    p.tsy = ac_scale(tail_h, d->h); p.tsx = ac_scale(tail_w, d->w);
+  p.x = o.x; p.w = o.w; p.bias = o.bias; p.gamma = o.gamma; p.mul = o.mul; p.res = o.res; p.res2 = o.res2; p.y = o.y;
+  p.ln_w = o.ln_w; p.ln_b = o.ln_b; p.ln_eps = d->ln_eps;
+  p.gate_w = o.gate_w; p.gate_bias = o.gate_bias;
+  p.pre = o.pre; p.ld_pre = o.ld_pre;
+  if (o.tail1) {
+    p.tail1 = o.tail1; p.tail2 = o.tail2; p.tH = o.tail_h; p.tW = o.tail_w;
+    p.tsy = ac_scale(o.tail_h, d->h); p.tsx = ac_scale(o.tail_w, d->w);
   }
-  if (ups) {
+  if (const prv2_ups_src* ups = o.ups) {
     p.xu = ups->x; p.uH = ups->h; p.uW = ups->w; p.ldxu = ups->ld; p.ups_c = ups->channels;
     p.xu_bstride = ups->bstride ? ups->bstride : (long long)ups->h * ups->w * ups->ld;
     p.usy = ac_scale(ups->h, d->h); p.usx = ac_scale(ups->w, d->w);
   }
-  PRV2_REQUIRE(!ln_weight || (d->cout <= 128 && d->convt_k == 0), "conv2d: fused LayerNorm needs cout <= 128 (got %d)", d->cout);
+  PRV2_REQUIRE(!o.ln_w || (d->cout <= 128 && d->convt_k == 0), "conv2d: fused LayerNorm needs cout <= 128 (got %d)", d->cout);
   p.N = d->n; p.H = d->h; p.W = d->w;
   p.Cin = d->cin; p.Cin_pad = (int)roundup(d->cin, BK); p.Cout = d->cout;
   p.convt_k = d->convt_k;
@@ -559,15 +552,15 @@ int prv2::conv2d_impl(const prv2_conv_desc* d, const float* x, const void* w_pac
   PRV2_REQUIRE(p.OH > 0 && p.OW > 0, "conv2d: empty output");
   PRV2_REQUIRE(d->ldy >= d->cout, "conv2d: ldy %d < cout %d", d->ldy, d->cout);
   p.ldx = d->ldx; p.ldy = d->ldy; p.ld_mul = d->ld_mul; p.ld_res = d->ld_res; p.ld_res2 = d->ld_res2;
-  PRV2_REQUIRE(!mul || d->ld_mul >= d->cout, "conv2d: ld_mul");
-  PRV2_REQUIRE(!res || d->ld_res >= d->cout, "conv2d: ld_res");
-  PRV2_REQUIRE(!res2 || d->ld_res2 >= d->cout, "conv2d: ld_res2");
+  PRV2_REQUIRE(!o.mul || d->ld_mul >= d->cout, "conv2d: ld_mul");
+  PRV2_REQUIRE(!o.res || d->ld_res >= d->cout, "conv2d: ld_res");
+  PRV2_REQUIRE(!o.res2 || d->ld_res2 >= d->cout, "conv2d: ld_res2");
   p.x_bstride = d->x_bstride ? d->x_bstride : (long long)d->h * d->w * d->ldx;
   const int kk = d->convt_k > 0 ? d->convt_k : 1;
   p.y_bstride = d->y_bstride ? d->y_bstride : (long long)p.OH * kk * p.OW * kk * d->ldy;
   p.M = (long long)d->n * p.OH * p.OW;
   p.relu_in = d->relu_in; p.act = d->act;
-  PRV2_REQUIRE((d->ldx % 4 == 0) && aligned16(x) && (p.x_bstride % 4 == 0) && d->ldx >= roundup(d->cin, 4),
+  PRV2_REQUIRE((d->ldx % 4 == 0) && aligned16(o.x) && (p.x_bstride % 4 == 0) && d->ldx >= roundup(d->cin, 4),
                "conv2d: x must be 16-byte aligned with ldx %% 4 == 0 and ldx >= roundup(cin,4) (ldx=%d cin=%d)", d->ldx, d->cin);
   p.vec_ok = 1;
   {
@@ -575,103 +568,158 @@ int prv2::conv2d_impl(const prv2_conv_desc* d, const float* x, const void* w_pac
     // bytes behind cout are the pad channels up to the pixel stride: those are then written too, as zeros
     const int c4 = (int)roundup(d->cout, 4);
     const bool padded = d->cout % 4 != 0 && d->convt_k == 0;
-    bool ve = (d->ldy % 4 == 0) && aligned16(y) && (p.y_bstride % 4 == 0) && (!padded || d->ldy == c4);
-    if (mul) ve = ve && (d->ld_mul % 4 == 0) && aligned16(mul) && (!padded || d->ld_mul == c4);
-    if (res) ve = ve && (d->ld_res % 4 == 0) && aligned16(res) && (!padded || d->ld_res == c4);
-    if (res2) ve = ve && (d->ld_res2 % 4 == 0) && aligned16(res2) && (!padded || d->ld_res2 == c4);
+    bool ve = (d->ldy % 4 == 0) && aligned16(o.y) && (p.y_bstride % 4 == 0) && (!padded || d->ldy == c4);
+    if (o.mul) ve = ve && (d->ld_mul % 4 == 0) && aligned16(o.mul) && (!padded || d->ld_mul == c4);
+    if (o.res) ve = ve && (d->ld_res % 4 == 0) && aligned16(o.res) && (!padded || d->ld_res == c4);
+    if (o.res2) ve = ve && (d->ld_res2 % 4 == 0) && aligned16(o.res2) && (!padded || d->ld_res2 == c4);
     if (d->convt_k > 0) ve = ve && (d->cout % 4 == 0);
     p.vec_epi = ve;
   }
   p.tiles_m = (int)cdiv(p.M, BM);
-  hipStream_t s = (hipStream_t)stream;
-  if (conv3x3_halo_supported(p) && !d->force_generic) {
-    if (has_tail_tile(d->cin, d->kh, d->kw, d->convt_k, d->prec))
-      p.w_tail = (const float*)w_packed + roundup(p.Ncols, 128) * 9 * p.Cin_pad;
-    // The fusion pyramid is 392x518, 196x259, 98x130, 49x65, 25x33: every width is 32k + {6, 3, 2, 1, 1}, i.e. the
-    // last 32-pixel tile column of the halo kernel would be 81-97 % padding.  A remainder of <= 8 columns goes to
-    // a second launch instead: the same kernel with 32-row x 8-pixel tiles (bf16 modes), or the generic kernel's
-    // column window (f32 mode); disjoint outputs, same stream.
-    const int rem = p.W % 32;
-    const bool strip = rem != 0 && rem <= 8 && p.W >= 64;
-    p.tiles_x = strip ? p.W / 32 : (int)cdiv(p.W, 32);
-    if (gate_w) {
-      PRV2_REQUIRE(conv3x3_halo16_gate_usable(p, d->prec) && d->part == 0, "conv3x3_ln_gate: layer not covered by the gate kernel (%d->%d, %dx%d, prec %d)",
-                   d->cin, d->cout, d->h, d->w, d->prec);
-      if (strip) {
-        p.rx0 = p.W - rem;
-        p.rw = rem;
-      }
-      launch_conv3x3_halo16_gate(p, d->prec, s);
-      PRV2_LAUNCH_CHECK("conv3x3_ln_gate(halo16)");
-      return 0;
-    }
-    PRV2_REQUIRE(!ups || conv3x3_halo16_ups_usable(p, d->prec), "conv2d_ups: layer not covered by the 128-column halo kernel (%d->%d, %dx%d, prec %d)",
-                 d->cin, d->cout, d->h, d->w, d->prec);
-    PRV2_REQUIRE(!tail1 || (conv3x3_halo16_usable(p, d->prec) && p.vec_epi), "conv2d_tail: layer not covered by the 16x16x32 halo kernels (%d->%d, %dx%d, prec %d)",
-                 d->cin, d->cout, d->h, d->w, d->prec);
-    PRV2_REQUIRE(!pre || conv3x3_halo16_usable(p, d->prec), "conv2d_pre: layer not covered by the 16x16x32 halo kernels (%d->%d, %dx%d, prec %d)",
-                 d->cin, d->cout, d->h, d->w, d->prec);
-    if (strip && conv3x3_halo16_usable(p, d->prec)) {  // bf16 modes: tiles and strip are one launch
-      PRV2_REQUIRE(d->part == 0, "conv2d: part=%d is only meaningful when the strip is a launch of its own (f32 mode)", d->part);
-      p.rx0 = p.W - rem;
-      p.rw = rem;
-      launch_conv3x3_halo(p, d->prec, s);
-      PRV2_LAUNCH_CHECK("conv2d(3x3 halo + strip)");
-      return 0;
-    }
-    PRV2_REQUIRE(d->part >= 0 && d->part <= 2 && (d->part == 0 || strip), "conv2d: part=%d but this conv has no remainder strip", d->part);
-    if (d->part != 2) {
-      launch_conv3x3_halo(p, d->prec, s);
-      PRV2_LAUNCH_CHECK("conv2d(3x3 halo)");
-    }
-    if (!strip || d->part == 1) return 0;
-    p.w_tail = nullptr;  // f32 mode: the strip goes through the generic kernel's column window
-    p.rx0 = p.W - rem;
-    p.rw = rem;
-    p.M = (long long)d->n * p.OH * rem;
-    p.tiles_m = (int)cdiv(p.M, BM);
-  } else
-  if (gate_w || ups || tail1 || pre) {
-    PRV2_REQUIRE(false, "%s: layer not covered by the halo kernels (%d->%d k%d, %dx%d)", ups ? "conv2d_ups" : (tail1 ? "conv2d_tail" : (pre ? "conv2d_pre" : "conv3x3_ln_gate")), d->cin, d->cout, d->kh, d->h, d->w);
-  } else
-  if (conv_few_in_supported(p) && !d->force_generic && aligned16(x)) {
-    const int ng = (p.Cout + 7) >> 3;
-    hipLaunchKernelGGL(conv_few_in_kernel, dim3(flat_grid(p.M * ng, 256)), dim3(256), 0, s, p, (int)d->prec);
-    set_kernel("conv_few_in_kernel", 64, d->prec);
-    PRV2_LAUNCH_CHECK("conv2d(few input channels)");
-    return 0;
-  }
-  if (conv1x1_small_supported(p) && !d->force_generic) {
-    const int ng = (p.Cout + 7) >> 3;
-    hipLaunchKernelGGL(conv1x1_small_kernel, dim3(flat_grid(p.M * ng, 256)), dim3(256), 0, s, p, (int)d->prec);
-    set_kernel("conv1x1_small_kernel", 64, d->prec);
-    PRV2_LAUNCH_CHECK("conv2d(1x1 small)");
-    return 0;
-  }
-  if (gemm16_supported(p, d->prec) && !d->force_generic) {
-    launch_gemm16(p, d->prec, s);
-    PRV2_LAUNCH_CHECK("conv2d(1x1 gemm16)");
-    return 0;
-  }
-#define PRV2_LAUNCH_IGEMM(BN_, PREC_) \
-  hipLaunchKernelGGL((igemm_kernel<BN_, PREC_>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p)
+  return 0;
+}
+
+// (b) The plan: which kernels run the layer.  No HIP call, and nothing is touched beside the message of a refusal.
+enum class ConvHalo { NONE, PLAIN, GATE };
+// the remainder strip: none / in the halo launch / a launch of its own on the generic kernel's column window / left to another call (part = 1)
+enum class ConvStrip { NONE, MERGED, SECOND_LAUNCH, OTHER_CALL };
+enum class ConvGeneric { NONE, FEW_IN, SMALL_1X1, GEMM16, IGEMM64, IGEMM128 };
+struct ConvPlan {
+  ConvHalo halo = ConvHalo::NONE;           // the halo launch over the tile columns [0, tiles_x) (+ a merged strip)
+  int tiles_x = 0;
+  ConvStrip strip = ConvStrip::NONE;
+  int rem = 0;                              // the strip's width in pixels
+  ConvGeneric generic = ConvGeneric::NONE;  // the other launch: the whole layer, or the strip's
+};
+
+// First rung, decided before the parameters of the other kernels exist: 3x3 convs with 256 output channels (a layer property: the choice never
+// depends on the batch).  The workgroup holds the whole channel row, so the LayerNorm is fused for this width too.
+static bool conv_goes_c256(const prv2_conv_desc* d, const ConvOperands& o) {
+  return !o.ups && !o.gate_w && !d->force_generic && !o.gamma && !o.mul && !o.res2 && d->part == 0 && conv3x3_c256_eligible(d, o.x, o.res, o.y) &&
+         (!o.pre || o.ln_w);
+}
+
+// f32 mode: the strip goes through the generic kernel's column window, with its own row count
+static void strip_window(IgemmParams& p, int rem) {
+  p.w_tail = nullptr;
+  p.rx0 = p.W - rem;
+  p.rw = rem;
+  p.M = (long long)p.N * p.OH * rem;
+  p.tiles_m = (int)cdiv(p.M, BM);
+}
+
+// the rungs below the halo kernels.  few_in: conv_few_in_kernel is only asked for a whole layer, never for a strip.
+static ConvGeneric conv_plan_generic(const prv2_conv_desc* d, const IgemmParams& p, bool few_in) {
+  if (few_in && conv_few_in_supported(p) && !d->force_generic && aligned16(p.x)) return ConvGeneric::FEW_IN;
+  if (conv1x1_small_supported(p) && !d->force_generic) return ConvGeneric::SMALL_1X1;
+  if (gemm16_supported(p, d->prec) && !d->force_generic) return ConvGeneric::GEMM16;
   // 64-column tiles also for wider layers whose 128-column grid would leave half the CUs idle (the 13 x 17 level of the
   // fusion pyramid: 25 row tiles) -- a workgroup's time is its serial K loop; not with a fused LayerNorm (needs the whole row)
   const bool narrow = p.Ncols > 64 && !p.ln_w && (long long)p.tiles_m * cdiv(p.Ncols, 128) <= 128;
-  if (p.Ncols > 64 && !narrow) {
-    p.tiles_n = (int)cdiv(p.Ncols, 128);
-    set_kernel("igemm_kernel", 128, d->prec);
-    if (d->prec == PRV2_PREC_F32) PRV2_LAUNCH_IGEMM(128, PRV2_PREC_F32);
-    else if (d->prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_IGEMM(128, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_IGEMM(128, PRV2_PREC_BF16);
-  } else {
-    p.tiles_n = (int)cdiv(p.Ncols, 64);
-    set_kernel("igemm_kernel", 64, d->prec);
-    if (d->prec == PRV2_PREC_F32) PRV2_LAUNCH_IGEMM(64, PRV2_PREC_F32);
-    else if (d->prec == PRV2_PREC_BF16X3) PRV2_LAUNCH_IGEMM(64, PRV2_PREC_BF16X3);
-    else PRV2_LAUNCH_IGEMM(64, PRV2_PREC_BF16);
+  return p.Ncols > 64 && !narrow ? ConvGeneric::IGEMM128 : ConvGeneric::IGEMM64;
+}
+
+static int conv_plan(const prv2_conv_desc* d, const ConvOperands& o, const IgemmParams& p, ConvPlan& plan) {
+  if (!conv3x3_halo_supported(p) || d->force_generic) {
+    PRV2_REQUIRE(!(o.gate_w || o.ups || o.tail1 || o.pre), "%s: layer not covered by the halo kernels (%d->%d k%d, %dx%d)",
+                 o.ups ? "conv2d_ups" : (o.tail1 ? "conv2d_tail" : (o.pre ? "conv2d_pre" : "conv3x3_ln_gate")), d->cin, d->cout, d->kh, d->h, d->w);
+    plan.generic = conv_plan_generic(d, p, true);
+    return 0;
   }
-#undef PRV2_LAUNCH_IGEMM
-  PRV2_LAUNCH_CHECK("conv2d");
+  // The fusion pyramid is 392x518, 196x259, 98x130, 49x65, 25x33: every width is 32k + {6, 3, 2, 1, 1}, i.e. the
+  // last 32-pixel tile column of the halo kernel would be 81-97 % padding.  A remainder of <= 8 columns goes to
+  // a second launch instead: the same kernel with 32-row x 8-pixel tiles (bf16 modes), or the generic kernel's
+  // column window (f32 mode); disjoint outputs, same stream.
+  const int rem = p.W % 32;
+  const bool strip = rem != 0 && rem <= 8 && p.W >= 64;
+  plan.tiles_x = strip ? p.W / 32 : (int)cdiv(p.W, 32);
+  plan.rem = strip ? rem : 0;
+  if (o.gate_w) {
+    PRV2_REQUIRE(conv3x3_halo16_gate_usable(p, d->prec) && d->part == 0, "conv3x3_ln_gate: layer not covered by the gate kernel (%d->%d, %dx%d, prec %d)",
+                 d->cin, d->cout, d->h, d->w, d->prec);
+    plan.halo = ConvHalo::GATE;
+    plan.strip = strip ? ConvStrip::MERGED : ConvStrip::NONE;
+    return 0;
+  }
+  PRV2_REQUIRE(!o.ups || conv3x3_halo16_ups_usable(p, d->prec), "conv2d_ups: layer not covered by the 128-column halo kernel (%d->%d, %dx%d, prec %d)",
+               d->cin, d->cout, d->h, d->w, d->prec);
+  PRV2_REQUIRE(!o.tail1 || (conv3x3_halo16_usable(p, d->prec) && p.vec_epi), "conv2d_tail: layer not covered by the 16x16x32 halo kernels (%d->%d, %dx%d, prec %d)",
+               d->cin, d->cout, d->h, d->w, d->prec);
+  PRV2_REQUIRE(!o.pre || conv3x3_halo16_usable(p, d->prec), "conv2d_pre: layer not covered by the 16x16x32 halo kernels (%d->%d, %dx%d, prec %d)",
+               d->cin, d->cout, d->h, d->w, d->prec);
+  plan.halo = ConvHalo::PLAIN;
+  if (strip && conv3x3_halo16_usable(p, d->prec)) {  // bf16 modes: tiles and strip are one launch
+    PRV2_REQUIRE(d->part == 0, "conv2d: part=%d is only meaningful when the strip is a launch of its own (f32 mode)", d->part);
+    plan.strip = ConvStrip::MERGED;
+    return 0;
+  }
+  PRV2_REQUIRE(d->part >= 0 && d->part <= 2 && (d->part == 0 || strip), "conv2d: part=%d but this conv has no remainder strip", d->part);
+  if (d->part == 2) plan.halo = ConvHalo::NONE;
+  if (!strip) return 0;
+  plan.strip = d->part == 1 ? ConvStrip::OTHER_CALL : ConvStrip::SECOND_LAUNCH;
+  if (d->part != 1) {  // the strip re-enters the ladder below the halo kernels
+    IgemmParams q = p;
+    strip_window(q, rem);
+    plan.generic = conv_plan_generic(d, q, false);
+  }
   return 0;
+}
+
+// (c) launch what the plan names
+static int conv_launch(const prv2_conv_desc* d, const ConvPlan& plan, IgemmParams& p, hipStream_t s) {
+  p.tiles_x = plan.tiles_x;
+  if (plan.halo != ConvHalo::NONE) {
+    if (has_tail_tile(d->cin, d->kh, d->kw, d->convt_k, d->prec)) p.w_tail = (const float*)p.w + roundup(p.Ncols, 128) * 9 * p.Cin_pad;
+    if (plan.strip == ConvStrip::MERGED) {
+      p.rx0 = p.W - plan.rem;
+      p.rw = plan.rem;
+    }
+    if (plan.halo == ConvHalo::GATE) {
+      launch_conv3x3_halo16_gate(p, d->prec, s);
+      PRV2_LAUNCH_CHECK("conv3x3_ln_gate(halo16)");
+    } else {
+      launch_conv3x3_halo(p, d->prec, s);
+      PRV2_LAUNCH_CHECK(plan.strip == ConvStrip::MERGED ? "conv2d(3x3 halo + strip)" : "conv2d(3x3 halo)");
+    }
+  }
+  if (plan.strip == ConvStrip::SECOND_LAUNCH) strip_window(p, plan.rem);
+  const int ng = (p.Cout + 7) >> 3;
+  switch (plan.generic) {
+    case ConvGeneric::NONE: break;
+    case ConvGeneric::FEW_IN:
+      hipLaunchKernelGGL(conv_few_in_kernel, dim3(flat_grid(p.M * ng, 256)), dim3(256), 0, s, p, (int)d->prec);
+      set_kernel("conv_few_in_kernel", 64, d->prec);
+      PRV2_LAUNCH_CHECK("conv2d(few input channels)");
+      break;
+    case ConvGeneric::SMALL_1X1:
+      hipLaunchKernelGGL(conv1x1_small_kernel, dim3(flat_grid(p.M * ng, 256)), dim3(256), 0, s, p, (int)d->prec);
+      set_kernel("conv1x1_small_kernel", 64, d->prec);
+      PRV2_LAUNCH_CHECK("conv2d(1x1 small)");
+      break;
+    case ConvGeneric::GEMM16:
+      launch_gemm16(p, d->prec, s);
+      PRV2_LAUNCH_CHECK("conv2d(1x1 gemm16)");
+      break;
+    case ConvGeneric::IGEMM128:
+    case ConvGeneric::IGEMM64: {
+      const int bn = plan.generic == ConvGeneric::IGEMM128 ? 128 : 64;
+      p.tiles_n = (int)cdiv(p.Ncols, bn);
+      set_kernel("igemm_kernel", bn, d->prec);
+      if (bn == 128) with_prec(d->prec, [&](auto prec) { hipLaunchKernelGGL((igemm_kernel<128, decltype(prec)::value>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p); });
+      else with_prec(d->prec, [&](auto prec) { hipLaunchKernelGGL((igemm_kernel<64, decltype(prec)::value>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p); });
+      PRV2_LAUNCH_CHECK("conv2d");
+      break;
+    }
+  }
+  return 0;
+}
+
+int prv2::conv2d_impl(const prv2_conv_desc* d, const ConvOperands& o, void* stream) {
+  if (int rc = conv_check_args(d, o)) return rc;
+  if (conv_goes_c256(d, o)) return ln_gate_impl(d, o, stream);
+  IgemmParams p;
+  ConvPlan plan;
+  if (int rc = conv_fill_params(d, o, p)) return rc;
+  if (int rc = conv_plan(d, o, p, plan)) return rc;
+  return conv_launch(d, plan, p, (hipStream_t)stream);
 }

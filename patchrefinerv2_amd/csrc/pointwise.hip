@@ -553,8 +553,6 @@ __global__ void __launch_bounds__(256) zoe_logbinom_depth_generic_kernel(const f
   }
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace prv2
 
 using namespace prv2;
