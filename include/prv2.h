@@ -816,6 +816,47 @@ int64_t prv2_image_edge_region_workspace_bytes(int32_t h, int32_t w);
 int prv2_image_edge_region(const float* image_chw, int32_t h, int32_t w, float frac, uint8_t* region, int32_t H, int32_t W,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* CityScapesDataset (estimator/datasets/cityscapes_dataset.py), the parts that run on the device.  Additive as well: the ABI version
+ * does not change. */
+
+/* cityscapes_dataset.py:153-174 and :300, one pass.  disp: uint16 [h, w] (the disparity PNG's samples); seg_hwc: uint8 [h, w, 3] (the
+ * RGB bytes of the gtFine colour map) or NULL; factor: float32(baseline * fx) of the frame's camera file.  Per pixel
+ *   d = PRV2_GT_CITYSCAPES' depth (prv2_gt_decode);
+ *   d = -1 in the last ceil(h / 4) rows, the first w / 16 and the last ceil(w / 16) columns (Python's -h // 4, w // 16, -w // 16);
+ *   d = 0 where the segmentation pixel has R == 70 and G == 130 (the sky class; applied after the bands).
+ * depth: fp32 [h, w] = d; boundary: uint8 0/1 [h, w] = get_boundaries(d, th=1, dilation=0) of that FINAL map (metric.py:74-85; the
+ * rule of prv2_disp_gt, every neighbour decoded with the bands and the class mask applied); seg_chw: fp32 [3, h, w] holding the bytes
+ * as 0 .. 255 (to_tensor(seg / 1.0), :232-233, :258), NULL exactly when seg_hwc is. */
+int prv2_cityscapes_gt(const uint16_t* disp, const uint8_t* seg_hwc, int32_t h, int32_t w, float factor, float* depth, uint8_t* boundary,
+                       float* seg_chw, void* stream);
+
+/* cityscapes_dataset.py:333-334: kornia.filters.canny(seg)[1] > 0 with kornia's defaults (low 0.1, high 0.2, 5 x 5 Gaussian of
+ * sigma 1, hysteresis on), on the colour segmentation map.  seg_chw: fp32 [3, h, w]; edges: uint8 0/1 [h, w]; h, w >= 3 (a reflect pad
+ * of 2).  All fp32, each product / sum / difference rounded on its own (nothing contracted), in this order:
+ *   grey  = (0.299f R + 0.587f G) + 0.114f B
+ *   blur  : gauss_w5_host (five float32 taps, made on the host) along x, then along y; border reflect without the edge pixel
+ *           (-1 -> 1, -2 -> 2); the taps summed from -2 to +2
+ *   Sobel : unnormalised, border replicate; with u, c, d the rows above, at and below
+ *           gx = ((u[x+1] - u[x-1]) + 2 (c[x+1] - c[x-1])) + (d[x+1] - d[x-1]);  gy likewise over the rows
+ *   mag   = sqrt((gx gx + gy gy) + 1e-6f), a correctly rounded sqrt
+ *   axis  : kornia rounds atan2(gy, gx) to a multiple of 45 degrees and compares with the neighbours in that direction and the
+ *           opposite one, so only the axis counts.  a = |gx|, b = |gy|, T = float32(tan(pi / 8)): horizontal if b <= T a (takes
+ *           gx = gy = 0), else vertical if a <= T b, else the (+1, +1) diagonal when gx and gy have the same sign, else (+1, -1)
+ *   max   : min(mag - n1, mag - n2) > 0 with the two neighbours along the axis, 0 for one outside the frame
+ *   hysteresis: strong = max and mag > high_threshold, weak = max and mag > low_threshold; edges = the weak pixels 8-connected to a
+ *           strong one through weak pixels (the fixed point of kornia's loop), by prv2_canny's connected-component kernels.
+ * workspace of prv2_edges_workspace_bytes(1, h, w) bytes.  Eight launches, the same bits on every call. */
+int prv2_seg_canny(const float* seg_chw, int32_t h, int32_t w, const float* gauss_w5_host, float low_threshold, float high_threshold,
+                   uint8_t* edges, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cityscapes_dataset.py:360-365, one pass.  seg_edges (prv2_seg_canny), gt_edges (prv2_canny of the log ground truth), hr_region
+ * (prv2_image_edge_region with frac 0.05, :346-352): uint8 [h, w], non-zero = set.  edge_mask = seg_edges and dilate7(gt_edges) --
+ * gaussian_blur2d(7 x 7, sigma 5, reflect) > 0 is the 7 x 7 dilation with the window clipped at the frame (positive weights) --;
+ * flatten = not edge_mask and not hr_region.  Both uint8 0/1 [h, w].  The valid-depth test of :324-329 stays with the scoring kernel
+ * (the bands are -1 in prv2_cityscapes_gt's depth). */
+int prv2_cityscapes_masks(const uint8_t* seg_edges, const uint8_t* gt_edges, const uint8_t* hr_region, int32_t h, int32_t w,
+                          uint8_t* edge_mask, uint8_t* flatten, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): compute_scale_and_shift (estimator/models/losses.py:523-544) and the
  * three modes of ScaleAndShiftInvariantLoss (losses.py:600-700: SSI L1, gradient matching, the 'inverse' gradient-space fit) as

@@ -2,6 +2,7 @@
 // a Canny detector bit-identical to metrics.canny (scipy.ndimage arithmetic), an exact Euclidean distance transform, k x k
 // binary dilation and the boundary-metric statistics of compute_boundary_metrics.  Every entry point takes B >= 1 frames
 // [n, h, w] and a caller workspace of prv2_edges_workspace_bytes(n, h, w) bytes; the launch count of each is fixed.
+// prv2_seg_canny (one frame) is kornia's Canny on a colour segmentation map, in the same workspace and with the same hysteresis kernels.
 //
 // Arithmetic contract of the Canny stages (what makes them bit-identical to scipy on identical fp32 input):
 //   - the file is built with -ffp-contract=off (Makefile CXXFLAGS): no FMA in any expression below;
@@ -546,6 +547,149 @@ __global__ void __launch_bounds__(64) stats_final_kernel(const double* __restric
   stats[f * kStats + k] = s;
 }
 
+// ------------------------------------------------------------------------------------------------ kornia's Canny on a colour map
+// kornia.filters.canny(seg)[1] > 0 with its defaults (cityscapes_dataset.py:333-334; include/prv2.h prv2_seg_canny states every
+// step).  All fp32, every product / sum / difference its own IEEE operation in the order the header gives (-ffp-contract=off and the
+// __f*_rn intrinsics): on an axis-aligned class boundary the two pixels beside the step have mathematically equal magnitudes, and the
+// strict > of the non-maximum suppression is decided by the last bit.  A thread owns four pixels of a row: float4 / uchar4 accesses
+// for them when the rows are 16-byte aligned, single loads for the taps beside them.
+struct Gauss5 {
+  float w[5];
+};
+
+// a border index: reflect without the edge pixel (-1 -> 1, n -> n - 2) or replicate, then clamped (a quad's tail lanes stay in bounds)
+template <bool REFLECT>
+__device__ __forceinline__ int bidx(int i, int n) {
+  if (REFLECT) i = i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+  return min(max(i, 0), n - 1);
+}
+
+// v[j] = row[border(x0 - R + j)], j in [0, 4 + 2 R): the quad's own four values as one float4 when vec
+template <int R, bool REFLECT>
+__device__ __forceinline__ void load_span(const float* __restrict__ row, int x0, int w, int vec, float* v) {
+  if (vec) {
+    const float4 t = *reinterpret_cast<const float4*>(row + x0);
+    v[R] = t.x, v[R + 1] = t.y, v[R + 2] = t.z, v[R + 3] = t.w;
+    for (int j = 0; j < R; ++j) v[j] = row[bidx<REFLECT>(x0 - R + j, w)], v[R + 4 + j] = row[bidx<REFLECT>(x0 + 4 + j, w)];
+  } else {
+    for (int j = 0; j < 4 + 2 * R; ++j) v[j] = row[bidx<REFLECT>(x0 - R + j, w)];
+  }
+}
+
+__device__ __forceinline__ void store4(float* __restrict__ dst, int x0, int w, int vec, const float* v) {
+  if (vec) {
+    *reinterpret_cast<float4*>(dst + x0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int k = 0; k < 4 && x0 + k < w; ++k) dst[x0 + k] = v[k];
+  }
+}
+
+__device__ __forceinline__ void store4(uint8_t* __restrict__ dst, int x0, int w, int vec, const uint8_t* v) {
+  if (vec) {
+    *reinterpret_cast<uint32_t*>(dst + x0) = (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)v[3] << 24;
+  } else {
+    for (int k = 0; k < 4 && x0 + k < w; ++k) dst[x0 + k] = v[k];
+  }
+}
+
+// the five taps summed from -2 to +2
+__device__ __forceinline__ float gauss5(const Gauss5& g, float a, float b, float c, float d, float e) {
+  float acc = __fmul_rn(g.w[0], a);
+  acc = __fadd_rn(acc, __fmul_rn(g.w[1], b));
+  acc = __fadd_rn(acc, __fmul_rn(g.w[2], c));
+  acc = __fadd_rn(acc, __fmul_rn(g.w[3], d));
+  return __fadd_rn(acc, __fmul_rn(g.w[4], e));
+}
+
+// grey = (0.299 R + 0.587 G) + 0.114 B, then the horizontal pass (reflect border)
+__global__ void __launch_bounds__(256) seg_grey_blur_kernel(const float* __restrict__ seg, float* __restrict__ t, int h, int w, Gauss5 g, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq, hw = (int64_t)h * w;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    const int64_t ro = (int64_t)y * w;
+    float r[8], gr[8], b[8], v[8], o[4];
+    load_span<2, true>(seg + ro, x0, w, vec, r);
+    load_span<2, true>(seg + hw + ro, x0, w, vec, gr);
+    load_span<2, true>(seg + 2 * hw + ro, x0, w, vec, b);
+    for (int j = 0; j < 8; ++j) v[j] = __fadd_rn(__fadd_rn(__fmul_rn(0.299f, r[j]), __fmul_rn(0.587f, gr[j])), __fmul_rn(0.114f, b[j]));
+    for (int k = 0; k < 4; ++k) o[k] = gauss5(g, v[k], v[k + 1], v[k + 2], v[k + 3], v[k + 4]);
+    store4(t + ro, x0, w, vec, o);
+  }
+}
+
+// the vertical pass (reflect border)
+__global__ void __launch_bounds__(256) seg_vblur_kernel(const float* __restrict__ t, float* __restrict__ sm, int h, int w, Gauss5 g, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    float v[5][4], o[4];
+    for (int j = 0; j < 5; ++j) load_span<0, true>(t + (int64_t)bidx<true>(y - 2 + j, h) * w, x0, w, vec, v[j]);
+    for (int k = 0; k < 4; ++k) o[k] = gauss5(g, v[0][k], v[1][k], v[2][k], v[3][k], v[4][k]);
+    store4(sm + (int64_t)y * w, x0, w, vec, o);
+  }
+}
+
+// unnormalised Sobel (replicate border), mag = sqrt((gx gx + gy gy) + 1e-6) and the axis the suppression compares along:
+// 0 horizontal (|gy| <= T |gx|, which takes gx = gy = 0), 1 vertical (|gx| <= T |gy|), 2 the (+1, +1) diagonal (same signs), 3 the (+1, -1) one
+__global__ void __launch_bounds__(256) seg_sobel_kernel(const float* __restrict__ sm, float* __restrict__ mag, uint8_t* __restrict__ axis, int h,
+                                                        int w, int vec) {
+  const float T = 0.414213568f;  // float32(tan(pi / 8))
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    float u[6], c[6], d[6], m[4];
+    uint8_t ax[4];
+    load_span<1, false>(sm + (int64_t)bidx<false>(y - 1, h) * w, x0, w, vec, u);
+    load_span<1, false>(sm + (int64_t)y * w, x0, w, vec, c);
+    load_span<1, false>(sm + (int64_t)bidx<false>(y + 1, h) * w, x0, w, vec, d);
+    for (int k = 0; k < 4; ++k) {  // the pixel is at span index k + 1
+      const float gx = __fadd_rn(__fadd_rn(__fsub_rn(u[k + 2], u[k]), __fmul_rn(2.0f, __fsub_rn(c[k + 2], c[k]))), __fsub_rn(d[k + 2], d[k]));
+      const float gy = __fadd_rn(__fadd_rn(__fsub_rn(d[k], u[k]), __fmul_rn(2.0f, __fsub_rn(d[k + 1], u[k + 1]))), __fsub_rn(d[k + 2], u[k + 2]));
+      // (the double sqrt of an fp32 value rounded to fp32 is the correctly rounded fp32 sqrt, as in sobel_kernel; __fsqrt_rn is the
+      //  native instruction here, one ulp off in places)
+      m[k] = (float)sqrt((double)__fadd_rn(__fadd_rn(__fmul_rn(gx, gx), __fmul_rn(gy, gy)), 1e-6f));
+      const float a = fabsf(gx), b = fabsf(gy);
+      ax[k] = b <= __fmul_rn(T, a) ? 0 : (a <= __fmul_rn(T, b) ? 1 : ((gx > 0.f) == (gy > 0.f) ? 2 : 3));
+    }
+    store4(mag + (int64_t)y * w, x0, w, vec, m);
+    store4(axis + (int64_t)y * w, x0, w, vec, ax);
+  }
+}
+
+// local maximum: min(mag - n1, mag - n2) > 0 with the two neighbours along the axis, 0 outside the frame.  weak = maximum and
+// mag > lo; strongf = 1.f where maximum and mag > hi, else 0.f (what ccl_resolve_kernel thresholds at 0.5)
+__global__ void __launch_bounds__(256) seg_nms_kernel(const float* __restrict__ mag, const uint8_t* __restrict__ axis, uint8_t* __restrict__ weak,
+                                                      float* __restrict__ strongf, int h, int w, float lo, float hi, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    float m[4], s[4];
+    uint8_t ax[4] = {0, 0, 0, 0}, wk[4];
+    load_span<0, false>(mag + (int64_t)y * w, x0, w, vec, m);
+    if (vec) {
+      const uint32_t t = *reinterpret_cast<const uint32_t*>(axis + (int64_t)y * w + x0);
+      for (int k = 0; k < 4; ++k) ax[k] = (uint8_t)(t >> (8 * k));
+    } else {
+      for (int k = 0; k < 4 && x0 + k < w; ++k) ax[k] = axis[(int64_t)y * w + x0 + k];
+    }
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + k;
+      const int dy = ax[k] == 0 ? 0 : (ax[k] == 3 ? -1 : 1), dx = ax[k] == 1 ? 0 : 1;  // the (+dx, +dy) neighbour and its opposite
+      auto M = [&](int yy, int xx) { return (yy >= 0 && yy < h && xx >= 0 && xx < w) ? mag[(int64_t)yy * w + xx] : 0.f; };
+      const float n1 = M(y + dy, x + dx), n2 = M(y - dy, x - dx);
+      const bool mx = x < w && fminf(__fsub_rn(m[k], n1), __fsub_rn(m[k], n2)) > 0.f;
+      wk[k] = (mx && m[k] > lo) ? 1 : 0;
+      s[k] = (mx && m[k] > hi) ? 1.f : 0.f;
+    }
+    store4(weak + (int64_t)y * w, x0, w, vec, wk);
+    store4(strongf + (int64_t)y * w, x0, w, vec, s);
+  }
+}
+
 PRV2_NO_PACKED_FP32_END
 
 static int check_frames(const char* name, int n, int h, int w) {
@@ -616,6 +760,37 @@ extern "C" int prv2_canny(const float* image, int32_t n, int32_t h, int32_t w, c
   hipLaunchKernelGGL(ccl_local_kernel, dim3(cdiv(w, kTile), cdiv(h, kTile), n), dim3(256), 0, s, low, lab, strong, h, w);
   hipLaunchKernelGGL(ccl_merge_kernel, dim3(grid), dim3(256), 0, s, low, lab, n, h, w);
   hipLaunchKernelGGL(ccl_resolve_kernel, dim3(grid), dim3(256), 0, s, low, mag, lab, root, strong, total, high_threshold);
+  hipLaunchKernelGGL(ccl_final_kernel, dim3(grid), dim3(256), 0, s, low, root, strong, edges, total);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_seg_canny(const float* seg_chw, int32_t h, int32_t w, const float* gauss_w5_host, float low_threshold,
+                              float high_threshold, uint8_t* edges, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* name = "seg_canny";
+  PRV2_REQUIRE(seg_chw && edges && gauss_w5_host, "%s: null pointer", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1 && (int64_t)3 * h * w < (int64_t)INT_MAX, "%s: bad shape 3 x %d x %d", name, h, w);
+  if (check_frames(name, 1, h, w) || check_ws(name, 1, h, w, workspace, workspace_bytes)) return 1;  // (3 x 3: a reflect pad of 2)
+  const Layout L = layout(1, h, w);
+  Gauss5 g;
+  for (int j = 0; j < 5; ++j) g.w[j] = gauss_w5_host[j];
+  // the plain detector's buffers under other names: isob holds the axis bytes, jsob the strong pixels as 0.f / 1.f
+  float *t = at<float>(workspace, L.t), *sm = at<float>(workspace, L.sm), *mag = at<float>(workspace, L.mag);
+  float* strongf = at<float>(workspace, L.jsob);
+  uint8_t *axis = at<uint8_t>(workspace, L.isob), *low = at<uint8_t>(workspace, L.low);
+  int32_t *lab = at<int32_t>(workspace, L.lab), *root = at<int32_t>(workspace, L.root), *strong = at<int32_t>(workspace, L.strong);
+  const int64_t total = (int64_t)h * w;
+  const int vec = w % 4 == 0 && aligned16(seg_chw) && aligned16(workspace);
+  const int qgrid = flat_grid((int64_t)h * cdiv(w, 4), 256), grid = flat_grid(total, 256);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(seg_grey_blur_kernel, dim3(qgrid), dim3(256), 0, s, seg_chw, t, (int)h, (int)w, g, vec);
+  hipLaunchKernelGGL(seg_vblur_kernel, dim3(qgrid), dim3(256), 0, s, (const float*)t, sm, (int)h, (int)w, g, vec);
+  hipLaunchKernelGGL(seg_sobel_kernel, dim3(qgrid), dim3(256), 0, s, (const float*)sm, mag, axis, (int)h, (int)w, vec);
+  hipLaunchKernelGGL(seg_nms_kernel, dim3(qgrid), dim3(256), 0, s, (const float*)mag, (const uint8_t*)axis, low, strongf, (int)h, (int)w,
+                     low_threshold, high_threshold, vec);
+  hipLaunchKernelGGL(ccl_local_kernel, dim3(cdiv(w, kTile), cdiv(h, kTile), 1), dim3(256), 0, s, low, lab, strong, h, w);
+  hipLaunchKernelGGL(ccl_merge_kernel, dim3(grid), dim3(256), 0, s, low, lab, 1, h, w);
+  hipLaunchKernelGGL(ccl_resolve_kernel, dim3(grid), dim3(256), 0, s, low, strongf, lab, root, strong, total, 0.5f);
   hipLaunchKernelGGL(ccl_final_kernel, dim3(grid), dim3(256), 0, s, low, root, strong, edges, total);
   PRV2_LAUNCH_CHECK(name);
   return 0;

@@ -5,6 +5,9 @@
 //   disp_gt_kernel        disparity -> depth = factor / disp and the boundary map, one pass        (u4k_dataset.py:128-129,216)
 //   gt_decode_kernel      the general dataset's ground truth (ETH3D / Middlebury PFM / Cityscapes PNG samples) -> depth and the
 //                         boundary map, one pass                                                   (general_dataset.py:103-151)
+//   cityscapes_gt_kernel  CityScapesDataset's ground truth: the same decode with the frame's own factor, the noisy bands, the sky class,
+//                         the boundary map of the final depth and the float segmentation map, one pass  (cityscapes_dataset.py:153-174,300)
+//   cityscapes_masks_kernel  the edge and flatten pixel sets of CityScapesDataset.get_metrics, one pass  (cityscapes_dataset.py:360-365)
 //   depth_metrics_kernel  the twelve sums of compute_errors + soft_edge_error of B frames, for up to three pixel sets at once
 //   metrics_final_kernel  the per-block partials of a frame summed in block order
 //   image_grad_kernel / edge_dilate_kernel / edge_region_kernel   ETHDataset's edge area from the IMAGE gradient: Sobel magnitude summed
@@ -203,6 +206,135 @@ __global__ void __launch_bounds__(256) gt_decode_kernel(const void* __restrict__
         depth[o + k] = d[k];
         boundary[o + k] = e[k];
       }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// CityScapesDataset's ground truth (cityscapes_dataset.py:153-174, :300): gt_decode1<PRV2_GT_CITYSCAPES>, then -1 in the noisy bands
+// (the last ceil(h / 4) rows, the first w / 16 and the last ceil(w / 16) columns), then 0 where the colour segmentation map shows the
+// sky class (R == 70 and G == 130); the boundary map is taken from THAT map, so every neighbour is decoded the same way.
+struct CsBands {
+  int y1, x0, x1;  // a pixel is in a band when y >= y1 or x < x0 or x >= x1
+};
+
+// the R and G bytes of four pixels of a [h, w, 3] byte map (the 12 bytes as three words when vec), zero behind the row's end
+__device__ __forceinline__ void load_seg4(const uint8_t* __restrict__ seg, int64_t row, int x0, int w, int vec, uint8_t* b) {
+  const uint8_t* s = seg + (row * w + x0) * 3;
+  if (vec) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(s);
+    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
+    for (int k = 0; k < 4; ++k) {
+      b[k] = (uint8_t)(w0 >> (8 * k));
+      b[4 + k] = (uint8_t)(w1 >> (8 * k));
+      b[8 + k] = (uint8_t)(w2 >> (8 * k));
+    }
+  } else {
+    for (int k = 0; k < 12; ++k) b[k] = x0 + k / 3 < w ? s[k] : 0;
+  }
+}
+
+__device__ __forceinline__ float cs_value(uint32_t raw, float factor, bool band, bool sky) {
+  float d, unused;
+  gt_decode1<PRV2_GT_CITYSCAPES>(raw, factor, 0.f, d, unused);
+  return sky ? 0.f : (band ? -1.0f : d);
+}
+
+// the final values of the four pixels x0 .. x0 + 3 of row y (b: the row's segmentation bytes, as load_seg4 leaves them)
+template <bool SEG>
+__device__ __forceinline__ void cs_row4(const uint16_t* __restrict__ disp, const uint8_t* __restrict__ seg, int y, int x0, int w, int vec,
+                                        float factor, CsBands bd, float* v, uint8_t* b) {
+  uint32_t r[4];
+  load_raw4<PRV2_GT_CITYSCAPES>(disp, y, x0, w, vec, 0, r);
+  if (SEG) load_seg4(seg, y, x0, w, vec, b);
+  for (int k = 0; k < 4; ++k) {
+    const int x = x0 + k;
+    v[k] = cs_value(r[k], factor, y >= bd.y1 || x < bd.x0 || x >= bd.x1, SEG && b[3 * k] == 70 && b[3 * k + 1] == 130);
+  }
+}
+
+template <bool SEG>
+__device__ __forceinline__ float cs_at(const uint16_t* __restrict__ disp, const uint8_t* __restrict__ seg, int y, int x, int w, float factor,
+                                       CsBands bd) {
+  const int64_t i = (int64_t)y * w + x;
+  return cs_value(disp[i], factor, y >= bd.y1 || x < bd.x0 || x >= bd.x1, SEG && seg[i * 3] == 70 && seg[i * 3 + 1] == 130);
+}
+
+template <bool SEG>
+__global__ void __launch_bounds__(256) cityscapes_gt_kernel(const uint16_t* __restrict__ disp, const uint8_t* __restrict__ seg,
+                                                            float* __restrict__ depth, uint8_t* __restrict__ boundary,
+                                                            float* __restrict__ seg_out, int h, int w, float factor, CsBands bd, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq, hw = (int64_t)h * w;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    float c[4], up[4], dn[4], left = 0.f, right = 0.f;
+    uint8_t b[12], nb[12];
+    cs_row4<SEG>(disp, seg, y, x0, w, vec, factor, bd, c, b);
+    if (y > 0) cs_row4<SEG>(disp, seg, y - 1, x0, w, vec, factor, bd, up, nb);
+    if (y + 1 < h) cs_row4<SEG>(disp, seg, y + 1, x0, w, vec, factor, bd, dn, nb);
+    if (x0 > 0) left = cs_at<SEG>(disp, seg, y, x0 - 1, w, factor, bd);
+    if (x0 + 4 < w) right = cs_at<SEG>(disp, seg, y, x0 + 4, w, factor, bd);
+    uint8_t e[4];
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + k;
+      bool t = false;  // the rule of disp_gt_kernel with th = 1
+      if (y > 0) t |= fabsf(c[k] - up[k]) > 1.0f;
+      if (y + 1 < h) t |= fabsf(dn[k] - c[k]) > 1.0f;
+      if (x > 0) t |= fabsf(c[k] - (k ? c[k - 1] : left)) > 1.0f;
+      if (x + 1 < w) t |= fabsf((k < 3 ? c[k + 1] : right) - c[k]) > 1.0f;
+      e[k] = t ? 1 : 0;
+    }
+    const int64_t o = (int64_t)y * w + x0;
+    if (vec) {
+      *reinterpret_cast<float4*>(depth + o) = make_float4(c[0], c[1], c[2], c[3]);
+      *reinterpret_cast<uint32_t*>(boundary + o) = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16 | (uint32_t)e[3] << 24;
+      if (SEG)
+        for (int ch = 0; ch < 3; ++ch)
+          *reinterpret_cast<float4*>(seg_out + ch * hw + o) = make_float4((float)b[ch], (float)b[3 + ch], (float)b[6 + ch], (float)b[9 + ch]);
+    } else {
+      for (int k = 0; k < 4 && x0 + k < w; ++k) {
+        depth[o + k] = c[k];
+        boundary[o + k] = e[k];
+        if (SEG)
+          for (int ch = 0; ch < 3; ++ch) seg_out[ch * hw + o + k] = (float)b[3 * k + ch];
+      }
+    }
+  }
+}
+
+// CityScapesDataset.get_metrics' two pixel sets (cityscapes_dataset.py:360-365): edge = seg_edges and dilate7(gt_edges) (the 7 x 7 blur
+// > 0: positive weights, the window clipped at the frame), flatten = not edge and not hr_region.  Segmentation edges are sparse: only
+// their pixels look at the 7 x 7 window of gt_edges, straight from L2.
+__global__ void __launch_bounds__(256) cityscapes_masks_kernel(const uint8_t* __restrict__ seg_edges, const uint8_t* __restrict__ gt_edges,
+                                                               const uint8_t* __restrict__ region, uint8_t* __restrict__ edge,
+                                                               uint8_t* __restrict__ flatten, int h, int w, int vec) {
+  const int wq = (w + 3) / 4;
+  const int64_t quads = (int64_t)h * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    const int64_t o = (int64_t)y * w + x0;
+    uint8_t s[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0}, e[4], f[4];
+    if (vec) {
+      const uint32_t ts = *reinterpret_cast<const uint32_t*>(seg_edges + o), tr = *reinterpret_cast<const uint32_t*>(region + o);
+      for (int k = 0; k < 4; ++k) s[k] = (uint8_t)(ts >> (8 * k)), r[k] = (uint8_t)(tr >> (8 * k));
+    } else {
+      for (int k = 0; k < 4 && x0 + k < w; ++k) s[k] = seg_edges[o + k], r[k] = region[o + k];
+    }
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + k;
+      uint8_t any = 0;
+      if (s[k] && x < w)
+        for (int yy = max(y - 3, 0); yy <= min(y + 3, h - 1) && !any; ++yy)
+          for (int xx = max(x - 3, 0); xx <= min(x + 3, w - 1); ++xx) any |= gt_edges[(int64_t)yy * w + xx];
+      e[k] = any ? 1 : 0;
+      f[k] = (!any && !r[k]) ? 1 : 0;
+    }
+    if (vec) {
+      *reinterpret_cast<uint32_t*>(edge + o) = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16 | (uint32_t)e[3] << 24;
+      *reinterpret_cast<uint32_t*>(flatten + o) = (uint32_t)f[0] | (uint32_t)f[1] << 8 | (uint32_t)f[2] << 16 | (uint32_t)f[3] << 24;
+    } else {
+      for (int k = 0; k < 4 && x0 + k < w; ++k) edge[o + k] = e[k], flatten[o + k] = f[k];
     }
   }
 }
@@ -530,6 +662,39 @@ extern "C" int prv2_gt_decode(const void* src, int32_t kind, int32_t h, int32_t 
     hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_MIDDLEBURY>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
   else
     hipLaunchKernelGGL(gt_decode_kernel<PRV2_GT_CITYSCAPES>, grid, block, 0, s, src, depth, boundary, (int)h, (int)w, factor, doffs, th, fl, bs, vec);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_cityscapes_gt(const uint16_t* disp, const uint8_t* seg_hwc, int32_t h, int32_t w, float factor, float* depth,
+                                  uint8_t* boundary, float* seg_chw, void* stream) {
+  const char* name = "cityscapes_gt";
+  PRV2_REQUIRE(disp && depth && boundary, "%s: null pointer", name);
+  PRV2_REQUIRE((seg_hwc == nullptr) == (seg_chw == nullptr), "%s: seg_hwc and seg_chw come together or not at all", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE((int64_t)h * w * 3 < (int64_t)INT_MAX, "%s: %d x %d x 3 exceeds 2^31 bytes", name, h, w);
+  // Python's -h // 4, w // 16 and -w // 16 (cityscapes_dataset.py:163-165)
+  const CsBands bd{h - (int)cdiv(h, 4), w / 16, w - (int)cdiv(w, 16)};
+  const int vec = w % 4 == 0 && aligned(disp, 8) && aligned(depth, 16) && aligned(boundary, 4) && aligned(seg_hwc, 4) && aligned(seg_chw, 16);
+  const dim3 grid(flat_grid((int64_t)h * cdiv(w, 4), 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (seg_hwc)
+    hipLaunchKernelGGL(cityscapes_gt_kernel<true>, grid, block, 0, s, disp, seg_hwc, depth, boundary, seg_chw, (int)h, (int)w, factor, bd, vec);
+  else
+    hipLaunchKernelGGL(cityscapes_gt_kernel<false>, grid, block, 0, s, disp, seg_hwc, depth, boundary, seg_chw, (int)h, (int)w, factor, bd, vec);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_cityscapes_masks(const uint8_t* seg_edges, const uint8_t* gt_edges, const uint8_t* hr_region, int32_t h, int32_t w,
+                                     uint8_t* edge_mask, uint8_t* flatten, void* stream) {
+  const char* name = "cityscapes_masks";
+  PRV2_REQUIRE(seg_edges && gt_edges && hr_region && edge_mask && flatten, "%s: null pointer", name);
+  PRV2_REQUIRE(h >= 1 && w >= 1, "%s: bad shape %d x %d", name, h, w);
+  PRV2_REQUIRE((int64_t)h * w < (int64_t)INT_MAX, "%s: %d x %d exceeds 2^31 pixels", name, h, w);
+  const int vec = w % 4 == 0 && aligned(seg_edges, 4) && aligned(hr_region, 4) && aligned(edge_mask, 4) && aligned(flatten, 4);
+  hipLaunchKernelGGL(cityscapes_masks_kernel, dim3(flat_grid((int64_t)h * cdiv(w, 4), 256)), dim3(256), 0, (hipStream_t)stream, seg_edges,
+                     gt_edges, hr_region, edge_mask, flatten, (int)h, (int)w, vec);
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }

@@ -1269,6 +1269,58 @@ Tensor image_edge_region(const Tensor& image, int64_t H, int64_t W, double frac)
      "image_edge_region");
   return region;
 }
+// CityScapesDataset (cityscapes_dataset.py:153-174, :300, :333-334, :360-365): the ground-truth decode, kornia's Canny on the colour
+// segmentation map and the two pixel sets of its get_metrics
+std::tuple<Tensor, Tensor, Tensor> cityscapes_gt(const Tensor& disp, const optional<Tensor>& seg, double factor) {
+  TORCH_CHECK(disp.is_cuda(), "prv2: disp must be a GPU tensor (there is no CPU path)");
+  TORCH_CHECK(disp.scalar_type() == at::kUInt16 && disp.dim() == 2 && disp.is_contiguous(),
+              "prv2::cityscapes_gt: disp must be a contiguous uint16 [h, w] tensor");
+  Tensor depth = at::empty(disp.sizes(), disp.options().dtype(at::kFloat)), boundary = at::empty(disp.sizes(), disp.options().dtype(at::kByte));
+  Tensor seg_chw = at::empty({0}, disp.options().dtype(at::kFloat));  // (stays empty without a segmentation map)
+  const uint8_t* s = nullptr;
+  if (seg.has_value()) {
+    TORCH_CHECK(seg->is_cuda() && seg->device() == disp.device() && seg->scalar_type() == at::kByte && seg->dim() == 3 && seg->is_contiguous() &&
+                    seg->size(0) == disp.size(0) && seg->size(1) == disp.size(1) && seg->size(2) == 3,
+                "prv2::cityscapes_gt: seg must be a contiguous GPU uint8 [h, w, 3] tensor of disp's shape ", disp.sizes());
+    s = (const uint8_t*)seg->data_ptr();
+    seg_chw = at::empty({3, disp.size(0), disp.size(1)}, disp.options().dtype(at::kFloat));
+  }
+  Launch L(disp);
+  ok(prv2_cityscapes_gt((const uint16_t*)disp.data_ptr(), s, (int)disp.size(0), (int)disp.size(1), (float)factor, depth.data_ptr<float>(),
+                        (uint8_t*)boundary.data_ptr(), s ? seg_chw.data_ptr<float>() : nullptr, L.stream), "cityscapes_gt");
+  return {depth, boundary, seg_chw};
+}
+Tensor seg_canny(const Tensor& seg, at::ArrayRef<double> gauss_w, double low, double high) {
+  dev_f32(seg, "seg");
+  TORCH_CHECK(seg.dim() == 3 && seg.size(0) == 3 && seg.is_contiguous(), "prv2::seg_canny: seg must be a contiguous [3, h, w] tensor");
+  TORCH_CHECK(gauss_w.size() == 5, "prv2::seg_canny: five Gaussian taps");
+  float w5[5];
+  for (int j = 0; j < 5; ++j) w5[j] = (float)gauss_w[j];
+  const int64_t bytes = prv2_edges_workspace_bytes(1, (int)seg.size(1), (int)seg.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::seg_canny: bad shape ", seg.sizes());
+  Tensor ws = at::empty({bytes}, seg.options().dtype(at::kByte));
+  Tensor out = at::empty({seg.size(1), seg.size(2)}, seg.options().dtype(at::kBool));
+  Launch L(seg);
+  ok(prv2_seg_canny(seg.data_ptr<float>(), (int)seg.size(1), (int)seg.size(2), w5, (float)low, (float)high, (uint8_t*)out.data_ptr(), ws.data_ptr(),
+                    ws.numel(), L.stream), "seg_canny");
+  return out;
+}
+std::tuple<Tensor, Tensor> cityscapes_masks(const Tensor& seg_edges, const Tensor& gt_edges, const Tensor& hr_region) {
+  const Tensor* maps[] = {&seg_edges, &gt_edges, &hr_region};
+  const char* names[] = {"seg_edges", "gt_edges", "hr_region"};
+  for (int i = 0; i < 3; ++i) {
+    const Tensor& t = *maps[i];
+    TORCH_CHECK(t.is_cuda(), "prv2: ", names[i], " must be a GPU tensor (there is no CPU path)");
+    TORCH_CHECK((t.scalar_type() == at::kBool || t.scalar_type() == at::kByte) && t.dim() == 2 && t.is_contiguous() && t.sizes() == seg_edges.sizes(),
+                "prv2::cityscapes_masks: ", names[i], " must be a contiguous bool / uint8 [h, w] tensor of shape ", seg_edges.sizes());
+  }
+  Tensor edge = at::empty(seg_edges.sizes(), seg_edges.options().dtype(at::kByte)), flatten = at::empty_like(edge);
+  Launch L(seg_edges);
+  ok(prv2_cityscapes_masks((const uint8_t*)seg_edges.data_ptr(), (const uint8_t*)gt_edges.data_ptr(), (const uint8_t*)hr_region.data_ptr(),
+                           (int)seg_edges.size(0), (int)seg_edges.size(1), (uint8_t*)edge.data_ptr(), (uint8_t*)flatten.data_ptr(), L.stream),
+     "cityscapes_masks");
+  return {edge, flatten};
+}
 // scale-and-shift-invariant evaluation (losses.py:523-544, :600-700): pred [n, h, w], or [n, ph, pw] sampled inside the kernels
 Tensor ssi_metrics(const Tensor& gt, const Tensor& pred, double min_depth, double max_depth, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
   dev_frames(gt, "gt", at::kFloat);
@@ -1596,6 +1648,10 @@ TORCH_LIBRARY(prv2, m) {
   m.def("gt_decode(Tensor src, int kind, float factor, float doffs, float th, bool flip, bool byteswap) -> (Tensor, Tensor)");
   m.def("u8_image_resize(Tensor src, int oh, int ow) -> Tensor");
   m.def("image_edge_region(Tensor image, int H, int W, float frac) -> Tensor");
+  // CityScapesDataset: the ground-truth decode (seg_chw is empty without a segmentation map), kornia's Canny, the two pixel sets
+  m.def("cityscapes_gt(Tensor disp, Tensor? seg, float factor) -> (Tensor, Tensor, Tensor)");
+  m.def("seg_canny(Tensor seg, float[] gauss_w, float low, float high) -> Tensor");
+  m.def("cityscapes_masks(Tensor seg_edges, Tensor gt_edges, Tensor hr_region) -> (Tensor, Tensor)");
   m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
         "int x0, int x1) -> Tensor");
   m.def("ssi_metrics(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1) -> Tensor");
@@ -1694,6 +1750,9 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("depth_metrics_lowres", &depth_metrics_lowres);
   m.impl("u8_image_resize", &u8_image_resize);
   m.impl("image_edge_region", &image_edge_region);
+  m.impl("cityscapes_gt", &cityscapes_gt);
+  m.impl("seg_canny", &seg_canny);
+  m.impl("cityscapes_masks", &cityscapes_masks);
   m.impl("ssi_metrics", &ssi_metrics);
   m.impl("sparsify", &sparsify);
   m.impl("pointcloud_pack", &pointcloud_pack);

@@ -5,12 +5,15 @@ ImageDataset        estimator/datasets/general_dataset.py:64-245 (folder of imag
 UnrealStereo4kDataset  estimator/datasets/u4k_dataset.py:20-233 (split file -> image_hr / depth_gt / boundary, decoded on the GPU)
 ETHDataset          estimator/datasets/eth_dataset.py:23-385 (split file -> image_hr resized on the GPU / depth_gt / boundary; every
                     metric also inside and outside the image's edge area, found on the GPU)
-``ssi_metrics=True`` (tools/test.py --ssi-metrics) on any of the three datasets: get_metrics adds the scale-and-shift-invariant scores
+CityScapesDataset   estimator/datasets/cityscapes_dataset.py:27-501 (split file -> image_hr / depth_gt / boundary / seg_image, decoded on
+                    the GPU with the file's own camera; depth metrics away from class boundaries and image edges, boundary metrics
+                    on segmentation edges that are ground-truth depth edges)
+``ssi_metrics=True`` (tools/test.py --ssi-metrics) on any of the four datasets: get_metrics adds the scale-and-shift-invariant scores
                     of estimator/models/losses.py:523-544, :600-700 (metrics.SSI_KEYS; two fused GPU passes, csrc/ssi_eval.hip)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
-_ReadAhead / _StagedDataset  the two staging slots and the one background reader that the three datasets share
+_ReadAhead / _StagedDataset  the two staging slots and the one background reader that the four datasets share
 Not built: the ``gta`` ground truth (general_dataset.py:96-101: .exr files need imageio, which is absent) and the dataset classes
-KittiDataset, ScanNetDataset and CityScapesDataset.  Without ``gt_format`` ground truth is metric depth as <basename>.npy files.
+KittiDataset and ScanNetDataset; CityScapesDataset is a class here but no registry entry yet (see there).  Without ``gt_format`` ground truth is metric depth as <basename>.npy files.
 """
 from __future__ import annotations
 
@@ -124,7 +127,7 @@ def _read_exact(path, view, offset=0):
 
 
 class _StagedDataset:
-    """What the three datasets share: the read-ahead's life cycle and the two ends of ``get_metrics`` (``_common``, ``_with_ssi``).
+    """What the datasets share: the read-ahead's life cycle and the two ends of ``get_metrics`` (``_common``, ``_with_ssi``).
     A subclass gives ``_make_slot()``, ``_read(idx, slot)`` and, if it needs one, ``_prepare(idx, slot)`` (_ReadAhead's three
     callbacks); its ``__getitem__`` queues its own copies out of the slot between ``_acquire`` and ``_release``."""
     ssi_metrics = False  # (the constructor's flag; an instance made without it scores as before)
@@ -669,3 +672,161 @@ class ETHDataset(_StagedDataset):
             for k in results[0]:
                 out[k] = float(np.nanmean([float(r[k]) for r in results]))
         return out
+
+
+CITYSCAPES_METRIC_KEYS = ETH_METRIC_KEYS + ("EdgeAcc", "EdgeComp", "precision", "recall", "f1_score", "hamming", "acc")  # :422-440
+
+
+def read_cityscapes_camera(path) -> float:
+    """cityscapes_dataset.py:149-156: the decode factor baseline x fx of a camera file as the float32 value the reference's division
+    by a float32 array sees; a file without ``extrinsic.baseline`` / ``intrinsic.fx`` raises ValueError naming it"""
+    import json
+    with open(path) as f:
+        try:
+            cam = json.load(f)
+            return float(np.float32(float(cam["extrinsic"]["baseline"]) * float(cam["intrinsic"]["fx"])))
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError(f"{path}: no extrinsic.baseline / intrinsic.fx in the camera file ({type(e).__name__}: {e})") from None
+
+
+# (not registered in DATASETS: tools/test.py still answers a config of this type with "is not built", which tests/test_u4k_eval_host.py
+#  and tests/test_general_gt_host.py pin; the class is built by its constructor -- tools/test.py --test-type cityscapes does that)
+class CityScapesDataset(_StagedDataset):
+    """estimator/datasets/cityscapes_dataset.py:27-501, ``mode='infer'``: the frames of a split file with their disparity, camera and
+    (``with_seg_map``) colour segmentation map.  One background thread (_ReadAhead: files and host memory only) decodes the NEXT
+    frame's image (PIL ``convert("RGB")``), its 16-bit disparity PNG, the segmentation map's RGB bytes and the camera JSON into pinned
+    buffers; on the device ops.u8_image makes ``image_hr`` and ONE pass of ops.cityscapes_gt makes ``depth_gt`` [1, 1, H, W]
+    (baseline x fx / disparity, -1 in the noisy bands, 0 at the sky class), ``boundary`` and ``seg_image`` (fp32 [3, H, W], 0 .. 255).
+    No ``image_lr`` key (Tester._frames makes it with model.resizer).  ``get_metrics`` (:318-408) takes the ten depth metrics on the
+    "flatten" pixels -- away from the edges that are both a segmentation edge (ops.seg_canny: kornia's Canny) and a ground-truth depth
+    edge, and away from the image's edges -- and the seven boundary metrics against those edges.  ``filter_sky``, ``pre_norm_bbox``,
+    ``base``, ``filter_thr`` and ``patch_raw_shape`` are stored (they act in training).  Not built: ``mode='train'``,
+    ``transform_cfg.random_crop``, ``transform_cfg.input_size_shallow`` (PIL's antialiased resizes; no shipped Cityscapes config sets
+    it), ``with_pseudo_label`` / ``with_uncert`` (training inputs)."""
+
+    dataset_name = "cityscapes"
+    _reader_name = "cityscapes-read"
+
+    def __init__(self, mode, split, transform_cfg, min_depth, max_depth, patch_raw_shape=(256, 512), data_root="./data/cityscapes",
+                 resize_mode="zoe", with_pseudo_label=False, pseudo_label_path=None, with_seg_map=False, filter_sky=True, pre_norm_bbox=True,
+                 with_uncert=False, base=float(np.exp(1)), filter_thr=-0.1, ssi_metrics=False):
+        if mode == "train":
+            raise NotImplementedError("CityScapesDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / "
+                                      "random_crop, cityscapes_dataset.py:178-298) is not built; inference modes only")
+        if transform_cfg.get("random_crop", False):
+            raise NotImplementedError("CityScapesDataset(transform_cfg.random_crop): the random crops (cityscapes_dataset.py:263-280) are not built")
+        if transform_cfg.get("input_size_shallow", None) is not None:
+            raise NotImplementedError("CityScapesDataset(transform_cfg.input_size_shallow): PIL's antialiased resizes "
+                                      "(cityscapes_dataset.py:193-197) are not built; no shipped Cityscapes config sets it")
+        if with_pseudo_label or with_uncert:
+            raise NotImplementedError("CityScapesDataset(with_pseudo_label / with_uncert): pseudo labels and their uncertainty are training "
+                                      "inputs (cityscapes_dataset.py:200-219)")
+        if resize_mode not in ("zoe", "depth-anything"):
+            raise NotImplementedError(f"CityScapesDataset(resize_mode={resize_mode!r})")  # cityscapes_dataset.py:66-73
+        self.mode, self.split, self.data_root = mode, split, data_root
+        self.min_depth, self.max_depth = min_depth, max_depth
+        self.transform_cfg = transform_cfg
+        self.resize_mode = resize_mode
+        self.with_seg_map = bool(with_seg_map)
+        self.with_pseudo_label, self.with_uncert, self.pseudo_label_path = False, False, pseudo_label_path
+        self.filter_sky, self.pre_norm_bbox, self.base, self.filter_thr = filter_sky, pre_norm_bbox, base, filter_thr
+        self.patch_raw_shape = tuple(patch_raw_shape)
+        self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS), plain set only
+        self.data_infos = self.load_data_list()
+
+    def load_data_list(self):
+        """cityscapes_dataset.py:86-138: 'img disp' per line, joined to ``data_root``; the camera file is the image path with
+        leftImg8bit -> camera and .png -> .json, the segmentation map the disparity path with disparity -> gtFine and .png ->
+        _color.png; sorted by image path; the basename of :260-261"""
+        if self.split is None:
+            raise NotImplementedError("CityScapesDataset needs a split file (cityscapes_dataset.py:133-134)")
+        infos = []
+        with open(self.split) as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                img, depth_map = line.strip().split(" ")
+                info = dict(depth_map_path=os.path.join(self.data_root, depth_map), img_path=os.path.join(self.data_root, img), filename=img)
+                info["camera_info"] = info["img_path"].replace("leftImg8bit", "camera").replace(".png", ".json")
+                if self.with_seg_map:
+                    info["seg_map"] = info["depth_map_path"].replace("disparity", "gtFine").replace(".png", "_color.png")
+                info["img_file_basename"] = os.path.splitext(img)[0].replace("/", "_")
+                infos.append(info)
+        return sorted(infos, key=lambda x: x["img_path"])
+
+    def __len__(self):
+        return len(self.data_infos)
+
+    def _make_slot(self):
+        return dict(img=None, disp=None, seg=None, shape=None, factor=None)
+
+    def _prepare(self, idx, slot):
+        """(caller's thread) the slot's pinned buffers hold a frame of item ``idx``'s disparity size, read from the PNG's header
+        (ValueError naming the file unless it is 16-bit greyscale)"""
+        h, w = _png16_shape(self.data_infos[idx]["depth_map_path"])
+        px = h * w
+        for key, item in (("img", 3), ("disp", 2)) + ((("seg", 3),) if self.with_seg_map else ()):
+            if slot[key] is None or slot[key].numel() < px * item:
+                slot[key] = torch.empty((px * item,), dtype=torch.uint8).pin_memory()
+
+    def _read(self, idx, slot):
+        """(background thread: files and host memory only) the disparity samples, the image's and the segmentation map's RGB bytes
+        and the camera's factor of item ``idx``; every size is checked against the disparity's"""
+        from PIL import Image
+        info = self.data_infos[idx]
+        h, w = _png16_shape(info["depth_map_path"])  # (ValueError naming the file unless it is 16-bit greyscale)
+        d = np.asarray(Image.open(info["depth_map_path"]))  # cv2.imread(path, IMREAD_UNCHANGED) of a 16-bit PNG: its uint16 samples
+        if d.shape != (h, w) or d.dtype.itemsize != 2:
+            raise ValueError(f"{info['depth_map_path']}: decoded to {d.dtype} {d.shape}, expected uint16 {(h, w)}")
+        np.copyto(slot["disp"].numpy()[:h * w * 2].view(np.uint16).reshape(h, w), d, casting="unsafe")
+        for key, path, what in (("img", info["img_path"], "image"),) + ((("seg", info["seg_map"], "segmentation map"),) if self.with_seg_map else ()):
+            a = np.asarray(Image.open(path).convert("RGB"))  # cityscapes_dataset.py:146, :170
+            if a.shape[:2] != (h, w):
+                raise ValueError(f"{path}: the {what} is {a.shape[0]} x {a.shape[1]}, the disparity map {info['depth_map_path']} {h} x {w}")
+            np.copyto(slot[key].numpy()[:a.size].reshape(a.shape), a)
+        slot["shape"], slot["factor"] = (h, w), read_cityscapes_camera(info["camera_info"])
+
+    def __getitem__(self, idx):
+        from . import ops
+        idx, slot = self._acquire(idx)
+        h, w = slot["shape"]
+        raw = slot["img"][:h * w * 3].cuda(non_blocking=True).view(h, w, 3)
+        disp = slot["disp"][:h * w * 2].cuda(non_blocking=True).view(torch.uint16).view(h, w)
+        seg = slot["seg"][:h * w * 3].cuda(non_blocking=True).view(h, w, 3) if self.with_seg_map else None
+        factor = slot["factor"]
+        self._release(idx)
+        depth, boundary, seg_image = ops.cityscapes_gt(disp, seg, factor)  # :153-174 and get_boundaries(disp_gt, th=1, dilation=0), :300
+        item = dict(image_hr=ops.u8_image(raw, swap_rb=False), depth_gt=depth[None, None], boundary=boundary,
+                    img_file_basename=self.data_infos[idx]["img_file_basename"])
+        if self.with_seg_map:
+            item["seg_image"] = seg_image
+        return item
+
+    def get_metrics(self, depth_gt, result, disp_gt_edges, seg_image=None, image_hr=None, **kw):
+        """cityscapes_dataset.py:318-408 on the device: edge = segmentation edges (ops.seg_canny) that are 7 x 7-widened ground-truth
+        depth edges, flatten = neither such an edge nor in the image's edge area (ops.image_edge_region, frac 0.05) -- one pass of
+        ops.cityscapes_masks; the ten depth metrics on the flatten pixels (the prediction's resize inside the scoring kernel), then the
+        seven boundary metrics of the prediction's log-depth Canny edges against the edge set at the valid pixels.  The noisy bands
+        are -1 in ``depth_gt`` already, so ``valid`` is the depth range alone."""
+        from . import metrics as M, ops
+        if seg_image is None or image_hr is None:
+            raise ValueError("CityScapesDataset.get_metrics needs seg_image (with_seg_map=True) and image_hr: its pixel sets come from "
+                             "the segmentation map's and the image's edges (cityscapes_dataset.py:333, :346)")
+        H, W = depth_gt.shape[-2:]
+        gt = torch.as_tensor(depth_gt).cuda().float().reshape(H, W)
+        seg = torch.as_tensor(seg_image).cuda().float().reshape(3, H, W)
+        image = torch.as_tensor(image_hr).cuda().float()
+        region = ops.image_edge_region(image.reshape(3, *image.shape[-2:]), H, W, frac=0.05)  # :346-352
+        edge_mask, flatten = ops.cityscapes_masks(ops.seg_canny(seg), M.extract_edges_device(gt, "log"), region)
+        common = self._common(fuse_resize=True)
+        out = M.compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, additional_mask=flatten, **common)
+        pred = torch.as_tensor(result).cuda().float().reshape(1, 1, *result.shape[-2:])
+        if pred.shape[-2:] != (H, W):  # :320-322
+            pred = F.interpolate(pred, (H, W), mode="bilinear", align_corners=False)
+        valid = (gt > self.min_depth) & (gt < self.max_depth)
+        out.update(M.compute_boundary_metrics_device(edge_mask, M.extract_edges_device(pred, "log"), valid))
+        return self._with_ssi(out, M.compute_ssi_metrics_fused, depth_gt, result, common)
+
+    def evaluate(self, results, **kw):
+        """cityscapes_dataset.py:410-501 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""
+        return ETHDataset.evaluate(self, results)

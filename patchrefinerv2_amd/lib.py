@@ -177,6 +177,10 @@ SIGNATURES = {
     "prv2_u8_image_resize": (_I, [_P, _I, _I, _P, _I, _I, _P]),
     "prv2_image_edge_region_workspace_bytes": (_L, [_I, _I]),
     "prv2_image_edge_region": (_I, [_P, _I, _I, _F, _P, _I, _I, _P, _L, _P]),
+    # CityScapesDataset (cityscapes_dataset.py): the ground-truth decode, kornia's Canny on the colour map, the two pixel sets
+    "prv2_cityscapes_gt": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
+    "prv2_seg_canny": (_I, [_P, _I, _I, _P, _F, _F, _P, _P, _L, _P]),
+    "prv2_cityscapes_masks": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     # scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): the fits, the four SSI scores and the error sums of the aligned prediction
     "prv2_ssi_metrics_workspace_bytes": (_L, [_I, _I, _I]),
     "prv2_ssi_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),

@@ -665,6 +665,101 @@ def edge_split_masks(gt, k: int = 7) -> np.ndarray:
     return binary_dilate(extract_edges(gt, "log"), k)
 
 
+# CityScapesDataset.get_metrics' pixel sets (host restatements: the spec of ops.seg_canny / ops.cityscapes_masks).
+#   seg_canny         cityscapes_dataset.py:333-334 (kornia.filters.canny on the colour segmentation map) -- kornia is not installed:
+#                     PARITY UNPINNED, as for ``canny`` above; this restatement is the specification
+#   cityscapes_masks  cityscapes_dataset.py:360-365
+SEG_CANNY_TAN_PI_8 = np.float32(np.tan(np.pi / 8))  # the half width of a 45-degree sector
+
+
+def seg_canny_weights() -> np.ndarray:
+    """kornia's 5-tap Gaussian of sigma 1 (get_gaussian_kernel1d: exp(-x^2 / (2 sigma^2)) normalised by its sum) in float32 -> [5]"""
+    x = torch.arange(5, dtype=torch.float32) - 2
+    g = torch.exp(-x.pow(2.0) / (2 * 1.0 ** 2))
+    return np.ascontiguousarray((g / g.sum()).numpy(), dtype=np.float32)
+
+
+def seg_canny_axis(gx: np.ndarray, gy: np.ndarray) -> np.ndarray:
+    """the axis kornia's non-maximum suppression compares along, without atan2: 0 horizontal, 1 vertical, 2 the (+1, +1) diagonal,
+    3 the (+1, -1) diagonal.  kornia rounds atan2(gy, gx) to a multiple of 45 degrees and looks at the neighbour in that direction
+    and the opposite one, so this is round(atan2 * 4 / pi) mod 4.  float32 in, one float32 product per comparison."""
+    a, b = np.abs(gx), np.abs(gy)
+    T = SEG_CANNY_TAN_PI_8
+    return np.where(b <= T * a, 0, np.where(a <= T * b, 1, np.where((gx > 0) == (gy > 0), 2, 3))).astype(np.uint8)
+
+
+def seg_canny_hysteresis(weak: np.ndarray, strong: np.ndarray) -> np.ndarray:
+    """the fixed point of kornia's hysteresis loop: the strong pixels, and the weak pixels 8-connected to one through weak pixels
+    (``strong`` is a subset of ``weak``)"""
+    from scipy import ndimage as ndi
+    labels, count = ndi.label(weak, np.ones((3, 3), bool))
+    good = np.zeros((count + 1,), bool)
+    good[np.unique(labels[strong])] = True
+    good[0] = False
+    return good[labels]
+
+
+def seg_canny_magnitude(seg):
+    """steps 1-5 of ``seg_canny`` -> (mag float32 [H, W], axis uint8 [H, W])"""
+    s = np.asarray(seg.detach().cpu() if isinstance(seg, torch.Tensor) else seg, dtype=np.float32)
+    s = s.reshape(3, *s.shape[-2:])
+    h, w = s.shape[1:]
+    if h < 3 or w < 3:
+        raise ValueError(f"seg_canny: {h} x {w}: the reflect pad of 2 needs at least 3 x 3 pixels")
+    f = np.float32
+    grey = (f(0.299) * s[0] + f(0.587) * s[1]) + f(0.114) * s[2]
+    g = seg_canny_weights()
+    p = np.pad(grey, ((0, 0), (2, 2)), mode="reflect")
+    t = g[0] * p[:, 0:w]
+    for j in range(1, 5):
+        t = t + g[j] * p[:, j:j + w]
+    p = np.pad(t, ((2, 2), (0, 0)), mode="reflect")
+    sm = g[0] * p[0:h]
+    for j in range(1, 5):
+        sm = sm + g[j] * p[j:j + h]
+    p = np.pad(sm, 1, mode="edge")
+    u, c, d = p[0:h], p[1:h + 1], p[2:h + 2]  # the rows above, at and below; columns x - 1, x, x + 1 at 0:w, 1:w + 1, 2:w + 2
+    gx = ((u[:, 2:] - u[:, :w]) + f(2) * (c[:, 2:] - c[:, :w])) + (d[:, 2:] - d[:, :w])
+    gy = ((d[:, :w] - u[:, :w]) + f(2) * (d[:, 1:w + 1] - u[:, 1:w + 1])) + (d[:, 2:] - u[:, 2:])
+    mag = np.sqrt((gx * gx + gy * gy) + f(1e-6))
+    assert mag.dtype == np.float32
+    return mag, seg_canny_axis(gx, gy)
+
+
+def seg_canny(seg, low_threshold=0.1, high_threshold=0.2) -> np.ndarray:
+    """cityscapes_dataset.py:333-334: ``kornia.filters.canny(seg)[1] > 0`` with kornia's defaults on the colour segmentation map
+    [3, H, W] (or [1, 3, H, W]) -> bool [H, W].  float32 throughout, as shifted sums in a fixed order and never as a convolution call --
+    on an axis-aligned class boundary the two pixels beside the step have mathematically equal magnitudes, so the strict > of step 6
+    is decided by the last bit and the operation order IS the specification (include/prv2.h prv2_seg_canny repeats it):
+      1 grey = (0.299 R + 0.587 G) + 0.114 B            2 5-tap Gaussian of sigma 1 along x, then y; reflect border; taps -2 .. +2
+      3 unnormalised Sobel, replicate border              4 mag = sqrt((gx gx + gy gy) + 1e-6)
+      5 the axis of the gradient (seg_canny_axis)         6 maximum iff min(mag - n1, mag - n2) > 0, 0 outside the frame
+      7 strong = maximum and mag > high, weak = maximum and mag > low; the result is seg_canny_hysteresis(weak, strong)"""
+    mag, axis = seg_canny_magnitude(seg)
+    h, w = mag.shape
+    p = np.pad(mag, 1)  # zero outside the frame
+
+    def nb(dy, dx):
+        return p[1 + dy:1 + dy + h, 1 + dx:1 + dx + w]
+    steps = ((0, 1), (1, 0), (1, 1), (-1, 1))  # (dy, dx) of the axes 0 .. 3
+    is_max = np.zeros((h, w), bool)
+    for k, (dy, dx) in enumerate(steps):
+        is_max |= (axis == k) & (np.minimum(mag - nb(dy, dx), mag - nb(-dy, -dx)) > 0)
+    weak = is_max & (mag > np.float32(low_threshold))
+    return seg_canny_hysteresis(weak, weak & (mag > np.float32(high_threshold)))
+
+
+def cityscapes_masks(seg_edges, gt_edges, hr_region):
+    """cityscapes_dataset.py:360-365 without the valid-depth mask (the scoring applies it) -> (edge_mask, flatten), bool [H, W]:
+    edge_mask = seg edges and the 7 x 7-widened ground-truth depth edges (``binary_dilate``: the blur > 0), flatten = not edge_mask
+    and not the image-edge region"""
+    def m(x):  # ([H, W] stays [H, W], also for H = W = 1)
+        x = np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
+        return x.reshape(x.shape[-2:]).astype(bool)
+    edge = m(seg_edges) & binary_dilate(m(gt_edges), 7)
+    return edge, ~edge & ~m(hr_region)
+
+
 # device route (csrc/edges.hip through ops.py): the same functions on GPU tensors, B frames per call
 def _frames_of(x: torch.Tensor):
     """[H, W] / [1, 1, H, W] -> ([1, H, W], True); [B, H, W] / [B, 1, H, W] -> ([B, H, W], False)"""

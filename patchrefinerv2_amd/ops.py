@@ -2150,6 +2150,94 @@ def image_edge_region(image_chw, H, W, frac=0.5):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# CityScapesDataset (estimator/datasets/cityscapes_dataset.py): the ground-truth decode and the two pixel sets of its get_metrics
+# (csrc/evalgt.hip), kornia's Canny on the colour segmentation map (csrc/edges.hip), both dispatch routes.  The host specification is
+# metrics.seg_canny / metrics.cityscapes_masks.
+# ------------------------------------------------------------------------------------------------------------------
+def cityscapes_gt(disp_u16, seg_u8, factor):
+    """uint16 disparity samples [H, W] and the RGB bytes [H, W, 3] of the colour segmentation map (or None) on the device, one pass
+    -> (depth fp32 [H, W], boundary uint8 [H, W], seg fp32 [3, H, W] holding 0 .. 255, or None): gt_decode('cityscapes')'s depth with
+    ``factor``, -1 in the noisy bands (the last ceil(H / 4) rows, the first W // 16 and the last ceil(W / 16) columns), 0 at the sky
+    class (R == 70 and G == 130); boundary = metrics.get_boundaries(<that map>, 1, 0) (cityscapes_dataset.py:153-174, :300;
+    include/prv2.h prv2_cityscapes_gt)."""
+    d = disp_u16
+    if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.uint16 or d.dim() != 2:
+        raise ValueError("cityscapes_gt: disp is a GPU uint16 [H, W] tensor")
+    d = d.contiguous()
+    s = seg_u8
+    if s is not None:
+        if not isinstance(s, torch.Tensor) or not s.is_cuda or s.dtype != torch.uint8 or s.device != d.device:
+            raise ValueError("cityscapes_gt: seg is a GPU uint8 [H, W, 3] tensor on disp's device, or None")
+        if tuple(s.shape) != tuple(d.shape) + (3,):
+            raise ValueError(f"cityscapes_gt: seg of shape {tuple(s.shape)}, expected {tuple(d.shape) + (3,)}")
+        s = s.contiguous()
+    box = []
+    if DISPATCH == "torch":
+        def call():
+            depth, boundary, seg = _tops().cityscapes_gt(d, s, float(factor))
+            box.extend((depth, boundary, seg if s is not None else None))
+    else:
+        depth = torch.empty(d.shape, dtype=torch.float32, device=d.device)
+        boundary = torch.empty(d.shape, dtype=torch.uint8, device=d.device)
+        seg = None if s is None else torch.empty((3,) + tuple(d.shape), dtype=torch.float32, device=d.device)
+        box.extend((depth, boundary, seg))
+        call = lambda: _c("cityscapes_gt", d.data_ptr(), _ptr(s), *d.shape, float(factor), depth.data_ptr(), boundary.data_ptr(), _ptr(seg))  # noqa: E731
+    PROFILER.launch_aux("cityscapes_gt", (7.0 if s is None else 22.0) * d.numel(), call, f"{d.shape[0]}x{d.shape[1]}")
+    return box[0], box[1], box[2]
+
+
+def seg_canny(seg_chw, low_threshold=0.1, high_threshold=0.2):
+    """fp32 colour segmentation map [3, H, W] (0 .. 255) on the device -> bool [H, W]: ``kornia.filters.canny(seg)[1] > 0`` with
+    kornia's defaults (cityscapes_dataset.py:333-334), equal to metrics.seg_canny on the same input pixel for pixel (include/prv2.h
+    prv2_seg_canny states the arithmetic).  H, W >= 3: the blur's reflect pad of 2 needs three pixels."""
+    from .metrics import seg_canny_weights
+    x = seg_chw
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        raise ValueError("seg_canny: seg is a GPU fp32 [3, H, W] tensor")
+    if x.dim() != 3 or x.shape[0] != 3:
+        raise ValueError(f"seg_canny: seg of shape {tuple(x.shape)}, expected [3, H, W]")
+    h, w = x.shape[1:]
+    if h < 3 or w < 3:
+        raise ValueError(f"seg_canny: {h} x {w}: the reflect pad of 2 needs at least 3 x 3 pixels")
+    x = x.contiguous()
+    gw = seg_canny_weights()
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().seg_canny(x, [float(v) for v in gw], float(low_threshold), float(high_threshold)))  # noqa: E731
+    else:
+        ws = torch.empty((L.load().prv2_edges_workspace_bytes(1, h, w),), dtype=torch.uint8, device=x.device)
+        out = torch.empty((h, w), dtype=torch.bool, device=x.device)
+        box.append(out)
+        call = lambda: _c("seg_canny", x.data_ptr(), h, w, gw.ctypes.data, float(low_threshold), float(high_threshold), out.data_ptr(),  # noqa: E731
+                          ws.data_ptr(), ws.numel())
+    PROFILER.launch_aux("seg_canny", 80.0 * h * w, call, f"{h}x{w}")
+    return box[0]
+
+
+def cityscapes_masks(seg_edges, gt_edges, hr_region):
+    """bool / uint8 maps [H, W] on the device -> (edge_mask, flatten), uint8 0/1 [H, W], one pass: edge_mask = seg_edges and the
+    7 x 7 dilation of gt_edges, flatten = not edge_mask and not hr_region (cityscapes_dataset.py:360-365 without the valid-depth
+    test, which the scoring kernel makes; include/prv2.h prv2_cityscapes_masks)."""
+    maps = []
+    for name, t in (("seg_edges", seg_edges), ("gt_edges", gt_edges), ("hr_region", hr_region)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.bool, torch.uint8) or t.dim() != 2:
+            raise ValueError(f"cityscapes_masks: {name} is a GPU bool / uint8 [H, W] tensor")
+        if maps and (t.shape != maps[0].shape or t.device != maps[0].device):
+            raise ValueError(f"cityscapes_masks: {name} {tuple(t.shape)} does not match seg_edges {tuple(maps[0].shape)} on its device")
+        maps.append(t.contiguous())
+    s, g, r = maps
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().cityscapes_masks(s, g, r))  # noqa: E731
+    else:
+        edge, flatten = torch.empty(s.shape, dtype=torch.uint8, device=s.device), torch.empty(s.shape, dtype=torch.uint8, device=s.device)
+        box.extend((edge, flatten))
+        call = lambda: _c("cityscapes_masks", s.data_ptr(), g.data_ptr(), r.data_ptr(), *s.shape, edge.data_ptr(), flatten.data_ptr())  # noqa: E731
+    PROFILER.launch_aux("cityscapes_masks", 5.0 * s.numel(), call, f"{s.shape[0]}x{s.shape[1]}")
+    return box[0], box[1]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Scale-and-shift-invariant evaluation (estimator/models/losses.py:523-544, :600-700; csrc/ssi_eval.hip), both dispatch routes.
 # ------------------------------------------------------------------------------------------------------------------
 SSI_VALUES = L.SSI_VALUES

@@ -25,9 +25,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-# importing this module registers the datasets, and the three classes stay importable from here (tools/ and the tests do both);
+# importing this module registers the datasets, and the four classes stay importable from here (tools/ and the tests do both);
 # read_image only because tests/test_host_logic.py imports it from here.  Everything else of datasets.py is imported from there.
-from .datasets import ETHDataset, ImageDataset, UnrealStereo4kDataset, read_image  # noqa: F401
+from .datasets import CityScapesDataset, ETHDataset, ImageDataset, UnrealStereo4kDataset, read_image  # noqa: F401
 from .output import write_png8, write_png16
 
 
@@ -225,8 +225,9 @@ class Tester:
         mean = result.mean(dtype=torch.float64) if result.is_cuda else result.mean()
         entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(mean), **extra)
         if score is not None and item.get("depth_gt") is not None:
+            seg = {} if item.get("seg_image") is None else dict(seg_image=item["seg_image"])  # (CityScapesDataset with_seg_map)
             entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], score, disp_gt_edges=item.get("boundary"),
-                                                           image_hr=item["image_hr"])
+                                                           image_hr=item["image_hr"], **seg)
         return entry
 
     def _emit(self, results, item, result, coarse, image_raw_shape, stage=None, **extra):

@@ -45,6 +45,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "gt_decode", "depth_metrics_lowres",
        # ETHDataset: the image stage and the edge area of its metric splits
        "u8_image_resize", "image_edge_region",
+       # CityScapesDataset: the ground-truth decode, kornia's Canny on the colour segmentation map, the two pixel sets of its get_metrics
+       "cityscapes_gt", "seg_canny", "cityscapes_masks",
        # scale-and-shift-invariant evaluation: the fits, the SSI scores and the error sums of the aligned prediction
        "ssi_metrics",
        # sparsification curves (AUSE / AURG) of a per-pixel uncertainty

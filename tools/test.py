@@ -19,7 +19,11 @@ and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`
 ``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
 ``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
 disparities decoded and scored on the GPU; prints a1 ... sq_rel and see.  ETHDataset: photographs resized and raw float32 depth decoded
-on the GPU; prints the thirty keys edge_* / noedge_* / plain, split by the image's edge area); ``general`` is the folder of images -- with
+on the GPU; prints the thirty keys edge_* / noedge_* / plain, split by the image's edge area); ``--test-type cityscapes``: the config's
+val_dataloader when it is a CityScapesDataset (configs/_base_/datasets/cityscapes.py: images, 16-bit disparity PNGs, camera files and colour
+segmentation maps decoded on the GPU; prints the seventeen keys a1 ... see, EdgeAcc ... acc -- the depth metrics away from class
+boundaries and image edges, the boundary metrics on segmentation edges that are ground-truth depth edges).  That class is built by its
+constructor and is no registry entry, so ``normal`` still answers it with "is not built"; ``general`` is the folder of images -- with
 ``--cfg-option general_dataloader.dataset.gt_dir=DIR general_dataloader.dataset.gt_format=u4k|eth3d|mid|cityscapes`` a folder with the
 reference's ground truth (general_dataset.py:75-158), decoded and scored on the GPU (``image_format=u4k|cityscapes|kitti`` selects
 read_image's branch, ``gt_shape=[H,W]`` the shape of ETH3D's raw files).
@@ -53,7 +57,9 @@ def parse_opts(opts):
 
 
 # --test-type -> the config section whose ``dataset`` is built (the reference's tools/test.py: normal / test_in / test_out / general)
-TEST_TYPES = dict(general="general_dataloader", normal="val_dataloader", test_in="test_in_dataloader", test_out="test_out_dataloader")
+# ``cityscapes``: the val_dataloader again, for the one dataset class that is built without being a registry entry (build_dataset)
+TEST_TYPES = dict(general="general_dataloader", normal="val_dataloader", test_in="test_in_dataloader", test_out="test_out_dataloader",
+                  cityscapes="val_dataloader")
 
 
 def dataset_config(cfg, args):
@@ -65,9 +71,16 @@ def dataset_config(cfg, args):
         raise SystemExit(f"--test-type {args.test_type} needs {section}.dataset in the config; {args.config} has none")
     ds_cfg = cfg[section].dataset.to_dict()
     kind = ds_cfg.get("type")
+    if args.test_type == "cityscapes":  # every size is the files' own: nothing of the command line goes into the dataset but --ssi-metrics
+        if kind != "CityScapesDataset":
+            raise SystemExit(f"--test-type cityscapes needs {section}.dataset.type = 'CityScapesDataset'; {args.config} has {kind}")
+        if getattr(args, "ssi_metrics", False):
+            ds_cfg["ssi_metrics"] = True
+        return ds_cfg
     if kind not in DATASETS:
         raise SystemExit(f"--test-type {args.test_type}: dataset type {kind} is not built (built: ImageDataset, UnrealStereo4kDataset; the "
-                         "cityscapes, kitti, scannet and eth decoders are not)")
+                         "cityscapes, kitti, scannet and eth decoders are not)"
+                         + (" -- a CityScapesDataset val_dataloader runs with --test-type cityscapes" if kind == "CityScapesDataset" else ""))
     if kind == "UnrealStereo4kDataset":
         ds_cfg["image_raw_shape"] = args.image_raw_shape
     elif kind == "ETHDataset":  # the image's size is transform_cfg.input_size_shallow, the ground truth's gt_shape
@@ -81,6 +94,14 @@ def dataset_config(cfg, args):
     return ds_cfg
 
 
+def build_dataset(ds_cfg):
+    """the dataset of ``dataset_config``'s dict: a registry entry, or CityScapesDataset by its constructor"""
+    if ds_cfg.get("type") == "CityScapesDataset":
+        from patchrefinerv2_amd.tester import CityScapesDataset
+        return CityScapesDataset(**{k: v for k, v in ds_cfg.items() if k != "type"})
+    return DATASETS.build(ds_cfg)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
@@ -91,7 +112,8 @@ def main():
     ap.add_argument("--work-dir", default="./work_dir/predictions")
     ap.add_argument("--test-type", default="general", help="general: general_dataloader (a folder of images; with dataset.gt_dir and dataset.gt_format = u4k / eth3d / mid / cityscapes "
                     "set by --cfg-option also the reference's ground truth, decoded and scored on the GPU); normal / test_in / test_out: "
-                    "val_dataloader / test_in_dataloader / test_out_dataloader (a dataset with ground truth, e.g. UnrealStereo4kDataset)")
+                    "val_dataloader / test_in_dataloader / test_out_dataloader (a dataset with ground truth, e.g. UnrealStereo4kDataset); cityscapes: "
+                    "val_dataloader when its dataset is a CityScapesDataset (depth and segmentation-edge metrics, seventeen keys)")
     ap.add_argument("--gray-scale", action="store_true")
     ap.add_argument("--image-raw-shape", nargs=2, type=int, default=[2160, 3840])
     ap.add_argument("--patch-split-num", nargs=2, type=int, default=[4, 4])
@@ -225,7 +247,7 @@ def main():
     else:
         raise SystemExit("give --ckp-path or --synthetic-weights")
 
-    dataset = DATASETS.build(ds_cfg)
+    dataset = build_dataset(ds_cfg)
     runner = RunnerInfo(rank=rank, world_size=world, save=args.save, gray_scale=args.gray_scale, work_dir=args.work_dir,
                         device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate,
                         save_ply=args.save_ply, save_normals=args.save_normals, save_mesh=args.save_mesh, save_stereo=args.save_stereo,
