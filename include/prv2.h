@@ -857,6 +857,26 @@ int prv2_seg_canny(const float* seg_chw, int32_t h, int32_t w, const float* gaus
 int prv2_cityscapes_masks(const uint8_t* seg_edges, const uint8_t* gt_edges, const uint8_t* hr_region, int32_t h, int32_t w,
                           uint8_t* edge_mask, uint8_t* flatten, void* stream);
 
+/* KittiDataset and ScanNetDataset (estimator/datasets/kitti_dataset.py, scannet_dataset.py), the part that runs on the device.
+ * Additive as well: the ABI version does not change. */
+enum prv2_depth16_grid {
+  PRV2_GRID_WINDOW = 0, /* kitti_dataset.py:123-131  Image.crop: output (y, x) reads source (top + y, left + x)                  */
+  PRV2_GRID_NEAREST = 1 /* scannet_dataset.py:112-118  Image.resize(size, NEAREST): output (y, x) reads source
+                           ((int)((y + 0.5) * (sh / H)), (int)((x + 0.5) * (sw / W))), float64, one product per index           */
+};
+
+/* kitti_dataset.py:123-131, :142, :203 and scannet_dataset.py:112-118, :132, :188, one pass.  src: uint16 [sh, sw], the samples of the
+ * depth PNG as the file holds them; the output map is [H, W].  PRV2_GRID_WINDOW: the H x W window whose first sample is (top, left) --
+ * the host computes KITTI's kb-crop offsets top = sh - 352, left = int((sw - 1216) / 2); top = left = 0 with H = sh, W = sw is the whole
+ * map.  PRV2_GRID_NEAREST: Pillow's NEAREST resize to H x W (top = left = 0): the scale sh / H is ONE float64 division, the index one
+ * float64 product truncated (adding the step up instead picks other pixels than Pillow does); equal sizes are the identity.
+ * depth: fp32 [H, W] = float32(sample) / divisor, an IEEE fp32 division (numpy's astype(float32) / 256.0 for KITTI, / 1000.0 for
+ * ScanNet, bit for bit); boundary: uint8 0/1 [H, W] = get_boundaries(depth, th, dilation=0) of that OUTPUT map (metric.py:74-85; the
+ * rule of prv2_disp_gt): a neighbour of an output pixel is the output's neighbour, read through the same grid rule.  The window's
+ * first sample need not be aligned (KITTI's left margin is 13): the loads narrow to what its address allows. */
+int prv2_depth16_gt(const uint16_t* src, int32_t sh, int32_t sw, int32_t grid, int32_t top, int32_t left, int32_t H, int32_t W,
+                    float divisor, float th, float* depth, uint8_t* boundary, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): compute_scale_and_shift (estimator/models/losses.py:523-544) and the
  * three modes of ScaleAndShiftInvariantLoss (losses.py:600-700: SSI L1, gradient matching, the 'inverse' gradient-space fit) as

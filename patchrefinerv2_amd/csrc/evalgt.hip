@@ -7,6 +7,9 @@
 //                         boundary map, one pass                                                   (general_dataset.py:103-151)
 //   cityscapes_gt_kernel  CityScapesDataset's ground truth: the same decode with the frame's own factor, the noisy bands, the sky class,
 //                         the boundary map of the final depth and the float segmentation map, one pass  (cityscapes_dataset.py:153-174,300)
+//   depth16_gt_kernel     KittiDataset's / ScanNetDataset's ground truth: the 16-bit samples of a depth PNG read through a window (the
+//                         kb-crop) or Pillow's NEAREST resize, / 256 or / 1000, and the boundary map of the re-gridded map, one pass
+//                                                                                        (kitti_dataset.py:123-142, scannet_dataset.py:112-132)
 //   cityscapes_masks_kernel  the edge and flatten pixel sets of CityScapesDataset.get_metrics, one pass  (cityscapes_dataset.py:360-365)
 //   depth_metrics_kernel  the twelve sums of compute_errors + soft_edge_error of B frames, for up to three pixel sets at once
 //   metrics_final_kernel  the per-block partials of a frame summed in block order
@@ -298,6 +301,93 @@ __global__ void __launch_bounds__(256) cityscapes_gt_kernel(const uint16_t* __re
         boundary[o + k] = e[k];
         if (SEG)
           for (int ch = 0; ch < 3; ++ch) seg_out[ch * hw + o + k] = (float)b[3 * k + ch];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// KittiDataset's and ScanNetDataset's ground truth (kitti_dataset.py:123-131, :142, :203; scannet_dataset.py:112-118, :132, :188): the
+// uint16 samples of a depth PNG, RE-GRIDDED as they are read -- output pixel (y, x) is source pixel (row(y), col(x)) -- then
+// depth = float32(sample) / divisor and the boundary map of the OUTPUT map: a neighbour of an output pixel is the output's neighbour,
+// mapped through the same rule.
+//   window   row(y) = top + y, col(x) = left + x                 (Image.crop: KITTI's kb-crop)
+//   NEAREST  row(y) = (int)((y + 0.5) * (sh / H)), likewise col  (Image.resize(NEAREST) of Pillow: ONE float64 product per index, the
+//            scale a float64 division made on the host; accumulating the step instead picks other pixels)
+struct D16Grid {
+  int top, left;  // window
+  double sy, sx;  // NEAREST: sh / H and sw / W
+};
+
+// the source index of output index i (the clamp never acts on an exact product; it keeps a rounded-up one inside the map)
+__device__ __forceinline__ int d16_index(int i, double scale, int n) { return min((int)(((double)i + 0.5) * scale), n - 1); }
+
+// the samples of the four output pixels x0 .. x0 + 3 of one output row (p: the source row, at the window's first column), zero behind
+// the row's end.  svec (window only, W % 4 == 0): 2 = the four samples are 8-byte aligned, 1 = 4-byte aligned (an even left margin), 0 =
+// neither (KITTI's margin of 13).  cx (NEAREST): the source columns of the output columns x0 - 1 .. x0 + 4.
+template <bool NEAREST>
+__device__ __forceinline__ void d16_row4(const uint16_t* __restrict__ p, int x0, int W, int svec, const int* cx, float divisor, float* v) {
+  uint32_t r[4];
+  if (NEAREST) {
+    for (int k = 0; k < 4; ++k) r[k] = x0 + k < W ? p[cx[k + 1]] : 0u;
+  } else if (svec == 2) {
+    const uint2 t = *reinterpret_cast<const uint2*>(p + x0);
+    r[0] = t.x & 0xffffu, r[1] = t.x >> 16, r[2] = t.y & 0xffffu, r[3] = t.y >> 16;
+  } else if (svec == 1) {
+    const uint32_t t0 = *reinterpret_cast<const uint32_t*>(p + x0), t1 = *reinterpret_cast<const uint32_t*>(p + x0 + 2);
+    r[0] = t0 & 0xffffu, r[1] = t0 >> 16, r[2] = t1 & 0xffffu, r[3] = t1 >> 16;
+  } else {
+    for (int k = 0; k < 4; ++k) r[k] = x0 + k < W ? p[x0 + k] : 0u;
+  }
+  for (int k = 0; k < 4; ++k) v[k] = (float)r[k] / divisor;  // IEEE division: numpy's astype(float32) / 256.0
+}
+
+template <bool NEAREST>
+__global__ void __launch_bounds__(256) depth16_gt_kernel(const uint16_t* __restrict__ src, float* __restrict__ depth,
+                                                         uint8_t* __restrict__ boundary, int sh, int sw, int H, int W, D16Grid g,
+                                                         float divisor, float th, int svec, int vec) {
+  const int wq = (W + 3) / 4;
+  const int64_t quads = (int64_t)H * wq;
+  for (int64_t q = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; q < quads; q += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(q / wq), x0 = (int)(q - (int64_t)y * wq) * 4;
+    int cx[6] = {0, 0, 0, 0, 0, 0};
+    if (NEAREST)
+      for (int j = 0; j < 6; ++j) {
+        const int X = x0 - 1 + j;
+        if (X >= 0 && X < W) cx[j] = d16_index(X, g.sx, sw);
+      }
+    // the source rows of output rows y - 1, y, y + 1 (at the window's first column)
+    const uint16_t* pc = src + (NEAREST ? (int64_t)d16_index(y, g.sy, sh) * sw : (int64_t)(g.top + y) * sw + g.left);
+    float c[4], up[4], dn[4], left = 0.f, right = 0.f;
+    d16_row4<NEAREST>(pc, x0, W, svec, cx, divisor, c);
+    if (y > 0) {
+      const uint16_t* pu = src + (NEAREST ? (int64_t)d16_index(y - 1, g.sy, sh) * sw : (int64_t)(g.top + y - 1) * sw + g.left);
+      d16_row4<NEAREST>(pu, x0, W, svec, cx, divisor, up);
+    }
+    if (y + 1 < H) {
+      const uint16_t* pd = src + (NEAREST ? (int64_t)d16_index(y + 1, g.sy, sh) * sw : (int64_t)(g.top + y + 1) * sw + g.left);
+      d16_row4<NEAREST>(pd, x0, W, svec, cx, divisor, dn);
+    }
+    if (x0 > 0) left = (float)pc[NEAREST ? cx[0] : x0 - 1] / divisor;
+    if (x0 + 4 < W) right = (float)pc[NEAREST ? cx[5] : x0 + 4] / divisor;
+    uint8_t e[4];
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + k;
+      bool b = false;  // the rule of disp_gt_kernel
+      if (y > 0) b |= fabsf(c[k] - up[k]) > th;
+      if (y + 1 < H) b |= fabsf(dn[k] - c[k]) > th;
+      if (x > 0) b |= fabsf(c[k] - (k ? c[k - 1] : left)) > th;
+      if (x + 1 < W) b |= fabsf((k < 3 ? c[k + 1] : right) - c[k]) > th;
+      e[k] = b ? 1 : 0;
+    }
+    const int64_t o = (int64_t)y * W + x0;
+    if (vec) {
+      *reinterpret_cast<float4*>(depth + o) = make_float4(c[0], c[1], c[2], c[3]);
+      *reinterpret_cast<uint32_t*>(boundary + o) = (uint32_t)e[0] | (uint32_t)e[1] << 8 | (uint32_t)e[2] << 16 | (uint32_t)e[3] << 24;
+    } else {
+      for (int k = 0; k < 4 && x0 + k < W; ++k) {
+        depth[o + k] = c[k];
+        boundary[o + k] = e[k];
       }
     }
   }
@@ -682,6 +772,38 @@ extern "C" int prv2_cityscapes_gt(const uint16_t* disp, const uint8_t* seg_hwc, 
     hipLaunchKernelGGL(cityscapes_gt_kernel<true>, grid, block, 0, s, disp, seg_hwc, depth, boundary, seg_chw, (int)h, (int)w, factor, bd, vec);
   else
     hipLaunchKernelGGL(cityscapes_gt_kernel<false>, grid, block, 0, s, disp, seg_hwc, depth, boundary, seg_chw, (int)h, (int)w, factor, bd, vec);
+  PRV2_LAUNCH_CHECK(name);
+  return 0;
+}
+
+extern "C" int prv2_depth16_gt(const uint16_t* src, int32_t sh, int32_t sw, int32_t grid, int32_t top, int32_t left, int32_t H, int32_t W,
+                               float divisor, float th, float* depth, uint8_t* boundary, void* stream) {
+  const char* name = "depth16_gt";
+  PRV2_REQUIRE(src && depth && boundary, "%s: null pointer", name);
+  PRV2_REQUIRE(sh >= 1 && sw >= 1, "%s: bad source shape %d x %d", name, sh, sw);
+  PRV2_REQUIRE(H >= 1 && W >= 1, "%s: bad output shape %d x %d", name, H, W);
+  PRV2_REQUIRE((int64_t)sh * sw < (int64_t)INT_MAX && (int64_t)H * W < (int64_t)INT_MAX, "%s: %d x %d -> %d x %d exceeds 2^31 pixels", name, sh,
+               sw, H, W);
+  PRV2_REQUIRE(grid == PRV2_GRID_WINDOW || grid == PRV2_GRID_NEAREST, "%s: unknown grid %d (enum prv2_depth16_grid)", name, grid);
+  PRV2_REQUIRE(divisor > 0.f, "%s: divisor %g is not positive", name, (double)divisor);  // (a NaN fails too)
+  if (grid == PRV2_GRID_WINDOW)
+    PRV2_REQUIRE(top >= 0 && left >= 0 && (int64_t)top + H <= sh && (int64_t)left + W <= sw,
+                 "%s: window of %d x %d at row %d, column %d lies outside the %d x %d source", name, H, W, top, left, sh, sw);
+  else
+    PRV2_REQUIRE(top == 0 && left == 0, "%s: the nearest grid takes no window offset (row %d, column %d)", name, top, left);
+  const int vec = W % 4 == 0 && aligned(depth, 16) && aligned(boundary, 4);
+  const dim3 grd(flat_grid((int64_t)H * cdiv(W, 4), 256)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  D16Grid g{top, left, (double)sh / (double)H, (double)sw / (double)W};
+  if (grid == PRV2_GRID_NEAREST && (H != sh || W != sw)) {
+    hipLaunchKernelGGL(depth16_gt_kernel<true>, grd, block, 0, s, src, depth, boundary, (int)sh, (int)sw, (int)H, (int)W, g, divisor, th, 0, vec);
+  } else {  // (equal sizes: the nearest rule is the identity, the whole-map window)
+    // the first sample of every window row is 8- / 4-byte aligned: four (two) samples per load; else one at a time
+    const uintptr_t a0 = (uintptr_t)src + 2 * ((uintptr_t)top * sw + left), step = 2 * (uintptr_t)sw;
+    const int svec = W % 4 ? 0 : (a0 % 8 == 0 && step % 8 == 0 ? 2 : (a0 % 4 == 0 && step % 4 == 0 ? 1 : 0));
+    hipLaunchKernelGGL(depth16_gt_kernel<false>, grd, block, 0, s, src, depth, boundary, (int)sh, (int)sw, (int)H, (int)W, g, divisor, th, svec,
+                       vec);
+  }
   PRV2_LAUNCH_CHECK(name);
   return 0;
 }

@@ -1321,6 +1321,22 @@ std::tuple<Tensor, Tensor> cityscapes_masks(const Tensor& seg_edges, const Tenso
      "cityscapes_masks");
   return {edge, flatten};
 }
+// KittiDataset / ScanNetDataset (kitti_dataset.py:123-142, scannet_dataset.py:112-132): the depth PNG's uint16 samples through a window
+// (nearest == false: H x W at (top, left)) or Pillow's NEAREST resize to H x W -> depth = sample / divisor and its boundary map
+std::tuple<Tensor, Tensor> depth16_gt(const Tensor& src, int64_t H, int64_t W, double divisor, int64_t top, int64_t left, bool nearest, double th) {
+  TORCH_CHECK(src.is_cuda(), "prv2: src must be a GPU tensor (there is no CPU path)");
+  TORCH_CHECK(src.scalar_type() == at::kUInt16 && src.dim() == 2 && src.is_contiguous(),
+              "prv2::depth16_gt: src must be a contiguous uint16 [sh, sw] tensor");
+  const int64_t lim = std::numeric_limits<int32_t>::max();
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= lim && W <= lim && top >= 0 && left >= 0 && top <= lim && left <= lim, "prv2::depth16_gt: bad output ", H,
+              " x ", W, " at (", top, ", ", left, ")");
+  Tensor depth = at::empty({H, W}, src.options().dtype(at::kFloat)), boundary = at::empty({H, W}, src.options().dtype(at::kByte));
+  Launch L(src);
+  ok(prv2_depth16_gt((const uint16_t*)src.data_ptr(), (int)src.size(0), (int)src.size(1), nearest ? PRV2_GRID_NEAREST : PRV2_GRID_WINDOW, (int)top,
+                     (int)left, (int)H, (int)W, (float)divisor, (float)th, depth.data_ptr<float>(), (uint8_t*)boundary.data_ptr(), L.stream),
+     "depth16_gt");
+  return {depth, boundary};
+}
 // scale-and-shift-invariant evaluation (losses.py:523-544, :600-700): pred [n, h, w], or [n, ph, pw] sampled inside the kernels
 Tensor ssi_metrics(const Tensor& gt, const Tensor& pred, double min_depth, double max_depth, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
   dev_frames(gt, "gt", at::kFloat);
@@ -1652,6 +1668,8 @@ TORCH_LIBRARY(prv2, m) {
   m.def("cityscapes_gt(Tensor disp, Tensor? seg, float factor) -> (Tensor, Tensor, Tensor)");
   m.def("seg_canny(Tensor seg, float[] gauss_w, float low, float high) -> Tensor");
   m.def("cityscapes_masks(Tensor seg_edges, Tensor gt_edges, Tensor hr_region) -> (Tensor, Tensor)");
+  // KittiDataset / ScanNetDataset: the depth PNG's samples through a window or Pillow's NEAREST resize
+  m.def("depth16_gt(Tensor src, int H, int W, float divisor, int top, int left, bool nearest, float th) -> (Tensor, Tensor)");
   m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
         "int x0, int x1) -> Tensor");
   m.def("ssi_metrics(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1) -> Tensor");
@@ -1753,6 +1771,7 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("cityscapes_gt", &cityscapes_gt);
   m.impl("seg_canny", &seg_canny);
   m.impl("cityscapes_masks", &cityscapes_masks);
+  m.impl("depth16_gt", &depth16_gt);
   m.impl("ssi_metrics", &ssi_metrics);
   m.impl("sparsify", &sparsify);
   m.impl("pointcloud_pack", &pointcloud_pack);

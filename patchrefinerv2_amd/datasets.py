@@ -8,12 +8,17 @@ ETHDataset          estimator/datasets/eth_dataset.py:23-385 (split file -> imag
 CityScapesDataset   estimator/datasets/cityscapes_dataset.py:27-501 (split file -> image_hr / depth_gt / boundary / seg_image, decoded on
                     the GPU with the file's own camera; depth metrics away from class boundaries and image edges, boundary metrics
                     on segmentation edges that are ground-truth depth edges)
-``ssi_metrics=True`` (tools/test.py --ssi-metrics) on any of the four datasets: get_metrics adds the scale-and-shift-invariant scores
+KittiDataset        estimator/datasets/kitti_dataset.py:22-295 (split file -> image_hr / depth_gt / boundary: the 16-bit depth PNG read through
+                    the 352 x 1216 kb-crop window on the GPU, / 256; the ten metrics inside the Garg crop)
+ScanNetDataset      estimator/datasets/scannet_dataset.py:25-404 (split file -> image_hr / depth_gt / boundary: the 16-bit depth PNG brought
+                    to the image's size by Pillow's NEAREST rule on the GPU, / 1000; every metric also inside and outside the widened
+                    ground-truth depth edges)
+``ssi_metrics=True`` (tools/test.py --ssi-metrics) on any of the datasets: get_metrics adds the scale-and-shift-invariant scores
                     of estimator/models/losses.py:523-544, :600-700 (metrics.SSI_KEYS; two fused GPU passes, csrc/ssi_eval.hip)
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
-_ReadAhead / _StagedDataset  the two staging slots and the one background reader that the four datasets share
-Not built: the ``gta`` ground truth (general_dataset.py:96-101: .exr files need imageio, which is absent) and the dataset classes
-KittiDataset and ScanNetDataset; CityScapesDataset is a class here but no registry entry yet (see there).  Without ``gt_format`` ground truth is metric depth as <basename>.npy files.
+_ReadAhead / _StagedDataset  the two staging slots and the one background reader that the datasets share
+Not built: the ``gta`` ground truth (general_dataset.py:96-101: .exr files need imageio, which is absent).  CityScapesDataset, KittiDataset
+and ScanNetDataset are classes here but no registry entries (see there).  Without ``gt_format`` ground truth is metric depth as <basename>.npy files.
 """
 from __future__ import annotations
 
@@ -223,15 +228,15 @@ def strip_gt_name(name: str) -> str:
     return name.replace(".npy", "").replace(".exr", "")
 
 
-def _png16_shape(path):
-    """(h, w) of a 16-bit one-channel PNG from its IHDR"""
+def _png16_shape(path, what="a Cityscapes disparity map"):
+    """(h, w) of a 16-bit one-channel PNG from its IHDR (``what``: the kind of file the message names)"""
     with open(path, "rb") as f:
         head = f.read(26)
     if len(head) < 26 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
         raise ValueError(f"{path}: not a PNG file")
     w, h, depth, ctype = struct.unpack(">IIBB", head[16:26])
     if depth != 16 or ctype != 0:
-        raise ValueError(f"{path}: bit depth {depth}, colour type {ctype}; a Cityscapes disparity map is 16-bit greyscale")
+        raise ValueError(f"{path}: bit depth {depth}, colour type {ctype}; {what} is 16-bit greyscale")
     return h, w
 
 
@@ -830,3 +835,242 @@ class CityScapesDataset(_StagedDataset):
     def evaluate(self, results, **kw):
         """cityscapes_dataset.py:410-501 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""
         return ETHDataset.evaluate(self, results)
+
+
+def _read_depth16(path, view, what):
+    """(background thread) the uint16 samples of the 16-bit greyscale PNG ``path`` as the file holds them into the byte array ``view``
+    -> (h, w); ValueError naming the file unless it is one"""
+    from PIL import Image
+    h, w = _png16_shape(path, what)
+    d = np.asarray(Image.open(path))  # np.asarray(Image.open(path)) of an I;16 image: its uint16 samples
+    if d.shape != (h, w) or d.dtype.itemsize != 2:
+        raise ValueError(f"{path}: decoded to {d.dtype} {d.shape}, expected uint16 {(h, w)}")
+    np.copyto(view[:h * w * 2].view(np.uint16).reshape(h, w), d, casting="unsafe")
+    return h, w
+
+
+def _pinned(slot, key, need):
+    """(caller's thread) ``slot[key]`` is a pinned byte buffer of at least ``need`` bytes"""
+    if slot[key] is None or slot[key].numel() < need:
+        slot[key] = torch.empty((need,), dtype=torch.uint8).pin_memory()
+
+
+# (KittiDataset and ScanNetDataset are not registered in DATASETS either, for CityScapesDataset's reason: tools/test.py --test-type
+#  kitti / scannet build them by their constructors)
+class KittiDataset(_StagedDataset):
+    """estimator/datasets/kitti_dataset.py:22-295, ``mode='infer'``: the 'img depth' pairs of a split file under ``data_root/raw`` and
+    ``data_root/depth`` (a depth of ``None`` skips the line).  One background thread (_ReadAhead: files and host memory only) decodes the
+    NEXT image with PIL -- through decode_image_u8's kb-crop when ``do_kb_crop`` -- and reads the depth PNG's uint16 samples UNCROPPED
+    into a pinned buffer; on the device ops.u8_image makes ``image_hr`` and ops.depth16_gt reads the samples through the crop's window
+    (top = h - 352, left = int((w - 1216) / 2), :123-131) -> ``depth_gt`` [1, 1, H, W] = samples / 256 (:142) and ``boundary`` (:203) in
+    one pass.  No ``image_lr`` key (Tester._frames makes it with model.resizer).  ``get_metrics`` (:219-222) is one fused pass inside the
+    Garg crop with the prediction's resize in the kernel; ``evaluate`` the per-key nanmean (sparse LiDAR: a frame without a valid pixel
+    in the crop is NaN and does not poison the mean).  ``patch_raw_shape`` and ``pre_norm_bbox`` are stored (they act in training).
+    Not built: ``mode='train'`` (:133-152, :168-200), ``with_pseudo_label`` (:92-99, :119-121), ``transform_cfg.random_crop``."""
+
+    dataset_name = "kitti"
+    _reader_name = "kitti-read"
+
+    def __init__(self, mode, data_root, split, transform_cfg, min_depth, max_depth, patch_raw_shape=(176, 304), resize_mode="zoe",
+                 with_pseudo_label=False, pseudo_label_path=None, do_kb_crop=True, pre_norm_bbox=True, ssi_metrics=False):
+        if mode == "train":
+            raise NotImplementedError("KittiDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / random_crop, "
+                                      "kitti_dataset.py:133-152, :168-200) is not built; inference modes only")
+        if transform_cfg.get("random_crop", False):
+            raise NotImplementedError("KittiDataset(transform_cfg.random_crop): the random crops (kitti_dataset.py:168-188) are not built")
+        if with_pseudo_label:
+            raise NotImplementedError("KittiDataset(with_pseudo_label): pseudo labels are training inputs (kitti_dataset.py:92-99, :119-121)")
+        if resize_mode not in ("zoe", "depth-anything"):
+            raise NotImplementedError(f"KittiDataset(resize_mode={resize_mode!r})")  # kitti_dataset.py:52-59
+        self.mode, self.data_root, self.split = mode, data_root, split
+        self.min_depth, self.max_depth = min_depth, max_depth
+        self.transform_cfg = transform_cfg
+        self.resize_mode = resize_mode
+        self.with_pseudo_label, self.pseudo_label_path = False, pseudo_label_path
+        self.patch_raw_shape, self.pre_norm_bbox, self.do_kb_crop = tuple(patch_raw_shape), pre_norm_bbox, bool(do_kb_crop)
+        self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS)
+        self.data_infos = self.load_data_list()
+
+    def load_data_list(self):
+        """kitti_dataset.py:66-107: 'img depth' per line, a depth of 'None' skips it; data_root/raw/<img> and data_root/depth/<depth>;
+        sorted by image path; the basename of :165-166"""
+        if self.split is None:
+            raise NotImplementedError("KittiDataset needs a split file (kitti_dataset.py:103-104)")
+        infos = []
+        with open(self.split) as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                img, depth = line.strip().split(" ")[0], line.strip().split(" ")[1]
+                if depth == "None":
+                    continue
+                infos.append(dict(depth_map_path=os.path.join(self.data_root, "depth", depth), img_path=os.path.join(self.data_root, "raw", img),
+                                  filename=img, img_file_basename=os.path.splitext(img)[0].replace("/", "_")))
+        return sorted(infos, key=lambda x: x["img_path"])
+
+    def __len__(self):
+        return len(self.data_infos)
+
+    def _make_slot(self):
+        return dict(img=None, depth=None, shape=None, img_shape=None)
+
+    def _prepare(self, idx, slot):
+        """(caller's thread) the slot's pinned buffers hold a frame of item ``idx``'s depth size, read from the PNG's header
+        (ValueError naming the file unless it is 16-bit greyscale)"""
+        h, w = _png16_shape(self.data_infos[idx]["depth_map_path"], "a KITTI depth map")
+        _pinned(slot, "img", h * w * 3)
+        _pinned(slot, "depth", h * w * 2)
+
+    def _read(self, idx, slot):
+        """(background thread: files and host memory only) the depth PNG's samples, uncropped, and the image's RGB bytes (kb-cropped
+        with ``do_kb_crop``); the two sizes are checked against each other and against the crop"""
+        from PIL import Image
+        info = self.data_infos[idx]
+        h, w = _read_depth16(info["depth_map_path"], slot["depth"].numpy(), "a KITTI depth map")
+        with Image.open(info["img_path"]) as im:
+            ih, iw = im.height, im.width
+        if (ih, iw) != (h, w):
+            raise ValueError(f"{info['img_path']}: the image is {ih} x {iw}, the depth map {info['depth_map_path']} {h} x {w}")
+        if self.do_kb_crop and (h < KB_CROP[0] or w < KB_CROP[1]):
+            raise ValueError(f"{info['depth_map_path']}: {h} x {w} (as {info['img_path']}) is smaller than the kb-crop {KB_CROP[0]} x {KB_CROP[1]}")
+        a, _ = decode_image_u8(info["img_path"], "kitti" if self.do_kb_crop else "cityscapes", None)  # kitti_dataset.py:114, :123-131
+        np.copyto(slot["img"].numpy()[:a.size].reshape(a.shape), a)
+        slot["shape"], slot["img_shape"] = (h, w), a.shape[:2]
+
+    def __getitem__(self, idx):
+        from . import ops
+        idx, slot = self._acquire(idx)
+        (h, w), (H, W) = slot["shape"], slot["img_shape"]
+        raw = slot["img"][:H * W * 3].cuda(non_blocking=True).view(H, W, 3)
+        samples = slot["depth"][:h * w * 2].cuda(non_blocking=True).view(torch.uint16).view(h, w)
+        self._release(idx)
+        # :126-127: top_margin = int(height - 352), left_margin = int((width - 1216) / 2); without the crop the whole map
+        window = (int(h - KB_CROP[0]), int((w - KB_CROP[1]) / 2)) if self.do_kb_crop else (0, 0)
+        depth, boundary = ops.depth16_gt(samples, (H, W), 256.0, window=window, th=1.0)  # :142 and get_boundaries(depth_gt, th=1, dilation=0), :203
+        return dict(image_hr=ops.u8_image(raw, swap_rb=False), depth_gt=depth[None, None], boundary=boundary,
+                    img_file_basename=self.data_infos[idx]["img_file_basename"])
+
+    def get_metrics(self, depth_gt, result, disp_gt_edges=None, **kw):
+        """kitti_dataset.py:219-222 through the fused kernel: the Garg crop, the prediction's resize inside the scoring pass"""
+        from .metrics import compute_metrics_fused, compute_ssi_metrics_fused
+        common = dict(self._common("kitti", fuse_resize=True), garg_crop=True)
+        out = compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, **common)
+        return self._with_ssi(out, compute_ssi_metrics_fused, depth_gt, result, common)
+
+    def evaluate(self, results, **kw):
+        """kitti_dataset.py:224-295 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""
+        return ETHDataset.evaluate(self, results)
+
+
+class ScanNetDataset(_StagedDataset):
+    """estimator/datasets/scannet_dataset.py:25-404, inference modes: the 'img depth' pairs (absolute paths) of a split file.  One
+    background thread (_ReadAhead: files and host memory only) decodes the NEXT image with PIL (``convert("RGB")``) and reads the depth
+    PNG's uint16 samples at their OWN size into a pinned buffer; on the device ops.u8_image makes ``image_hr`` and ops.depth16_gt brings
+    the samples to the image's size by the rule of PIL's ``resize(image.size, Image.NEAREST)`` (:112-118) -> ``depth_gt`` [1, 1, H, W] =
+    samples / 1000 (:132) and ``boundary`` (:188) in one pass.  No ``image_lr`` key.  ``get_metrics`` (:209-244) widens the log-depth
+    Canny edges of the ground truth by 7 x 7 on the device and scores inside them, outside them and everywhere in ONE fused pass, the
+    prediction's resize inside it: ``edge_*``, ``noedge_*``, then the plain keys.  ``evaluate`` / ``evaluate_consistency`` are the
+    per-key nanmean.  ``patch_raw_shape`` and ``pre_norm_bbox`` are stored.  Not built: ``mode='train'`` (:120-129, :139-146),
+    ``transform_cfg.random_crop`` (:156-173), ``with_pseudo_label`` (:90-93, :121-124)."""
+
+    dataset_name = "scannet"
+    _reader_name = "scannet-read"
+
+    def __init__(self, mode, split, transform_cfg, min_depth, max_depth, with_pseudo_label=False, pseudo_label_path=None,
+                 patch_raw_shape=(720, 960), resize_mode="zoe", pre_norm_bbox=True, ssi_metrics=False):
+        if mode == "train":
+            raise NotImplementedError("ScanNetDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip, "
+                                      "scannet_dataset.py:120-129, :139-146) is not built; inference modes only")
+        if transform_cfg.get("random_crop", False):
+            raise NotImplementedError("ScanNetDataset(transform_cfg.random_crop): the random crops (scannet_dataset.py:156-173) are not built")
+        if with_pseudo_label:
+            raise NotImplementedError("ScanNetDataset(with_pseudo_label): pseudo labels are training inputs (scannet_dataset.py:90-93, :121-124)")
+        if resize_mode not in ("zoe", "depth-anything"):
+            raise NotImplementedError(f"ScanNetDataset(resize_mode={resize_mode!r})")  # scannet_dataset.py:53-60
+        self.mode, self.split = mode, split
+        self.min_depth, self.max_depth = min_depth, max_depth
+        self.transform_cfg = transform_cfg
+        self.resize_mode = resize_mode
+        self.with_pseudo_label, self.pseudo_label_path = False, pseudo_label_path
+        self.patch_raw_shape, self.pre_norm_bbox = tuple(patch_raw_shape), pre_norm_bbox
+        self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS), plain set only
+        self.data_infos = self.load_data_list()
+
+    @staticmethod
+    def basename_of(img_path):
+        """scannet_dataset.py:191-193, literally (the reference's 'bad hack': scene id and frame number of a ScanNet++ path)"""
+        img_file_basename, _ = os.path.splitext(img_path)
+        img_file_basename = img_file_basename.replace("/", "_")[1:]
+        return img_file_basename[-34:-24] + "_" + img_file_basename[-6:]
+
+    def load_data_list(self):
+        """scannet_dataset.py:67-102: 'img depth' per line (absolute paths), sorted by image path"""
+        if self.split is None:
+            raise NotImplementedError("ScanNetDataset needs a split file (scannet_dataset.py:97-98)")
+        infos = []
+        with open(self.split) as f:
+            for line in f:
+                if not line.strip():
+                    continue
+                img, depth_map = line.strip().split(" ")
+                infos.append(dict(depth_map_path=depth_map, img_path=img, depth_fields=[], img_file_basename=self.basename_of(img)))
+        return sorted(infos, key=lambda x: x["img_path"])
+
+    def __len__(self):
+        return len(self.data_infos)
+
+    def _make_slot(self):
+        return dict(img=None, depth=None, shape=None, img_shape=None)
+
+    def _prepare(self, idx, slot):
+        """(caller's thread) the slot's pinned buffers hold item ``idx``'s image and depth samples (both headers are read here; ValueError
+        naming the depth file unless it is 16-bit greyscale)"""
+        from PIL import Image
+        info = self.data_infos[idx]
+        h, w = _png16_shape(info["depth_map_path"], "a ScanNet depth map")
+        with Image.open(info["img_path"]) as im:
+            _pinned(slot, "img", im.height * im.width * 3)
+        _pinned(slot, "depth", h * w * 2)
+
+    def _read(self, idx, slot):
+        """(background thread: files and host memory only) the image's RGB bytes and the depth PNG's samples at their own size"""
+        from PIL import Image
+        info = self.data_infos[idx]
+        a = np.asarray(Image.open(info["img_path"]).convert("RGB"))  # scannet_dataset.py:109
+        if slot["img"].numel() < a.size:
+            raise ValueError(f"{info['img_path']}: decoded to {a.shape}, more than its header announced")
+        np.copyto(slot["img"].numpy()[:a.size].reshape(a.shape), a)
+        slot["shape"] = _read_depth16(info["depth_map_path"], slot["depth"].numpy(), "a ScanNet depth map")
+        slot["img_shape"] = a.shape[:2]
+
+    def __getitem__(self, idx):
+        from . import ops
+        idx, slot = self._acquire(idx)
+        (h, w), (H, W) = slot["shape"], slot["img_shape"]
+        raw = slot["img"][:H * W * 3].cuda(non_blocking=True).view(H, W, 3)
+        samples = slot["depth"][:h * w * 2].cuda(non_blocking=True).view(torch.uint16).view(h, w)
+        self._release(idx)
+        # :115-118 resize(image.size, NEAREST), :132 / 1000.0 (mm to m), get_boundaries(depth_gt, th=1, dilation=0), :188
+        depth, boundary = ops.depth16_gt(samples, (H, W), 1000.0, nearest=True, th=1.0)
+        return dict(image_hr=ops.u8_image(raw, swap_rb=False), depth_gt=depth[None, None], boundary=boundary,
+                    img_file_basename=self.data_infos[idx]["img_file_basename"])
+
+    def get_metrics(self, depth_gt, result, disp_gt_edges=None, **kw):
+        """scannet_dataset.py:209-244: the edge area is the 7 x 7-widened log-depth Canny edges of the ground truth
+        (metrics.edge_split_masks, on the device), then the reference's three compute_metrics calls as ONE fused pass over the three
+        pixel sets -> ``edge_*``, ``noedge_*``, then the plain keys.  It needs no ``image_hr``."""
+        from . import metrics as M
+        H, W = depth_gt.shape[-2:]
+        gt = torch.as_tensor(depth_gt).cuda().float().reshape(H, W)
+        region = M.edge_split_masks_device(gt, 7)  # ops.binary_dilate(extract_edges_device(gt, 'log'), 7)
+        common = self._common(fuse_resize=True)
+        out = eth_metric_order(M.compute_metrics_fused(gt[None, None], result, disp_gt_edges=disp_gt_edges, region=region, **common))
+        return self._with_ssi(out, M.compute_ssi_metrics_fused, depth_gt, result, common)  # (after the reference's thirty keys)
+
+    def evaluate(self, results, **kw):
+        """scannet_dataset.py:246-339 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""
+        return ETHDataset.evaluate(self, results)
+
+    def evaluate_consistency(self, results, **kw):
+        """scannet_dataset.py:342-404 without the table: the nanmean of ``consistency_error``"""
+        return ETHDataset.evaluate(self, [dict(consistency_error=r["consistency_error"]) for r in results])

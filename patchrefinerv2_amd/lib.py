@@ -181,6 +181,9 @@ SIGNATURES = {
     "prv2_cityscapes_gt": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "prv2_seg_canny": (_I, [_P, _I, _I, _P, _F, _F, _P, _P, _L, _P]),
     "prv2_cityscapes_masks": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    # KittiDataset / ScanNetDataset (kitti_dataset.py, scannet_dataset.py): the 16-bit depth PNG's samples through a window or Pillow's
+    # NEAREST resize -> depth and its boundary map
+    "prv2_depth16_gt": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
     # scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): the fits, the four SSI scores and the error sums of the aligned prediction
     "prv2_ssi_metrics_workspace_bytes": (_L, [_I, _I, _I]),
     "prv2_ssi_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),

@@ -665,6 +665,38 @@ def edge_split_masks(gt, k: int = 7) -> np.ndarray:
     return binary_dilate(extract_edges(gt, "log"), k)
 
 
+# KittiDataset's / ScanNetDataset's ground truth on the host (the spec of ops.depth16_gt).
+def pil_nearest_index(n_out: int, n_in: int) -> np.ndarray:
+    """the source index of every output index of PIL's ``Image.resize(size, Image.NEAREST)`` along one axis -> int64 [n_out]:
+    floor((i + 0.5) * (n_in / n_out)), the scale ONE float64 division and every index ONE float64 product (checked against Pillow in
+    tests/test_kitti_scannet_host.py; adding the step up instead of multiplying picks other pixels).  Equal sizes: the identity."""
+    if n_out < 1 or n_in < 1:
+        raise ValueError(f"pil_nearest_index: {n_in} -> {n_out}")
+    scale = np.float64(n_in) / np.float64(n_out)
+    return np.minimum(((np.arange(n_out, dtype=np.float64) + 0.5) * scale).astype(np.int64), n_in - 1)
+
+
+def depth16_decode_spec(samples, divisor, window=None, out_hw=None, th=1.0):
+    """the uint16 samples [sh, sw] of a depth PNG -> (depth float32, boundary uint8) as the reference makes them:
+    ``window=(top, left, h, w)``: ``Image.crop`` (kitti_dataset.py:123-131; None with ``out_hw`` None: the whole map); ``out_hw=(H, W)``:
+    ``Image.resize((W, H), Image.NEAREST)`` (scannet_dataset.py:112-118); depth = samples.astype(float32) / divisor (kitti_dataset.py:142
+    with 256.0, scannet_dataset.py:132 with 1000.0); boundary = get_boundaries(depth, th, dilation=0) of THAT map (:203 / :188)."""
+    s = np.asarray(samples)
+    if s.dtype != np.uint16 or s.ndim != 2:
+        raise ValueError(f"depth16_decode_spec: samples are uint16 [H, W], not {s.dtype} {s.shape}")
+    if window is not None and out_hw is not None:
+        raise ValueError("depth16_decode_spec: give window or out_hw, not both")
+    if window is not None:
+        top, left, h, w = (int(v) for v in window)
+        if top < 0 or left < 0 or h < 1 or w < 1 or top + h > s.shape[0] or left + w > s.shape[1]:
+            raise ValueError(f"depth16_decode_spec: the window of {h} x {w} at ({top}, {left}) lies outside the {s.shape[0]} x {s.shape[1]} map")
+        s = s[top:top + h, left:left + w]
+    elif out_hw is not None:
+        s = s[pil_nearest_index(int(out_hw[0]), s.shape[0])[:, None], pil_nearest_index(int(out_hw[1]), s.shape[1])[None, :]]
+    depth = s.astype(np.float32) / np.float32(divisor)
+    return depth, get_boundaries(depth, th=np.float32(th), dilation=0).astype(np.uint8)
+
+
 # CityScapesDataset.get_metrics' pixel sets (host restatements: the spec of ops.seg_canny / ops.cityscapes_masks).
 #   seg_canny         cityscapes_dataset.py:333-334 (kornia.filters.canny on the colour segmentation map) -- kornia is not installed:
 #                     PARITY UNPINNED, as for ``canny`` above; this restatement is the specification

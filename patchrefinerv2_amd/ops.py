@@ -2238,6 +2238,44 @@ def cityscapes_masks(seg_edges, gt_edges, hr_region):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# KittiDataset / ScanNetDataset (estimator/datasets/kitti_dataset.py, scannet_dataset.py): the ground truth of a 16-bit depth PNG,
+# re-gridded as it is decoded (csrc/evalgt.hip), both dispatch routes.  The host specification is metrics.depth16_decode_spec.
+# ------------------------------------------------------------------------------------------------------------------
+def depth16_gt(src_u16, out_hw=None, divisor=256.0, window=None, nearest=False, th=1.0):
+    """the uint16 samples [sh, sw] of a depth PNG on the device, one pass -> (depth fp32 [H, W] = float32(sample) / divisor, boundary
+    uint8 [H, W] = metrics.get_boundaries(depth, th, 0)), (H, W) = ``out_hw`` (None: the source's shape).  ``window=(top, left)``: output
+    (y, x) is source (top + y, left + x) -- KITTI's kb-crop (kitti_dataset.py:123-131, divisor 256); None is (0, 0).  ``nearest=True``:
+    the grid of PIL's ``resize((W, H), Image.NEAREST)`` (metrics.pil_nearest_index) -- ScanNet's ground truth at the image's size
+    (scannet_dataset.py:112-118, divisor 1000).  include/prv2.h prv2_depth16_gt."""
+    s = src_u16
+    if not isinstance(s, torch.Tensor) or not s.is_cuda or s.dtype != torch.uint16 or s.dim() != 2:
+        raise ValueError("depth16_gt: src is a GPU uint16 [H, W] tensor")
+    if nearest and window is not None:
+        raise ValueError("depth16_gt: give window or nearest=True, not both")
+    sh, sw = s.shape
+    H, W = (sh, sw) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    top, left = (0, 0) if window is None else (int(window[0]), int(window[1]))
+    if H < 1 or W < 1 or sh < 1 or sw < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"depth16_gt: bad shape {sh} x {sw} -> {H} x {W}")
+    if not nearest and (top < 0 or left < 0 or top + H > sh or left + W > sw):
+        raise ValueError(f"depth16_gt: the window of {H} x {W} at ({top}, {left}) lies outside the {sh} x {sw} source")
+    if not float(divisor) > 0:
+        raise ValueError(f"depth16_gt: divisor {divisor} is not positive")
+    s = s.contiguous()
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().depth16_gt(s, H, W, float(divisor), top, left, bool(nearest), float(th)))  # noqa: E731
+    else:
+        depth = torch.empty((H, W), dtype=torch.float32, device=s.device)
+        boundary = torch.empty((H, W), dtype=torch.uint8, device=s.device)
+        box.extend((depth, boundary))
+        call = lambda: _c("depth16_gt", s.data_ptr(), sh, sw, int(bool(nearest)), top, left, H, W, float(divisor), float(th),  # noqa: E731
+                          depth.data_ptr(), boundary.data_ptr())
+    PROFILER.launch_aux("depth16_gt", 7.0 * H * W, call, f"{sh}x{sw}->{H}x{W}")
+    return box[0], box[1]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Scale-and-shift-invariant evaluation (estimator/models/losses.py:523-544, :600-700; csrc/ssi_eval.hip), both dispatch routes.
 # ------------------------------------------------------------------------------------------------------------------
 SSI_VALUES = L.SSI_VALUES

@@ -25,9 +25,10 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-# importing this module registers the datasets, and the four classes stay importable from here (tools/ and the tests do both);
+# importing this module registers the datasets, and the six classes stay importable from here (tools/ and the tests do both);
 # read_image only because tests/test_host_logic.py imports it from here.  Everything else of datasets.py is imported from there.
-from .datasets import CityScapesDataset, ETHDataset, ImageDataset, UnrealStereo4kDataset, read_image  # noqa: F401
+from .datasets import (CityScapesDataset, ETHDataset, ImageDataset, KittiDataset, ScanNetDataset, UnrealStereo4kDataset,  # noqa: F401
+                       read_image)
 from .output import write_png8, write_png16
 
 

@@ -47,6 +47,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "u8_image_resize", "image_edge_region",
        # CityScapesDataset: the ground-truth decode, kornia's Canny on the colour segmentation map, the two pixel sets of its get_metrics
        "cityscapes_gt", "seg_canny", "cityscapes_masks",
+       # KittiDataset / ScanNetDataset: the depth PNG's samples through the kb-crop window or Pillow's NEAREST resize
+       "depth16_gt",
        # scale-and-shift-invariant evaluation: the fits, the SSI scores and the error sums of the aligned prediction
        "ssi_metrics",
        # sparsification curves (AUSE / AURG) of a per-pixel uncertainty

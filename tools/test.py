@@ -22,8 +22,12 @@ disparities decoded and scored on the GPU; prints a1 ... sq_rel and see.  ETHDat
 on the GPU; prints the thirty keys edge_* / noedge_* / plain, split by the image's edge area); ``--test-type cityscapes``: the config's
 val_dataloader when it is a CityScapesDataset (configs/_base_/datasets/cityscapes.py: images, 16-bit disparity PNGs, camera files and colour
 segmentation maps decoded on the GPU; prints the seventeen keys a1 ... see, EdgeAcc ... acc -- the depth metrics away from class
-boundaries and image edges, the boundary metrics on segmentation edges that are ground-truth depth edges).  That class is built by its
-constructor and is no registry entry, so ``normal`` still answers it with "is not built"; ``general`` is the folder of images -- with
+boundaries and image edges, the boundary metrics on segmentation edges that are ground-truth depth edges); ``--test-type kitti``: the
+val_dataloader when it is a KittiDataset (configs/_base_/datasets/kitti.py: 16-bit depth PNGs read through the 352 x 1216 kb-crop on the
+GPU; prints the ten keys a1 ... see inside the Garg crop); ``--test-type scannet``: the val_dataloader when it is a ScanNetDataset
+(configs/_base_/datasets/scannet.py: 16-bit depth PNGs brought to the image's size by Pillow's NEAREST rule on the GPU; prints the thirty
+keys edge_* / noedge_* / plain, split by the widened ground-truth depth edges).  These three classes are built by their
+constructors and are no registry entries, so ``normal`` still answers them with "is not built"; ``general`` is the folder of images -- with
 ``--cfg-option general_dataloader.dataset.gt_dir=DIR general_dataloader.dataset.gt_format=u4k|eth3d|mid|cityscapes`` a folder with the
 reference's ground truth (general_dataset.py:75-158), decoded and scored on the GPU (``image_format=u4k|cityscapes|kitti`` selects
 read_image's branch, ``gt_shape=[H,W]`` the shape of ETH3D's raw files).
@@ -57,9 +61,12 @@ def parse_opts(opts):
 
 
 # --test-type -> the config section whose ``dataset`` is built (the reference's tools/test.py: normal / test_in / test_out / general)
-# ``cityscapes``: the val_dataloader again, for the one dataset class that is built without being a registry entry (build_dataset)
+# ``cityscapes`` / ``kitti`` / ``scannet``: the val_dataloader again, for the dataset classes that are built without being registry
+# entries (build_dataset)
 TEST_TYPES = dict(general="general_dataloader", normal="val_dataloader", test_in="test_in_dataloader", test_out="test_out_dataloader",
-                  cityscapes="val_dataloader")
+                  cityscapes="val_dataloader", kitti="val_dataloader", scannet="val_dataloader")
+# test type -> the class it builds by its constructor
+CONSTRUCTED = dict(cityscapes="CityScapesDataset", kitti="KittiDataset", scannet="ScanNetDataset")
 
 
 def dataset_config(cfg, args):
@@ -71,16 +78,17 @@ def dataset_config(cfg, args):
         raise SystemExit(f"--test-type {args.test_type} needs {section}.dataset in the config; {args.config} has none")
     ds_cfg = cfg[section].dataset.to_dict()
     kind = ds_cfg.get("type")
-    if args.test_type == "cityscapes":  # every size is the files' own: nothing of the command line goes into the dataset but --ssi-metrics
-        if kind != "CityScapesDataset":
-            raise SystemExit(f"--test-type cityscapes needs {section}.dataset.type = 'CityScapesDataset'; {args.config} has {kind}")
+    if args.test_type in CONSTRUCTED:  # every size is the files' own: nothing of the command line goes into the dataset but --ssi-metrics
+        if kind != CONSTRUCTED[args.test_type]:
+            raise SystemExit(f"--test-type {args.test_type} needs {section}.dataset.type = '{CONSTRUCTED[args.test_type]}'; {args.config} has {kind}")
         if getattr(args, "ssi_metrics", False):
             ds_cfg["ssi_metrics"] = True
         return ds_cfg
     if kind not in DATASETS:
+        route = {v: k for k, v in CONSTRUCTED.items()}.get(kind)
         raise SystemExit(f"--test-type {args.test_type}: dataset type {kind} is not built (built: ImageDataset, UnrealStereo4kDataset; the "
                          "cityscapes, kitti, scannet and eth decoders are not)"
-                         + (" -- a CityScapesDataset val_dataloader runs with --test-type cityscapes" if kind == "CityScapesDataset" else ""))
+                         + (f" -- a {kind} val_dataloader runs with --test-type {route}" if route else ""))
     if kind == "UnrealStereo4kDataset":
         ds_cfg["image_raw_shape"] = args.image_raw_shape
     elif kind == "ETHDataset":  # the image's size is transform_cfg.input_size_shallow, the ground truth's gt_shape
@@ -95,10 +103,10 @@ def dataset_config(cfg, args):
 
 
 def build_dataset(ds_cfg):
-    """the dataset of ``dataset_config``'s dict: a registry entry, or CityScapesDataset by its constructor"""
-    if ds_cfg.get("type") == "CityScapesDataset":
-        from patchrefinerv2_amd.tester import CityScapesDataset
-        return CityScapesDataset(**{k: v for k, v in ds_cfg.items() if k != "type"})
+    """the dataset of ``dataset_config``'s dict: a registry entry, or CityScapesDataset / KittiDataset / ScanNetDataset by its constructor"""
+    if ds_cfg.get("type") in CONSTRUCTED.values():
+        from patchrefinerv2_amd import tester
+        return getattr(tester, ds_cfg["type"])(**{k: v for k, v in ds_cfg.items() if k != "type"})
     return DATASETS.build(ds_cfg)
 
 
@@ -113,7 +121,9 @@ def main():
     ap.add_argument("--test-type", default="general", help="general: general_dataloader (a folder of images; with dataset.gt_dir and dataset.gt_format = u4k / eth3d / mid / cityscapes "
                     "set by --cfg-option also the reference's ground truth, decoded and scored on the GPU); normal / test_in / test_out: "
                     "val_dataloader / test_in_dataloader / test_out_dataloader (a dataset with ground truth, e.g. UnrealStereo4kDataset); cityscapes: "
-                    "val_dataloader when its dataset is a CityScapesDataset (depth and segmentation-edge metrics, seventeen keys)")
+                    "val_dataloader when its dataset is a CityScapesDataset (depth and segmentation-edge metrics, seventeen keys); kitti: "
+                    "val_dataloader when its dataset is a KittiDataset (kb-crop, Garg crop, ten keys); scannet: val_dataloader when its dataset is "
+                    "a ScanNetDataset (edge_* / noedge_* / plain, thirty keys)")
     ap.add_argument("--gray-scale", action="store_true")
     ap.add_argument("--image-raw-shape", nargs=2, type=int, default=[2160, 3840])
     ap.add_argument("--patch-split-num", nargs=2, type=int, default=[4, 4])
