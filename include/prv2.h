@@ -1128,6 +1128,50 @@ int prv2_temporal_step(const float* depth, const float* image, int32_t n, int32_
                        int32_t tau, double rho, double anchor, float* state_depth, uint8_t* luma0, uint8_t* luma1, int32_t state_present,
                        float* out, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth-of-field export (csrc/bokeh.hip): the frame re-rendered through a thin lens focused at one distance ("portrait mode"), from
+ * its metric depth map: B >= 1 dense frames [n, h, w] (h, w >= 1; n * h * w < 2^29).  Not in the reference.  One launch, no host
+ * synchronisation (the focus distance is read from the device map), no atomics on memory: the same input gives the same bits on
+ * every call.  Added without an ABI bump (additive).  The host specification is bokeh_render_host / bokeh_image_host of
+ * patchrefinerv2_amd/output.py, which the kernel equals bit for bit.  Everything is fp32, round to nearest, no contraction.
+ *   valid      Z finite and lo < Z < hi ("Geometry export"); zk = valid ? Z : +inf; iz = valid ? 1 / Z : 0 (invalid: infinitely far)
+ *   focus      Zf = focus when focus > 0 (finite), else the map at the focus pixel (min(h - 1, floor(focus_v h)), min(w - 1,
+ *              floor(focus_u w))), products in float64; that pixel not valid: r = 0 everywhere (the image itself) and focus_out = NaN
+ *   radius     k = (fx * aperture) * 0.5 on the host; r = min(max_radius, k |iz - 1 / Zf|) (a NaN product gives max_radius): the
+ *              thin-lens circle of confusion in pixels for Zf much larger than the focal length; m = max(r, 0.5); ia = 1 / (m m)
+ *   window     for output p the taps q = p + (dx, dy) inside the frame, dy = -R .. R outer, dx = -R .. R inner, R = ceil(max_radius);
+ *              dist = fp32(sqrt(dx dx + dy dy))
+ *   disc       own = zk_q <= zk_p or r_q <= r_p; (me, ie) = own ? (m_q, ia_q) : (m_p, ia_p): a source spreads over its own disc
+ *              unless it lies behind p with the larger disc -- a defocused background does not bleed over a sharp foreground
+ *   weight     cov = clamp((me + 0.5) - dist, 0, 1); wgt = cov ie; where wgt > 0: sw = sw + wgt, sc[ch] = sc[ch] + (wgt c_q[ch])
+ *   result     sc[ch] / sw (sw > 0: the centre tap has cov >= 0.5).  A tap of weight 0 changes no bit, so a tile walks only the
+ *              offsets the largest m in its reach can cover
+ *   colour     image fp32 [n, 3, ih, iw] sampled as prv2_pointcloud_pack does; a non-finite colour counts as 0; byte = "Geometry
+ *              export" on result * 255
+ * ------------------------------------------------------------------------------------------ */
+
+/* the largest max_radius prv2_bokeh_render / _rows take (32: a window of 65 x 65 taps; it sets the pitch of the LDS band) */
+int32_t prv2_bokeh_max_radius(void);
+
+/* measurement only: on = 0 makes every tile walk the full window, on = 1 (the default) bounds the walk per tile, on < 0 changes
+ * nothing; returns the previous setting.  Process-wide; the bits of the result do not depend on it. */
+int32_t prv2_bokeh_tile_bound(int32_t on);
+
+/* out: DEVICE fp32 [n, 3, h, w]; focus_out: DEVICE fp32 [n], the Zf of every frame (NaN: its focus pixel was not valid).  fx > 0
+ * finite; aperture >= 0 finite (metres); focus finite (<= 0 or NaN: use the focus point); focus_u, focus_v in [0, 1]; max_radius
+ * in [0, prv2_bokeh_max_radius()]; lo, hi not NaN.  Every argument is checked before anything is launched (prv2_last_error). */
+int prv2_bokeh_render(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx, float aperture,
+                      float focus, float focus_u, float focus_v, float max_radius, float lo, float hi, float* out, float* focus_out,
+                      void* stream);
+
+/* the same frames as RGB scanlines (bpp 3; a scanline buffer of the output stage: [h][1 + 3 w] bytes per frame; rows 16-byte
+ * aligned, rows_fstride a multiple of 16 and >= prv2_rows_bytes(h, w, 3); the tail up to the next multiple of 16 is zero): the
+ * bytes of prv2_bokeh_render's result.  A workgroup assembles its tile's part of every scanline in LDS and stores it once: byte
+ * stores at the ragged ends, 16-byte stores inside; no byte is read back. */
+int prv2_bokeh_rows(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx, float aperture,
+                    float focus, float focus_u, float focus_v, float max_radius, float lo, float hi, uint8_t* rows, int64_t rows_fstride,
+                    float* focus_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1486,6 +1486,37 @@ Tensor stereo_rows(const Tensor& depth, const Tensor& image, double fx, double b
   return rows;
 }
 
+// depth-of-field export (include/prv2.h "Depth-of-field export"): B frames re-rendered through a thin lens -> (fp32 planes or scanlines,
+// the focus distance every frame used)
+void bokeh_image(const Tensor& depth, const Tensor& image, const char* op) {
+  dev_frames(depth, "depth", at::kFloat);
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
+                  image.size(1) == 3 && image.device() == depth.device(), "prv2::", op, ": image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+}
+std::tuple<Tensor, Tensor> bokeh_render(const Tensor& depth, const Tensor& image, double fx, double aperture, double focus, double focus_u,
+                                        double focus_v, double max_radius, double lo, double hi) {
+  bokeh_image(depth, image, "bokeh_render");
+  Tensor out = at::empty({depth.size(0), 3, depth.size(1), depth.size(2)}, depth.options());
+  Tensor used = at::empty({depth.size(0)}, depth.options());
+  Launch L(depth);
+  ok(prv2_bokeh_render(depth.data_ptr<float>(), image.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2),
+                       (int)image.size(2), (int)image.size(3), (float)fx, (float)aperture, (float)focus, (float)focus_u, (float)focus_v,
+                       (float)max_radius, (float)lo, (float)hi, out.data_ptr<float>(), used.data_ptr<float>(), L.stream), "bokeh_render");
+  return {out, used};
+}
+std::tuple<Tensor, Tensor> bokeh_rows(const Tensor& depth, const Tensor& image, double fx, double aperture, double focus, double focus_u,
+                                      double focus_v, double max_radius, double lo, double hi) {
+  bokeh_image(depth, image, "bokeh_rows");
+  Tensor rows = alloc_rows(depth, 3);
+  Tensor used = at::empty({depth.size(0)}, depth.options());
+  Launch L(depth);
+  ok(prv2_bokeh_rows(depth.data_ptr<float>(), image.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2),
+                     (int)image.size(2), (int)image.size(3), (float)fx, (float)aperture, (float)focus, (float)focus_u, (float)focus_v,
+                     (float)max_radius, (float)lo, (float)hi, (uint8_t*)rows.data_ptr(), rows.size(1), used.data_ptr<float>(), L.stream),
+     "bokeh_rows");
+  return {rows, used};
+}
+
 // temporal stabilisation (include/prv2.h "Temporal stabilisation"): n frames in sequence order; the state (its map and the two luma
 // buffers, the previous luma in luma0) is updated in place -> (out [n, h, w], stats int64 [n, PRV2_TEMPORAL_STATS] on the device)
 std::tuple<Tensor, Tensor> temporal_step_(const Tensor& depth, const Tensor& image, double alpha, int64_t tau, double rho, double anchor,
@@ -1681,6 +1712,8 @@ TORCH_LIBRARY(prv2, m) {
   m.def("stereo_source(Tensor depth, float fx, float baseline, float convergence, float lo, float hi, float edge_thr) -> (Tensor, Tensor)");
   m.def("stereo_rows(Tensor depth, Tensor image, float fx, float baseline, float convergence, float lo, float hi, float edge_thr, int layout) -> Tensor");
   m.def("temporal_step_(Tensor depth, Tensor image, float alpha, int tau, float rho, float anchor, Tensor(a!) state_depth, Tensor(b!) luma0, Tensor(c!) luma1, bool state_present) -> (Tensor, Tensor)");
+  m.def("bokeh_render(Tensor depth, Tensor image, float fx, float aperture, float focus, float focus_u, float focus_v, float max_radius, float lo, float hi) -> (Tensor, Tensor)");
+  m.def("bokeh_rows(Tensor depth, Tensor image, float fx, float aperture, float focus, float focus_u, float focus_v, float max_radius, float lo, float hi) -> (Tensor, Tensor)");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1780,4 +1813,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("stereo_source", &stereo_source);
   m.impl("stereo_rows", &stereo_rows);
   m.impl("temporal_step_", &temporal_step_);
+  m.impl("bokeh_render", &bokeh_render);
+  m.impl("bokeh_rows", &bokeh_rows);
 }

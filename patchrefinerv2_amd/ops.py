@@ -1930,6 +1930,84 @@ def stereo_rows(depth, image, intrinsics, baseline, convergence=math.inf, depth_
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Depth-of-field export (csrc/bokeh.hip): frames [B, H, W] re-rendered through a thin lens, as fp32 planes or as scanlines, both
+# dispatch routes.  The host specification is output.bokeh_render_host / output.bokeh_image_host.
+# ------------------------------------------------------------------------------------------------------------------
+def bokeh_max_radius() -> int:
+    """the largest ``max_radius`` the kernel takes (include/prv2.h prv2_bokeh_max_radius)"""
+    return int(L.load().prv2_bokeh_max_radius())
+
+
+def _bokeh_inputs(what, depth, image, intrinsics, aperture, focus, focus_point, max_radius, depth_range):
+    """the arguments bokeh_render and bokeh_rows share, checked -> (frames fp32 [B, H, W], image fp32 [B, 3, Hi, Wi], fx, aperture,
+    focus (0.0: use the focus point), u, v, max_radius, lo, hi) with the scalars as Python floats that hold float32 values"""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
+        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
+    d = _edge_frames(depth, torch.float32)
+    k, (lo, hi) = _camera(intrinsics, depth_range, what)
+    ap, rm = float(np.float32(aperture)), float(np.float32(max_radius))
+    if not (math.isfinite(ap) and ap >= 0.0):
+        raise ValueError(f"{what}: aperture {aperture}: finite and not below 0 (metres)")
+    if not 0.0 <= rm <= bokeh_max_radius():
+        raise ValueError(f"{what}: max_radius {max_radius}: in [0, {bokeh_max_radius()}] pixels (prv2_bokeh_max_radius)")
+    zf = 0.0
+    if focus is not None:
+        zf = float(np.float32(focus))
+        if not (math.isfinite(zf) and zf > 0.0):
+            raise ValueError(f"{what}: focus {focus}: a finite distance greater than 0 (None: the focus point)")
+    u, v = (float(np.float32(c)) for c in focus_point)
+    if not (0.0 <= u <= 1.0 and 0.0 <= v <= 1.0):
+        raise ValueError(f"{what}: focus point {tuple(focus_point)} outside [0, 1]^2")
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
+        raise ValueError(f"{what}: image is a GPU tensor on the depth map's device")
+    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"{what}: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    return d, img, k[0], ap, zf, u, v, rm, lo, hi
+
+
+def bokeh_render(depth, image, intrinsics, aperture=0.025, focus=None, focus_point=(0.5, 0.5), max_radius=16.0, depth_range=(0.0, math.inf)):
+    """fp32 depth frames [B, H, W] re-rendered through a thin lens -> (out fp32 [B, 3, H, W], focus fp32 [B]), both on the device:
+    output.bokeh_render_host is the specification (include/prv2.h prv2_bokeh_render).  ``image``: fp32 [B, 3, Hi, Wi] ([3, Hi, Wi]
+    for one frame), any size, sampled nearest.  ``intrinsics``: fx, fy, cx, cy of the [H, W] grid (fx is used); ``aperture``: the
+    lens diameter in metres; ``focus``: the distance in focus, or None for the depth at ``focus_point`` (u, v) in [0, 1]^2, read on
+    the device; ``max_radius``: the cap of the circle of confusion in pixels (<= ``bokeh_max_radius()``).  ``focus``: the distance
+    every frame used, NaN where its focus pixel was not valid (that frame is the image itself)."""
+    d, img, fx, ap, zf, u, v, rm, lo, hi = _bokeh_inputs("bokeh_render", depth, image, intrinsics, aperture, focus, focus_point, max_radius,
+                                                          depth_range)
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().bokeh_render(d, img, fx, ap, zf, u, v, rm, lo, hi))  # noqa: E731
+    else:
+        out = torch.empty((d.shape[0], 3, d.shape[1], d.shape[2]), dtype=torch.float32, device=d.device)
+        used = torch.empty((d.shape[0],), dtype=torch.float32, device=d.device)
+        box.extend((out, used))
+        call = lambda: _c("bokeh_render", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], fx, ap, zf, u, v, rm, lo, hi,  # noqa: E731
+                          out.data_ptr(), used.data_ptr())
+    # per pixel: the map and the three colour samples read, three planes written (the window is re-read from cache and LDS)
+    PROFILER.launch_aux("bokeh_render", d.numel() * 28.0, call, f"{d.shape[0]}x{d.shape[1]}x{d.shape[2]} r{rm:g}")
+    return box[0], box[1]
+
+
+def bokeh_rows(depth, image, intrinsics, aperture=0.025, focus=None, focus_point=(0.5, 0.5), max_radius=16.0, depth_range=(0.0, math.inf)):
+    """``bokeh_render`` as RGB scanlines -> (scanline buffer uint8 [B, prv2_rows_bytes(H, W, 3)], focus fp32 [B]): the bytes of
+    output.bokeh_image_host (include/prv2.h prv2_bokeh_rows); the arguments as ``bokeh_render``."""
+    d, img, fx, ap, zf, u, v, rm, lo, hi = _bokeh_inputs("bokeh_rows", depth, image, intrinsics, aperture, focus, focus_point, max_radius,
+                                                          depth_range)
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().bokeh_rows(d, img, fx, ap, zf, u, v, rm, lo, hi))  # noqa: E731
+    else:
+        rows = _rows(d, 3)
+        used = torch.empty((d.shape[0],), dtype=torch.float32, device=d.device)
+        box.extend((rows, used))
+        call = lambda: _c("bokeh_rows", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], fx, ap, zf, u, v, rm, lo, hi,  # noqa: E731
+                          rows.data_ptr(), rows.shape[1], used.data_ptr())
+    PROFILER.launch_aux("bokeh_rows", d.numel() * 19.0, call, f"{d.shape[0]}x{d.shape[1]}x{d.shape[2]} r{rm:g}")
+    return box[0], box[1]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Temporal stabilisation (csrc/temporal.hip): the frames of a sequence aligned to and blended with the previous output, both dispatch
 # routes.  The host specification is temporal.temporal_step_host; temporal.TemporalStabilizer keeps the state.
 # ------------------------------------------------------------------------------------------------------------------

@@ -24,6 +24,8 @@ mesh_faces_host / mesh_ply_bytes
                          the host specification of the mesh's faces (likewise) and the PLY file of vertices and faces
 stereo_source_host / stereo_view_host / stereo_image_host
                          the host specification of the right-eye view (csrc/stereo.hip equals it byte for byte)
+bokeh_render_host / bokeh_image_host
+                         the host specification of the depth-of-field view (csrc/bokeh.hip equals it bit for bit)
 OutputStage              side stream, ring of pinned staging slots, writer pool
 
 Geometry export (``runner_info.save_ply`` / ``save_normals``; tools/test.py --save-ply / --save-normals): <name>.ply, a binary
@@ -33,6 +35,8 @@ little-endian point cloud of the result map (float x, y, z + uchar red, green, b
 four kept neighbours at most, none across a depth discontinuity (``mesh_faces_host``).  ``runner_info.save_stereo`` (--save-stereo)
 adds <name>_right.png (or _sbs / _anaglyph): the frame seen from a second eye ``stereo_baseline`` metres to the right
 (``stereo_source_host``: a per-row forward warp with a depth test, disocclusions filled from the farther side).
+``runner_info.save_bokeh`` (--save-bokeh) adds <name>_bokeh.png: the frame seen through a thin lens of ``bokeh_aperture`` metres
+focused at ``bokeh_focus`` metres or at the depth under ``bokeh_focus_point`` (``bokeh_render_host``).
 """
 from __future__ import annotations
 
@@ -480,10 +484,143 @@ def _stereo_options(stereo):
     return float(stereo.get("baseline", 0.065)), float(stereo.get("convergence", math.inf)), layout
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# depth-of-field export: the host specification of the frame seen through a thin lens (numpy float32, one rounding per operation in
+# the order written; csrc/bokeh.hip equals it bit for bit).
+#
+# A tap of weight 0 changes no bit: wgt is never negative or NaN, x + 0 = x and x + 0 * c = x for every finite c.  So the host and
+# the kernel may both bound their loops by the largest m in reach: with s = float32(M + 0.5), M the largest m, an offset with
+# max(|dx|, |dy|) >= ceil(s) has dist >= s >= float32(me + 0.5) and cov = 0.  This is what makes tiling legal: a tile of the kernel
+# walks only the window the radii in its reach can cover, and this loop only the window the frame's radii can.
+#
+# The loop visits one offset per pass over the frame, (2 R + 1)^2 passes: about a second for 270 x 480 at max_radius 8, minutes for
+# 2160 x 3840 at 16.  It is the specification, not a route for 4K frames.
+# ------------------------------------------------------------------------------------------------------------------
+BOKEH_DEFAULTS = dict(aperture=0.025, focus=None, focus_point=(0.5, 0.5), max_radius=16.0)
+
+
+def bokeh_focus_host(depth, focus=None, focus_point=(0.5, 0.5), depth_range=(0.0, math.inf)):
+    """-> float32: the distance in focus.  ``focus`` (finite, > 0) when given; else the map at the focus point (u, v) in [0, 1]^2,
+    pixel (min(h - 1, floor(v h)), min(w - 1, floor(u w))) with u, v rounded to float32 and the products in float64; NaN when that
+    pixel is not valid (finite, lo < Z < hi)"""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    h, w = d.shape
+    if focus is not None:
+        zf = F32(focus)
+        if not (np.isfinite(zf) and zf > 0):
+            raise ValueError(f"focus {focus}: a finite distance greater than 0 (None: the focus point)")
+        return zf
+    u, v = (float(F32(c)) for c in focus_point)
+    if not (0.0 <= u <= 1.0 and 0.0 <= v <= 1.0):
+        raise ValueError(f"focus point {tuple(focus_point)} outside [0, 1]^2")
+    zf = d[min(h - 1, int(math.floor(v * h))), min(w - 1, int(math.floor(u * w)))]
+    return zf if bool(_valid_depth(zf, depth_range)) else F32(np.nan)
+
+
+def bokeh_discs_host(depth, fx, aperture, zf, max_radius, depth_range=(0.0, math.inf)):
+    """-> zk, r, m, ia float32 [h, w]: valid = finite and lo < Z < hi; zk = valid ? Z : inf; iz = valid ? 1 / Z : 0; k = (fx *
+    aperture) * 0.5; r = min(max_radius, k |iz - 1 / zf|) (a NaN product gives max_radius; a NaN ``zf``: r = 0 everywhere);
+    m = max(r, 0.5); ia = 1 / (m m)"""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    valid = _valid_depth(d, depth_range)
+    with np.errstate(all="ignore"):
+        zk = np.where(valid, d, F32(np.inf)).astype(F32)
+        if np.isnan(zf):
+            r = np.zeros(d.shape, F32)
+        else:
+            iz = np.where(valid, F32(1) / d, F32(0)).astype(F32)
+            k = F32(F32(F32(fx) * F32(aperture)) * F32(0.5))
+            r = np.fmin(F32(max_radius), k * np.abs(iz - F32(F32(1) / F32(zf)))).astype(F32)
+        m = np.maximum(r, F32(0.5))
+        ia = (F32(1) / (m * m)).astype(F32)
+    return zk, r, m, ia
+
+
+def _bokeh_arguments(intrinsics, aperture, max_radius):
+    fx, ap, rm = F32(np.asarray(intrinsics, dtype=np.float64).reshape(-1)[0]), F32(aperture), F32(max_radius)
+    if not (np.isfinite(fx) and fx > 0):
+        raise ValueError(f"intrinsics: fx {fx} is finite and positive")
+    if not (np.isfinite(ap) and ap >= 0):
+        raise ValueError(f"aperture {aperture}: finite and not below 0 (metres)")
+    if not rm >= 0:
+        raise ValueError(f"max_radius {max_radius}: not below 0 (pixels)")
+    return fx, ap, rm
+
+
+def bokeh_render_host(depth, image, intrinsics, aperture=0.025, focus=None, focus_point=(0.5, 0.5), max_radius=16.0,
+                      depth_range=(0.0, math.inf)):
+    """The specification of ``ops.bokeh_render`` for one frame -> (out float32 [3, h, w], focus float32): the frame seen through a
+    thin lens of diameter ``aperture`` metres focused at ``bokeh_focus_host``'s distance, the circle of confusion capped at
+    ``max_radius`` pixels.  ``image`` [3, hi, wi], any size, is sampled to the map's grid with the cloud's nearest rule; a
+    non-finite colour counts as 0.  With the maps of ``bokeh_discs_host``, output p sums the taps q = p + (dx, dy) inside the frame,
+    dy = -R .. R outer, dx = -R .. R inner, R = ceil(max_radius): dist = float32(sqrt(dx dx + dy dy)); own = zk_q <= zk_p or
+    r_q <= r_p; (me, ie) = own ? (m_q, ia_q) : (m_p, ia_p) -- a source spreads over its own disc unless it lies behind p with the
+    larger one, so a defocused background does not bleed over a sharp foreground while a defocused foreground spreads over what lies
+    behind it; cov = clip((me + 0.5) - dist, 0, 1); wgt = cov ie; where wgt > 0: sw += wgt, sc[ch] += wgt c_q[ch] (a multiply,
+    then an add).  out = sc / sw (sw > 0: the centre tap has cov >= 0.5).  A NaN focus (an invalid focus pixel) renders r = 0
+    everywhere: the sampled image itself."""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    h, w = d.shape
+    fx, ap, rm = _bokeh_arguments(intrinsics, aperture, max_radius)
+    zf = bokeh_focus_host(d, focus, focus_point, depth_range)
+    zk, r, m, ia = bokeh_discs_host(d, fx, ap, zf, rm, depth_range)
+    img = np.asarray(image, dtype=F32)
+    c = img[:, sample_indices(h, img.shape[1])[:, None], sample_indices(w, img.shape[2])[None, :]]
+    c = np.where(np.isfinite(c), c, F32(0)).astype(F32)
+    R = int(math.ceil(float(rm)))
+    R = min(R, int(math.ceil(float(F32(m.max() + F32(0.5))))) - 1)  # (the offsets beyond have weight 0 everywhere: see above)
+    sw, sc = np.zeros((h, w), F32), np.zeros((3, h, w), F32)
+    for dy in range(-R, R + 1):
+        y0, y1 = max(0, -dy), min(h, h - dy)
+        if y0 >= y1:
+            continue
+        for dx in range(-R, R + 1):
+            x0, x1 = max(0, -dx), min(w, w - dx)
+            if x0 >= x1:
+                continue
+            dist = F32(math.sqrt(dx * dx + dy * dy))
+            P, Q = (slice(y0, y1), slice(x0, x1)), (slice(y0 + dy, y1 + dy), slice(x0 + dx, x1 + dx))
+            own = (zk[Q] <= zk[P]) | (r[Q] <= r[P])
+            me, ie = np.where(own, m[Q], m[P]), np.where(own, ia[Q], ia[P])
+            cov = np.clip((me + F32(0.5)) - dist, F32(0), F32(1))
+            wgt = (cov * ie).astype(F32)
+            on = wgt > 0
+            sw[P] = np.where(on, sw[P] + wgt, sw[P])
+            for ch in range(3):
+                sc[ch][P] = np.where(on, sc[ch][P] + wgt * c[ch][Q], sc[ch][P])
+    return (sc / sw).astype(F32), F32(zf)
+
+
+def bokeh_image_host(depth, image, intrinsics, aperture=0.025, focus=None, focus_point=(0.5, 0.5), max_radius=16.0,
+                     depth_range=(0.0, math.inf)) -> np.ndarray:
+    """The specification of ``ops.bokeh_rows`` for one frame -> uint8 [h, w, 3]: ``color_bytes(out * 255)`` of ``bokeh_render_host``
+    (the stereo view's byte rule)"""
+    out, _ = bokeh_render_host(depth, image, intrinsics, aperture, focus, focus_point, max_radius, depth_range)
+    with np.errstate(all="ignore"):
+        return np.ascontiguousarray(np.moveaxis(color_bytes(out * F32(255)), 0, -1))
+
+
+def _bokeh_options(bokeh):
+    """the ``bokeh`` dict of ``submit_geometry`` / ``write_geometry_host`` -> dict(aperture, focus, focus_point, max_radius)"""
+    unknown = set(bokeh) - set(BOKEH_DEFAULTS)
+    if unknown:
+        raise ValueError(f"bokeh: unknown keys {sorted(unknown)} ({', '.join(BOKEH_DEFAULTS)})")
+    opt = {**BOKEH_DEFAULTS, **bokeh}
+    focus = None if opt["focus"] is None else float(opt["focus"])
+    u, v = (float(c) for c in opt["focus_point"])
+    return dict(aperture=float(opt["aperture"]), focus=focus, focus_point=(u, v), max_radius=float(opt["max_radius"]))
+
+
+def _warn_bokeh_focus(base, focus):
+    if np.isnan(focus):
+        print(f"warning: {os.path.basename(base)}_bokeh.png: the focus pixel holds no valid depth; the image is written as it is", flush=True)
+
+
 def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True,
-                        mesh=False, stereo=None):
-    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png, <base>_mesh.ply and (``stereo``: a dict of
-    baseline, convergence, layout) <base>_right.png / _sbs.png / _anaglyph.png from the host specification"""
+                        mesh=False, stereo=None, bokeh=None):
+    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png, <base>_mesh.ply, (``stereo``: a dict of
+    baseline, convergence, layout) <base>_right.png / _sbs.png / _anaglyph.png and (``bokeh``: a dict of aperture, focus, focus_point,
+    max_radius) <base>_bokeh.png from the host specification"""
     if ply or mesh:
         v = pointcloud_host(depth, image, intrinsics, depth_range, edge_thr, stride)
     if ply:
@@ -498,6 +635,12 @@ def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, m
     if stereo is not None:
         baseline, convergence, layout = _stereo_options(stereo)
         write_png8(f"{base}_{layout}.png", stereo_image_host(depth, image, intrinsics, baseline, convergence, depth_range, edge_thr, layout))
+    if bokeh is not None:
+        opt = _bokeh_options(bokeh)
+        out, focus = bokeh_render_host(depth, image, intrinsics, depth_range=depth_range, **opt)
+        _warn_bokeh_focus(base, focus)
+        with np.errstate(all="ignore"):
+            write_png8(base + "_bokeh.png", np.ascontiguousarray(np.moveaxis(color_bytes(out * F32(255)), 0, -1)))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -604,7 +747,7 @@ class OutputStage:
         self.device_deflate = bool(device_deflate)
         self.stream = None
         self.copy_stream = None  # device_deflate / point clouds: the writer threads' D2H copies
-        self._slots = [dict(buf=None, sizes=None, ply=None, ply_n=None, mesh=None, mesh_n=None, futures=[]) for _ in range(self.depth)]
+        self._slots = [dict(buf=None, sizes=None, ply=None, ply_n=None, mesh=None, mesh_n=None, focus=None, futures=[]) for _ in range(self.depth)]
         self._loose = []  # files queued from host rows (write_rows)
         self._next = 0
         self._error = None
@@ -621,6 +764,16 @@ class OutputStage:
             data = png_bytes(header, rows)
             with open(path, "wb") as f:
                 f.write(data)
+        except BaseException as e:  # kept for flush()
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+
+    def _check_focus(self, base, focus, event):
+        """the depth-of-field view's warning: wait for the copy of the focus distance the kernel used (pinned float32 [1])"""
+        try:
+            event.synchronize()
+            _warn_bokeh_focus(base, float(focus[0]))
         except BaseException as e:  # kept for flush()
             with self._lock:
                 if self._error is None:
@@ -781,7 +934,7 @@ class OutputStage:
 
     @torch.no_grad()
     def submit_geometry(self, base: str, result: torch.Tensor, image_hr, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1,
-                        ply=True, normals=True, mesh=False, stereo=None):
+                        ply=True, normals=True, mesh=False, stereo=None, bokeh=None):
         """the geometry of one frame, from the device map: <base>.ply (``ply``: the point cloud of ``pointcloud_host``, coloured
         from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size), <base>_normal.png (``normals``: the map of
         ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``) and
@@ -790,7 +943,10 @@ class OutputStage:
         The vertex and face buffers are sized for their bounds (15 bytes per strided pixel, 26 per cell); only the frame's counts
         go to pinned memory with an event, and a file's writer thread copies exactly its 15 N (+ 13 M) bytes on the copy stream.
         ``stereo`` (a dict of baseline, convergence, layout; default 0.065, inf, 'right') adds <base>_right.png, <base>_sbs.png or
-        <base>_anaglyph.png: the view of ``stereo_image_host`` coloured from ``image_hr``, through the PNG path as the normal map."""
+        <base>_anaglyph.png: the view of ``stereo_image_host`` coloured from ``image_hr``, through the PNG path as the normal map.
+        ``bokeh`` (a dict of aperture, focus, focus_point, max_radius; default 0.025, None, (0.5, 0.5), 16) adds <base>_bokeh.png: the
+        frame of ``bokeh_image_host`` through the same path; the focus distance is read on the device, and only its four bytes come
+        back, for the warning of a frame whose focus pixel holds no valid depth."""
         from . import ops
         dev = result.device
         slot = self._begin(dev)
@@ -802,7 +958,7 @@ class OutputStage:
             jobs = []
             if normals:
                 jobs.append((base + "_normal.png", w, h, 3, ops.normal_rows(d, intrinsics, depth_range)))
-            if ply or mesh or stereo is not None:
+            if ply or mesh or stereo is not None or bokeh is not None:
                 img = torch.as_tensor(image_hr)
                 if img.dim() == 4 and img.shape[0] == 1:
                     img = img[0]
@@ -811,6 +967,17 @@ class OutputStage:
                 baseline, convergence, layout = _stereo_options(stereo)
                 jobs.append((f"{base}_{layout}.png", w * (2 if layout == "sbs" else 1), h, 3,
                              ops.stereo_rows(d, img, intrinsics, baseline, convergence, depth_range, edge_thr, layout)))
+            if bokeh is not None:
+                rows, focus = ops.bokeh_rows(d, img, intrinsics, depth_range=depth_range, **_bokeh_options(bokeh))
+                jobs.append((base + "_bokeh.png", w, h, 3, rows))
+                if slot["focus"] is None:
+                    slot["focus"] = torch.empty((1,), dtype=torch.float32, pin_memory=True)
+                slot["focus"].copy_(focus, non_blocking=True)
+                with self._lock:
+                    self.bytes_d2h += 4
+                ev = torch.cuda.Event()
+                ev.record(self.stream)
+                slot["futures"].append(self.pool.submit(self._check_focus, base, slot["focus"], ev))
             if jobs:
                 self._stage(slot, jobs)
             if ply or mesh:

@@ -9,7 +9,8 @@ stream differs from zlib's).
 ``runner_info.save_ply`` / ``save_normals`` (--save-ply / --save-normals, with ``save``) add the frame's geometry: <name>.ply (a
 binary point cloud of the result map, coloured from the image) and <name>_normal.png (its surface normals);
 ``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles) and
-``runner_info.save_stereo`` (--save-stereo) <name>_right.png / _sbs.png / _anaglyph.png (the right-eye view) -- from the device map
+``runner_info.save_stereo`` (--save-stereo) <name>_right.png / _sbs.png / _anaglyph.png (the right-eye view),
+``runner_info.save_bokeh`` (--save-bokeh) <name>_bokeh.png (the frame with a synthetic depth of field) -- from the device map
 with the output stage, from output.py's host specification otherwise; the same files either way.
 ``runner_info.temporal_stabilize`` (--temporal-stabilize; ``temporal_alpha`` / ``_tau`` / ``_rho`` / ``_anchor``) treats the dataset as
 one video: every result map goes through temporal.TemporalStabilizer before it is saved, exported or scored.
@@ -207,10 +208,12 @@ class Tester:
         """the keyword arguments of ``submit_geometry`` / ``write_geometry_host`` for a result map, None without ``save_ply`` /
         ``save_normals`` / ``save_mesh`` / ``save_stereo``: the camera of ``runner_info.intrinsics`` (fx fy cx cy in pixels of the raw grid) or ``runner_info.fov``
         (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``; with ``save_stereo`` the
-        ``stereo`` dict of ``stereo_baseline`` (default 0.065), ``stereo_convergence`` (inf) and ``stereo_layout`` ('right')"""
+        ``stereo`` dict of ``stereo_baseline`` (default 0.065), ``stereo_convergence`` (inf) and ``stereo_layout`` ('right'); with
+        ``save_bokeh`` the ``bokeh`` dict of ``bokeh_aperture`` (0.025), ``bokeh_focus`` (None: the depth under ``bokeh_focus_point``,
+        default (0.5, 0.5)) and ``bokeh_max_radius`` (16)"""
         info = self.runner_info
-        ply, normals, mesh, stereo = (bool(getattr(info, k, False)) for k in ("save_ply", "save_normals", "save_mesh", "save_stereo"))
-        if not (info.save and (ply or normals or mesh or stereo)):
+        ply, normals, mesh, stereo, bokeh = (bool(getattr(info, k, False)) for k in ("save_ply", "save_normals", "save_mesh", "save_stereo", "save_bokeh"))
+        if not (info.save and (ply or normals or mesh or stereo or bokeh)):
             return None
         from .output import camera_intrinsics
         k = camera_intrinsics(image_raw_shape, result.shape[-2:], getattr(info, "intrinsics", None), getattr(info, "fov", None) or 60.0)
@@ -218,7 +221,10 @@ class Tester:
                     edge_thr=float(getattr(info, "ply_edge_thr", 0.05)), stride=int(getattr(info, "ply_stride", 1)), ply=ply, normals=normals, mesh=mesh,
                     **(dict(stereo=dict(baseline=float(getattr(info, "stereo_baseline", 0.065)),
                                         convergence=float(getattr(info, "stereo_convergence", float("inf"))),
-                                        layout=getattr(info, "stereo_layout", "right"))) if stereo else {}))
+                                        layout=getattr(info, "stereo_layout", "right"))) if stereo else {}),
+                    **(dict(bokeh=dict(aperture=float(getattr(info, "bokeh_aperture", 0.025)), focus=getattr(info, "bokeh_focus", None),
+                                       focus_point=tuple(getattr(info, "bokeh_focus_point", None) or (0.5, 0.5)),
+                                       max_radius=float(getattr(info, "bokeh_max_radius", 16.0)))) if bokeh else {}))
 
     def _entry(self, item, result, score=None, **extra):
         """one frame's result entry.  ``mean``: a host map's fp32 mean, a device map's float64 sum on the device (equal within that

@@ -61,6 +61,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "stereo_rows", "stereo_source",
        # temporal stabilisation: frames of a sequence aligned to and blended with the previous output (state tensors updated in place)
        "temporal_step_",
+       # depth-of-field export: frames re-rendered through a thin lens, as fp32 planes or as scanlines (each with the focus used)
+       "bokeh_render", "bokeh_rows",
        # the gate kernels with the coarse-tap gather inside (tables instead of ``pre``)
        "conv3x3_ln_gate_taps", "conv3x3_ln_gate_f6_taps")
 _loaded = False

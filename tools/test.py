@@ -14,6 +14,8 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`` (pixels of the --image-raw-shape grid) or ``--fov DEG``
 (horizontal, default 60); ``--ply-stride S``, ``--ply-edge-thr T`` (flying-pixel filter, <= 0 off), ``--ply-depth-range LO HI``.
 ``--save-mesh``: with ``--save``, <name>_mesh.ply: the same vertices plus a face element, triangles along the pixel grid (same camera and --ply-* options).
+``--save-bokeh``: with ``--save``, <name>_bokeh.png: the frame with a synthetic depth of field (``--bokeh-aperture M``, ``--bokeh-focus Z`` or
+``--bokeh-focus-point U V``, ``--bokeh-max-radius PX``; same camera and --ply-depth-range).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
 ``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
@@ -184,6 +186,16 @@ def main():
                     help="--save-stereo: the depth that keeps its column (nearer pops out, farther recedes); inf: parallel axes")
     ap.add_argument("--stereo-layout", default="right", choices=["right", "sbs", "anaglyph"],
                     help="--save-stereo: right = the view, sbs = left | right (twice the width), anaglyph = red of left, green and blue of right")
+    ap.add_argument("--save-bokeh", action="store_true",
+                    help="with --save: <name>_bokeh.png, the frame seen through a thin lens (synthetic depth of field): every pixel spreads over "
+                         "its circle of confusion fx * aperture / 2 * |1 / Z - 1 / focus| pixels, a defocused background kept off a sharp "
+                         "foreground (camera of --intrinsics / --fov, validity of --ply-depth-range); made on the GPU with --device-output, "
+                         "by the host specification otherwise (minutes per 4K frame)")
+    ap.add_argument("--bokeh-aperture", type=float, default=0.025, metavar="M", help="--save-bokeh: the lens diameter in metres (0.025: 50 mm at f/2)")
+    ap.add_argument("--bokeh-focus", type=float, default=None, metavar="Z", help="--save-bokeh: the distance in focus in metres (default: the depth under --bokeh-focus-point)")
+    ap.add_argument("--bokeh-focus-point", nargs=2, type=float, default=[0.5, 0.5], metavar=("U", "V"),
+                    help="--save-bokeh without --bokeh-focus: focus on the depth at this point of the frame, (0, 0) top left, (1, 1) bottom right")
+    ap.add_argument("--bokeh-max-radius", type=float, default=16.0, metavar="PX", help="--save-bokeh: the cap of the circle of confusion in pixels (at most 32)")
     ap.add_argument("--temporal-stabilize", action="store_true",
                     help="treat the frames as one video, in dataset order: every result map is aligned to the previous output by a gated "
                          "least-squares scale and shift and blended with it where the image has not changed (patchrefinerv2_amd/temporal.py; "
@@ -207,8 +219,16 @@ def main():
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
-    if (args.save_ply or args.save_normals or args.save_mesh or args.save_stereo) and not args.save:
-        ap.error("--save-ply / --save-normals / --save-mesh / --save-stereo need --save (they add files to the frames it writes)")
+    if (args.save_ply or args.save_normals or args.save_mesh or args.save_stereo or args.save_bokeh) and not args.save:
+        ap.error("--save-ply / --save-normals / --save-mesh / --save-stereo / --save-bokeh need --save (they add files to the frames it writes)")
+    if args.bokeh_focus is not None and not (0 < args.bokeh_focus < float("inf")):
+        ap.error(f"--bokeh-focus {args.bokeh_focus}: a finite distance greater than 0")
+    if not all(0.0 <= c <= 1.0 for c in args.bokeh_focus_point):
+        ap.error(f"--bokeh-focus-point {args.bokeh_focus_point}: inside [0, 1] x [0, 1]")
+    if not 0.0 <= args.bokeh_max_radius <= 32.0:
+        ap.error(f"--bokeh-max-radius {args.bokeh_max_radius}: in [0, 32]")
+    if not 0.0 <= args.bokeh_aperture < float("inf"):
+        ap.error(f"--bokeh-aperture {args.bokeh_aperture}: finite and not below 0")
     if args.stereo_convergence == 0 or args.stereo_convergence != args.stereo_convergence:
         ap.error(f"--stereo-convergence {args.stereo_convergence}: a depth other than 0")
     if args.ply_stride < 1:
@@ -262,6 +282,8 @@ def main():
                         device_output=args.device_output, output_workers=args.output_workers, device_deflate=args.device_deflate,
                         save_ply=args.save_ply, save_normals=args.save_normals, save_mesh=args.save_mesh, save_stereo=args.save_stereo,
                         stereo_baseline=args.stereo_baseline, stereo_convergence=args.stereo_convergence, stereo_layout=args.stereo_layout,
+                        save_bokeh=args.save_bokeh, bokeh_aperture=args.bokeh_aperture, bokeh_focus=args.bokeh_focus,
+                        bokeh_focus_point=tuple(args.bokeh_focus_point), bokeh_max_radius=args.bokeh_max_radius,
                         intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
                         ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range),
                         temporal_stabilize=args.temporal_stabilize, temporal_alpha=args.temporal_alpha, temporal_tau=args.temporal_tau,
