@@ -1172,6 +1172,75 @@ int prv2_bokeh_rows(const float* depth, const float* image, int32_t n, int32_t h
                     float focus, float focus_u, float focus_v, float max_radius, float lo, float hi, uint8_t* rows, int64_t rows_fstride,
                     float* focus_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Novel-view export (csrc/view.hip): the frame seen from a camera that has moved (a "3D photo", one frame of a parallax clip), from
+ * its metric depth map: B >= 1 dense frames [n, h, w] and nv >= 1 poses per call (h, w >= 1; n * nv * h * w < 2^29;
+ * w <= prv2_stereo_max_width()).  Not in the reference.  The map's own mesh is rasterised exactly, with a depth test: three kernels
+ * (clear, raster, resolve) chained on the caller's stream, no host synchronisation, no allocation.  The depth test is an unsigned
+ * 64-bit minimum on memory, which has no order: the same input gives the same bits on every call.  Added without an ABI bump
+ * (additive).  The host specification is view_source_host / view_image_host of patchrefinerv2_amd/output.py, which the kernels equal
+ * bit for bit.  Everything is fp32, one rounding per operation in the order written, no contraction, correctly rounded division;
+ * after "fixed" everything but the interpolation of "depth" is integer arithmetic.
+ *   camera     "Geometry export": Z = D[y, x], X = (((float)x + 0.5) - cx) * Z / fx, Y likewise; valid: Z finite and lo < Z < hi
+ *   pose       M: fp32 [12], a row-major 3 x 4 matrix [R | t], made on the host in float64 and rounded once:
+ *              Xc = ((M0 X + M1 Y) + M2 Z) + M3, Yc and Zc with rows 1 and 2
+ *   project    iz = 1 / Zc; fu = fx * (Xc / Zc) + cx; fv = fy * (Yc / Zc) + cy
+ *              a vertex is "seen" when valid, Zc finite and > 0, iz finite, |fu| < 65536 and |fv| < 65536
+ *              (there is no clipping at a near plane: a face with a vertex that is not seen is dropped)
+ *   fixed      ux = (int)rint(fu * 16), uy = (int)rint(fv * 16), ties to even; the centre of view pixel (px, py) is (16 px + 8, 16 py + 8)
+ *   points     every seen vertex is a candidate for the view pixel (ux >> 4, uy >> 4) (arithmetic shift = floor), when that lies in
+ *              the frame, with q = iz and its own index
+ *   faces      "Mesh export" at stride 1 with "kept" read as "valid" (the flying-pixel filter does not apply, as in "Stereo export"):
+ *              same diagonal rule, same candidates in the same order, same "joined" rule with edge_thr; all three vertices seen
+ *              A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) in fixed units; A = 0: no face; s = sign(A)
+ *              (a face seen from behind is drawn: there is no culling)
+ *   box        px from ceil((min ux - 8) / 16) to floor((max ux - 8) / 16), py likewise
+ *              a face whose box spans more than prv2_view_max_face() = 16 pixel centres in x or in y is dropped (stretched more than
+ *              16-fold: it belongs to no surface worth showing); then the box is cut to the frame
+ *   cover      w0 = s E12(p), w1 = s E20(p), w2 = s E01(p), Eij(p) = (xj - xi)(py' - yi) - (yj - yi)(px' - xi) at the pixel centre p'
+ *              p is covered when all three are >= 0 (edges inclusive: a centre on a shared edge belongs to both faces and the depth
+ *              test decides, so a surface has no cracks); w0 + w1 + w2 = |A| < 2^24, so the conversions below are exact
+ *   depth      q = (((float)w0 * iz0 + (float)w1 * iz1) + (float)w2 * iz2) / (float)|A|
+ *              (1 / Zc is linear in the view, so this is perspective-correct)
+ *   source     the vertex with the largest w, the first of (0, 1, 2) between equals: its pixel index y * w + x
+ *   test       key = ((0xFFFFFFFF - bits(q)) << 32) | source
+ *              a view pixel keeps the smallest key over all its candidates: the largest q, between equal q the smallest source index
+ *              No candidate: a hole (src = -1, iz = 0)
+ *   fill       "Stereo export"'s rule on every row of the view, with the winners' q for the comparison:
+ *              a hole takes the source of the nearest shown column to its left, l, or right, r; r's when q_r < q_l (the farther side),
+ *              else l's; the one that exists at a border; -1 in a row that shows nothing
+ *   colour     image fp32 [n, 3, ih, iw] sampled as prv2_pointcloud_pack does at the filled source pixel; byte = "Geometry export";
+ *              (0, 0, 0) for -1
+ * ------------------------------------------------------------------------------------------ */
+
+/* the pixel centres a face's box may span in x and in y (16) */
+int32_t prv2_view_max_face(void);
+
+/* measurement only: which of the three kernels prv2_view_source / _rows launch, as a mask (1 clear, 2 raster, 4 resolve; 7 is the
+ * default; mask < 0 changes nothing); returns the previous mask.  Process-wide.  With a kernel left out the results are not the
+ * specification's. */
+int32_t prv2_view_stages(int32_t mask);
+
+/* bytes of workspace prv2_view_source / _rows need for n frames and nv poses of h x w: one 64-bit key per view pixel (-1 for bad
+ * arguments, n * nv * h * w >= 2^29 among them) */
+int64_t prv2_view_workspace_bytes(int32_t n, int32_t nv, int32_t h, int32_t w);
+
+/* poses: DEVICE fp32 [nv][12].  src, filled: DEVICE int32 [n, nv, h, w]: the source pixel (y * w + x of the frame) every pixel of
+ * every view shows (-1: hole), and the same with the holes filled by the rule above.  iz: DEVICE fp32 [n, nv, h, w], the winners' q
+ * (0: hole), or null.  workspace: DEVICE, 16-byte aligned, prv2_view_workspace_bytes(n, nv, h, w).  fx, fy > 0, all four finite;
+ * lo, hi, edge_thr not NaN.  Every argument is checked before anything is launched (prv2_last_error). */
+int prv2_view_source(const float* depth, int32_t n, int32_t h, int32_t w, float fx, float fy, float cx, float cy, const float* poses, int32_t nv,
+                     float lo, float hi, float edge_thr, int32_t* src, int32_t* filled, float* iz, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
+/* the views as RGB scanlines (bpp 3; scanline buffers of the output stage, one per (frame, view): [h][1 + 3 w] bytes at
+ * rows[(f * nv + v) * rows_vstride]; rows 16-byte aligned, rows_vstride a multiple of 16 and >= prv2_rows_bytes(h, w, 3); the tail
+ * up to the next multiple of 16 is zero).  A workgroup assembles its scanline in LDS and stores it once: byte stores at the ragged
+ * ends, 16-byte stores inside; no byte is read back. */
+int prv2_view_rows(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx, float fy, float cx,
+                   float cy, const float* poses, int32_t nv, float lo, float hi, float edge_thr, uint8_t* rows, int64_t rows_vstride,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

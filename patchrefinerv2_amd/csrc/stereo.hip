@@ -13,14 +13,13 @@
 //     and the test is ONE 64-bit LDS integer min per covered column (ds_min_u64: no compare-and-swap loop in the generated code, and
 //     no second pass or barrier as the two-pass 32-bit form needs).  A minimum does not depend on arrival order: same bytes every call;
 //   - fill: a hole takes the source of the nearest shown column on its left or right: the right one when its winner has the larger Z,
-//     else the left one; the one that exists at the frame's border; -1 in a row that shows nothing.
-#include "rows.h"
+//     else the left one; the one that exists at the frame's border; -1 in a row that shows nothing (row_fill.h, shared with view.hip).
+#include "row_fill.h"
 
 namespace prv2 {
 namespace {
 
 constexpr int kStereoMaxWidth = 8192;  // the widest row a workgroup keeps in LDS (8 bytes per column: 64 KiB of the CU's 160)
-constexpr unsigned long long kHole = ~0ull;
 
 struct StereoArgs {
   const float* depth;  // [n, h, w]
@@ -51,15 +50,6 @@ __device__ __forceinline__ uint32_t ordered_bits(float z) {
   return (b & 0x80000000u) ? ~b : b | 0x80000000u;
 }
 
-// the nearest sample of an axis of n_in values for position i of n_out
-__device__ __forceinline__ int nearest(int i, int n_out, int n_in) { return (int)(((int64_t)(2 * i + 1) * n_in) / (2 * (int64_t)n_out)); }
-
-// clamp(rint(v), 0, 255), ties to even, NaN -> 0
-__device__ __forceinline__ uint32_t stereo_byte(float v) {
-  const float r = rintf(v);
-  return !(r > 0.0f) ? 0u : r >= 255.0f ? 255u : (uint32_t)r;
-}
-
 // CAP: columns of LDS (w <= CAP).  ROWS: write the scanline of the layout, else the int32 src / filled maps.
 template <int CAP, bool ROWS>
 __global__ void __launch_bounds__(256) stereo_kernel(StereoArgs a) {
@@ -67,7 +57,7 @@ __global__ void __launch_bounds__(256) stereo_kernel(StereoArgs a) {
   __shared__ uint4 key4[CAP / 2];  // the depth-test keys; later the scanline's bytes
   __shared__ int32_t seg_left[CAP / 64], seg_right[CAP / 64];  // per 64 columns: the last / first shown column, then their scans
   unsigned long long* key = (unsigned long long*)key4;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, y = blockIdx.x, f = blockIdx.y, w = a.w;
+  const int tid = threadIdx.x, y = blockIdx.x, f = blockIdx.y, w = a.w;
   const float* d = a.depth + ((int64_t)f * a.h + y) * w;
 
 #pragma unroll
@@ -97,65 +87,8 @@ __global__ void __launch_bounds__(256) stereo_kernel(StereoArgs a) {
   }
   __syncthreads();
 
-  // the last and the first shown column of every 64-column segment (segment i * 4 + wave = columns of step i of this wave)
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    if (i * 256 >= w) break;  // (the same for every lane)
-    const int q = i * 256 + tid;
-    const unsigned long long b = __ballot(q < w && key[q] != kHole);
-    if (lane == 0) {
-      const int q64 = i * 256 + wave * 64;
-      seg_left[i * 4 + wave] = b ? q64 + 63 - __clzll((long long)b) : -1;
-      seg_right[i * 4 + wave] = b ? q64 + __ffsll((unsigned long long)b) - 1 : w;
-    }
-  }
-  __syncthreads();
-  const int nseg = (w + 255) / 256 * 4;
-  if (tid == 0) {  // max-scan: the last shown column before each segment
-    int run = -1;
-    for (int s = 0; s < nseg; ++s) {
-      const int v = seg_left[s];
-      seg_left[s] = run;
-      run = v > run ? v : run;
-    }
-  }
-  if (tid == 64) {  // min-scan from the right: the first shown column behind each segment
-    int run = w;
-    for (int s = nseg - 1; s >= 0; --s) {
-      const int v = seg_right[s];
-      seg_right[s] = run;
-      run = v < run ? v : run;
-    }
-  }
-  __syncthreads();
-
   int32_t shown[PER], fill[PER];  // a lane's columns: the winning source (-1: hole), and with the holes filled
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    shown[i] = fill[i] = -1;
-    if (i * 256 >= w) break;
-    const int q = i * 256 + tid, q64 = i * 256 + wave * 64;
-    const bool on = q < w && key[q] != kHole;
-    const unsigned long long b = __ballot(on);
-    if (q >= w) continue;
-    if (on) {
-      shown[i] = fill[i] = (int32_t)(uint32_t)key[q];
-      continue;
-    }
-    const unsigned long long below = b & ((1ull << lane) - 1ull), above = b & ~((1ull << lane) - 1ull);  // (this lane's bit is clear)
-    const int l = below ? q64 + 63 - __clzll((long long)below) : seg_left[i * 4 + wave];
-    const int r = above ? q64 + __ffsll(above) - 1 : seg_right[i * 4 + wave];
-    if (r < w) {
-      const unsigned long long kr = key[r];
-      fill[i] = (int32_t)(uint32_t)kr;
-      if (l >= 0) {
-        const unsigned long long kl = key[l];
-        if (!((uint32_t)(kr >> 32) > (uint32_t)(kl >> 32))) fill[i] = (int32_t)(uint32_t)kl;
-      }
-    } else if (l >= 0) {
-      fill[i] = (int32_t)(uint32_t)key[l];
-    }
-  }
+  row_fill<CAP>(key, seg_left, seg_right, w, tid, shown, fill);
 
   if (!ROWS) {
     const int64_t o = ((int64_t)f * a.h + y) * w;

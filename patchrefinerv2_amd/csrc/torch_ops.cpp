@@ -1517,6 +1517,45 @@ std::tuple<Tensor, Tensor> bokeh_rows(const Tensor& depth, const Tensor& image, 
   return {rows, used};
 }
 
+// novel-view export (include/prv2.h "Novel-view export"): B frames seen from nv poses (fp32 [nv, 12] on the device) -> the source maps
+// [B, nv, H, W], or scanlines [B, nv, bytes]; the key workspace is allocated here
+Tensor view_workspace(const Tensor& depth, const Tensor& poses, const char* op) {
+  dev_frames(depth, "depth", at::kFloat);
+  stereo_width(depth, op);
+  TORCH_CHECK(poses.is_cuda() && poses.scalar_type() == at::kFloat && poses.dim() == 2 && poses.size(0) >= 1 && poses.size(1) == 12 &&
+                  poses.is_contiguous() && poses.device() == depth.device(), "prv2::", op, ": poses must be a contiguous GPU fp32 [nv, 12] tensor");
+  const int64_t bytes = prv2_view_workspace_bytes((int)depth.size(0), (int)std::min<int64_t>(poses.size(0), INT32_MAX), (int)depth.size(1), (int)depth.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::", op, ": ", depth.size(0), " frames x ", poses.size(0), " views of ", depth.size(1), " x ", depth.size(2),
+              " exceed 2^29 pixels");
+  return at::empty({bytes}, depth.options().dtype(at::kByte));
+}
+std::tuple<Tensor, Tensor, Tensor> view_source(const Tensor& depth, at::ArrayRef<double> intrinsics, const Tensor& poses, double lo, double hi,
+                                               double edge_thr) {
+  Tensor ws = view_workspace(depth, poses, "view_source");
+  const double* k = camera4(intrinsics, "view_source");
+  const std::vector<int64_t> shape = {depth.size(0), poses.size(0), depth.size(1), depth.size(2)};
+  Tensor src = at::empty(shape, depth.options().dtype(at::kInt)), filled = at::empty(shape, depth.options().dtype(at::kInt));
+  Tensor iz = at::empty(shape, depth.options());
+  Launch L(depth);
+  ok(prv2_view_source(depth.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2), (float)k[0], (float)k[1], (float)k[2],
+                      (float)k[3], poses.data_ptr<float>(), (int)poses.size(0), (float)lo, (float)hi, (float)edge_thr, src.data_ptr<int32_t>(),
+                      filled.data_ptr<int32_t>(), iz.data_ptr<float>(), ws.data_ptr(), ws.numel(), L.stream), "view_source");
+  return {src, filled, iz};
+}
+Tensor view_rows(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, const Tensor& poses, double lo, double hi, double edge_thr) {
+  Tensor ws = view_workspace(depth, poses, "view_rows");
+  bokeh_image(depth, image, "view_rows");
+  const double* k = camera4(intrinsics, "view_rows");
+  const int64_t bytes = prv2_rows_bytes((int)depth.size(1), (int)depth.size(2), 3);
+  TORCH_CHECK(bytes > 0, "prv2::view_rows: bad frame shape ", depth.sizes());
+  Tensor rows = at::empty({depth.size(0), poses.size(0), bytes}, depth.options().dtype(at::kByte));
+  Launch L(depth);
+  ok(prv2_view_rows(depth.data_ptr<float>(), image.data_ptr<float>(), (int)depth.size(0), (int)depth.size(1), (int)depth.size(2), (int)image.size(2),
+                    (int)image.size(3), (float)k[0], (float)k[1], (float)k[2], (float)k[3], poses.data_ptr<float>(), (int)poses.size(0), (float)lo,
+                    (float)hi, (float)edge_thr, (uint8_t*)rows.data_ptr(), bytes, ws.data_ptr(), ws.numel(), L.stream), "view_rows");
+  return rows;
+}
+
 // temporal stabilisation (include/prv2.h "Temporal stabilisation"): n frames in sequence order; the state (its map and the two luma
 // buffers, the previous luma in luma0) is updated in place -> (out [n, h, w], stats int64 [n, PRV2_TEMPORAL_STATS] on the device)
 std::tuple<Tensor, Tensor> temporal_step_(const Tensor& depth, const Tensor& image, double alpha, int64_t tau, double rho, double anchor,
@@ -1714,6 +1753,8 @@ TORCH_LIBRARY(prv2, m) {
   m.def("temporal_step_(Tensor depth, Tensor image, float alpha, int tau, float rho, float anchor, Tensor(a!) state_depth, Tensor(b!) luma0, Tensor(c!) luma1, bool state_present) -> (Tensor, Tensor)");
   m.def("bokeh_render(Tensor depth, Tensor image, float fx, float aperture, float focus, float focus_u, float focus_v, float max_radius, float lo, float hi) -> (Tensor, Tensor)");
   m.def("bokeh_rows(Tensor depth, Tensor image, float fx, float aperture, float focus, float focus_u, float focus_v, float max_radius, float lo, float hi) -> (Tensor, Tensor)");
+  m.def("view_source(Tensor depth, float[] intrinsics, Tensor poses, float lo, float hi, float edge_thr) -> (Tensor, Tensor, Tensor)");
+  m.def("view_rows(Tensor depth, Tensor image, float[] intrinsics, Tensor poses, float lo, float hi, float edge_thr) -> Tensor");
 }
 
 // every op takes GPU tensors: registered for the CUDA dispatch key (= HIP on PyTorch-ROCm).  Calling one with CPU tensors
@@ -1815,4 +1856,6 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("temporal_step_", &temporal_step_);
   m.impl("bokeh_render", &bokeh_render);
   m.impl("bokeh_rows", &bokeh_rows);
+  m.impl("view_source", &view_source);
+  m.impl("view_rows", &view_rows);
 }

@@ -214,6 +214,12 @@ SIGNATURES = {
     "prv2_bokeh_tile_bound": (_I, [_I]),
     "prv2_bokeh_render": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P]),
     "prv2_bokeh_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _P, _L, _P, _P]),
+    # novel-view export (csrc/view.hip): B frames seen from nv camera poses, as source maps or as scanlines
+    "prv2_view_max_face": (_I, []),
+    "prv2_view_stages": (_I, [_I]),
+    "prv2_view_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "prv2_view_source": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _P, _I, _F, _F, _F, _P, _P, _P, _P, _L, _P]),
+    "prv2_view_rows": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _I, _F, _F, _F, _P, _L, _P, _L, _P]),
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
 TEMPORAL_STATS = 12  # PRV2_TEMPORAL_STATS: 8-byte words per frame of prv2_temporal_step's stats

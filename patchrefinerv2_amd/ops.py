@@ -2008,6 +2008,87 @@ def bokeh_rows(depth, image, intrinsics, aperture=0.025, focus=None, focus_point
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Novel-view export (csrc/view.hip): frames [B, H, W] seen from a list of camera poses, as source maps or as scanlines, both
+# dispatch routes.  The host specification is output.view_source_host / output.view_image_host; output.view_poses makes the poses.
+# ------------------------------------------------------------------------------------------------------------------
+def view_max_face() -> int:
+    """the pixel centres a face's box may span each way before it is dropped (include/prv2.h prv2_view_max_face)"""
+    return int(L.load().prv2_view_max_face())
+
+
+def _view_inputs(what, depth, intrinsics, poses, depth_range, edge_thr):
+    """the arguments view_source and view_rows share, checked -> (frames fp32 [B, H, W], k, poses fp32 [NV, 12] on the frames'
+    device, lo, hi, edge_thr, workspace bytes)"""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
+        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
+    d = _edge_frames(depth, torch.float32)
+    k, (lo, hi) = _camera(intrinsics, depth_range, what)
+    thr = float(np.float32(edge_thr))
+    if math.isnan(thr):
+        raise ValueError(f"{what}: edge_thr must not be NaN")
+    if isinstance(poses, torch.Tensor):
+        p = poses.detach().to(torch.float32)
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(poses, dtype=np.float32)))
+    if p.dim() == 1:
+        p = p[None]
+    if p.dim() != 2 or p.shape[0] < 1 or p.shape[1] != 12:
+        raise ValueError(f"{what}: poses are [NV, 12] (or [12]): row-major 3 x 4 matrices [R | t] (got {tuple(p.shape)})")
+    limit = L.load().prv2_stereo_max_width()
+    if d.shape[2] > limit:
+        raise ValueError(f"{what}: a row of {d.shape[2]} columns is wider than the {limit} the kernel keeps in LDS (prv2_stereo_max_width)")
+    nbytes = L.load().prv2_view_workspace_bytes(d.shape[0], min(p.shape[0], 2 ** 31 - 1), d.shape[1], d.shape[2])
+    if nbytes <= 0:
+        raise ValueError(f"{what}: {d.shape[0]} frames x {p.shape[0]} views of {d.shape[1]} x {d.shape[2]} exceed 2^29 pixels")
+    return d, k, p.to(d.device).contiguous(), lo, hi, thr, int(nbytes)
+
+
+def view_source(depth, intrinsics, poses, depth_range=(0.0, math.inf), edge_thr=0.05):
+    """fp32 depth frames [B, H, W] seen from the camera poses ``poses`` ([NV, 12] or [12], a host array or a tensor: row-major
+    [R | t] of output.view_poses; uploaded here) -> (src, filled int32 [B, NV, H, W], iz fp32 [B, NV, H, W]) on the device: the source
+    pixel y * W + x every pixel of every view shows (-1: a hole), the same with the holes filled from the farther side, and the
+    winners' 1 / Zc (0: a hole) -- output.view_source_host for every (frame, pose); include/prv2.h prv2_view_source.
+    ``intrinsics``: fx, fy, cx, cy of the [H, W] grid."""
+    d, k, p, lo, hi, thr, nbytes = _view_inputs("view_source", depth, intrinsics, poses, depth_range, edge_thr)
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().view_source(d, k, p, lo, hi, thr))  # noqa: E731
+    else:
+        shape = (d.shape[0], p.shape[0], d.shape[1], d.shape[2])
+        box.extend((torch.empty(shape, dtype=torch.int32, device=d.device), torch.empty(shape, dtype=torch.int32, device=d.device),
+                    torch.empty(shape, dtype=torch.float32, device=d.device)))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=d.device)
+        call = lambda: _c("view_source", d.data_ptr(), *d.shape, *k, p.data_ptr(), p.shape[0], lo, hi, thr, box[0].data_ptr(),  # noqa: E731
+                          box[1].data_ptr(), box[2].data_ptr(), ws.data_ptr(), nbytes)
+    # per view pixel: the key cleared, about seven 8-byte minima at the identity pose, the key read, three maps written
+    PROFILER.launch_aux("view_source", d.numel() * p.shape[0] * 84.0, call, f"{d.shape[0]}x{p.shape[0]}x{d.shape[1]}x{d.shape[2]}")
+    return box[0], box[1], box[2]
+
+
+def view_rows(depth, image, intrinsics, poses, depth_range=(0.0, math.inf), edge_thr=0.05):
+    """``view_source``'s views as RGB scanlines -> scanline buffers uint8 [B, NV, prv2_rows_bytes(H, W, 3)]: the bytes of
+    output.view_image_host for every (frame, pose) (include/prv2.h prv2_view_rows).  ``image``: fp32 [B, 3, Hi, Wi] ([3, Hi, Wi] for
+    one frame), any size, sampled nearest; the other arguments as ``view_source``."""
+    d, k, p, lo, hi, thr, nbytes = _view_inputs("view_rows", depth, intrinsics, poses, depth_range, edge_thr)
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
+        raise ValueError("view_rows: image is a GPU tensor on the depth map's device")
+    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
+    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
+        raise ValueError(f"view_rows: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().view_rows(d, img, k, p, lo, hi, thr))  # noqa: E731
+    else:
+        rows = torch.empty((d.shape[0], p.shape[0], L.load().prv2_rows_bytes(d.shape[1], d.shape[2], 3)), dtype=torch.uint8, device=d.device)
+        box.append(rows)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=d.device)
+        call = lambda: _c("view_rows", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], *k, p.data_ptr(), p.shape[0], lo, hi,  # noqa: E731
+                          thr, rows.data_ptr(), rows.shape[2], ws.data_ptr(), nbytes)
+    PROFILER.launch_aux("view_rows", d.numel() * p.shape[0] * 87.0, call, f"{d.shape[0]}x{p.shape[0]}x{d.shape[1]}x{d.shape[2]}")
+    return box[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Temporal stabilisation (csrc/temporal.hip): the frames of a sequence aligned to and blended with the previous output, both dispatch
 # routes.  The host specification is temporal.temporal_step_host; temporal.TemporalStabilizer keeps the state.
 # ------------------------------------------------------------------------------------------------------------------

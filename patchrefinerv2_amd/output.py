@@ -26,6 +26,8 @@ stereo_source_host / stereo_view_host / stereo_image_host
                          the host specification of the right-eye view (csrc/stereo.hip equals it byte for byte)
 bokeh_render_host / bokeh_image_host
                          the host specification of the depth-of-field view (csrc/bokeh.hip equals it bit for bit)
+view_source_host / view_image_host / view_poses
+                         the host specification of the views from a moved camera (csrc/view.hip equals it bit for bit) and their path
 OutputStage              side stream, ring of pinned staging slots, writer pool
 
 Geometry export (``runner_info.save_ply`` / ``save_normals``; tools/test.py --save-ply / --save-normals): <name>.ply, a binary
@@ -37,6 +39,8 @@ adds <name>_right.png (or _sbs / _anaglyph): the frame seen from a second eye ``
 (``stereo_source_host``: a per-row forward warp with a depth test, disocclusions filled from the farther side).
 ``runner_info.save_bokeh`` (--save-bokeh) adds <name>_bokeh.png: the frame seen through a thin lens of ``bokeh_aperture`` metres
 focused at ``bokeh_focus`` metres or at the depth under ``bokeh_focus_point`` (``bokeh_render_host``).
+``runner_info.save_views`` = N (--save-views N) adds <name>_view_000.png ...: the frame seen from N poses of a closed camera path
+(``view_poses``), the map's own mesh rasterised with a depth test (``view_source_host``).
 """
 from __future__ import annotations
 
@@ -616,11 +620,191 @@ def _warn_bokeh_focus(base, focus):
         print(f"warning: {os.path.basename(base)}_bokeh.png: the focus pixel holds no valid depth; the image is written as it is", flush=True)
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# novel-view export: the host specification of the frame seen from a camera that has moved (include/prv2.h "Novel-view export";
+# numpy float32 up to the fixed-point vertex positions, integers after them; csrc/view.hip equals it bit for bit).
+#
+# The depth map's own mesh (``mesh_faces_host``'s cells at stride 1, "kept" read as "valid") is rasterised with a depth test.  The
+# faces are walked all at once: one pass over them per offset inside a face's box of pixel centres, up to the largest box that
+# occurs -- 2 x 2 passes at the identity pose, 16 x 16 at most.  A pass costs a few dozen numpy operations over every face: it is
+# the specification, not a route for 4K frames.
+# ------------------------------------------------------------------------------------------------------------------
+VIEW_MOTIONS = ("circle", "sway", "dolly")
+VIEW_DEFAULTS = dict(count=8, motion="circle", amplitude=0.05, focus=math.inf)
+VIEW_MAX_COUNT = 120
+VIEW_MAX_FACE = 16  # prv2_view_max_face(): the pixel centres a face's box may span in x and in y
+VIEW_CHUNK = 4      # views per launch of the output stage: bounds the key workspace and the pinned staging
+IDENTITY_POSE = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def view_poses(count, motion="circle", amplitude=0.05, focus=math.inf) -> np.ndarray:
+    """the closed camera path of the novel-view export -> float32 [count, 12], each a row-major 3 x 4 matrix [R | t] that takes a
+    point of the frame's camera (x right, y down, z forward) to view k's.  theta = 2 pi k / count; the eye e is ``amplitude`` *
+    (cos, sin, 0) for 'circle', (sin, 0, 0) for 'sway', (0, 0, sin) for 'dolly'.  ``focus`` = inf: R = I (parallel axes); else the
+    camera keeps looking at (0, 0, focus): f = normalise((0, 0, focus) - e), r = normalise(cross((0, 1, 0), f)), d = cross(f, r), R has
+    the rows r, d, f.  t = -R e.  float64 throughout, rounded once."""
+    count, amplitude, focus = int(count), float(amplitude), float(focus)
+    if not 1 <= count <= VIEW_MAX_COUNT:
+        raise ValueError(f"view count {count}: 1 to {VIEW_MAX_COUNT}")
+    if motion not in VIEW_MOTIONS:
+        raise ValueError(f"view motion {motion!r}: one of {VIEW_MOTIONS}")
+    if not (math.isfinite(amplitude) and amplitude >= 0.0):
+        raise ValueError(f"view amplitude {amplitude}: finite and not below 0 (metres)")
+    if not focus > 0.0:  # (NaN as well)
+        raise ValueError(f"view focus {focus}: a depth greater than 0 (inf: parallel axes)")
+    out = np.empty((count, 3, 4), dtype=np.float64)
+    for k in range(count):
+        th = 2.0 * math.pi * k / count
+        e = amplitude * np.array({"circle": (math.cos(th), math.sin(th), 0.0), "sway": (math.sin(th), 0.0, 0.0),
+                                  "dolly": (0.0, 0.0, math.sin(th))}[motion], dtype=np.float64)
+        R = np.eye(3, dtype=np.float64)
+        if not math.isinf(focus):
+            f = np.array((0.0, 0.0, focus)) - e
+            f /= np.linalg.norm(f)
+            r = np.cross((0.0, 1.0, 0.0), f)
+            r /= np.linalg.norm(r)
+            R = np.stack([r, np.cross(f, r), f])
+        out[k, :, :3], out[k, :, 3] = R, -(R @ e)
+    return out.reshape(count, 12).astype(F32)
+
+
+def _view_vertices(d, intrinsics, pose, depth_range):
+    """-> valid, seen bool [h, w]; ux, uy int64 [h, w] (1/16 pixel, 0 where not seen); iz float32 [h, w]: the specification's
+    "camera", "pose", "project" and "fixed" steps"""
+    fx, fy, cx, cy = (F32(v) for v in intrinsics)
+    M = [F32(v) for v in np.asarray(pose, dtype=F32).reshape(12)]
+    valid = _valid_depth(d, depth_range)
+    X, Y, Z = backproject_host(d, intrinsics)
+    with np.errstate(all="ignore"):
+        Xc, Yc, Zc = (((M[4 * r] * X + M[4 * r + 1] * Y) + M[4 * r + 2] * Z) + M[4 * r + 3] for r in range(3))
+        iz = (F32(1) / Zc).astype(F32)
+        fu, fv = fx * (Xc / Zc) + cx, fy * (Yc / Zc) + cy
+        seen = valid & np.isfinite(Zc) & (Zc > 0) & np.isfinite(iz) & (np.abs(fu) < F32(65536)) & (np.abs(fv) < F32(65536))
+        ux = np.rint(np.where(seen, fu, F32(0)) * F32(16)).astype(np.int64)
+        uy = np.rint(np.where(seen, fv, F32(0)) * F32(16)).astype(np.int64)
+    return valid, seen, ux, uy, iz
+
+
+def _view_keys(q, source):
+    """the depth-test key: ((0xFFFFFFFF - bits(q)) << 32) | source (the smallest key wins: the largest q, then the smallest source)"""
+    bits = np.ascontiguousarray(q, dtype=F32).view(np.uint32).astype(np.uint64)
+    return ((np.uint64(0xFFFFFFFF) - bits) << np.uint64(32)) | source.astype(np.uint64)
+
+
+def view_source_host(depth, intrinsics, pose=IDENTITY_POSE, depth_range=(0.0, math.inf), edge_thr=0.05, max_face=VIEW_MAX_FACE):
+    """The specification of ``ops.view_source`` for one frame and one pose -> (src, filled int32 [h, w], iz float32 [h, w]): the
+    source pixel (y * w + x) every pixel of the view shows, -1 for a hole; the same with the holes of every row filled from the
+    farther side (the stereo view's rule, on the winners' 1 / Zc); and the winners' interpolated 1 / Zc, 0 for a hole.  ``pose``: 12
+    floats, the row-major [R | t] of ``view_poses``.  Every seen vertex is a candidate for the pixel it falls into; every face of
+    the map's mesh whose three vertices are seen, whose box spans at most ``max_face`` pixel centres each way and whose area is not
+    zero is a candidate for the centres it covers, edges included, front or back.  A pixel keeps the candidate of the largest
+    1 / Zc, between equal ones the smallest source index.  include/prv2.h has every operation in order."""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    h, w = d.shape
+    valid, seen, ux, uy, iz = _view_vertices(d, intrinsics, pose, depth_range)
+    keys = np.full((h * w,), np.uint64(0xFFFFFFFFFFFFFFFF), dtype=np.uint64)
+    index = np.arange(h * w, dtype=np.int64).reshape(h, w)
+    # points
+    px, py = ux >> 4, uy >> 4
+    on = seen & (px >= 0) & (px < w) & (py >= 0) & (py < h)
+    np.minimum.at(keys, (py * w + px)[on], _view_keys(iz[on], index[on]))
+    # faces
+    if h >= 2 and w >= 2:
+        corner = dict(a=(slice(None, -1), slice(None, -1)), b=(slice(None, -1), slice(1, None)), c=(slice(1, None), slice(None, -1)),
+                      d=(slice(1, None), slice(1, None)))
+        zc = {n: d[c] for n, c in corner.items()}
+        kept = {n: valid[c] for n, c in corner.items()}
+        thr = F32(edge_thr)
+
+        def joined(p, q):
+            if not thr > 0:
+                return kept[p] & kept[q]
+            with np.errstate(all="ignore"):
+                return kept[p] & kept[q] & ~(np.abs(zc[p] - zc[q]) > thr * np.minimum(zc[p], zc[q]))
+
+        def ok(tri):
+            p, q, r = tri
+            return joined(p, q) & joined(q, r) & joined(p, r) & seen[corner[p]] & seen[corner[q]] & seen[corner[r]]
+
+        with np.errstate(all="ignore"):
+            four = kept["a"] & kept["b"] & kept["c"] & kept["d"]
+            ad = np.where(four, np.abs(zc["a"] - zc["d"]) <= np.abs(zc["b"] - zc["c"]), kept["a"] & kept["d"])
+        per_vertex = []  # [3] of (x, y, iz, index) over the faces that exist, the two candidates of every cell
+        emit = np.stack([np.where(ad, ok(t_ad), ok(t_bc)) for t_ad, t_bc in (("acd", "acb"), ("adb", "bcd"))])
+        for k in range(3):
+            per_vertex.append([np.stack([np.where(ad, a[corner[t_ad[k]]], a[corner[t_bc[k]]]) for t_ad, t_bc in (("acd", "acb"), ("adb", "bcd"))])[emit]
+                               for a in (ux, uy, iz, index)])
+        (x0, y0, i0, s0), (x1, y1, i1, s1), (x2, y2, i2, s2) = per_vertex
+        A = (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0)
+        bx0, bx1 = (np.minimum(np.minimum(x0, x1), x2) + 7) >> 4, (np.maximum(np.maximum(x0, x1), x2) - 8) >> 4
+        by0, by1 = (np.minimum(np.minimum(y0, y1), y2) + 7) >> 4, (np.maximum(np.maximum(y0, y1), y2) - 8) >> 4
+        use = (A != 0) & (bx1 - bx0 + 1 <= int(max_face)) & (by1 - by0 + 1 <= int(max_face))
+        bx0, bx1, by0, by1 = np.maximum(bx0, 0), np.minimum(bx1, w - 1), np.maximum(by0, 0), np.minimum(by1, h - 1)
+        use &= (bx0 <= bx1) & (by0 <= by1)
+        x0, y0, i0, s0, x1, y1, i1, s1, x2, y2, i2, s2, A, bx0, bx1, by0, by1 = (
+            v[use] for v in (x0, y0, i0, s0, x1, y1, i1, s1, x2, y2, i2, s2, A, bx0, bx1, by0, by1))
+        if A.size:
+            s, area = np.sign(A), np.abs(A).astype(F32)
+            for dy in range(int((by1 - by0).max()) + 1):
+                for dx in range(int((bx1 - bx0).max()) + 1):
+                    px, py = bx0 + dx, by0 + dy
+                    cx16, cy16 = 16 * px + 8, 16 * py + 8
+                    w0 = s * ((x2 - x1) * (cy16 - y1) - (y2 - y1) * (cx16 - x1))
+                    w1 = s * ((x0 - x2) * (cy16 - y2) - (y0 - y2) * (cx16 - x2))
+                    w2 = s * ((x1 - x0) * (cy16 - y0) - (y1 - y0) * (cx16 - x0))
+                    on = (px <= bx1) & (py <= by1) & (w0 >= 0) & (w1 >= 0) & (w2 >= 0)
+                    if not on.any():
+                        continue
+                    f0, f1, f2 = w0[on].astype(F32), w1[on].astype(F32), w2[on].astype(F32)
+                    q = ((f0 * i0[on] + f1 * i1[on]) + f2 * i2[on]) / area[on]
+                    source = np.where((w0[on] >= w1[on]) & (w0[on] >= w2[on]), s0[on], np.where(w1[on] >= w2[on], s1[on], s2[on]))
+                    np.minimum.at(keys, (py * w + px)[on], _view_keys(q, source))
+    keys = keys.reshape(h, w)
+    shown = keys != np.uint64(0xFFFFFFFFFFFFFFFF)
+    src = np.where(shown, (keys & np.uint64(0xFFFFFFFF)).astype(np.int64), -1)
+    inv = (keys >> np.uint64(32)).astype(np.int64)  # 0xFFFFFFFF - bits(q): the larger, the farther
+    q_out = np.where(shown, (np.uint64(0xFFFFFFFF) - (keys >> np.uint64(32))).astype(np.uint32).view(F32), F32(0)).astype(F32)
+    # the fill: nearest shown column on either side of the view's row
+    cols = np.arange(w, dtype=np.int64)[None, :]
+    left = np.maximum.accumulate(np.where(shown, cols, -1), axis=1)
+    right = np.minimum.accumulate(np.where(shown, cols, w)[:, ::-1], axis=1)[:, ::-1]
+    has_l, has_r = left >= 0, right < w
+    rows = np.arange(h)[:, None]
+    l, r = np.maximum(left, 0), np.minimum(right, w - 1)
+    take_r = has_r & (~has_l | (inv[rows, r] > inv[rows, l]))
+    filled = np.where(shown, src, np.where(take_r, src[rows, r], np.where(has_l, src[rows, l], -1)))
+    return src.astype(np.int32), filled.astype(np.int32), q_out
+
+
+def view_image_host(depth, image, intrinsics, pose=IDENTITY_POSE, depth_range=(0.0, math.inf), edge_thr=0.05, max_face=VIEW_MAX_FACE) -> np.ndarray:
+    """The specification of ``ops.view_rows`` for one frame and one pose -> uint8 [h, w, 3]: every pixel of the view shows the image
+    (image [3, hi, wi], any size, the cloud's nearest sample and byte rule) at its ``filled`` source pixel of ``view_source_host``,
+    (0, 0, 0) where that is -1"""
+    _, filled, _ = view_source_host(depth, intrinsics, pose, depth_range, edge_thr, max_face)
+    h, w = filled.shape
+    at = np.maximum(filled, 0).astype(np.int64)
+    view = _sampled_bytes(image, h, w, at // w, at % w)
+    view[filled < 0] = 0
+    return view
+
+
+def _view_options(views):
+    """the ``views`` dict of ``submit_geometry`` / ``write_geometry_host`` -> dict(count, motion, amplitude, focus), checked"""
+    unknown = set(views) - set(VIEW_DEFAULTS)
+    if unknown:
+        raise ValueError(f"views: unknown keys {sorted(unknown)} ({', '.join(VIEW_DEFAULTS)})")
+    opt = {**VIEW_DEFAULTS, **views}
+    opt = dict(count=int(opt["count"]), motion=opt["motion"], amplitude=float(opt["amplitude"]), focus=float(opt["focus"]))
+    view_poses(**opt)  # (the checks)
+    return opt
+
+
 def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True,
-                        mesh=False, stereo=None, bokeh=None):
+                        mesh=False, stereo=None, bokeh=None, views=None):
     """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png, <base>_mesh.ply, (``stereo``: a dict of
-    baseline, convergence, layout) <base>_right.png / _sbs.png / _anaglyph.png and (``bokeh``: a dict of aperture, focus, focus_point,
-    max_radius) <base>_bokeh.png from the host specification"""
+    baseline, convergence, layout) <base>_right.png / _sbs.png / _anaglyph.png, (``bokeh``: a dict of aperture, focus, focus_point,
+    max_radius) <base>_bokeh.png and (``views``: a dict of count, motion, amplitude, focus) <base>_view_000.png ... from the host
+    specification"""
     if ply or mesh:
         v = pointcloud_host(depth, image, intrinsics, depth_range, edge_thr, stride)
     if ply:
@@ -641,6 +825,9 @@ def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, m
         _warn_bokeh_focus(base, focus)
         with np.errstate(all="ignore"):
             write_png8(base + "_bokeh.png", np.ascontiguousarray(np.moveaxis(color_bytes(out * F32(255)), 0, -1)))
+    if views is not None:
+        for k, pose in enumerate(view_poses(**_view_options(views))):
+            write_png8(f"{base}_view_{k:03d}.png", view_image_host(depth, image, intrinsics, pose, depth_range, edge_thr))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -934,7 +1121,7 @@ class OutputStage:
 
     @torch.no_grad()
     def submit_geometry(self, base: str, result: torch.Tensor, image_hr, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1,
-                        ply=True, normals=True, mesh=False, stereo=None, bokeh=None):
+                        ply=True, normals=True, mesh=False, stereo=None, bokeh=None, views=None):
         """the geometry of one frame, from the device map: <base>.ply (``ply``: the point cloud of ``pointcloud_host``, coloured
         from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size), <base>_normal.png (``normals``: the map of
         ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``) and
@@ -946,7 +1133,10 @@ class OutputStage:
         <base>_anaglyph.png: the view of ``stereo_image_host`` coloured from ``image_hr``, through the PNG path as the normal map.
         ``bokeh`` (a dict of aperture, focus, focus_point, max_radius; default 0.025, None, (0.5, 0.5), 16) adds <base>_bokeh.png: the
         frame of ``bokeh_image_host`` through the same path; the focus distance is read on the device, and only its four bytes come
-        back, for the warning of a frame whose focus pixel holds no valid depth."""
+        back, for the warning of a frame whose focus pixel holds no valid depth.
+        ``views`` (a dict of count, motion, amplitude, focus; default 8, 'circle', 0.05, inf) adds <base>_view_000.png ...: the frames
+        of ``view_image_host`` along the camera path of ``view_poses``, rendered ``VIEW_CHUNK`` views per launch, each chunk in a
+        staging slot of its own, so the depth-test keys (8 bytes per view pixel) and the pinned scanlines stay bounded."""
         from . import ops
         dev = result.device
         slot = self._begin(dev)
@@ -958,7 +1148,7 @@ class OutputStage:
             jobs = []
             if normals:
                 jobs.append((base + "_normal.png", w, h, 3, ops.normal_rows(d, intrinsics, depth_range)))
-            if ply or mesh or stereo is not None or bokeh is not None:
+            if ply or mesh or stereo is not None or bokeh is not None or views is not None:
                 img = torch.as_tensor(image_hr)
                 if img.dim() == 4 and img.shape[0] == 1:
                     img = img[0]
@@ -980,6 +1170,11 @@ class OutputStage:
                 slot["futures"].append(self.pool.submit(self._check_focus, base, slot["focus"], ev))
             if jobs:
                 self._stage(slot, jobs)
+            if views is not None:
+                poses = view_poses(**_view_options(views))
+                for k0 in range(0, len(poses), VIEW_CHUNK):
+                    rows = ops.view_rows(d, img, intrinsics, poses[k0:k0 + VIEW_CHUNK], depth_range, edge_thr)
+                    self._stage(self._begin(dev), [(f"{base}_view_{k0 + k:03d}.png", w, h, 3, rows[:, k]) for k in range(rows.shape[1])])
             if ply or mesh:
                 if mesh:
                     verts, counts, faces, n_faces = ops.mesh_pack(d, img, intrinsics, depth_range, edge_thr, stride)

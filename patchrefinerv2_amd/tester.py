@@ -10,7 +10,9 @@ stream differs from zlib's).
 binary point cloud of the result map, coloured from the image) and <name>_normal.png (its surface normals);
 ``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles) and
 ``runner_info.save_stereo`` (--save-stereo) <name>_right.png / _sbs.png / _anaglyph.png (the right-eye view),
-``runner_info.save_bokeh`` (--save-bokeh) <name>_bokeh.png (the frame with a synthetic depth of field) -- from the device map
+``runner_info.save_bokeh`` (--save-bokeh) <name>_bokeh.png (the frame with a synthetic depth of field),
+``runner_info.save_views`` = N (--save-views N; 0: off) <name>_view_000.png ... (the frame seen from N poses of a closed camera path:
+``view_motion``, ``view_amplitude``, ``view_focus``) -- from the device map
 with the output stage, from output.py's host specification otherwise; the same files either way.
 ``runner_info.temporal_stabilize`` (--temporal-stabilize; ``temporal_alpha`` / ``_tau`` / ``_rho`` / ``_anchor``) treats the dataset as
 one video: every result map goes through temporal.TemporalStabilizer before it is saved, exported or scored.
@@ -210,10 +212,12 @@ class Tester:
         (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``; with ``save_stereo`` the
         ``stereo`` dict of ``stereo_baseline`` (default 0.065), ``stereo_convergence`` (inf) and ``stereo_layout`` ('right'); with
         ``save_bokeh`` the ``bokeh`` dict of ``bokeh_aperture`` (0.025), ``bokeh_focus`` (None: the depth under ``bokeh_focus_point``,
-        default (0.5, 0.5)) and ``bokeh_max_radius`` (16)"""
+        default (0.5, 0.5)) and ``bokeh_max_radius`` (16); with ``save_views`` = N > 0 the ``views`` dict of N, ``view_motion`` ('circle'),
+        ``view_amplitude`` (0.05) and ``view_focus`` (inf)"""
         info = self.runner_info
         ply, normals, mesh, stereo, bokeh = (bool(getattr(info, k, False)) for k in ("save_ply", "save_normals", "save_mesh", "save_stereo", "save_bokeh"))
-        if not (info.save and (ply or normals or mesh or stereo or bokeh)):
+        views = int(getattr(info, "save_views", 0) or 0)
+        if not (info.save and (ply or normals or mesh or stereo or bokeh or views)):
             return None
         from .output import camera_intrinsics
         k = camera_intrinsics(image_raw_shape, result.shape[-2:], getattr(info, "intrinsics", None), getattr(info, "fov", None) or 60.0)
@@ -224,7 +228,9 @@ class Tester:
                                         layout=getattr(info, "stereo_layout", "right"))) if stereo else {}),
                     **(dict(bokeh=dict(aperture=float(getattr(info, "bokeh_aperture", 0.025)), focus=getattr(info, "bokeh_focus", None),
                                        focus_point=tuple(getattr(info, "bokeh_focus_point", None) or (0.5, 0.5)),
-                                       max_radius=float(getattr(info, "bokeh_max_radius", 16.0)))) if bokeh else {}))
+                                       max_radius=float(getattr(info, "bokeh_max_radius", 16.0)))) if bokeh else {}),
+                    **(dict(views=dict(count=views, motion=getattr(info, "view_motion", "circle"), amplitude=float(getattr(info, "view_amplitude", 0.05)),
+                                       focus=float(getattr(info, "view_focus", float("inf"))))) if views else {}))
 
     def _entry(self, item, result, score=None, **extra):
         """one frame's result entry.  ``mean``: a host map's fp32 mean, a device map's float64 sum on the device (equal within that

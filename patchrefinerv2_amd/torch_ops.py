@@ -63,6 +63,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "temporal_step_",
        # depth-of-field export: frames re-rendered through a thin lens, as fp32 planes or as scanlines (each with the focus used)
        "bokeh_render", "bokeh_rows",
+       # novel-view export: frames seen from a list of camera poses, as source maps or as scanlines
+       "view_source", "view_rows",
        # the gate kernels with the coarse-tap gather inside (tables instead of ``pre``)
        "conv3x3_ln_gate_taps", "conv3x3_ln_gate_f6_taps")
 _loaded = False

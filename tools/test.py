@@ -16,6 +16,8 @@ and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`
 ``--save-mesh``: with ``--save``, <name>_mesh.ply: the same vertices plus a face element, triangles along the pixel grid (same camera and --ply-* options).
 ``--save-bokeh``: with ``--save``, <name>_bokeh.png: the frame with a synthetic depth of field (``--bokeh-aperture M``, ``--bokeh-focus Z`` or
 ``--bokeh-focus-point U V``, ``--bokeh-max-radius PX``; same camera and --ply-depth-range).
+``--save-views N``: with ``--save``, <name>_view_000.png ... <name>_view_{N-1:03d}.png: the frame seen from N poses of a closed camera path
+(``--view-motion circle|sway|dolly``, ``--view-amplitude M``, ``--view-focus Z``; same camera, --ply-edge-thr and --ply-depth-range).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
 ``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
@@ -196,6 +198,16 @@ def main():
     ap.add_argument("--bokeh-focus-point", nargs=2, type=float, default=[0.5, 0.5], metavar=("U", "V"),
                     help="--save-bokeh without --bokeh-focus: focus on the depth at this point of the frame, (0, 0) top left, (1, 1) bottom right")
     ap.add_argument("--bokeh-max-radius", type=float, default=16.0, metavar="PX", help="--save-bokeh: the cap of the circle of confusion in pixels (at most 32)")
+    ap.add_argument("--save-views", type=int, default=0, metavar="N",
+                    help="with --save: <name>_view_000.png ... <name>_view_{N-1:03d}.png, the frame seen from N (1 to 120) poses of a closed "
+                         "camera path: the result map's own mesh rasterised with a depth test, disocclusions filled from the farther side "
+                         "(camera of --intrinsics / --fov, validity of --ply-depth-range, surfaces split by --ply-edge-thr); made on the GPU "
+                         "with --device-output, by the host specification otherwise (the specification, not a route for 4K frames: minutes each)")
+    ap.add_argument("--view-motion", default="circle", choices=["circle", "sway", "dolly"],
+                    help="--save-views: the eye's path: circle = around the optical axis, sway = left and right, dolly = forward and back")
+    ap.add_argument("--view-amplitude", type=float, default=0.05, metavar="M", help="--save-views: how far the eye moves, in metres")
+    ap.add_argument("--view-focus", type=float, default=float("inf"), metavar="Z",
+                    help="--save-views: the depth of the point on the optical axis the camera keeps looking at; inf: it only translates")
     ap.add_argument("--temporal-stabilize", action="store_true",
                     help="treat the frames as one video, in dataset order: every result map is aligned to the previous output by a gated "
                          "least-squares scale and shift and blended with it where the image has not changed (patchrefinerv2_amd/temporal.py; "
@@ -219,8 +231,15 @@ def main():
     args = ap.parse_args()
     if args.device_deflate and not args.device_output:
         ap.error("--device-deflate needs --device-output (it deflates the device route's scanlines)")
-    if (args.save_ply or args.save_normals or args.save_mesh or args.save_stereo or args.save_bokeh) and not args.save:
-        ap.error("--save-ply / --save-normals / --save-mesh / --save-stereo / --save-bokeh need --save (they add files to the frames it writes)")
+    if (args.save_ply or args.save_normals or args.save_mesh or args.save_stereo or args.save_bokeh or args.save_views) and not args.save:
+        ap.error("--save-ply / --save-normals / --save-mesh / --save-stereo / --save-bokeh / --save-views need --save (they add files to the "
+                 "frames it writes)")
+    if not 0 <= args.save_views <= 120:
+        ap.error(f"--save-views {args.save_views}: 1 to 120 views")
+    if not 0.0 <= args.view_amplitude < float("inf"):
+        ap.error(f"--view-amplitude {args.view_amplitude}: finite and not below 0")
+    if not args.view_focus > 0.0:
+        ap.error(f"--view-focus {args.view_focus}: a depth greater than 0 (inf: the camera only translates)")
     if args.bokeh_focus is not None and not (0 < args.bokeh_focus < float("inf")):
         ap.error(f"--bokeh-focus {args.bokeh_focus}: a finite distance greater than 0")
     if not all(0.0 <= c <= 1.0 for c in args.bokeh_focus_point):
@@ -284,6 +303,7 @@ def main():
                         stereo_baseline=args.stereo_baseline, stereo_convergence=args.stereo_convergence, stereo_layout=args.stereo_layout,
                         save_bokeh=args.save_bokeh, bokeh_aperture=args.bokeh_aperture, bokeh_focus=args.bokeh_focus,
                         bokeh_focus_point=tuple(args.bokeh_focus_point), bokeh_max_radius=args.bokeh_max_radius,
+                        save_views=args.save_views, view_motion=args.view_motion, view_amplitude=args.view_amplitude, view_focus=args.view_focus,
                         intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
                         ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range),
                         temporal_stabilize=args.temporal_stabilize, temporal_alpha=args.temporal_alpha, temporal_tau=args.temporal_tau,
