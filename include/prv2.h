@@ -915,6 +915,46 @@ int prv2_ssi_metrics(const float* gt, const float* pred, int32_t n, int32_t h, i
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Boundary F1 evaluation (csrc/boundary_eval.hip): the scale-invariant boundary F1 of Depth Pro (Bochkovskii et al., 2024) of n
+ * frames.  Not in the reference; metrics.compute_boundary_f1 is the numpy statement of the definition.  Additive: the ABI version
+ * does not change.
+ *   mask         a pixel is valid when it lies inside the crop and gt > min_depth && gt < max_depth (fp32 comparisons, a NaN ground
+ *                truth is not valid: the test of prv2_ssi_metrics)
+ *   prediction   cleaned at a valid pixel as compute_metrics cleans it (NaN -> min_depth, clamp to [min_depth, max_depth]); never read
+ *                at an invalid pixel
+ *   pairs        a horizontal pair is (x, y), (x + 1, y), a vertical pair (x, y), (x, y + 1); a pair counts only if BOTH pixels are
+ *                valid; n_h and n_v are the numbers of such pairs
+ *   boundary     for a depth map, a pair (a, b) (a = the left or top value, b = the right or bottom value) and a threshold t, fp32
+ *                compare-after-multiply with no division (the product rounded to fp32, not contracted):
+ *                horizontal  L: a > t * b (left is farther), R: b > t * a;  vertical  T: a > t * b (top is farther), B: b > t * a
+ *                (Depth Pro applies the ratio test to inverse depth, which swaps L <-> R and T <-> B in prediction and ground truth alike:
+ *                the same counts up to the rounding of the division)
+ *   counts       per threshold i and direction d in the order (L, T, R, B), over the valid pairs: tp = pairs flagged in prediction AND
+ *                ground truth, np = flagged in the prediction, ng = flagged in the ground truth
+ * The scores (P_i = 1/4 sum_d tp / max(np, 1), R_i likewise with ng, F_i = 2 P_i R_i / (P_i + R_i), weights t_i / sum t) are formed on
+ * the host: metrics.boundary_from_values.
+ * ------------------------------------------------------------------------------------------ */
+
+#define PRV2_BOUNDARY_MAX_THRESHOLDS 16
+/* float64 values per frame prv2_boundary_f1 writes for T thresholds */
+#define PRV2_BOUNDARY_VALUES(T) (2 + 12 * (T))
+
+/* bytes of workspace prv2_boundary_f1 needs for n frames of h x w (-1 for a bad shape or frame count); proportional to n */
+int64_t prv2_boundary_f1_workspace_bytes(int32_t n, int32_t h, int32_t w);
+
+/* gt: fp32 [n, h, w]; pred: fp32 [n, ph, pw].  ph == h and pw == w: the prediction is loaded; otherwise it is sampled at the valid
+ * pixels as prv2_depth_metrics_lowres samples it (bilinear, align_corners=False).  The crop is rows [y0, y1) x columns [x0, x1).
+ * thresholds: HOST array of n_thresholds (1 .. PRV2_BOUNDARY_MAX_THRESHOLDS) finite fp32 ratios > 1, in any order (they travel in the
+ * kernel's arguments).  out: DEVICE float64 [n, PRV2_BOUNDARY_VALUES(T)], integers below 2^53 (exact):
+ *    0, 1                     n_h, n_v
+ *    2 + (4 i + d) * 3 + k    threshold i, direction d in (L, T, R, B), k in (tp, np, ng)
+ * One pass over the maps writes per-block rows of 64-bit integers into the workspace, a second kernel adds them in block order: no
+ * global atomics, the same bits on every call, and for a frame alone or among others. */
+int prv2_boundary_f1(const float* gt, const float* pred, int32_t n, int32_t h, int32_t w, int32_t ph, int32_t pw, float min_depth,
+                     float max_depth, int32_t y0, int32_t y1, int32_t x0, int32_t x1, const float* thresholds, int32_t n_thresholds, double* out,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Sparsification (csrc/sparsify.hip): does a per-pixel uncertainty mark the pixels where the depth is wrong?  The sparsification
  * curves behind AUSE / AURG (Ilg et al. 2018; Poggi et al. 2020) of n frames.  Not in the reference (its tester only writes the
  * uncertainty, estimator/tester/tester.py:132-181); the definition below is this project's, chosen so that ties need no tie-break,

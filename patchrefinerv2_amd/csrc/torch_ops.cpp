@@ -1354,6 +1354,27 @@ Tensor ssi_metrics(const Tensor& gt, const Tensor& pred, double min_depth, doubl
      "ssi_metrics");
   return out;
 }
+// boundary F1 evaluation (include/prv2.h "Boundary F1 evaluation"): pred [n, h, w], or [n, ph, pw] sampled inside the kernel
+Tensor boundary_f1(const Tensor& gt, const Tensor& pred, double min_depth, double max_depth, int64_t y0, int64_t y1, int64_t x0, int64_t x1,
+                   at::ArrayRef<double> thresholds) {
+  dev_frames(gt, "gt", at::kFloat);
+  dev_frames(pred, "pred", at::kFloat);
+  TORCH_CHECK(pred.size(0) == gt.size(0) && pred.device() == gt.device(), "prv2::boundary_f1: pred must hold gt's ", gt.size(0),
+              " frames on its device");
+  TORCH_CHECK(!thresholds.empty() && thresholds.size() <= PRV2_BOUNDARY_MAX_THRESHOLDS, "prv2::boundary_f1: ", thresholds.size(),
+              " thresholds, not in [1, ", PRV2_BOUNDARY_MAX_THRESHOLDS, "]");
+  const int64_t bytes = prv2_boundary_f1_workspace_bytes((int)gt.size(0), (int)gt.size(1), (int)gt.size(2));
+  TORCH_CHECK(bytes > 0, "prv2::boundary_f1: bad frame shape ", gt.sizes());
+  std::vector<float> t(thresholds.begin(), thresholds.end());
+  Tensor ws = at::empty({bytes}, gt.options().dtype(at::kByte));
+  Tensor out = at::empty({gt.size(0), (int64_t)PRV2_BOUNDARY_VALUES(t.size())}, gt.options().dtype(at::kDouble));
+  Launch L(gt);
+  ok(prv2_boundary_f1(gt.data_ptr<float>(), pred.data_ptr<float>(), (int)gt.size(0), (int)gt.size(1), (int)gt.size(2), (int)pred.size(1),
+                      (int)pred.size(2), (float)min_depth, (float)max_depth, (int)y0, (int)y1, (int)x0, (int)x1, t.data(), (int)t.size(),
+                      out.data_ptr<double>(), ws.data_ptr(), ws.numel(), L.stream),
+     "boundary_f1");
+  return out;
+}
 // sparsification curves of a per-pixel uncertainty (include/prv2.h "Sparsification"): thresholds, bucket sums, suffix sums
 Tensor sparsify(const Tensor& gt, const Tensor& pred, const Tensor& uncert, const optional<Tensor>& count, double min_count, double min_depth,
                 double max_depth, int64_t levels) {
@@ -1743,6 +1764,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("depth_metrics_lowres(Tensor gt, Tensor pred, Tensor? boundary, Tensor? region, float min_depth, float max_depth, int y0, int y1, "
         "int x0, int x1) -> Tensor");
   m.def("ssi_metrics(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1) -> Tensor");
+  m.def("boundary_f1(Tensor gt, Tensor pred, float min_depth, float max_depth, int y0, int y1, int x0, int x1, float[] thresholds) -> Tensor");
   m.def("sparsify(Tensor gt, Tensor pred, Tensor uncert, Tensor? count, float min_count, float min_depth, float max_depth, int levels) -> Tensor");
   // geometry export: PLY vertex records (written into ``vertices``; returns the per-frame counts) and surface-normal scanlines
   m.def("pointcloud_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices) -> Tensor");
@@ -1847,6 +1869,7 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("cityscapes_masks", &cityscapes_masks);
   m.impl("depth16_gt", &depth16_gt);
   m.impl("ssi_metrics", &ssi_metrics);
+  m.impl("boundary_f1", &boundary_f1);
   m.impl("sparsify", &sparsify);
   m.impl("pointcloud_pack", &pointcloud_pack);
   m.impl("normal_rows", &normal_rows);

@@ -15,6 +15,8 @@ ScanNetDataset      estimator/datasets/scannet_dataset.py:25-404 (split file -> 
                     ground-truth depth edges)
 ``ssi_metrics=True`` (tools/test.py --ssi-metrics) on any of the datasets: get_metrics adds the scale-and-shift-invariant scores
                     of estimator/models/losses.py:523-544, :600-700 (metrics.SSI_KEYS; two fused GPU passes, csrc/ssi_eval.hip)
+``boundary_f1=True`` (tools/test.py --boundary-f1) on any of the datasets: get_metrics adds the scale-invariant boundary F1 of Depth Pro
+                    (metrics.BOUNDARY_KEYS; one fused GPU pass, csrc/boundary_eval.hip) after every other key
 read_image          estimator/datasets/general_dataset.py:22-62 (RGB/255 -> bicubic, align_corners=True)
 _ReadAhead / _StagedDataset  the two staging slots and the one background reader that the datasets share
 Not built: the ``gta`` ground truth (general_dataset.py:96-101: .exr files need imageio, which is absent).  CityScapesDataset, KittiDataset
@@ -132,10 +134,11 @@ def _read_exact(path, view, offset=0):
 
 
 class _StagedDataset:
-    """What the datasets share: the read-ahead's life cycle and the two ends of ``get_metrics`` (``_common``, ``_with_ssi``).
+    """What the datasets share: the read-ahead's life cycle and the two ends of ``get_metrics`` (``_common``, ``_with_extras``).
     A subclass gives ``_make_slot()``, ``_read(idx, slot)`` and, if it needs one, ``_prepare(idx, slot)`` (_ReadAhead's three
     callbacks); its ``__getitem__`` queues its own copies out of the slot between ``_acquire`` and ``_release``."""
     ssi_metrics = False  # (the constructor's flag; an instance made without it scores as before)
+    boundary_f1 = False  # (likewise)
     _ahead = None        # the staging slots and their reader, made by the first item
     _prepare = None
     _reader_name = "read-ahead"
@@ -162,11 +165,23 @@ class _StagedDataset:
         """compute_metrics' arguments that no dataset varies (``extra``: fuse_resize)"""
         return dict(min_depth_eval=self.min_depth, max_depth_eval=self.max_depth, garg_crop=False, eigen_crop=False, dataset=dataset, **extra)
 
-    def _with_ssi(self, out, ssi, depth_gt, result, common):
-        """``out``, and with ``ssi_metrics`` (losses.py:523-544, :600-700) ``ssi``'s scores of the plain pixel set after its keys"""
+    def _with_extras(self, out, ssi, depth_gt, result, common):
+        """``out``, and after its keys the opt-in scores of the plain pixel set: with ``ssi_metrics`` (losses.py:523-544, :600-700)
+        ``ssi``'s scores, then with ``boundary_f1`` the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS) -- by the fused route
+        wherever ``ssi`` is the fused one (with its ``fuse_resize``), by the host specification otherwise"""
         if self.ssi_metrics:
             out.update(ssi(depth_gt, result, **common))
+        if self.boundary_f1:
+            from functools import partial
+            from . import metrics as M
+            fused = partial(M.compute_boundary_f1_fused, **getattr(ssi, "keywords", {}))  # (ImageDataset hands a partial with fuse_resize)
+            out.update((M.compute_boundary_f1 if ssi is M.compute_ssi_metrics else fused)(depth_gt, result, **common))
         return out
+
+    def boundary_args(self):
+        """compute_metrics' arguments the dataset's boundary F1 is scored with (KittiDataset: inside its Garg crop) -- what the tester
+        scores the coarse prediction with, next to the result's"""
+        return self._common(getattr(self, "dataset_name", ""))
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -272,7 +287,7 @@ class ImageDataset(_StagedDataset):
 
     def __init__(self, rgb_image_dir, mode="", min_depth=1e-3, max_depth=80, gt_dir=None, image_resolution=(2160, 3840),
                  dataset_name="", network_process_size=(384, 512), resize_mode="zoe", edge_metrics=False, gt_format=None, image_format=None,
-                 gt_shape=(4032, 6048), ssi_metrics=False):
+                 gt_shape=(4032, 6048), ssi_metrics=False, boundary_f1=False):
         if gt_format == "gta":
             raise NotImplementedError("ImageDataset(gt_format='gta'): the .exr ground truth (general_dataset.py:96-101) needs imageio, "
                                       "which is not installed")
@@ -285,6 +300,7 @@ class ImageDataset(_StagedDataset):
         self.edge_metrics = bool(edge_metrics)
         # ssi_metrics: get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS) over the plain pixel set
         self.ssi_metrics = bool(ssi_metrics)
+        self.boundary_f1 = bool(boundary_f1)  # get_metrics adds the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS), plain set only
         self.files = sorted(os.listdir(rgb_image_dir))
         # ground truth: metric depth as <gt_dir>/<basename>.npy, or (gt_format) the reference's per-dataset files
         self.gt_dir = gt_dir
@@ -427,7 +443,7 @@ class ImageDataset(_StagedDataset):
             out.update(self._edge_metrics(depth_gt, result, dev, score, with_edges))
         # the ssi scores on the device whenever the maps are there, else the host restatement
         ssi = partial(M.compute_ssi_metrics_fused, fuse_resize=True) if self.gt_format is not None or dev else M.compute_ssi_metrics
-        return self._with_ssi(out, ssi, depth_gt, result, common)
+        return self._with_extras(out, ssi, depth_gt, result, common)
 
     def _edge_metrics(self, depth_gt, result, dev, score, common):
         """boundary metrics of the prediction (bilinearly resized to the GT's shape) against the GT's log-depth Canny edges at the
@@ -467,7 +483,7 @@ class UnrealStereo4kDataset(_StagedDataset):
     _reader_name = "u4k-read"
 
     def __init__(self, mode, data_root, split, transform_cfg, min_depth, max_depth, consistency=False, overlap=0, patch_raw_shape=(540, 960),
-                 resize_mode="zoe", pre_norm_bbox=True, image_raw_shape=(2160, 3840), ssi_metrics=False):
+                 resize_mode="zoe", pre_norm_bbox=True, image_raw_shape=(2160, 3840), ssi_metrics=False, boundary_f1=False):
         if mode == "train":
             raise NotImplementedError("UnrealStereo4kDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / "
                                       "random_crop, u4k_dataset.py:131-213) is not built; inference modes only")
@@ -483,6 +499,7 @@ class UnrealStereo4kDataset(_StagedDataset):
         self.resize_mode = resize_mode
         self.image_raw_shape = (int(image_raw_shape[0]), int(image_raw_shape[1]))
         self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS)
+        self.boundary_f1 = bool(boundary_f1)  # get_metrics adds the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS), plain set only
         self.data_infos = self.load_data_list()
 
     def load_data_list(self):
@@ -546,7 +563,7 @@ class UnrealStereo4kDataset(_StagedDataset):
         from .metrics import compute_metrics_fused, compute_ssi_metrics_fused
         common = self._common()
         out = compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, **common)
-        return self._with_ssi(out, compute_ssi_metrics_fused, depth_gt, result, common)
+        return self._with_extras(out, compute_ssi_metrics_fused, depth_gt, result, common)
 
 
 ETH_METRIC_KEYS = ("a1", "a2", "a3", "abs_rel", "rmse", "log_10", "rmse_log", "silog", "sq_rel", "see")  # compute_metrics' order
@@ -575,7 +592,7 @@ class ETHDataset(_StagedDataset):
     _reader_name = "eth-read"
 
     def __init__(self, mode, split, transform_cfg, min_depth, max_depth, stitcher_stage=0, overlap=0, crop_strategy="random",
-                 resize_mode="zoe", gt_shape=(4032, 6048), ssi_metrics=False):
+                 resize_mode="zoe", gt_shape=(4032, 6048), ssi_metrics=False, boundary_f1=False):
         if mode == "train":
             raise NotImplementedError("ETHDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip, "
                                       "eth_dataset.py:144-167) is not built; inference modes only")
@@ -590,6 +607,7 @@ class ETHDataset(_StagedDataset):
         self.stitcher_stage, self.overlap, self.crop_strategy = stitcher_stage, overlap, crop_strategy
         self.gt_shape = (int(gt_shape[0]), int(gt_shape[1]))
         self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS), plain set only
+        self.boundary_f1 = bool(boundary_f1)  # get_metrics adds the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS), plain set only
         shallow = transform_cfg.get("input_size_shallow", None)
         self.input_size_shallow = None if shallow is None else (int(shallow[0]), int(shallow[1]))
         self.data_infos = self.load_data_list()
@@ -665,7 +683,7 @@ class ETHDataset(_StagedDataset):
         region = ops.image_edge_region(image.reshape(3, *image.shape[-2:]), *depth_gt.shape[-2:])  # ([1, 3, h, w] in the reference)
         common = self._common(fuse_resize=True)
         out = eth_metric_order(compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, region=region, **common))
-        return self._with_ssi(out, compute_ssi_metrics_fused, depth_gt, result, common)  # (after the reference's thirty keys)
+        return self._with_extras(out, compute_ssi_metrics_fused, depth_gt, result, common)  # (after the reference's thirty keys)
 
     def evaluate(self, results, **kw):
         """eth_dataset.py:292-385 without the table: np.nanmean of every key over the frames' metric dicts (a frame whose edge or
@@ -714,7 +732,7 @@ class CityScapesDataset(_StagedDataset):
 
     def __init__(self, mode, split, transform_cfg, min_depth, max_depth, patch_raw_shape=(256, 512), data_root="./data/cityscapes",
                  resize_mode="zoe", with_pseudo_label=False, pseudo_label_path=None, with_seg_map=False, filter_sky=True, pre_norm_bbox=True,
-                 with_uncert=False, base=float(np.exp(1)), filter_thr=-0.1, ssi_metrics=False):
+                 with_uncert=False, base=float(np.exp(1)), filter_thr=-0.1, ssi_metrics=False, boundary_f1=False):
         if mode == "train":
             raise NotImplementedError("CityScapesDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / "
                                       "random_crop, cityscapes_dataset.py:178-298) is not built; inference modes only")
@@ -737,6 +755,7 @@ class CityScapesDataset(_StagedDataset):
         self.filter_sky, self.pre_norm_bbox, self.base, self.filter_thr = filter_sky, pre_norm_bbox, base, filter_thr
         self.patch_raw_shape = tuple(patch_raw_shape)
         self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS), plain set only
+        self.boundary_f1 = bool(boundary_f1)  # get_metrics adds the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS), plain set only
         self.data_infos = self.load_data_list()
 
     def load_data_list(self):
@@ -830,7 +849,7 @@ class CityScapesDataset(_StagedDataset):
             pred = F.interpolate(pred, (H, W), mode="bilinear", align_corners=False)
         valid = (gt > self.min_depth) & (gt < self.max_depth)
         out.update(M.compute_boundary_metrics_device(edge_mask, M.extract_edges_device(pred, "log"), valid))
-        return self._with_ssi(out, M.compute_ssi_metrics_fused, depth_gt, result, common)
+        return self._with_extras(out, M.compute_ssi_metrics_fused, depth_gt, result, common)
 
     def evaluate(self, results, **kw):
         """cityscapes_dataset.py:410-501 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""
@@ -872,7 +891,7 @@ class KittiDataset(_StagedDataset):
     _reader_name = "kitti-read"
 
     def __init__(self, mode, data_root, split, transform_cfg, min_depth, max_depth, patch_raw_shape=(176, 304), resize_mode="zoe",
-                 with_pseudo_label=False, pseudo_label_path=None, do_kb_crop=True, pre_norm_bbox=True, ssi_metrics=False):
+                 with_pseudo_label=False, pseudo_label_path=None, do_kb_crop=True, pre_norm_bbox=True, ssi_metrics=False, boundary_f1=False):
         if mode == "train":
             raise NotImplementedError("KittiDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip / random_crop, "
                                       "kitti_dataset.py:133-152, :168-200) is not built; inference modes only")
@@ -889,6 +908,7 @@ class KittiDataset(_StagedDataset):
         self.with_pseudo_label, self.pseudo_label_path = False, pseudo_label_path
         self.patch_raw_shape, self.pre_norm_bbox, self.do_kb_crop = tuple(patch_raw_shape), pre_norm_bbox, bool(do_kb_crop)
         self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS)
+        self.boundary_f1 = bool(boundary_f1)  # get_metrics adds the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS), plain set only
         self.data_infos = self.load_data_list()
 
     def load_data_list(self):
@@ -955,7 +975,10 @@ class KittiDataset(_StagedDataset):
         from .metrics import compute_metrics_fused, compute_ssi_metrics_fused
         common = dict(self._common("kitti", fuse_resize=True), garg_crop=True)
         out = compute_metrics_fused(depth_gt, result, disp_gt_edges=disp_gt_edges, **common)
-        return self._with_ssi(out, compute_ssi_metrics_fused, depth_gt, result, common)
+        return self._with_extras(out, compute_ssi_metrics_fused, depth_gt, result, common)
+
+    def boundary_args(self):
+        return dict(self._common("kitti"), garg_crop=True)
 
     def evaluate(self, results, **kw):
         """kitti_dataset.py:224-295 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""
@@ -977,7 +1000,7 @@ class ScanNetDataset(_StagedDataset):
     _reader_name = "scannet-read"
 
     def __init__(self, mode, split, transform_cfg, min_depth, max_depth, with_pseudo_label=False, pseudo_label_path=None,
-                 patch_raw_shape=(720, 960), resize_mode="zoe", pre_norm_bbox=True, ssi_metrics=False):
+                 patch_raw_shape=(720, 960), resize_mode="zoe", pre_norm_bbox=True, ssi_metrics=False, boundary_f1=False):
         if mode == "train":
             raise NotImplementedError("ScanNetDataset(mode='train'): the training pipeline (aug_rotate / aug_color / aug_flip, "
                                       "scannet_dataset.py:120-129, :139-146) is not built; inference modes only")
@@ -994,6 +1017,7 @@ class ScanNetDataset(_StagedDataset):
         self.with_pseudo_label, self.pseudo_label_path = False, pseudo_label_path
         self.patch_raw_shape, self.pre_norm_bbox = tuple(patch_raw_shape), pre_norm_bbox
         self.ssi_metrics = bool(ssi_metrics)  # get_metrics adds the scale-and-shift-invariant scores (metrics.SSI_KEYS), plain set only
+        self.boundary_f1 = bool(boundary_f1)  # get_metrics adds the scale-invariant boundary F1 (metrics.BOUNDARY_KEYS), plain set only
         self.data_infos = self.load_data_list()
 
     @staticmethod
@@ -1065,7 +1089,7 @@ class ScanNetDataset(_StagedDataset):
         region = M.edge_split_masks_device(gt, 7)  # ops.binary_dilate(extract_edges_device(gt, 'log'), 7)
         common = self._common(fuse_resize=True)
         out = eth_metric_order(M.compute_metrics_fused(gt[None, None], result, disp_gt_edges=disp_gt_edges, region=region, **common))
-        return self._with_ssi(out, M.compute_ssi_metrics_fused, depth_gt, result, common)  # (after the reference's thirty keys)
+        return self._with_extras(out, M.compute_ssi_metrics_fused, depth_gt, result, common)  # (after the reference's thirty keys)
 
     def evaluate(self, results, **kw):
         """scannet_dataset.py:246-339 without the table: np.nanmean of every key over the frames' metric dicts, as ETHDataset's"""

@@ -187,6 +187,9 @@ SIGNATURES = {
     # scale-and-shift-invariant evaluation (csrc/ssi_eval.hip): the fits, the four SSI scores and the error sums of the aligned prediction
     "prv2_ssi_metrics_workspace_bytes": (_L, [_I, _I, _I]),
     "prv2_ssi_metrics": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _P, _L, _P]),
+    # boundary F1 evaluation (csrc/boundary_eval.hip): the occluding-boundary counts of prediction and ground truth per ratio and direction
+    "prv2_boundary_f1_workspace_bytes": (_L, [_I, _I, _I]),
+    "prv2_boundary_f1": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _I, _I, _I, _P, _I, _P, _P, _L, _P]),
     # sparsification curves of a per-pixel uncertainty (csrc/sparsify.hip): thresholds by the radix select, bucket sums, suffix sums
     "prv2_sparsify_workspace_bytes": (_L, [_I, _I, _I, _I]),
     "prv2_sparsify": (_I, [_P, _P, _P, _P, _D, _I, _I, _I, _F, _F, _I, _P, _P, _L, _P]),
@@ -224,11 +227,17 @@ SIGNATURES = {
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
 TEMPORAL_STATS = 12  # PRV2_TEMPORAL_STATS: 8-byte words per frame of prv2_temporal_step's stats
 SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS
+BOUNDARY_MAX_THRESHOLDS = 16  # PRV2_BOUNDARY_MAX_THRESHOLDS
 
 
 def sparsify_values(levels: int) -> int:
     """PRV2_SPARSIFY_VALUES(L): float64 values per frame of prv2_sparsify"""
     return 1 + 10 * int(levels)
+
+
+def boundary_values(thresholds: int) -> int:
+    """PRV2_BOUNDARY_VALUES(T): float64 values per frame of prv2_boundary_f1"""
+    return 2 + 12 * int(thresholds)
 
 _lib = None
 

@@ -11,6 +11,9 @@ compute_scale_and_shift   estimator/models/losses.py:523-544 (the least-squares 
 compute_ssi_metrics       estimator/models/losses.py:600-700 (ScaleAndShiftInvariantLoss' three modes as evaluation scores) and
                           compute_errors on the aligned prediction; float64 numpy, the oracle of compute_ssi_metrics_fused
                           (csrc/ssi_eval.hip: two fused GPU passes, one D2H); pinned by tests/golden/ssi_eval.npz
+compute_boundary_f1       NOT in the reference: the scale-invariant boundary F1 of Depth Pro (Bochkovskii et al., 2024) from ratio tests on
+                          neighbouring pixels, numpy; the specification and oracle of compute_boundary_f1_fused
+                          (csrc/boundary_eval.hip: one fused GPU pass of integer counts, one D2H)
 compute_uncertainty_metrics   NOT in the reference: the sparsification scores AUSE / AURG (Ilg et al. 2018; Poggi et al. 2020) of a
                           per-pixel uncertainty against ground truth, numpy; the specification and oracle of
                           compute_uncertainty_metrics_fused (csrc/sparsify.hip: thresholds by the radix select, one D2H)
@@ -341,6 +344,146 @@ def compute_ssi_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Scale-invariant boundary F1 (Depth Pro, Bochkovskii et al., 2024): how sharp a prediction's occluding boundaries are, and whether
+# the depth step across them has the right size and direction.  NOT in the reference; this is the definition (include/prv2.h
+# "Boundary F1 evaluation" states it for the kernel), compute_boundary_f1 is its numpy statement and the oracle of
+# compute_boundary_f1_fused (csrc/boundary_eval.hip).
+#   Inputs       ground truth g [H, W] fp32; prediction p brought to [H, W] exactly as compute_metrics brings it there
+#                (F.interpolate(bilinear, align_corners=False), or the in-kernel sample); min_depth_eval, max_depth_eval; the crop window
+#                of _eval_crop.
+#   Mask         A pixel is valid when it lies inside the crop and g > min && g < max.  A NaN ground truth is not valid.
+#   Prediction cleaning   The prediction at a valid pixel is cleaned as compute_metrics cleans it: NaN -> min, clamp to [min, max].
+#                Every compared value is therefore finite and positive.  The prediction is never read at an invalid pixel.
+#   Pairs        A horizontal pair is (x, y), (x + 1, y) and a vertical pair is (x, y), (x, y + 1).  A pair counts only if BOTH pixels
+#                are valid.  n_h and n_v are the numbers of such pairs.
+#   Thresholds   t_i = float32(np.linspace(1.05, 1.25, T)[i]), with T = 10 by default and 1 <= T <= 16.
+#   Boundary test   All tests are fp32 compare-after-multiply with no division: a > t * b, product rounded to fp32, not contracted.
+#                For a depth map d, a pair (a, b) (a = left or top value, b = right or bottom value) and a threshold t:
+#                horizontal  L: a > t * b (left is farther); R: b > t * a;   vertical  T: a > t * b (top is farther); B: b > t * a.
+#   Relation to Depth Pro   Depth Pro applies the ratio test to inverse depth.  That swaps L <-> R and T <-> B in prediction and ground
+#                truth alike, so the counts below are the same up to the rounding of the division.
+#   Counts       Per threshold i and direction d in the order (L, T, R, B), over the valid pairs: tp[i][d] = pairs flagged in
+#                prediction AND ground truth; np[i][d] = flagged in the prediction; ng[i][d] = flagged in the ground truth.
+#   Per-threshold scores   P_i = 1/4 sum_d tp / max(np, 1);  R_i = 1/4 sum_d tp / max(ng, 1);
+#                F_i = 0 if P_i + R_i == 0 else 2 P_i R_i / (P_i + R_i).
+#   Weights      w_i = t_i / sum t, computed in float64 from the fp32 thresholds.
+#   Keys         si_boundary_f1 = sum w_i F_i, si_boundary_p = sum w_i P_i, si_boundary_r = sum w_i R_i.  n_h + n_v == 0 gives NaN for
+#                all three: nothing can be scored then, and the frame drops out of the dataset's nanmean.  curves=True adds
+#                boundary_thresholds, boundary_p, boundary_r, boundary_f1 (lists of length T).
+# ------------------------------------------------------------------------------------------------------------------
+BOUNDARY_KEYS = ("si_boundary_f1", "si_boundary_p", "si_boundary_r")
+BOUNDARY_MAX_THRESHOLDS = 16  # PRV2_BOUNDARY_MAX_THRESHOLDS
+
+
+def boundary_thresholds(T: int = 10) -> np.ndarray:
+    """the T ratios float32(np.linspace(1.05, 1.25, T)), 1 <= T <= 16"""
+    if not 1 <= int(T) <= BOUNDARY_MAX_THRESHOLDS:
+        raise ValueError(f"boundary_thresholds: T = {T} is not in [1, {BOUNDARY_MAX_THRESHOLDS}]")
+    return np.linspace(1.05, 1.25, int(T)).astype(np.float32)
+
+
+def _boundary_thresholds(thresholds) -> np.ndarray:
+    """``thresholds`` (None: the ten defaults) as a checked fp32 array: 1 .. 16 finite ratios > 1"""
+    th = boundary_thresholds() if thresholds is None else np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if not 1 <= th.size <= BOUNDARY_MAX_THRESHOLDS:
+        raise ValueError(f"boundary F1: {th.size} thresholds, not in [1, {BOUNDARY_MAX_THRESHOLDS}]")
+    if not (np.isfinite(th) & (th > 1)).all():
+        raise ValueError(f"boundary F1: every threshold is a finite ratio > 1, got {th.tolist()}")
+    return th
+
+
+def boundary_counts(g32: np.ndarray, p32: np.ndarray, m: np.ndarray, thresholds) -> np.ndarray:
+    """the row of ops.boundary_f1 for one frame, with whole-array boolean operations: fp32 ground truth and CLEANED fp32 prediction
+    [H, W], the bool mask m and T thresholds -> float64 [2 + 12 T]: n_h, n_v, then for i, for d in (L, T, R, B): tp, np, ng"""
+    th = np.asarray(thresholds, dtype=np.float32)
+    g = np.where(m, g32, np.float32(1)).astype(np.float32)  # (outside the mask nothing is looked at)
+    p = np.where(m, p32, np.float32(1)).astype(np.float32)
+    hm, vm = m[:, :-1] & m[:, 1:], m[:-1] & m[1:]
+    row = [float(hm.sum()), float(vm.sum())]
+
+    def flags(d, t):  # L, T, R, B of one map: compare after the fp32 multiply
+        ha, hb, va, vb = d[:, :-1], d[:, 1:], d[:-1], d[1:]
+        return (ha > t * hb) & hm, (va > t * vb) & vm, (hb > t * ha) & hm, (vb > t * va) & vm
+    with np.errstate(over="ignore"):
+        for t in th:
+            for fp, fg in zip(flags(p, t), flags(g, t)):
+                row += [float((fp & fg).sum()), float(fp.sum()), float(fg.sum())]
+    return np.asarray(row, dtype=np.float64)
+
+
+def boundary_from_values(row, thresholds, curves=False) -> dict:
+    """one frame's row of ops.boundary_f1 (include/prv2.h prv2_boundary_f1: n_h, n_v, then [T][L, T, R, B][tp, np, ng]) and its
+    thresholds -> the dict of BOUNDARY_KEYS (``curves``: also boundary_thresholds / boundary_p / boundary_r / boundary_f1, lists of
+    length T); NaN everywhere without a valid pair"""
+    th = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    v = np.asarray(row, dtype=np.float64)
+    if v.shape != (2 + 12 * th.size,):
+        raise ValueError(f"boundary_from_values: a row of {v.size} values for {th.size} thresholds (2 + 12 T)")
+    nan = float("nan")
+    if v[0] + v[1] == 0:
+        out = {k: nan for k in BOUNDARY_KEYS}
+        if curves:
+            out.update(boundary_thresholds=[float(t) for t in th], boundary_p=[nan] * th.size, boundary_r=[nan] * th.size,
+                       boundary_f1=[nan] * th.size)
+        return out
+    c = v[2:].reshape(th.size, 4, 3)
+    tp, n_p, n_g = c[..., 0], c[..., 1], c[..., 2]
+    P = (tp / np.maximum(n_p, 1.0)).sum(1) / 4.0
+    R = (tp / np.maximum(n_g, 1.0)).sum(1) / 4.0
+    F1 = np.array([0.0 if a + b == 0 else 2.0 * a * b / (a + b) for a, b in zip(P, R)])
+    w = th.astype(np.float64) / th.astype(np.float64).sum()
+    out = dict(si_boundary_f1=float((w * F1).sum()), si_boundary_p=float((w * P).sum()), si_boundary_r=float((w * R).sum()))
+    if curves:
+        out.update(boundary_thresholds=[float(t) for t in th], boundary_p=P.tolist(), boundary_r=R.tolist(), boundary_f1=F1.tolist())
+    return out
+
+
+def compute_boundary_f1(gt, pred, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu", min_depth_eval=0.1, max_depth_eval=10,
+                        thresholds=None, curves=False, return_counts=False):
+    """The scale-invariant boundary F1 of one frame on the host (the definition above): compute_metrics' own arguments, resize
+    (bilinear, align_corners=False) and cleaning of the prediction, its mask (valid range and crop; a NaN ground truth is not valid), then
+    the counts by whole-array boolean operations and the scores through ``boundary_from_values``.  Depth Pro applies the ratio test to
+    inverse depth, which swaps L <-> R and T <-> B in prediction and ground truth alike: the same counts up to the rounding of its
+    division.  ``return_counts``: (dict, the float64 row of ops.boundary_f1)."""
+    th = _boundary_thresholds(thresholds)
+    gt, pred = torch.as_tensor(gt).detach().cpu().float(), torch.as_tensor(pred).detach().cpu().float()
+    if gt.shape[-2:] != pred.shape[-2:] and interpolate:
+        pred = F.interpolate(pred.reshape(1, 1, *pred.shape[-2:]), gt.shape[-2:], mode="bilinear", align_corners=False)
+    g32 = gt.reshape(gt.shape[-2:]).numpy()
+    p32 = pred.reshape(pred.shape[-2:]).numpy().copy()
+    mn, mx = np.float32(min_depth_eval), np.float32(max_depth_eval)
+    with np.errstate(invalid="ignore"):
+        p32[p32 < mn] = mn  # compute_metrics' cleaning (metric.py:98-101), the bounds as fp32 values
+        p32[p32 > mx] = mx
+        p32[np.isinf(p32)] = mx
+        p32[np.isnan(p32)] = mn
+        h, w = g32.shape
+        y0, y1, x0, x1 = _eval_crop(h, w, garg_crop, eigen_crop, dataset)
+        m = np.zeros((h, w), bool)
+        m[y0:y1, x0:x1] = True
+        m &= (g32 > mn) & (g32 < mx)  # fp32 comparisons; a NaN is not valid
+    row = boundary_counts(g32, p32, m, th)
+    out = boundary_from_values(row, th, curves)
+    return (out, row) if return_counts else out
+
+
+@torch.no_grad()
+def compute_boundary_f1_fused(gt: torch.Tensor, pred: torch.Tensor, interpolate=True, garg_crop=False, eigen_crop=True, dataset="nyu",
+                              min_depth_eval=0.1, max_depth_eval=10, thresholds=None, curves=False, fuse_resize=False):
+    """``compute_boundary_f1`` from one fused pass on the GPU (csrc/boundary_eval.hip, ops.boundary_f1): the integer counts of every
+    frame, ONE D2H of 2 + 12 T float64 values per frame, the scores through ``boundary_from_values`` (equal counts give equal floats).
+    A dict for one map ([H, W] / [1, 1, H, W]), a list of dicts for B maps.  Inputs on the host are copied to the GPU: there is no CPU
+    path.  ``fuse_resize``: a prediction of another resolution is sampled inside the kernel (the operations of F.interpolate, the
+    resized map is never written) instead of being resized first."""
+    from . import ops
+    th = _boundary_thresholds(thresholds)
+    g, p, single, _lowres, crop = _fused_inputs(gt, pred, interpolate, fuse_resize, garg_crop, eigen_crop, dataset)
+    vals = ops.boundary_f1(g, p, min_depth_eval, max_depth_eval, crop, th).cpu().numpy()  # the one D2H
+    rows = [boundary_from_values(v, th, curves) for v in vals]
+    return rows[0] if single else rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Sparsification scores of a per-pixel uncertainty (the pseudo-label writer's ``uncertainty`` / ``count_map``): does a high uncertainty
 # mark the pixels where the depth is wrong?  The definition (include/prv2.h "Sparsification" states it for the kernels):
 #   valid   min < gt < max (compute_metrics' rule, no crop); pred cleaned as metric.py:98-101; n valid pixels, n = 0 -> NaN everywhere
@@ -475,9 +618,14 @@ def compute_uncertainty_metrics_fused(gt: torch.Tensor, pred: torch.Tensor, unce
 
 
 def evaluate(per_frame: list) -> dict:
-    """mean of every metric over the frames (general_dataset.py evaluate / mmengine-style collect)."""
-    keys = per_frame[0].keys()
-    return {k: float(np.mean([float(m[k]) for m in per_frame])) for k in keys}
+    """mean of every metric over the frames (general_dataset.py evaluate / mmengine-style collect).  The boundary F1 keys
+    (BOUNDARY_KEYS, and their coarse_ twins) skip a frame whose score is NaN -- one without a valid pair; NaN when no frame is left."""
+    def mean(k):
+        v = [float(m[k]) for m in per_frame]
+        if k.endswith(BOUNDARY_KEYS):
+            v = [x for x in v if not np.isnan(x)] or [float("nan")]
+        return float(np.mean(v))
+    return {k: mean(k) for k in per_frame[0].keys()}
 
 
 def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None,

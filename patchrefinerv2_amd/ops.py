@@ -2468,6 +2468,45 @@ def ssi_metrics(gt, pred, min_depth=1e-3, max_depth=80.0, crop=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Boundary F1 evaluation (the scale-invariant boundary F1 of Depth Pro; csrc/boundary_eval.hip), both dispatch routes.
+# ------------------------------------------------------------------------------------------------------------------
+BOUNDARY_MAX_THRESHOLDS = L.BOUNDARY_MAX_THRESHOLDS
+
+
+def boundary_f1(gt, pred, min_depth=1e-3, max_depth=80.0, crop=None, thresholds=None):
+    """fp32 frames gt [B, H, W] and pred [B, H, W] (or [B, h, w]: sampled inside the kernel as ``depth_metrics_lowres`` samples it) ->
+    float64 [B, 2 + 12 T] on the device: n_h, n_v, then per threshold and direction (L, T, R, B) the counts tp, np, ng of the
+    occluding-boundary pairs (the definition and the layout: include/prv2.h "Boundary F1 evaluation"; metrics.boundary_from_values
+    makes the scores).  The mask is min_depth < gt < max_depth inside ``crop`` = (y0, y1, x0, x1), None: the whole frame.
+    ``thresholds``: 1 .. 16 finite ratios > 1, None: metrics.boundary_thresholds().  One pass, no host synchronisation; integer counts:
+    bit-identical from call to call and for a frame alone or in a batch."""
+    g, p = _edge_frames(gt, torch.float32), _edge_frames(pred, torch.float32)
+    if g.shape[0] != p.shape[0]:
+        raise ValueError(f"boundary_f1: gt {tuple(g.shape)} and pred {tuple(p.shape)} differ in their frame count")
+    if thresholds is None:
+        from .metrics import boundary_thresholds
+        thresholds = boundary_thresholds()
+    th = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+    if not 1 <= th.size <= BOUNDARY_MAX_THRESHOLDS:
+        raise ValueError(f"boundary_f1: {th.size} thresholds, not in [1, {BOUNDARY_MAX_THRESHOLDS}]")
+    y0, y1, x0, x1 = (0, g.shape[1], 0, g.shape[2]) if crop is None else (int(v) for v in crop)
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.append(_tops().boundary_f1(g, p, float(min_depth), float(max_depth), y0, y1, x0, x1, [float(t) for t in th]))  # noqa: E731
+    else:
+        wsb = L.load().prv2_boundary_f1_workspace_bytes(*g.shape)
+        if wsb < 0:
+            raise ValueError(f"boundary_f1: bad frame shape {tuple(g.shape)}")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=g.device)
+        out = torch.empty((g.shape[0], L.boundary_values(th.size)), dtype=torch.float64, device=g.device)
+        box.append(out)
+        call = lambda: _c("boundary_f1", g.data_ptr(), p.data_ptr(), *g.shape, p.shape[1], p.shape[2], float(min_depth), float(max_depth),  # noqa: E731
+                          y0, y1, x0, x1, th.ctypes.data, int(th.size), out.data_ptr(), ws.data_ptr(), wsb)
+    PROFILER.launch_aux("boundary_f1", 4.0 * g.numel() + 4.0 * p.numel(), call, f"{g.shape[0]}x{g.shape[1]}x{g.shape[2]}<-{p.shape[1]}x{p.shape[2]} T{th.size}")
+    return box[0]
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Sparsification curves of a per-pixel uncertainty (AUSE / AURG; csrc/sparsify.hip), both dispatch routes.
 # ------------------------------------------------------------------------------------------------------------------
 SPARSIFY_MAX_LEVELS = L.SPARSIFY_MAX_LEVELS

@@ -232,15 +232,22 @@ class Tester:
                     **(dict(views=dict(count=views, motion=getattr(info, "view_motion", "circle"), amplitude=float(getattr(info, "view_amplitude", 0.05)),
                                        focus=float(getattr(info, "view_focus", float("inf"))))) if views else {}))
 
-    def _entry(self, item, result, score=None, **extra):
+    def _entry(self, item, result, score=None, coarse=None, **extra):
         """one frame's result entry.  ``mean``: a host map's fp32 mean, a device map's float64 sum on the device (equal within that
-        sum's rounding).  ``score``: the map the dataset scores when the item carries ground truth"""
+        sum's rounding).  ``score``: the map the dataset scores when the item carries ground truth.  ``coarse``: the model's coarse
+        prediction of the frame; a dataset with ``boundary_f1`` then also gets ``coarse_si_boundary_f1 / _p / _r``: the coarse map's
+        boundary scores with the same arguments, sampled to the ground truth's grid inside the kernel (one more call per frame) --
+        beside ``si_boundary_*`` they say how much boundary quality the refiner added"""
         mean = result.mean(dtype=torch.float64) if result.is_cuda else result.mean()
         entry = dict(name=item["img_file_basename"], shape=tuple(result.shape), mean=float(mean), **extra)
         if score is not None and item.get("depth_gt") is not None:
             seg = {} if item.get("seg_image") is None else dict(seg_image=item["seg_image"])  # (CityScapesDataset with_seg_map)
             entry["metrics"] = self.dataloader.get_metrics(item["depth_gt"], score, disp_gt_edges=item.get("boundary"),
                                                            image_hr=item["image_hr"], **seg)
+            if coarse is not None and getattr(self.dataloader, "boundary_f1", False):
+                from .metrics import compute_boundary_f1_fused
+                scores = compute_boundary_f1_fused(item["depth_gt"], coarse, fuse_resize=True, **self.dataloader.boundary_args())
+                entry["metrics"].update({"coarse_" + k: v for k, v in scores.items()})
         return entry
 
     def _emit(self, results, item, result, coarse, image_raw_shape, stage=None, **extra):
@@ -255,7 +262,7 @@ class Tester:
             geo = self._geometry(result, image_raw_shape)
             if geo is not None:
                 stage.submit_geometry(base, result, item["image_hr"], **geo)
-            results.append(self._entry(item, result, score=result, **extra))
+            results.append(self._entry(item, result, score=result, coarse=coarse, **extra))
             return
         score = result  # (a device map is scored where it is)
         result = result.cpu()  # BaselinePretrain(target='coarse') hands back the device tensor (baseline_pretrain.py:464)
@@ -274,7 +281,7 @@ class Tester:
                 from .output import write_geometry_host
                 image = torch.as_tensor(item["image_hr"]).cpu().float().numpy()
                 write_geometry_host(base, result.squeeze().numpy(), image.reshape(3, *image.shape[-2:]), geo.pop("intrinsics"), **geo)
-        results.append(self._entry(item, result, score=score, **extra))
+        results.append(self._entry(item, result, score=score, coarse=coarse, **extra))
 
     @torch.no_grad()
     def generate_pl(self, cai_mode="r32", process_num=4, image_raw_shape=(2160, 3840), patch_split_num=(4, 4), count_thr=0.05, seed=None,

@@ -51,6 +51,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "depth16_gt",
        # scale-and-shift-invariant evaluation: the fits, the SSI scores and the error sums of the aligned prediction
        "ssi_metrics",
+       # boundary F1 evaluation: the occluding-boundary counts of prediction and ground truth per ratio and direction
+       "boundary_f1",
        # sparsification curves (AUSE / AURG) of a per-pixel uncertainty
        "sparsify",
        # geometry export: PLY vertex records and surface-normal scanlines

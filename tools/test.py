@@ -20,6 +20,8 @@ and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`
 (``--view-motion circle|sway|dolly``, ``--view-amplitude M``, ``--view-focus Z``; same camera, --ply-edge-thr and --ply-depth-range).
 ``--edge-metrics``: frames with ground truth are also scored on their depth edges (boundary metrics, edge_* / noedge_* splits).
 ``--ssi-metrics``: frames with ground truth are also scored after a least-squares scale and shift (ssi_* and gm keys, every --test-type).
+``--boundary-f1``: frames with ground truth also get the scale-invariant boundary F1 (si_boundary_* keys, and coarse_si_boundary_* of the
+coarse prediction; every --test-type).
 ``--uncert-metrics``: with ``--generate-pl``, frames with ground truth get the sparsification scores of the uncertainty map (AUSE / AURG).
 ``--test-type normal|test_in|test_out``: the config's val / test_in / test_out dataloader (UnrealStereo4kDataset: raw images and
 disparities decoded and scored on the GPU; prints a1 ... sq_rel and see.  ETHDataset: photographs resized and raw float32 depth decoded
@@ -82,11 +84,13 @@ def dataset_config(cfg, args):
         raise SystemExit(f"--test-type {args.test_type} needs {section}.dataset in the config; {args.config} has none")
     ds_cfg = cfg[section].dataset.to_dict()
     kind = ds_cfg.get("type")
-    if args.test_type in CONSTRUCTED:  # every size is the files' own: nothing of the command line goes into the dataset but --ssi-metrics
+    if args.test_type in CONSTRUCTED:  # every size is the files' own: nothing of the command line goes into the dataset but --ssi-metrics and --boundary-f1
         if kind != CONSTRUCTED[args.test_type]:
             raise SystemExit(f"--test-type {args.test_type} needs {section}.dataset.type = '{CONSTRUCTED[args.test_type]}'; {args.config} has {kind}")
         if getattr(args, "ssi_metrics", False):
             ds_cfg["ssi_metrics"] = True
+        if getattr(args, "boundary_f1", False):
+            ds_cfg["boundary_f1"] = True
         return ds_cfg
     if kind not in DATASETS:
         route = {v: k for k, v in CONSTRUCTED.items()}.get(kind)
@@ -103,6 +107,8 @@ def dataset_config(cfg, args):
             ds_cfg["edge_metrics"] = True
     if getattr(args, "ssi_metrics", False):  # every dataset class takes it
         ds_cfg["ssi_metrics"] = True
+    if getattr(args, "boundary_f1", False):  # likewise
+        ds_cfg["boundary_f1"] = True
     return ds_cfg
 
 
@@ -160,6 +166,10 @@ def main():
                     help="with ground truth (any --test-type): add the scale-and-shift-invariant scores ssi_scale, ssi_shift, ssi_l1, ssi_gm, gm, "
                          "ssi_gm_inv and ssi_a1 ... ssi_sq_rel (losses.py:523-544, :600-700: the prediction aligned to the ground truth by a "
                          "least-squares scale and shift), two fused GPU passes per frame")
+    ap.add_argument("--boundary-f1", action="store_true",
+                    help="with ground truth (any --test-type): add the scale-invariant boundary F1 of Depth Pro -- si_boundary_f1, si_boundary_p, "
+                         "si_boundary_r (ratio tests on neighbouring pixels at ten ratios 1.05 .. 1.25, four directions), one fused GPU pass per "
+                         "frame; with a model that has a coarse prediction also coarse_si_boundary_* of that map")
     ap.add_argument("--uncert-metrics", action="store_true",
                     help="with --generate-pl and ground truth (any --test-type whose dataset has it): score the uncertainty map against the "
                          "depth error -- ause_abs_rel, aurg_abs_rel, ause_rmse, aurg_rmse (sparsification curves over 20 levels, pixels under "
