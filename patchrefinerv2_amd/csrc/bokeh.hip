@@ -21,7 +21,7 @@
 // the four outputs of the lane.  dist is the same for every lane at a tap: a lane holds column `lane` of the table's row |dy| and the
 // tap takes it with v_readlane.  LDS: 3 x 16 x 128 x 8 = 48 KiB of band + 4.3 KiB of table (three workgroups per CU at any radius up
 // to the cap, kBokehMaxRadius = 32, which only sets the band's pitch of 64 + 2 x 32 columns).
-#include "rows.h"
+#include "scene.h"
 
 namespace prv2 {
 namespace {
@@ -36,12 +36,12 @@ int g_tile_bound = 1;  // prv2_bokeh_tile_bound: 0 walks the full window in ever
 
 struct BokehArgs {
   const float* depth;  // [n, h, w]
-  const float* image;  // [n, 3, ih, iw]
+  ImageSrc img;        // [n, 3, ih, iw]
   float k;             // fx * aperture * 0.5
   float focus;         // > 0: the focus distance; else the focus pixel's depth
   float rm;            // max_radius
-  float lo, hi;
-  int32_t h, w, ih, iw;
+  Camera cam;          // (the kernel reads its depth range; fx is in k)
+  int32_t h, w;
   int32_t fy, fx;      // the focus pixel
   int32_t R;           // ceil(max_radius)
   int32_t bound;       // per-tile walk bound on
@@ -67,24 +67,11 @@ __device__ __forceinline__ void block_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-__device__ __forceinline__ bool bokeh_valid(const BokehArgs& a, float z) { return fabsf(z) < __builtin_inff() && z > a.lo && z < a.hi; }
-
 // the circle of confusion of a depth, in pixels.  flat: the focus pixel is invalid and every radius is 0
 __device__ __forceinline__ float bokeh_radius(const BokehArgs& a, float z, float invf, bool flat) {
   if (flat) return 0.0f;
-  const float iz = bokeh_valid(a, z) ? __fdiv_rn(1.0f, z) : 0.0f;
+  const float iz = valid_z(a.cam, z) ? __fdiv_rn(1.0f, z) : 0.0f;
   return fminf(a.rm, __fmul_rn(a.k, fabsf(__fsub_rn(iz, invf))));  // (fminf: a NaN product gives Rm)
-}
-
-// the nearest sample of an axis of n_in values for position i of n_out
-__device__ __forceinline__ int bokeh_nearest(int i, int n_out, int n_in) {
-  return n_in == n_out ? i : (int)(((int64_t)(2 * i + 1) * n_in) / (2 * (int64_t)n_out));
-}
-
-// clamp(rint(v), 0, 255), ties to even, NaN -> 0
-__device__ __forceinline__ uint32_t bokeh_byte(float v) {
-  const float r = rintf(v);
-  return !(r > 0.0f) ? 0u : r >= 255.0f ? 255u : (uint32_t)r;
 }
 
 // float32(sqrt(n)) of an integer 0 <= n < 2^24, correctly rounded (__fsqrt_rn compiles to the bare v_sqrt_f32 here: 1 ulp).  The hardware's
@@ -136,7 +123,7 @@ __global__ void __launch_bounds__(256) bokeh_kernel(BokehArgs a) {
   bool flat = false;
   if (!(zf > 0.0f)) {
     zf = d[(int64_t)a.fy * w + a.fx];
-    flat = !bokeh_valid(a, zf);
+    flat = !valid_z(a.cam, zf);
   }
   const float invf = flat ? 0.0f : __fdiv_rn(1.0f, zf);
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) a.focus_out[f] = flat ? __builtin_nanf("") : zf;
@@ -178,15 +165,15 @@ __global__ void __launch_bounds__(256) bokeh_kernel(BokehArgs a) {
     if (px < w && py < h) {
       z = d[(int64_t)py * w + px];
       r = bokeh_radius(a, z, invf, flat);
-      z = bokeh_valid(a, z) ? z : __builtin_inff();
+      z = valid_z(a.cam, z) ? z : __builtin_inff();
     }
     const float m = fmaxf(r, 0.5f);
     p[j].zk = z, p[j].r = r, p[j].h = __fadd_rn(m, 0.5f), p[j].ia = __fdiv_rn(1.0f, __fmul_rn(m, m));
     p[j].sw = p[j].sc[0] = p[j].sc[1] = p[j].sc[2] = 0.0f;
   }
 
-  const float* img = a.image + (int64_t)f * 3 * a.ih * a.iw;
-  const int64_t plane = (int64_t)a.ih * a.iw;
+  const float* img = a.img.frame(f);
+  const int64_t plane = a.img.plane();
   const int ncols = kTW + 2 * Rt, sy_end = ty0 + kTH + Rt;  // source rows [ty0 - Rt, sy_end), columns [tx0 - Rt, tx0 - Rt + ncols)
   for (int sy0 = ty0 - Rt; sy0 < sy_end; sy0 += kBand) {
     block_sync();  // (the previous band is consumed)
@@ -196,8 +183,8 @@ __global__ void __launch_bounds__(256) bokeh_kernel(BokehArgs a) {
       if (sy >= 0 && sy < h && sy < sy_end && sx >= 0 && sx < w) {
         const float z = d[(int64_t)sy * w + sx];
         const float r = bokeh_radius(a, z, invf, flat), m = fmaxf(r, 0.5f);
-        const float* c = img + (int64_t)bokeh_nearest(sy, h, a.ih) * a.iw + bokeh_nearest(sx, w, a.iw);
-        zr = pair(bokeh_valid(a, z) ? z : __builtin_inff(), r);
+        const float* c = img + (int64_t)nearest(sy, h, a.img.ih) * a.img.iw + nearest(sx, w, a.img.iw);
+        zr = pair(valid_z(a.cam, z) ? z : __builtin_inff(), r);
         ic = pair(__fdiv_rn(1.0f, __fmul_rn(m, m)), finite_or_zero(c[0]));
         gb = pair(finite_or_zero(c[plane]), finite_or_zero(c[2 * plane]));
       }
@@ -275,7 +262,7 @@ __global__ void __launch_bounds__(256) bokeh_kernel(BokehArgs a) {
     if (px < w) {
       uint8_t* q = row + (1 + 3 * px - c0);
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) q[ch] = (uint8_t)bokeh_byte(__fmul_rn(__fdiv_rn(p[j].sc[ch], p[j].sw), 255.0f));
+      for (int ch = 0; ch < 3; ++ch) q[ch] = (uint8_t)color_byte(__fmul_rn(__fdiv_rn(p[j].sc[ch], p[j].sw), 255.0f));
     }
   }
   block_sync();
@@ -294,14 +281,11 @@ PRV2_NO_PACKED_FP32_END
 
 static int check_bokeh(const char* name, const float* depth, const float* image, int n, int h, int w, int ih, int iw, float fx, float aperture,
                        float focus, float focus_u, float focus_v, float max_radius, float lo, float hi, const float* focus_out) {
-  PRV2_REQUIRE(depth && image && focus_out, "%s: null pointer (depth, image, focus_out)", name);
-  if (check_map(name, n, h, w)) return 1;
-  PRV2_REQUIRE(ih >= 1 && iw >= 1 && (int64_t)n * 3 * ih * iw < (int64_t)INT_MAX, "%s: bad image shape %d x %d", name, ih, iw);
-  PRV2_REQUIRE(fx > 0.0f && fx < __builtin_inff(), "%s: focal length %g: finite and positive", name, (double)fx);
+  PRV2_REQUIRE(depth && focus_out, "%s: null pointer (depth, focus_out)", name);
+  if (check_map(name, n, h, w) || check_image(name, image, n, ih, iw) || check_camera(name, fx, fx, 0.0f, 0.0f) || check_range(name, lo, hi, 0.0f)) return 1;
   PRV2_REQUIRE(aperture >= 0.0f && aperture < __builtin_inff(), "%s: aperture %g: finite and not below 0", name, (double)aperture);
   PRV2_REQUIRE(max_radius >= 0.0f && max_radius <= (float)kBokehMaxRadius, "%s: max_radius %g: in [0, %d] (prv2_bokeh_max_radius)", name,
                (double)max_radius, kBokehMaxRadius);
-  PRV2_REQUIRE(lo == lo && hi == hi, "%s: NaN in the depth range", name);
   PRV2_REQUIRE(!(focus > 0.0f) || focus < __builtin_inff(), "%s: focus %g: a finite distance (0, less or NaN: the focus point)", name, (double)focus);
   PRV2_REQUIRE(focus_u >= 0.0f && focus_u <= 1.0f && focus_v >= 0.0f && focus_v <= 1.0f, "%s: focus point (%g, %g) outside [0, 1]^2", name,
                (double)focus_u, (double)focus_v);
@@ -311,12 +295,12 @@ static int check_bokeh(const char* name, const float* depth, const float* image,
 static BokehArgs bokeh_args(const float* depth, const float* image, int h, int w, int ih, int iw, float fx, float aperture, float focus, float focus_u,
                             float focus_v, float max_radius, float lo, float hi, float* focus_out) {
   BokehArgs a{};
-  a.depth = depth, a.image = image;
+  a.depth = depth, a.img = ImageSrc{image, ih, iw};
   a.k = fx * aperture * 0.5f;  // (fp32, one rounding per product: the host specification's k)
   a.focus = focus > 0.0f ? focus : 0.0f;
   a.rm = max_radius;
-  a.lo = lo, a.hi = hi;
-  a.h = h, a.w = w, a.ih = ih, a.iw = iw;
+  a.cam = Camera{fx, fx, 0.0f, 0.0f, lo, hi};
+  a.h = h, a.w = w;
   const int fy = (int)floor((double)focus_v * h), fxp = (int)floor((double)focus_u * w);
   a.fy = fy < h - 1 ? fy : h - 1, a.fx = fxp < w - 1 ? fxp : w - 1;
   a.R = (int)ceilf(max_radius);

@@ -9,10 +9,10 @@
 //   - the file is built with -ffp-contract=off; every fp32 operation is written with __f*_rn (IEEE, one rounding each, in the order
 //     of the restatement); division and square root are the correctly rounded ones (sqrtf: HIP's __fsqrt_rn is the native,
 //     1-ulp instruction);
-//   - camera: Z = D[y, x], X = (((float)x + 0.5) - cx) * Z / fx, Y likewise with cy, fy;
-//   - valid: Z finite and lo < Z < hi; flying: a valid in-frame 4-neighbour Zn with |Z - Zn| > thr * min(Z, Zn) (thr > 0);
+//   - camera, valid, joined, the colour sample and its bytes, the faces of a cell: scene.h; Z = D[y, x];
+//   - flying: a valid in-frame 4-neighbour Zn that is not joined to Z;
 //   - kept: valid, not flying, y % stride == 0 and x % stride == 0.
-#include "rows.h"
+#include "scene.h"
 
 namespace prv2 {
 namespace {
@@ -22,11 +22,6 @@ constexpr int kRounds = kRun / 256;
 constexpr int kSegs = kRounds * 4;  // (step, wave) segments of 64 consecutive pixels
 constexpr int kRecord = 15;    // bytes of a vertex
 
-struct Camera {
-  float fx, fy, cx, cy;  // in pixels of the depth map's grid
-  float lo, hi;          // valid: lo < Z < hi
-};
-
 struct CloudArgs {
   const float* depth;  // [n, h, w]
   Camera cam;
@@ -35,11 +30,7 @@ struct CloudArgs {
   int32_t nblk;        // blocks (runs) per frame
 };
 
-__device__ __forceinline__ bool valid_z(const Camera& c, float z) { return fabsf(z) < __builtin_inff() && z > c.lo && z < c.hi; }
-
-__device__ __forceinline__ bool flying(const Camera& c, float thr, float z, float zn) {
-  return valid_z(c, zn) && fabsf(__fsub_rn(z, zn)) > __fmul_rn(thr, fminf(z, zn));
-}
+__device__ __forceinline__ bool flying(const Camera& c, float thr, float z, float zn) { return valid_z(c, zn) && !joined(thr, z, zn); }
 
 // the keep predicate of pixel (y, x) of frame ``d``; z = d[y * w + x]
 __device__ __forceinline__ bool keep_pixel(const CloudArgs& a, const float* __restrict__ d, int y, int x, float z) {
@@ -52,19 +43,6 @@ __device__ __forceinline__ bool keep_pixel(const CloudArgs& a, const float* __re
   if (y > 0) fly = fly || flying(a.cam, a.thr, z, d[i - a.w]);
   if (y + 1 < a.h) fly = fly || flying(a.cam, a.thr, z, d[i + a.w]);
   return !fly;
-}
-
-__device__ __forceinline__ float cam_x(const Camera& c, int x, float z) {
-  return __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)x, 0.5f), c.cx), z), c.fx);
-}
-__device__ __forceinline__ float cam_y(const Camera& c, int y, float z) {
-  return __fdiv_rn(__fmul_rn(__fsub_rn(__fadd_rn((float)y, 0.5f), c.cy), z), c.fy);
-}
-
-// clamp(rint(v), 0, 255), ties to even, NaN -> 0
-__device__ __forceinline__ uint32_t byte_of(float v) {
-  const float r = rintf(v);
-  return !(r > 0.0f) ? 0u : r >= 255.0f ? 255u : (uint32_t)r;
 }
 
 // One step of a block over its run: lane t evaluates pixel p0 + t (p0 a multiple of 64 inside the frame's pixel range or behind it).
@@ -141,8 +119,8 @@ __global__ void __launch_bounds__(256) cloud_scan_kernel(int32_t* __restrict__ c
 // range starts and ends at any byte alignment and the dwords at its two ends may belong to the neighbouring runs as well: the LDS image
 // is shifted so that LDS offset == global address (mod 16), the bytes up to the first and from the last 16-byte boundary are stored one
 // by one and only the aligned interior with 16-byte stores.  Nothing outside the range is written (or read).
-__global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, const float* __restrict__ image, int32_t ih, int32_t iw,
-                                                         const int32_t* __restrict__ offsets, uint8_t* __restrict__ out, int64_t out_fstride) {
+__global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, ImageSrc src, const int32_t* __restrict__ offsets,
+                                                         uint8_t* __restrict__ out, int64_t out_fstride) {
   __shared__ uint4 buf4[(kRun * kRecord + 16 + 15) / 16];
   __shared__ int32_t seg[kSegs + 1];
   uint8_t* buf = (uint8_t*)buf4;
@@ -173,15 +151,14 @@ __global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, const floa
   if (cnt == 0) return;
   uint8_t* dst = out + (int64_t)f * out_fstride + (int64_t)kRecord * offsets[(int64_t)f * a.nblk + blockIdx.x];
   const int shift = (int)((uintptr_t)dst & 15);
-  const float* img = image + (int64_t)f * 3 * ih * iw;
-  const int64_t plane = (int64_t)ih * iw;
+  const float* img = src.frame(f);
+  const int64_t plane = src.plane();
 #pragma unroll
   for (int r = 0; r < kRounds; ++r) {
     if (rank[r] < 0) continue;
     const int64_t p = p0 + r * 256 + tid;
     const int y = (int)(p / a.w), x = (int)(p - (int64_t)y * a.w);
-    const int sy = (int)(((int64_t)(2 * y + 1) * ih) / (2 * (int64_t)a.h)), sx = (int)(((int64_t)(2 * x + 1) * iw) / (2 * (int64_t)a.w));
-    const float* c = img + (int64_t)sy * iw + sx;
+    const float* c = img + (int64_t)nearest(y, a.h, src.ih) * src.iw + nearest(x, a.w, src.iw);
     const uint32_t w0 = __float_as_uint(cam_x(a.cam, x, z[r])), w1 = __float_as_uint(cam_y(a.cam, y, z[r])), w2 = __float_as_uint(z[r]);
     uint8_t* rec = buf + shift + kRecord * (seg[r * 4 + wave] + rank[r]);
 #pragma unroll
@@ -190,9 +167,9 @@ __global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, const floa
       rec[4 + b] = (uint8_t)(w1 >> (8 * b));
       rec[8 + b] = (uint8_t)(w2 >> (8 * b));
     }
-    rec[12] = (uint8_t)byte_of(__fmul_rn(c[0], 255.0f));
-    rec[13] = (uint8_t)byte_of(__fmul_rn(c[plane], 255.0f));
-    rec[14] = (uint8_t)byte_of(__fmul_rn(c[2 * plane], 255.0f));
+    rec[12] = (uint8_t)color_byte(__fmul_rn(c[0], 255.0f));
+    rec[13] = (uint8_t)color_byte(__fmul_rn(c[plane], 255.0f));
+    rec[14] = (uint8_t)color_byte(__fmul_rn(c[2 * plane], 255.0f));
   }
   __syncthreads();
   store_ragged(dst, buf4, shift, kRecord * cnt, tid);
@@ -251,34 +228,23 @@ __global__ void __launch_bounds__(256) mesh_index_kernel(CloudArgs a, const int3
   }
 }
 
-__device__ __forceinline__ bool joined(float thr, float zp, float zq) {
-  return !(thr > 0.0f) || !(fabsf(__fsub_rn(zp, zq)) > __fmul_rn(thr, fminf(zp, zq)));
-}
-
-// the faces of cell c of a frame (idx, d: the frame's index map and depth) -> their number; tri: their vertices, first candidate first.
-// Four corners kept: the diagonal a-d if |Za - Zd| <= |Zb - Zc|, else b-c; three: the diagonal whose ends are kept; fewer: no face.
-// a-d: (a, c, d) then (a, d, b); b-c: (a, c, b) then (b, c, d); a candidate needs its three corners kept and its three edges joined.
+// the faces of cell c of a frame (idx, d: the frame's index map and depth) -> their number; tri: their vertices, first candidate first
+// (scene.h cell_rule; a corner is kept where it has a vertex)
 __device__ __forceinline__ int cell_faces(const MeshArgs& m, const float* __restrict__ d, const int32_t* __restrict__ idx, int c, int32_t (&tri)[6]) {
   const int gy = c / (m.gw - 1), gx = c - gy * (m.gw - 1);
   const int32_t* i0 = idx + (int64_t)gy * m.gw + gx;
   const int32_t ia = i0[0], ib = i0[1], ic = i0[m.gw], id = i0[m.gw + 1];
-  const int kept = (ia >= 0) + (ib >= 0) + (ic >= 0) + (id >= 0);
-  if (kept < 3) return 0;
+  if ((ia >= 0) + (ib >= 0) + (ic >= 0) + (id >= 0) < 3) return 0;  // (no face: the depths are not read)
   const int64_t down = (int64_t)m.stride * m.w;
   const float* z0 = d + gy * down + (int64_t)gx * m.stride;
-  const float za = z0[0], zb = z0[m.stride], zc = z0[down], zd = z0[down + m.stride];  // (a corner's Z counts only where it is kept)
-  const bool ad = kept == 4 ? fabsf(__fsub_rn(za, zd)) <= fabsf(__fsub_rn(zb, zc)) : (ia >= 0 && id >= 0);
-  const bool ac = ia >= 0 && ic >= 0 && joined(m.thr, za, zc), cd = ic >= 0 && id >= 0 && joined(m.thr, zc, zd);
-  const bool ab = ia >= 0 && ib >= 0 && joined(m.thr, za, zb), bd = ib >= 0 && id >= 0 && joined(m.thr, zb, zd);
-  const bool dg = ad ? joined(m.thr, za, zd) : joined(m.thr, zb, zc);  // (both ends of the chosen diagonal are kept)
-  const bool first = dg && ac && (ad ? cd : ab), second = dg && bd && (ad ? ab : cd);
-  const int32_t f0[3] = {ia, ic, ad ? id : ib}, f1[3] = {ad ? ia : ib, ad ? id : ic, ad ? ib : id};
+  const CellFaces cf = cell_rule(m.thr, z0[0], z0[m.stride], z0[down], z0[down + m.stride], ia >= 0, ib >= 0, ic >= 0, id >= 0);
+  const int32_t f0[3] = {ia, ic, cf.ad ? id : ib}, f1[3] = {cf.ad ? ia : ib, cf.ad ? id : ic, cf.ad ? ib : id};
 #pragma unroll
   for (int v = 0; v < 3; ++v) {
-    tri[v] = first ? f0[v] : f1[v];
+    tri[v] = cf.first ? f0[v] : f1[v];
     tri[3 + v] = f1[v];
   }
-  return (int)first + (int)second;
+  return (int)cf.first + (int)cf.second;
 }
 
 // One step of a block over its run of cells: lane t evaluates cell c.  Returns the cell's faces; ``below``: faces of lower lanes of this
@@ -411,27 +377,19 @@ struct NormalOp {
     if (!(fabsf(nx) < inf && fabsf(ny) < inf && fabsf(nz) < inf)) return 0u;
     const float dot = __fadd_rn(__fadd_rn(__fmul_rn(nx, X), __fmul_rn(ny, Y)), __fmul_rn(nz, Z));
     if (dot > 0.0f) nx = -nx, ny = -ny, nz = -nz;
-    const uint32_t r = byte_of(__fmul_rn(__fadd_rn(__fmul_rn(nx, 0.5f), 0.5f), 255.0f));
-    const uint32_t g = byte_of(__fmul_rn(__fadd_rn(__fmul_rn(ny, 0.5f), 0.5f), 255.0f));
-    const uint32_t b = byte_of(__fmul_rn(__fadd_rn(__fmul_rn(nz, 0.5f), 0.5f), 255.0f));
+    const uint32_t r = color_byte(__fmul_rn(__fadd_rn(__fmul_rn(nx, 0.5f), 0.5f), 255.0f));
+    const uint32_t g = color_byte(__fmul_rn(__fadd_rn(__fmul_rn(ny, 0.5f), 0.5f), 255.0f));
+    const uint32_t b = color_byte(__fmul_rn(__fadd_rn(__fmul_rn(nz, 0.5f), 0.5f), 255.0f));
     return r | g << 8 | b << 16;
   }
 };
 
 static int64_t cloud_blocks(int h, int w) { return cdiv((int64_t)h * w, kRun); }
 
-static int check_camera(const char* name, float fx, float fy, float cx, float cy) {
-  PRV2_REQUIRE(fx > 0.0f && fy > 0.0f && fx < __builtin_inff() && fy < __builtin_inff(), "%s: focal lengths %g, %g: finite and positive", name,
-               (double)fx, (double)fy);
-  PRV2_REQUIRE(cx == cx && cy == cy && fabsf(cx) < __builtin_inff() && fabsf(cy) < __builtin_inff(), "%s: principal point %g, %g: finite", name,
-               (double)cx, (double)cy);
-  return 0;
-}
-
-static int check_cloud(const char* name, const float* depth, int n, int h, int w, float fx, float fy, float cx, float cy, int stride,
-                       const void* workspace, int64_t workspace_bytes) {
+static int check_cloud(const char* name, const float* depth, int n, int h, int w, float fx, float fy, float cx, float cy, float lo, float hi,
+                       float edge_thr, int stride, const void* workspace, int64_t workspace_bytes) {
   PRV2_REQUIRE(depth != nullptr, "%s: null pointer (depth)", name);
-  if (check_map(name, n, h, w) || check_camera(name, fx, fy, cx, cy)) return 1;
+  if (check_map(name, n, h, w) || check_camera(name, fx, fy, cx, cy) || check_range(name, lo, hi, edge_thr)) return 1;
   PRV2_REQUIRE(stride >= 1, "%s: stride %d < 1", name, stride);
   PRV2_REQUIRE(workspace != nullptr, "%s: null workspace", name);
   PRV2_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: the workspace must be 4-byte aligned", name);
@@ -496,7 +454,7 @@ extern "C" int prv2_pointcloud_count(const float* depth, int32_t n, int32_t h, i
                                      float edge_thr, int32_t stride, int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* name = "pointcloud_count";
   PRV2_REQUIRE(counts != nullptr, "%s: null pointer (counts)", name);
-  if (check_cloud(name, depth, n, h, w, fx, fy, cx, cy, stride, workspace, workspace_bytes)) return 1;
+  if (check_cloud(name, depth, n, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride, workspace, workspace_bytes)) return 1;
   const CloudArgs a = cloud_args(depth, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride);
   hipLaunchKernelGGL(cloud_count_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, (int32_t*)workspace);
   hipLaunchKernelGGL(cloud_scan_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, (int32_t*)workspace, a.nblk, counts);
@@ -508,13 +466,12 @@ extern "C" int prv2_pointcloud_pack(const float* depth, const float* image, int3
                                     float fy, float cx, float cy, float lo, float hi, float edge_thr, int32_t stride, const void* workspace,
                                     int64_t workspace_bytes, uint8_t* vertices, int64_t vertices_fstride, void* stream) {
   const char* name = "pointcloud_pack";
-  PRV2_REQUIRE(image && vertices, "%s: null pointer", name);
-  if (check_cloud(name, depth, n, h, w, fx, fy, cx, cy, stride, workspace, workspace_bytes)) return 1;
-  PRV2_REQUIRE(ih >= 1 && iw >= 1 && (int64_t)n * 3 * ih * iw < (int64_t)INT_MAX, "%s: bad image shape %d x %d", name, ih, iw);
+  PRV2_REQUIRE(vertices != nullptr, "%s: null pointer (vertices)", name);
+  if (check_image(name, image, n, ih, iw) || check_cloud(name, depth, n, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride, workspace, workspace_bytes)) return 1;
   PRV2_REQUIRE(vertices_fstride >= prv2_pointcloud_bound(h, w, stride), "%s: frame stride %lld of the vertex buffer < %lld (prv2_pointcloud_bound)",
                name, (long long)vertices_fstride, (long long)prv2_pointcloud_bound(h, w, stride));
   const CloudArgs a = cloud_args(depth, h, w, fx, fy, cx, cy, lo, hi, edge_thr, stride);
-  hipLaunchKernelGGL(cloud_pack_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, image, ih, iw,
+  hipLaunchKernelGGL(cloud_pack_kernel, dim3((unsigned)a.nblk, n), dim3(256), 0, (hipStream_t)stream, a, ImageSrc{image, ih, iw},
                      (const int32_t*)workspace, vertices, vertices_fstride);
   PRV2_LAUNCH_CHECK(name);
   return 0;
@@ -576,7 +533,8 @@ extern "C" int prv2_normal_rows(const float* depth, int32_t n, int32_t h, int32_
                                 uint8_t* rows, int64_t rows_fstride, void* stream) {
   const char* name = "normal_rows";
   PRV2_REQUIRE(depth != nullptr, "%s: null pointer (depth)", name);
-  if (check_map(name, n, h, w) || check_camera(name, fx, fy, cx, cy) || check_rows(name, rows, rows_fstride, n, h, w, 3)) return 1;
+  if (check_map(name, n, h, w) || check_camera(name, fx, fy, cx, cy) || check_range(name, lo, hi, 0.0f)) return 1;
+  if (check_rows(name, rows, rows_fstride, n, h, w, 3)) return 1;
   NormalOp op{depth, Camera{fx, fy, cx, cy, lo, hi}, h, w};
   launch_rows(op, nullptr, 0, n, h, w, rows, rows_fstride, (hipStream_t)stream);
   PRV2_LAUNCH_CHECK(name);

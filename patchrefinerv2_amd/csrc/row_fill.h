@@ -1,22 +1,13 @@
 // What the re-rendered views share (csrc/stereo.hip, csrc/view.hip): a row of 64-bit depth-test keys in LDS -- the smallest key of a
-// column wins, its high word orders the winners by distance (the larger, the farther), its low word is the winner's source -- the
-// fill of the row's holes from the farther side, and the colour rule of the point cloud.
+// column wins, its high word orders the winners by distance (the larger, the farther), its low word is the winner's source -- and the
+// fill of the row's holes from the farther side.  (The rules of the depth map and the colour image: scene.h.)
 #pragma once
-#include "rows.h"
+#include "scene.h"
 
 namespace prv2 {
 namespace {
 
 constexpr unsigned long long kHole = ~0ull;
-
-// the nearest sample of an axis of n_in values for position i of n_out
-__device__ __forceinline__ int nearest(int i, int n_out, int n_in) { return (int)(((int64_t)(2 * i + 1) * n_in) / (2 * (int64_t)n_out)); }
-
-// clamp(rint(v), 0, 255), ties to even, NaN -> 0
-__device__ __forceinline__ uint32_t stereo_byte(float v) {
-  const float r = rintf(v);
-  return !(r > 0.0f) ? 0u : r >= 255.0f ? 255u : (uint32_t)r;
-}
 
 // The fill of a row of w <= CAP keys in LDS, by a block of 256 lanes; lane tid owns the columns i * 256 + tid.  Call it after the
 // barrier that ends the writes of the keys.  shown: the winning source of a lane's columns (-1: hole); fill: the same, a hole taking

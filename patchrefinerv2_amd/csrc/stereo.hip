@@ -23,18 +23,17 @@ constexpr int kStereoMaxWidth = 8192;  // the widest row a workgroup keeps in LD
 
 struct StereoArgs {
   const float* depth;  // [n, h, w]
-  const float* image;  // [n, 3, ih, iw] (rows mode)
+  ImageSrc img;        // [n, 3, ih, iw] (rows mode)
   float k, c;          // fx * baseline, k / convergence
-  float lo, hi, thr;
-  int32_t h, w, ih, iw;
+  Camera cam;          // (the kernel reads its depth range; fx is in k)
+  float thr;
+  int32_t h, w;
   int32_t layout;      // PRV2_STEREO_RIGHT / _SBS / _ANAGLYPH (rows mode)
   uint8_t* rows;       // rows mode: scanlines of [h][1 + 3 wout], wout = w or 2 w (sbs)
   int64_t rows_fstride;
   int32_t* src;        // source mode: [n, h, w] each
   int32_t* filled;
 };
-
-__device__ __forceinline__ bool stereo_valid(const StereoArgs& a, float z) { return fabsf(z) < __builtin_inff() && z > a.lo && z < a.hi; }
 
 // the target column of source pixel x, in [-1, w]
 __device__ __forceinline__ int stereo_target(const StereoArgs& a, int x, float z) {
@@ -71,12 +70,12 @@ __global__ void __launch_bounds__(256) stereo_kernel(StereoArgs a) {
     const int x = i * 256 + tid;
     if (x >= w) continue;
     const float z = d[x];
-    if (!stereo_valid(a, z)) continue;
+    if (!valid_z(a.cam, z)) continue;
     const int t = stereo_target(a, x, z);
     int e = t;
     if (x + 1 < w) {
       const float zn = d[x + 1];
-      if (stereo_valid(a, zn) && (!(a.thr > 0.0f) || !(fabsf(__fsub_rn(z, zn)) > __fmul_rn(a.thr, fminf(z, zn))))) {
+      if (valid_z(a.cam, zn) && joined(a.thr, z, zn)) {
         const int tn = stereo_target(a, x + 1, zn) - 1;
         e = tn > t ? tn : t;
       }
@@ -110,29 +109,29 @@ __global__ void __launch_bounds__(256) stereo_kernel(StereoArgs a) {
   const int nb = (int)rowb + (y == a.h - 1 ? (int)((total + 15) / 16 * 16 - total) : 0);
   if (tid < 16) buf[shift + rowb + tid] = 0;
   if (tid == 0) buf[shift] = 0;
-  const float* img = a.image + (int64_t)f * 3 * a.ih * a.iw + (int64_t)nearest(y, a.h, a.ih) * a.iw;
-  const int64_t plane = (int64_t)a.ih * a.iw;
+  const float* img = a.img.frame(f) + (int64_t)nearest(y, a.h, a.img.ih) * a.img.iw;
+  const int64_t plane = a.img.plane();
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int q = i * 256 + tid;
     if (q >= w) continue;
     uint32_t r = 0, g = 0, b = 0;
     if (fill[i] >= 0) {
-      const float* c = img + nearest(fill[i], w, a.iw);
-      if (a.layout != PRV2_STEREO_ANAGLYPH) r = stereo_byte(__fmul_rn(c[0], 255.0f));
-      g = stereo_byte(__fmul_rn(c[plane], 255.0f));
-      b = stereo_byte(__fmul_rn(c[2 * plane], 255.0f));
+      const float* c = img + nearest(fill[i], w, a.img.iw);
+      if (a.layout != PRV2_STEREO_ANAGLYPH) r = color_byte(__fmul_rn(c[0], 255.0f));
+      g = color_byte(__fmul_rn(c[plane], 255.0f));
+      b = color_byte(__fmul_rn(c[2 * plane], 255.0f));
     }
     uint8_t* px = buf + shift + 1 + 3 * (a.layout == PRV2_STEREO_SBS ? w + q : q);
     if (a.layout != PRV2_STEREO_RIGHT) {  // the left eye: the image itself on the depth map's grid
-      const float* c = img + nearest(q, w, a.iw);
+      const float* c = img + nearest(q, w, a.img.iw);
       if (a.layout == PRV2_STEREO_ANAGLYPH) {
-        r = stereo_byte(__fmul_rn(c[0], 255.0f));
+        r = color_byte(__fmul_rn(c[0], 255.0f));
       } else {
         uint8_t* left = buf + shift + 1 + 3 * q;
-        left[0] = (uint8_t)stereo_byte(__fmul_rn(c[0], 255.0f));
-        left[1] = (uint8_t)stereo_byte(__fmul_rn(c[plane], 255.0f));
-        left[2] = (uint8_t)stereo_byte(__fmul_rn(c[2 * plane], 255.0f));
+        left[0] = (uint8_t)color_byte(__fmul_rn(c[0], 255.0f));
+        left[1] = (uint8_t)color_byte(__fmul_rn(c[plane], 255.0f));
+        left[2] = (uint8_t)color_byte(__fmul_rn(c[2 * plane], 255.0f));
       }
     }
     px[0] = (uint8_t)r, px[1] = (uint8_t)g, px[2] = (uint8_t)b;
@@ -144,14 +143,10 @@ __global__ void __launch_bounds__(256) stereo_kernel(StereoArgs a) {
 static int check_stereo(const char* name, const float* depth, int n, int h, int w, float fx, float baseline, float convergence, float lo, float hi,
                         float edge_thr) {
   PRV2_REQUIRE(depth != nullptr, "%s: null pointer (depth)", name);
-  if (check_map(name, n, h, w)) return 1;
-  PRV2_REQUIRE(w <= kStereoMaxWidth, "%s: a row of %d columns is wider than the %d a workgroup keeps in LDS (prv2_stereo_max_width)", name, w,
-               kStereoMaxWidth);
-  PRV2_REQUIRE(fx > 0.0f && fx < __builtin_inff(), "%s: focal length %g: finite and positive", name, (double)fx);
+  if (check_map(name, n, h, w) || check_row_width(name, w) || check_camera(name, fx, fx, 0.0f, 0.0f) || check_range(name, lo, hi, edge_thr)) return 1;
   PRV2_REQUIRE(fabsf(baseline) < __builtin_inff(), "%s: baseline %g: finite", name, (double)baseline);
   PRV2_REQUIRE(convergence == convergence && convergence != 0.0f, "%s: convergence %g: a distance other than 0 (inf: parallel axes)", name,
                (double)convergence);
-  PRV2_REQUIRE(lo == lo && hi == hi && edge_thr == edge_thr, "%s: NaN in the depth range or edge_thr", name);
   return 0;
 }
 
@@ -160,7 +155,7 @@ static StereoArgs stereo_args(const float* depth, int h, int w, float fx, float 
   a.depth = depth;
   a.k = fx * baseline;  // (fp32, one rounding: the host specification's k)
   a.c = fabsf(convergence) == __builtin_inff() ? 0.0f : a.k / convergence;
-  a.lo = lo, a.hi = hi, a.thr = thr;
+  a.cam = Camera{fx, fx, 0.0f, 0.0f, lo, hi}, a.thr = thr;
   a.h = h, a.w = w;
   return a;
 }
@@ -197,12 +192,11 @@ extern "C" int prv2_stereo_rows(const float* depth, const float* image, int32_t 
                                 int64_t rows_fstride, void* stream) {
   const char* name = "stereo_rows";
   if (check_stereo(name, depth, n, h, w, fx, baseline, convergence, lo, hi, edge_thr)) return 1;
-  PRV2_REQUIRE(image != nullptr, "%s: null pointer (image)", name);
-  PRV2_REQUIRE(ih >= 1 && iw >= 1 && (int64_t)n * 3 * ih * iw < (int64_t)INT_MAX, "%s: bad image shape %d x %d", name, ih, iw);
+  if (check_image(name, image, n, ih, iw)) return 1;
   PRV2_REQUIRE(layout == PRV2_STEREO_RIGHT || layout == PRV2_STEREO_SBS || layout == PRV2_STEREO_ANAGLYPH, "%s: layout %d", name, layout);
   if (check_rows(name, rows, rows_fstride, n, h, layout == PRV2_STEREO_SBS ? 2 * w : w, 3)) return 1;
   StereoArgs a = stereo_args(depth, h, w, fx, baseline, convergence, lo, hi, edge_thr);
-  a.image = image, a.ih = ih, a.iw = iw, a.layout = layout, a.rows = rows, a.rows_fstride = rows_fstride;
+  a.img = ImageSrc{image, ih, iw}, a.layout = layout, a.rows = rows, a.rows_fstride = rows_fstride;
   launch_stereo<true>(a, n, (hipStream_t)stream);
   PRV2_LAUNCH_CHECK(name);
   return 0;

@@ -1405,13 +1405,17 @@ const double* camera4(at::ArrayRef<double> k, const char* op) {
   TORCH_CHECK(k.size() == 4, "prv2::", op, ": intrinsics are fx, fy, cx, cy (got ", k.size(), " values)");
   return k.data();
 }
+// the depth frames and their colour image, of any size, as every export that samples it takes them
+void scene_image(const Tensor& depth, const Tensor& image, const char* op) {
+  dev_frames(depth, "depth", at::kFloat);
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
+                  image.size(1) == 3 && image.device() == depth.device(), "prv2::", op, ": image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+}
 // counts int64 [n]; frame f's records are vertices[f, :15 * counts[f]] (the rest of ``vertices`` is left as it is)
 Tensor pointcloud_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, double lo, double hi, double edge_thr,
                        int64_t stride, Tensor vertices) {
-  dev_frames(depth, "depth", at::kFloat);
+  scene_image(depth, image, "pointcloud_pack");
   const double* k = camera4(intrinsics, "pointcloud_pack");
-  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
-                  image.size(1) == 3 && image.device() == depth.device(), "prv2::pointcloud_pack: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
   const int n = (int)depth.size(0), h = (int)depth.size(1), w = (int)depth.size(2);
   const int64_t bytes = prv2_pointcloud_workspace_bytes(n, h, w), bound = prv2_pointcloud_bound(h, w, (int)stride);
   TORCH_CHECK(bytes > 0, "prv2::pointcloud_pack: bad frame shape ", depth.sizes());
@@ -1433,10 +1437,8 @@ Tensor pointcloud_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<do
 // pixels.  -> (N, M) int64 [n]; frame f's faces are faces[f, :13 * M[f]] (the rest of ``faces`` is left as it is)
 std::tuple<Tensor, Tensor> mesh_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, double lo, double hi, double edge_thr,
                                      int64_t stride, Tensor vertices, Tensor faces) {
-  dev_frames(depth, "depth", at::kFloat);
+  scene_image(depth, image, "mesh_pack");
   const double* k = camera4(intrinsics, "mesh_pack");
-  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
-                  image.size(1) == 3 && image.device() == depth.device(), "prv2::mesh_pack: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
   const int n = (int)depth.size(0), h = (int)depth.size(1), w = (int)depth.size(2);
   TORCH_CHECK(stride >= 1 && stride <= INT_MAX, "prv2::mesh_pack: stride ", stride, " < 1");
   const int64_t cloud_bytes = prv2_pointcloud_workspace_bytes(n, h, w), bytes = prv2_mesh_workspace_bytes(n, h, w, (int)stride);
@@ -1491,10 +1493,8 @@ std::tuple<Tensor, Tensor> stereo_source(const Tensor& depth, double fx, double 
 }
 Tensor stereo_rows(const Tensor& depth, const Tensor& image, double fx, double baseline, double convergence, double lo, double hi, double edge_thr,
                    int64_t layout) {
-  dev_frames(depth, "depth", at::kFloat);
+  scene_image(depth, image, "stereo_rows");
   stereo_width(depth, "stereo_rows");
-  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
-                  image.size(1) == 3 && image.device() == depth.device(), "prv2::stereo_rows: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
   TORCH_CHECK(layout == PRV2_STEREO_RIGHT || layout == PRV2_STEREO_SBS || layout == PRV2_STEREO_ANAGLYPH, "prv2::stereo_rows: layout ", layout);
   const int64_t wout = depth.size(2) * (layout == PRV2_STEREO_SBS ? 2 : 1);
   const int64_t bytes = prv2_rows_bytes((int)depth.size(1), (int)wout, 3);
@@ -1509,14 +1509,9 @@ Tensor stereo_rows(const Tensor& depth, const Tensor& image, double fx, double b
 
 // depth-of-field export (include/prv2.h "Depth-of-field export"): B frames re-rendered through a thin lens -> (fp32 planes or scanlines,
 // the focus distance every frame used)
-void bokeh_image(const Tensor& depth, const Tensor& image, const char* op) {
-  dev_frames(depth, "depth", at::kFloat);
-  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == depth.size(0) &&
-                  image.size(1) == 3 && image.device() == depth.device(), "prv2::", op, ": image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
-}
 std::tuple<Tensor, Tensor> bokeh_render(const Tensor& depth, const Tensor& image, double fx, double aperture, double focus, double focus_u,
                                         double focus_v, double max_radius, double lo, double hi) {
-  bokeh_image(depth, image, "bokeh_render");
+  scene_image(depth, image, "bokeh_render");
   Tensor out = at::empty({depth.size(0), 3, depth.size(1), depth.size(2)}, depth.options());
   Tensor used = at::empty({depth.size(0)}, depth.options());
   Launch L(depth);
@@ -1527,7 +1522,7 @@ std::tuple<Tensor, Tensor> bokeh_render(const Tensor& depth, const Tensor& image
 }
 std::tuple<Tensor, Tensor> bokeh_rows(const Tensor& depth, const Tensor& image, double fx, double aperture, double focus, double focus_u,
                                       double focus_v, double max_radius, double lo, double hi) {
-  bokeh_image(depth, image, "bokeh_rows");
+  scene_image(depth, image, "bokeh_rows");
   Tensor rows = alloc_rows(depth, 3);
   Tensor used = at::empty({depth.size(0)}, depth.options());
   Launch L(depth);
@@ -1565,7 +1560,7 @@ std::tuple<Tensor, Tensor, Tensor> view_source(const Tensor& depth, at::ArrayRef
 }
 Tensor view_rows(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, const Tensor& poses, double lo, double hi, double edge_thr) {
   Tensor ws = view_workspace(depth, poses, "view_rows");
-  bokeh_image(depth, image, "view_rows");
+  scene_image(depth, image, "view_rows");
   const double* k = camera4(intrinsics, "view_rows");
   const int64_t bytes = prv2_rows_bytes((int)depth.size(1), (int)depth.size(2), 3);
   TORCH_CHECK(bytes > 0, "prv2::view_rows: bad frame shape ", depth.sizes());

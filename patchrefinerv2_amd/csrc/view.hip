@@ -27,10 +27,11 @@ constexpr int kUnseen = INT_MIN;  // ux of a vertex that is not seen
 
 struct ViewArgs {
   const float* depth;  // [n, h, w]
-  const float* image;  // [n, 3, ih, iw] (rows mode)
+  ImageSrc img;        // [n, 3, ih, iw] (rows mode)
   const float* poses;  // [nv, 12]
-  float fx, fy, cx, cy, lo, hi, thr;
-  int32_t h, w, ih, iw, nv;
+  Camera cam;
+  float thr;
+  int32_t h, w, nv;
   unsigned long long* keys;  // [n, nv, h, w]
   int32_t* src;        // source mode: [n, nv, h, w] each
   int32_t* filled;
@@ -46,10 +47,6 @@ struct Vert {
 
 __device__ __forceinline__ unsigned long long view_key(float q, int source) {
   return (unsigned long long)(0xFFFFFFFFu - __float_as_uint(q)) << 32 | (unsigned)source;
-}
-
-__device__ __forceinline__ bool view_joined(float thr, float zp, float zq) {  // (both valid)
-  return !(thr > 0.0f) || !(fabsf(__fsub_rn(zp, zq)) > __fmul_rn(thr, fminf(zp, zq)));
 }
 
 __global__ void __launch_bounds__(256) view_clear(uint4* keys4, int64_t n16, unsigned long long* tail) {
@@ -107,14 +104,14 @@ __global__ void __launch_bounds__(256) view_raster(ViewArgs a) {
     p.ux = kUnseen, p.uy = 0, p.iz = 0.0f, p.z = __builtin_nanf("");
     if (x < w && y < h) {
       const float z = d[(int64_t)y * w + x];
-      if (fabsf(z) < __builtin_inff() && z > a.lo && z < a.hi) {
+      if (valid_z(a.cam, z)) {
         p.z = z;
-        const float X = __fdiv_rn((((float)x + 0.5f) - a.cx) * z, a.fx), Y = __fdiv_rn((((float)y + 0.5f) - a.cy) * z, a.fy);
+        const float X = cam_x(a.cam, x, z), Y = cam_y(a.cam, y, z);
         const float xc = ((m[0] * X + m[1] * Y) + m[2] * z) + m[3];
         const float yc = ((m[4] * X + m[5] * Y) + m[6] * z) + m[7];
         const float zc = ((m[8] * X + m[9] * Y) + m[10] * z) + m[11];
         const float iz = __fdiv_rn(1.0f, zc);
-        const float fu = a.fx * __fdiv_rn(xc, zc) + a.cx, fv = a.fy * __fdiv_rn(yc, zc) + a.cy;
+        const float fu = a.cam.fx * __fdiv_rn(xc, zc) + a.cam.cx, fv = a.cam.fy * __fdiv_rn(yc, zc) + a.cam.cy;
         if (fabsf(zc) < __builtin_inff() && zc > 0.0f && fabsf(iz) < __builtin_inff() && fabsf(fu) < 65536.0f && fabsf(fv) < 65536.0f) {
           p.ux = (int)rintf(fu * 16.0f), p.uy = (int)rintf(fv * 16.0f), p.iz = iz;
         }
@@ -136,20 +133,16 @@ __global__ void __launch_bounds__(256) view_raster(ViewArgs a) {
     }
     if (x + 1 >= w || y + 1 >= h) continue;
     const Vert B = vert[ly * kVertW + lx + 1], C = vert[(ly + 1) * kVertW + lx], D = vert[(ly + 1) * kVertW + lx + 1];
-    const bool ka = A.z == A.z, kb = B.z == B.z, kc = C.z == C.z, kd = D.z == D.z;
-    const int kept = (int)ka + (int)kb + (int)kc + (int)kd;
-    if (kept < 3) continue;
-    const bool ad = kept == 4 ? fabsf(__fsub_rn(A.z, D.z)) <= fabsf(__fsub_rn(B.z, C.z)) : (ka && kd);
+    // the cell's faces (a corner is kept where its Z is valid), each drawn where its three vertices are seen
+    const CellFaces cf = cell_rule(a.thr, A.z, B.z, C.z, D.z, A.z == A.z, B.z == B.z, C.z == C.z, D.z == D.z);
+    const bool sa = A.ux != kUnseen, sb = B.ux != kUnseen, sc = C.ux != kUnseen, sd = D.ux != kUnseen;
     const int ib = ia + 1, ic = ia + w, id = ia + w + 1;
-    const float thr = a.thr;
-    if (ad) {  // (a, c, d) then (a, d, b)
-      const bool j_ad = view_joined(thr, A.z, D.z) && A.ux != kUnseen && D.ux != kUnseen;
-      if (j_ad && kc && C.ux != kUnseen && view_joined(thr, A.z, C.z) && view_joined(thr, C.z, D.z)) view_face(keys, h, w, A, C, D, ia, ic, id);
-      if (j_ad && kb && B.ux != kUnseen && view_joined(thr, D.z, B.z) && view_joined(thr, A.z, B.z)) view_face(keys, h, w, A, D, B, ia, id, ib);
-    } else {   // (a, c, b) then (b, c, d)
-      const bool j_bc = kb && kc && view_joined(thr, B.z, C.z) && B.ux != kUnseen && C.ux != kUnseen;
-      if (j_bc && ka && A.ux != kUnseen && view_joined(thr, A.z, C.z) && view_joined(thr, A.z, B.z)) view_face(keys, h, w, A, C, B, ia, ic, ib);
-      if (j_bc && kd && D.ux != kUnseen && view_joined(thr, C.z, D.z) && view_joined(thr, B.z, D.z)) view_face(keys, h, w, B, C, D, ib, ic, id);
+    if (cf.ad) {  // (a, c, d) then (a, d, b)
+      if (cf.first && sa && sc && sd) view_face(keys, h, w, A, C, D, ia, ic, id);
+      if (cf.second && sa && sd && sb) view_face(keys, h, w, A, D, B, ia, id, ib);
+    } else {      // (a, c, b) then (b, c, d)
+      if (cf.first && sa && sc && sb) view_face(keys, h, w, A, C, B, ia, ic, ib);
+      if (cf.second && sb && sc && sd) view_face(keys, h, w, B, C, D, ib, ic, id);
     }
   }
 }
@@ -191,8 +184,8 @@ __global__ void __launch_bounds__(256) view_resolve(ViewArgs a) {
   const int nb = (int)rowb + (y == a.h - 1 ? (int)((total + 15) / 16 * 16 - total) : 0);
   if (tid < 16) buf[shift + rowb + tid] = 0;
   if (tid == 0) buf[shift] = 0;
-  const float* img = a.image + (int64_t)f * 3 * a.ih * a.iw;
-  const int64_t plane = (int64_t)a.ih * a.iw;
+  const float* img = a.img.frame(f);
+  const int64_t plane = a.img.plane();
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const int q = i * 256 + tid;
@@ -200,10 +193,10 @@ __global__ void __launch_bounds__(256) view_resolve(ViewArgs a) {
     uint32_t r = 0, g = 0, b = 0;
     if (fill[i] >= 0) {
       const int sy = fill[i] / w, sx = fill[i] - sy * w;
-      const float* c = img + (int64_t)nearest(sy, a.h, a.ih) * a.iw + nearest(sx, w, a.iw);
-      r = stereo_byte(__fmul_rn(c[0], 255.0f));
-      g = stereo_byte(__fmul_rn(c[plane], 255.0f));
-      b = stereo_byte(__fmul_rn(c[2 * plane], 255.0f));
+      const float* c = img + (int64_t)nearest(sy, a.h, a.img.ih) * a.img.iw + nearest(sx, w, a.img.iw);
+      r = color_byte(__fmul_rn(c[0], 255.0f));
+      g = color_byte(__fmul_rn(c[plane], 255.0f));
+      b = color_byte(__fmul_rn(c[2 * plane], 255.0f));
     }
     uint8_t* px = buf + shift + 1 + 3 * q;
     px[0] = (uint8_t)r, px[1] = (uint8_t)g, px[2] = (uint8_t)b;
@@ -225,11 +218,7 @@ static int check_view(const char* name, const float* depth, int n, int h, int w,
   if (check_map(name, n, h, w)) return 1;
   PRV2_REQUIRE(nv >= 1 && nv <= 65535, "%s: view count %d out of range [1, 65535]", name, nv);
   PRV2_REQUIRE(view_pixels(n, nv, h, w) > 0, "%s: %d frames x %d views of %d x %d exceed 2^29 pixels", name, n, nv, h, w);
-  PRV2_REQUIRE(w <= prv2_stereo_max_width(), "%s: a row of %d columns is wider than the %d a workgroup keeps in LDS (prv2_stereo_max_width)", name, w,
-               prv2_stereo_max_width());
-  PRV2_REQUIRE(fx > 0.0f && fx < __builtin_inff() && fy > 0.0f && fy < __builtin_inff() && fabsf(cx) < __builtin_inff() && fabsf(cy) < __builtin_inff(),
-               "%s: intrinsics %g %g %g %g: finite, fx and fy positive", name, (double)fx, (double)fy, (double)cx, (double)cy);
-  PRV2_REQUIRE(lo == lo && hi == hi && edge_thr == edge_thr, "%s: NaN in the depth range or edge_thr", name);
+  if (check_row_width(name, w) || check_camera(name, fx, fy, cx, cy) || check_range(name, lo, hi, edge_thr)) return 1;
   PRV2_REQUIRE(workspace != nullptr && aligned16(workspace), "%s: the workspace must be 16-byte aligned", name);
   PRV2_REQUIRE(workspace_bytes >= 8 * view_pixels(n, nv, h, w), "%s: workspace of %lld bytes, %lld needed (prv2_view_workspace_bytes)", name,
                (long long)workspace_bytes, (long long)(8 * view_pixels(n, nv, h, w)));
@@ -240,7 +229,7 @@ static ViewArgs view_args(const float* depth, int h, int w, float fx, float fy, 
                           float thr, void* workspace) {
   ViewArgs a{};
   a.depth = depth, a.poses = poses;
-  a.fx = fx, a.fy = fy, a.cx = cx, a.cy = cy, a.lo = lo, a.hi = hi, a.thr = thr;
+  a.cam = Camera{fx, fy, cx, cy, lo, hi}, a.thr = thr;
   a.h = h, a.w = w, a.nv = nv;
   a.keys = (unsigned long long*)workspace;
   return a;
@@ -299,11 +288,10 @@ extern "C" int prv2_view_rows(const float* depth, const float* image, int32_t n,
                               int64_t rows_vstride, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* name = "view_rows";
   if (check_view(name, depth, n, h, w, fx, fy, cx, cy, poses, nv, lo, hi, edge_thr, workspace, workspace_bytes)) return 1;
-  PRV2_REQUIRE(image != nullptr, "%s: null pointer (image)", name);
-  PRV2_REQUIRE(ih >= 1 && iw >= 1 && (int64_t)n * 3 * ih * iw < (int64_t)INT_MAX, "%s: bad image shape %d x %d", name, ih, iw);
+  if (check_image(name, image, n, ih, iw)) return 1;
   if (check_rows(name, rows, rows_vstride, n, h, w, 3)) return 1;
   ViewArgs a = view_args(depth, h, w, fx, fy, cx, cy, poses, nv, lo, hi, edge_thr, workspace);
-  a.image = image, a.ih = ih, a.iw = iw, a.rows = rows, a.rows_vstride = rows_vstride;
+  a.img = ImageSrc{image, ih, iw}, a.rows = rows, a.rows_vstride = rows_vstride;
   launch_view<true>(a, n, (hipStream_t)stream);
   PRV2_LAUNCH_CHECK(name);
   return 0;

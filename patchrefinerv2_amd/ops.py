@@ -1773,22 +1773,41 @@ def _camera(intrinsics, depth_range, what):
     return k, (lo, hi)
 
 
-def _cloud_inputs(what, depth, image, intrinsics, depth_range, edge_thr, stride):
-    """the arguments pointcloud_pack and mesh_pack share, checked -> (frames fp32 [B, H, W], image fp32 [B, 3, Hi, Wi], k, lo, hi,
-    edge_thr, stride)"""
+_NO_IMAGE = object()  # the export samples no image
+
+
+def _scene_inputs(what, depth, intrinsics, depth_range, image=_NO_IMAGE, edge_thr=None, max_width=False):
+    """the arguments every export computed from a depth map shares, checked -> (frames fp32 [B, H, W], image fp32 [B, 3, Hi, Wi] or
+    None, k, lo, hi, edge_thr or None) with the scalars as Python floats that hold float32 values.  ``max_width``: the frames' rows
+    must fit prv2_stereo_max_width()"""
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
+        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
     d = _edge_frames(depth, torch.float32)
     k, (lo, hi) = _camera(intrinsics, depth_range, what)
-    stride, thr = int(stride), float(np.float32(edge_thr))
-    if stride < 1:
-        raise ValueError(f"{what}: stride {stride} < 1")
-    if math.isnan(thr):
-        raise ValueError(f"{what}: edge_thr must not be NaN")
+    thr = None
+    if edge_thr is not None:
+        thr = float(np.float32(edge_thr))
+        if math.isnan(thr):
+            raise ValueError(f"{what}: edge_thr must not be NaN")
+    if max_width:
+        limit = L.load().prv2_stereo_max_width()
+        if d.shape[2] > limit:
+            raise ValueError(f"{what}: a row of {d.shape[2]} columns is wider than the {limit} the kernel keeps in LDS (prv2_stereo_max_width)")
+    if image is _NO_IMAGE:
+        return d, None, k, lo, hi, thr
     if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
         raise ValueError(f"{what}: image is a GPU tensor on the depth map's device")
     img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
     if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
         raise ValueError(f"{what}: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
-    return d, img, k, lo, hi, thr, stride
+    return d, img, k, lo, hi, thr
+
+
+def _cloud_inputs(what, depth, image, intrinsics, depth_range, edge_thr, stride):
+    """``_scene_inputs`` of pointcloud_pack and mesh_pack, and their stride"""
+    if int(stride) < 1:
+        raise ValueError(f"{what}: stride {int(stride)} < 1")
+    return (*_scene_inputs(what, depth, intrinsics, depth_range, image, edge_thr), int(stride))
 
 
 def _record_buffer(what, out, d, bound):
@@ -1858,8 +1877,7 @@ def mesh_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.
 def normal_rows(depth, intrinsics, depth_range=(0.0, math.inf)):
     """the camera-facing surface normals of fp32 depth frames [B, H, W] as RGB scanlines (n * 0.5 + 0.5 in bytes; (0, 0, 0)
     where there is no normal) -> scanline buffer (include/prv2.h prv2_normal_rows)"""
-    d = _edge_frames(depth, torch.float32)
-    k, (lo, hi) = _camera(intrinsics, depth_range, "normal_rows")
+    d, _, k, lo, hi, _ = _scene_inputs("normal_rows", depth, intrinsics, depth_range)
     if DISPATCH == "torch":
         return _tops().normal_rows(d, k, lo, hi)
     rows = _rows(d, 3)
@@ -1874,24 +1892,16 @@ def normal_rows(depth, intrinsics, depth_range=(0.0, math.inf)):
 STEREO_LAYOUTS = {"right": 0, "sbs": 1, "anaglyph": 2}  # PRV2_STEREO_RIGHT / _SBS / _ANAGLYPH
 
 
-def _stereo_inputs(what, depth, intrinsics, baseline, convergence, depth_range, edge_thr):
-    """the arguments stereo_rows and stereo_source share, checked -> (frames fp32 [B, H, W], fx, baseline, convergence, lo, hi,
-    edge_thr) with the scalars as Python floats that hold float32 values"""
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
-        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
-    d = _edge_frames(depth, torch.float32)
-    k, (lo, hi) = _camera(intrinsics, depth_range, what)
-    base, conv, thr = (float(np.float32(v)) for v in (baseline, convergence, edge_thr))
+def _stereo_inputs(what, depth, intrinsics, baseline, convergence, depth_range, edge_thr, image=_NO_IMAGE):
+    """``_scene_inputs`` of stereo_rows and stereo_source, and their baseline and convergence -> (frames, image or None, fx, baseline,
+    convergence, lo, hi, edge_thr)"""
+    d, img, k, lo, hi, thr = _scene_inputs(what, depth, intrinsics, depth_range, image, edge_thr, max_width=True)
+    base, conv = float(np.float32(baseline)), float(np.float32(convergence))
     if not math.isfinite(base):
         raise ValueError(f"{what}: baseline {baseline} must be finite")
     if math.isnan(conv) or conv == 0.0:
         raise ValueError(f"{what}: convergence {convergence}: a distance other than 0 (inf: parallel axes)")
-    if math.isnan(thr):
-        raise ValueError(f"{what}: edge_thr must not be NaN")
-    limit = L.load().prv2_stereo_max_width()
-    if d.shape[2] > limit:
-        raise ValueError(f"{what}: a row of {d.shape[2]} columns is wider than the {limit} the kernel keeps in LDS (prv2_stereo_max_width)")
-    return d, k[0], base, conv, lo, hi, thr
+    return d, img, k[0], base, conv, lo, hi, thr
 
 
 def stereo_source(depth, intrinsics, baseline, convergence=math.inf, depth_range=(0.0, math.inf), edge_thr=0.05):
@@ -1899,7 +1909,7 @@ def stereo_source(depth, intrinsics, baseline, convergence=math.inf, depth_range
     source column every column of the view shows (-1: a hole), and the same with the holes filled from the farther side
     (output.stereo_source_host; include/prv2.h prv2_stereo_source).  ``intrinsics``: fx, fy, cx, cy of the [H, W] grid (fx is used);
     ``baseline``: metres to the right; ``convergence``: the depth that keeps its column (inf: parallel axes)."""
-    d, fx, base, conv, lo, hi, thr = _stereo_inputs("stereo_source", depth, intrinsics, baseline, convergence, depth_range, edge_thr)
+    d, _, fx, base, conv, lo, hi, thr = _stereo_inputs("stereo_source", depth, intrinsics, baseline, convergence, depth_range, edge_thr)
     if DISPATCH == "torch":
         return tuple(_tops().stereo_source(d, fx, base, conv, lo, hi, thr))
     src, filled = torch.empty(d.shape, dtype=torch.int32, device=d.device), torch.empty(d.shape, dtype=torch.int32, device=d.device)
@@ -1914,12 +1924,7 @@ def stereo_rows(depth, image, intrinsics, baseline, convergence=math.inf, depth_
     for one frame), any size, sampled nearest; the other arguments as ``stereo_source``."""
     if layout not in STEREO_LAYOUTS:
         raise ValueError(f"stereo_rows: layout {layout!r}: one of {tuple(STEREO_LAYOUTS)}")
-    d, fx, base, conv, lo, hi, thr = _stereo_inputs("stereo_rows", depth, intrinsics, baseline, convergence, depth_range, edge_thr)
-    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
-        raise ValueError("stereo_rows: image is a GPU tensor on the depth map's device")
-    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
-    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
-        raise ValueError(f"stereo_rows: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    d, img, fx, base, conv, lo, hi, thr = _stereo_inputs("stereo_rows", depth, intrinsics, baseline, convergence, depth_range, edge_thr, image)
     if DISPATCH == "torch":
         return _tops().stereo_rows(d, img, fx, base, conv, lo, hi, thr, STEREO_LAYOUTS[layout])
     wout = d.shape[2] * (2 if layout == "sbs" else 1)
@@ -1939,12 +1944,9 @@ def bokeh_max_radius() -> int:
 
 
 def _bokeh_inputs(what, depth, image, intrinsics, aperture, focus, focus_point, max_radius, depth_range):
-    """the arguments bokeh_render and bokeh_rows share, checked -> (frames fp32 [B, H, W], image fp32 [B, 3, Hi, Wi], fx, aperture,
-    focus (0.0: use the focus point), u, v, max_radius, lo, hi) with the scalars as Python floats that hold float32 values"""
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
-        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
-    d = _edge_frames(depth, torch.float32)
-    k, (lo, hi) = _camera(intrinsics, depth_range, what)
+    """``_scene_inputs`` of bokeh_render and bokeh_rows, and their lens -> (frames, image, fx, aperture, focus (0.0: use the focus
+    point), u, v, max_radius, lo, hi)"""
+    d, img, k, lo, hi, _ = _scene_inputs(what, depth, intrinsics, depth_range, image)
     ap, rm = float(np.float32(aperture)), float(np.float32(max_radius))
     if not (math.isfinite(ap) and ap >= 0.0):
         raise ValueError(f"{what}: aperture {aperture}: finite and not below 0 (metres)")
@@ -1958,11 +1960,6 @@ def _bokeh_inputs(what, depth, image, intrinsics, aperture, focus, focus_point, 
     u, v = (float(np.float32(c)) for c in focus_point)
     if not (0.0 <= u <= 1.0 and 0.0 <= v <= 1.0):
         raise ValueError(f"{what}: focus point {tuple(focus_point)} outside [0, 1]^2")
-    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
-        raise ValueError(f"{what}: image is a GPU tensor on the depth map's device")
-    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
-    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
-        raise ValueError(f"{what}: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
     return d, img, k[0], ap, zf, u, v, rm, lo, hi
 
 
@@ -2016,16 +2013,10 @@ def view_max_face() -> int:
     return int(L.load().prv2_view_max_face())
 
 
-def _view_inputs(what, depth, intrinsics, poses, depth_range, edge_thr):
-    """the arguments view_source and view_rows share, checked -> (frames fp32 [B, H, W], k, poses fp32 [NV, 12] on the frames'
-    device, lo, hi, edge_thr, workspace bytes)"""
-    if not isinstance(depth, torch.Tensor) or not depth.is_cuda or depth.dim() not in (2, 3):
-        raise ValueError(f"{what}: depth is a GPU tensor [H, W] or [B, H, W]")
-    d = _edge_frames(depth, torch.float32)
-    k, (lo, hi) = _camera(intrinsics, depth_range, what)
-    thr = float(np.float32(edge_thr))
-    if math.isnan(thr):
-        raise ValueError(f"{what}: edge_thr must not be NaN")
+def _view_inputs(what, depth, intrinsics, poses, depth_range, edge_thr, image=_NO_IMAGE):
+    """``_scene_inputs`` of view_source and view_rows, and their poses -> (frames, image or None, k, poses fp32 [NV, 12] on the
+    frames' device, lo, hi, edge_thr, workspace bytes)"""
+    d, img, k, lo, hi, thr = _scene_inputs(what, depth, intrinsics, depth_range, image, edge_thr, max_width=True)
     if isinstance(poses, torch.Tensor):
         p = poses.detach().to(torch.float32)
     else:
@@ -2034,13 +2025,10 @@ def _view_inputs(what, depth, intrinsics, poses, depth_range, edge_thr):
         p = p[None]
     if p.dim() != 2 or p.shape[0] < 1 or p.shape[1] != 12:
         raise ValueError(f"{what}: poses are [NV, 12] (or [12]): row-major 3 x 4 matrices [R | t] (got {tuple(p.shape)})")
-    limit = L.load().prv2_stereo_max_width()
-    if d.shape[2] > limit:
-        raise ValueError(f"{what}: a row of {d.shape[2]} columns is wider than the {limit} the kernel keeps in LDS (prv2_stereo_max_width)")
     nbytes = L.load().prv2_view_workspace_bytes(d.shape[0], min(p.shape[0], 2 ** 31 - 1), d.shape[1], d.shape[2])
     if nbytes <= 0:
         raise ValueError(f"{what}: {d.shape[0]} frames x {p.shape[0]} views of {d.shape[1]} x {d.shape[2]} exceed 2^29 pixels")
-    return d, k, p.to(d.device).contiguous(), lo, hi, thr, int(nbytes)
+    return d, img, k, p.to(d.device).contiguous(), lo, hi, thr, int(nbytes)
 
 
 def view_source(depth, intrinsics, poses, depth_range=(0.0, math.inf), edge_thr=0.05):
@@ -2049,7 +2037,7 @@ def view_source(depth, intrinsics, poses, depth_range=(0.0, math.inf), edge_thr=
     pixel y * W + x every pixel of every view shows (-1: a hole), the same with the holes filled from the farther side, and the
     winners' 1 / Zc (0: a hole) -- output.view_source_host for every (frame, pose); include/prv2.h prv2_view_source.
     ``intrinsics``: fx, fy, cx, cy of the [H, W] grid."""
-    d, k, p, lo, hi, thr, nbytes = _view_inputs("view_source", depth, intrinsics, poses, depth_range, edge_thr)
+    d, _, k, p, lo, hi, thr, nbytes = _view_inputs("view_source", depth, intrinsics, poses, depth_range, edge_thr)
     box = []
     if DISPATCH == "torch":
         call = lambda: box.extend(_tops().view_source(d, k, p, lo, hi, thr))  # noqa: E731
@@ -2069,12 +2057,7 @@ def view_rows(depth, image, intrinsics, poses, depth_range=(0.0, math.inf), edge
     """``view_source``'s views as RGB scanlines -> scanline buffers uint8 [B, NV, prv2_rows_bytes(H, W, 3)]: the bytes of
     output.view_image_host for every (frame, pose) (include/prv2.h prv2_view_rows).  ``image``: fp32 [B, 3, Hi, Wi] ([3, Hi, Wi] for
     one frame), any size, sampled nearest; the other arguments as ``view_source``."""
-    d, k, p, lo, hi, thr, nbytes = _view_inputs("view_rows", depth, intrinsics, poses, depth_range, edge_thr)
-    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.device != d.device:
-        raise ValueError("view_rows: image is a GPU tensor on the depth map's device")
-    img = (image[None] if image.dim() == 3 else image).to(torch.float32).contiguous()
-    if img.dim() != 4 or img.shape[0] != d.shape[0] or img.shape[1] != 3 or img.shape[2] < 1 or img.shape[3] < 1:
-        raise ValueError(f"view_rows: image is [B, 3, Hi, Wi] with the depth map's B = {d.shape[0]} (got {tuple(image.shape)})")
+    d, img, k, p, lo, hi, thr, nbytes = _view_inputs("view_rows", depth, intrinsics, poses, depth_range, edge_thr, image)
     box = []
     if DISPATCH == "torch":
         call = lambda: box.append(_tops().view_rows(d, img, k, p, lo, hi, thr))  # noqa: E731

@@ -18,13 +18,16 @@ DEV = "cuda"
 F32 = np.float32
 INF = float("inf")
 INVALID = np.array([np.nan, np.inf, -np.inf, 0.0, -1.5, 0.2, 9.0], dtype=F32)
-# (frames, rows, columns), max_radius, image size as a multiple of the map's
+# (frames, rows, columns), max_radius, image size as a multiple of the map's (or its rows and columns)
 CASES = [((1, 1, 1), 4.0, 1),      # the smallest frame
          ((1, 5, 9), 8.0, 1),      # a window larger than the frame
          ((1, 37, 53), 5.0, 1),    # ragged in both directions against the tile
          ((2, 64, 80), 8.0, 1),    # two frames, the second with another depth under the focus point; four tile rows, two tile columns
          ((1, 9, 300), None, 1),   # one tile row, the widest window (None: the cap)
          ((1, 130, 70), 2.5, 2)]   # a fractional radius, the image at twice the map's size
+# the two branches of the image's nearest sampling (csrc/scene.h nearest) that CASES leaves out
+SAMPLING = [((1, 37, 53), 5.0, (23, 91)),  # no multiple of the map's size: the division, with a remainder
+            ((1, 1, 300), 8.0, 1)]         # the map's size on a ragged row: the shortcut
 SCENES = ("bar_sharp", "bar_blur", "slant", "random", "invalid", "invalid_focus", "in_focus")
 torch.set_grad_enabled(False)
 
@@ -95,12 +98,13 @@ def _host(name, case):
     from patchrefinerv2_amd.output import bokeh_render_host
     shape, rm, scale = case
     rm = _cap() if rm is None else rm
-    key = (name, shape, rm)
+    key = (name, shape, rm, scale)
     if key not in _HOST:
         B, h, w = shape
         d, kw = _scene(name, B, h, w, rm)
         k = _camera(h, w)
-        img = np.stack([_image(h * scale, w * scale, f) for f in range(B)])
+        hi, wi = scale if isinstance(scale, tuple) else (h * scale, w * scale)
+        img = np.stack([_image(hi, wi, f) for f in range(B)])
         res = [bokeh_render_host(d[f], img[f], k, **kw) for f in range(B)]
         _HOST[key] = (d, img, k, kw, np.stack([r[0] for r in res]), np.array([r[1] for r in res], dtype=F32))
     return _HOST[key]
@@ -152,6 +156,21 @@ def test_planes_focus_and_rows_equal_the_host_specification(ops, case, name):
         assert not np.array_equal(want, _sampled(img, h, w))
     if name == "random" and B == 2:
         assert focus.tolist() == [2.5, 3.5]
+
+
+@pytest.mark.parametrize("case", SAMPLING, ids=lambda c: "x".join(map(str, c[0])))
+def test_image_sampling_branches_equal_the_host_specification(ops, case):
+    (B, h, w), _, _ = case
+    d, img, k, kw, want, focus = _host("random", case)
+    assert (img.shape[2:] == (h, w)) == (case[2] == 1)
+    dd, di = torch.from_numpy(d).to(DEV), torch.from_numpy(img).to(DEV)
+    out, used = ops.bokeh_render(dd, di, k, **kw)
+    assert torch.equal(out.cpu(), torch.from_numpy(want)), int((out.cpu().numpy() != want).sum())
+    assert _same_floats(used.cpu().numpy(), focus), (used.cpu().numpy(), focus)
+    rows, used = ops.bokeh_rows(dd, di, k, **kw)
+    got = _rows_to_image(rows, h, w)
+    assert np.array_equal(got, _to_bytes(want)), int((got != _to_bytes(want)).sum())
+    assert _same_floats(used.cpu().numpy(), focus)
 
 
 def test_a_batch_equals_its_frames_alone_and_a_second_call(ops):

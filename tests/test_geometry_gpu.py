@@ -189,6 +189,32 @@ def test_wrappers_validate_their_arguments(ops):
         ops.normal_rows(d, [0.0, 5.0, 2.5, 2.0])
 
 
+def test_the_exports_share_one_wording_of_the_shared_checks(ops):
+    """pointcloud_pack, stereo_rows, bokeh_rows and view_rows make one check of the image and of edge_thr (ops._scene_inputs), not four:
+    the same wrong argument gets the same message behind the op's name"""
+    d, img, k = torch.ones(1, 4, 5, device=DEV), torch.ones(1, 3, 4, 5, device=DEV), [5.0, 5.0, 2.5, 2.0]
+    pose = np.eye(4, dtype=F32)[:3].reshape(12)
+    calls = {"pointcloud_pack": lambda image, **kw: ops.pointcloud_pack(d, image, k, **kw),
+             "stereo_rows": lambda image, **kw: ops.stereo_rows(d, image, k, 0.1, **kw),
+             "view_rows": lambda image, **kw: ops.view_rows(d, image, k, pose, **kw),
+             "bokeh_rows": lambda image, **kw: ops.bokeh_rows(d, image, k, **kw)}
+
+    def messages(names, image, **kw):
+        out = []
+        for name in names:
+            with pytest.raises(ValueError) as e:
+                calls[name](image, **kw)
+            assert str(e.value).startswith(name + ": ")
+            out.append(str(e.value)[len(name) + 2:])
+        return out
+
+    for image in (torch.ones(2, 3, 4, 5, device=DEV), img.cpu()):
+        got = messages(list(calls), image)
+        assert len(set(got)) == 1 and "image" in got[0], got
+    got = messages(list(calls)[:3], img, edge_thr=float("nan"))  # (the depth of field takes no threshold)
+    assert len(set(got)) == 1 and "edge_thr" in got[0], got
+
+
 # ------------------------------------------------------------------------------------------------------------------ Tester
 def _model_and_data(tmp_path):
     from patchrefinerv2_amd import models, weights as W  # noqa: F401  (registers the model classes)

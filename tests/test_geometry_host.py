@@ -266,3 +266,8 @@ def test_wrappers_validate_before_touching_the_gpu():
         ops._camera([1.0, 1.0, 2.0, 2.0], (float("nan"), 1.0), "x")
     k, (lo, hi) = ops._camera(np.array([0.1, 0.2, 0.3, 0.4]), (0.0, float("inf")), "x")
     assert k == [float(F32(v)) for v in (0.1, 0.2, 0.3, 0.4)] and lo == 0.0 and hi == float("inf")
+    d, img, K = torch.zeros(1, 4, 4), torch.zeros(1, 3, 4, 4), [5.0, 5.0, 2.0, 2.0]
+    with pytest.raises(ValueError, match="GPU"):  # a host depth map
+        ops.pointcloud_pack(d, img, K)
+    with pytest.raises(ValueError, match="GPU"):
+        ops.normal_rows(d, K)

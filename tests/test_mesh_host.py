@@ -262,6 +262,12 @@ def test_entry_points_reject_bad_arguments_without_gpu():
         L.check(pack(faces=None), "mesh_pack")
 
 
+def test_wrapper_validates_before_touching_the_gpu():
+    from patchrefinerv2_amd import ops
+    with pytest.raises(ValueError, match="GPU"):  # a host depth map
+        ops.mesh_pack(torch.zeros(1, 4, 4), torch.zeros(1, 3, 4, 4), [5.0, 5.0, 2.0, 2.0])
+
+
 def test_cli_save_mesh_needs_save():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "test.py"), "no_such_config.py", "--save-mesh"], cwd=ROOT, capture_output=True,
                        text=True, timeout=300)
