@@ -1169,6 +1169,48 @@ int prv2_temporal_step(const float* depth, const float* image, int32_t n, int32_
                        float* out, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Temporal motion (csrc/motion.hip): an optional motion stage in front of the stabiliser's step, so that a moving camera no longer
+ * gates the frame out.  Not in the reference.  A dense field of block vectors between the frame's luma L and the previous luma P is
+ * found by an integer block-matching search, the state (y, P) is moved by it, and the step above runs on the moved state.  Bytes and
+ * integer sums throughout: the same bits on every call and however a sequence is cut into calls; no atomics, no allocation, no host
+ * synchronisation.  Added without an ABI bump (additive).  The host specification is temporal_motion_host / temporal_warp_host /
+ * temporal_step_host(motion_range=R) of patchrefinerv2_amd/temporal.py, which the kernels equal bit for bit.
+ *   clamp      every index that leaves its map is clamped into it: cy(i) = min(max(i, 0), h - 1), cx and cq (quarter map) likewise
+ *   vector     m = (my, mx): pixel p of the frame was at p + m in the previous frame
+ *   quarter    hq = ceil(h / 4), wq = ceil(w / 4); Q[i, j] = (sum over a, b < 4 of L[cy(4i + a), cx(4j + b)] + 8) >> 4; QP from P
+ *   blocks     16 x 16 pixels, nby = ceil(h / 16), nbx = ceil(w / 16)
+ *   coarse     block (by, bx) owns the 8 x 8 window of Q at rows 4by - 2 .. 4by + 5, columns 4bx - 2 .. 4bx + 5; for |dy|, |dx| <= R:
+ *              S(d) = sum over the window of |Q[cq(i), cq(j)] - QP[cq(i + dy), cq(j + dx)]|; the smallest (S, dy^2 + dx^2, dy, dx) in
+ *              lexicographic order wins and is taken if S + 64 < S(0, 0), else the block's coarse vector is (0, 0)
+ *   median     v^ = the component-wise median (fifth smallest) of the nine coarse vectors of the 3 x 3 blocks, block indices clamped
+ *   fine       c = 4 v^ + e, e in [-3, 3]^2; T(c) = sum over the block's npix pixels inside the frame of |L[y, x] - P[cy(y + c_y),
+ *              cx(x + c_x)]|; the smallest (T, ey^2 + ex^2, ey, ex) wins; m = c if T + npix < T(0, 0), else (0, 0).  |m| <= 4R + 3
+ *   warp       pixel p takes its block's m; p + m inside the frame: yw[p] = y[p + m], Pw[p] = P[p + m]; elsewhere yw[p] = the quiet NaN
+ *              0x7FC00000 (not valid: the pixel is not gated) and Pw[p] = 0
+ *   step       "Temporal stabilisation" with (yw, Pw) in place of the state; the new state is (out, L), the un-warped luma.  A frame
+ *              without a state runs no motion stage: its motion row and vectors are zero
+ * ------------------------------------------------------------------------------------------ */
+#define PRV2_TEMPORAL_MOTION_STATS 8 /* 8-byte words per frame of prv2_temporal_motion_step's motion_stats */
+
+/* bytes of workspace prv2_temporal_motion_step needs for frames of h x w, whatever their count: the step's partials, the warped state,
+ * the two quarter maps and the blocks' records (-1 for bad arguments, as prv2_temporal_workspace_bytes) */
+int64_t prv2_temporal_motion_workspace_bytes(int32_t h, int32_t w);
+
+/* prv2_temporal_step with the motion stage: the same arguments, conventions and stats, and
+ *   motion_range  R, an integer in 1 .. 16 (quarter pixels: vectors of up to 4R + 3 pixels a component)
+ *   motion_stats  DEVICE, 8-byte aligned, [n][PRV2_TEMPORAL_MOTION_STATS] int64 per frame: 0 blocks, 1 blocks with m != 0, 2 sum my,
+ *                 3 sum mx, 4 sum (|my| + |mx|), 5 max(|my|, |mx|) over the blocks, 6 sum T(m) (T(0, 0) for a zeroed block),
+ *                 7 sum T(0, 0); all zero for a frame whose stage did not run
+ *   vectors       DEVICE int16 [n][nby][nbx][2] (my, mx), or NULL
+ *   workspace     DEVICE, 8-byte aligned, prv2_temporal_motion_workspace_bytes(h, w)
+ * Per frame with a state six launches (luma and Q, QP, coarse search, median and refinement, warp, stats) come before the step's four; a
+ * frame without one has a single launch that zeroes its row and vectors.  Every argument is checked before anything is launched. */
+int prv2_temporal_motion_step(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, double alpha,
+                              int32_t tau, double rho, double anchor, int32_t motion_range, float* state_depth, uint8_t* luma0, uint8_t* luma1,
+                              int32_t state_present, float* out, int64_t* stats, int64_t* motion_stats, int16_t* vectors, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Depth-of-field export (csrc/bokeh.hip): the frame re-rendered through a thin lens focused at one distance ("portrait mode"), from
  * its metric depth map: B >= 1 dense frames [n, h, w] (h, w >= 1; n * h * w < 2^29).  Not in the reference.  One launch, no host
  * synchronisation (the focus distance is read from the device map), no atomics on memory: the same input gives the same bits on

@@ -1598,6 +1598,39 @@ std::tuple<Tensor, Tensor> temporal_step_(const Tensor& depth, const Tensor& ima
   return {out, stats};
 }
 
+// the same with the motion stage in front (include/prv2.h "Temporal motion") -> (out, stats, motion stats int64 [n,
+// PRV2_TEMPORAL_MOTION_STATS], the blocks' vectors int16 [n, nby, nbx, 2]), the last three on the device
+std::tuple<Tensor, Tensor, Tensor, Tensor> temporal_motion_step_(const Tensor& depth, const Tensor& image, double alpha, int64_t tau, double rho,
+                                                                 double anchor, int64_t motion_range, Tensor state_depth, Tensor luma0, Tensor luma1,
+                                                                 bool state_present) {
+  dev_frames(depth, "depth", at::kFloat);
+  const int64_t n = depth.size(0), h = depth.size(1), w = depth.size(2);
+  TORCH_CHECK(image.is_cuda() && image.scalar_type() == at::kFloat && image.dim() == 4 && image.is_contiguous() && image.size(0) == n &&
+                  image.size(1) == 3 && image.device() == depth.device(),
+              "prv2::temporal_motion_step_: image must be a contiguous GPU fp32 [n, 3, ih, iw] tensor");
+  TORCH_CHECK(state_depth.is_cuda() && state_depth.scalar_type() == at::kFloat && state_depth.is_contiguous() && state_depth.dim() == 2 &&
+                  state_depth.size(0) == h && state_depth.size(1) == w && state_depth.device() == depth.device(),
+              "prv2::temporal_motion_step_: state_depth must be a contiguous GPU fp32 [h, w] tensor of the frames' shape");
+  for (const Tensor* l : {&luma0, &luma1})
+    TORCH_CHECK(l->is_cuda() && l->scalar_type() == at::kByte && l->is_contiguous() && l->dim() == 2 && l->size(0) == h && l->size(1) == w &&
+                    l->device() == depth.device(),
+                "prv2::temporal_motion_step_: a luma buffer must be a contiguous GPU uint8 [h, w] tensor of the frames' shape");
+  const int64_t bytes = prv2_temporal_motion_workspace_bytes((int)h, (int)w);
+  TORCH_CHECK(bytes > 0, "prv2::temporal_motion_step_: bad frame shape ", depth.sizes(), " (at most 2^25 pixels)");
+  Tensor ws = at::empty({bytes}, depth.options().dtype(at::kByte));
+  Tensor out = at::empty_like(depth), stats = at::empty({n, PRV2_TEMPORAL_STATS}, depth.options().dtype(at::kLong));
+  Tensor mstats = at::empty({n, PRV2_TEMPORAL_MOTION_STATS}, depth.options().dtype(at::kLong));
+  Tensor vectors = at::empty({n, (h + 15) / 16, (w + 15) / 16, 2}, depth.options().dtype(at::kShort));
+  Launch L(depth);
+  ok(prv2_temporal_motion_step(depth.data_ptr<float>(), image.data_ptr<float>(), (int)n, (int)h, (int)w, (int)image.size(2), (int)image.size(3),
+                               alpha, (int)std::min<int64_t>(std::max<int64_t>(tau, -1), 256), rho, anchor,
+                               (int)std::min<int64_t>(std::max<int64_t>(motion_range, -1), 256), state_depth.data_ptr<float>(),
+                               (uint8_t*)luma0.data_ptr(), (uint8_t*)luma1.data_ptr(), state_present ? 1 : 0, out.data_ptr<float>(),
+                               stats.data_ptr<int64_t>(), mstats.data_ptr<int64_t>(), vectors.data_ptr<int16_t>(), ws.data_ptr(), ws.numel(),
+                               L.stream), "temporal_motion_step");
+  return {out, stats, mstats, vectors};
+}
+
 // ZoeDepth metric-bins head, elementwise parts (attractor.py:45-57,186-206; dist_layers.py:29-69,100-116; zoedepth_v1.py:219)
 Tensor zoe_attractor(const Tensor& attr, const Tensor& bins, double alpha) {
   const int64_t lda = nhwc_ld(attr, "attr"), ldb = nhwc_ld(bins, "bins");
@@ -1768,6 +1801,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("stereo_source(Tensor depth, float fx, float baseline, float convergence, float lo, float hi, float edge_thr) -> (Tensor, Tensor)");
   m.def("stereo_rows(Tensor depth, Tensor image, float fx, float baseline, float convergence, float lo, float hi, float edge_thr, int layout) -> Tensor");
   m.def("temporal_step_(Tensor depth, Tensor image, float alpha, int tau, float rho, float anchor, Tensor(a!) state_depth, Tensor(b!) luma0, Tensor(c!) luma1, bool state_present) -> (Tensor, Tensor)");
+  m.def("temporal_motion_step_(Tensor depth, Tensor image, float alpha, int tau, float rho, float anchor, int motion_range, Tensor(a!) state_depth, Tensor(b!) luma0, Tensor(c!) luma1, bool state_present) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("bokeh_render(Tensor depth, Tensor image, float fx, float aperture, float focus, float focus_u, float focus_v, float max_radius, float lo, float hi) -> (Tensor, Tensor)");
   m.def("bokeh_rows(Tensor depth, Tensor image, float fx, float aperture, float focus, float focus_u, float focus_v, float max_radius, float lo, float hi) -> (Tensor, Tensor)");
   m.def("view_source(Tensor depth, float[] intrinsics, Tensor poses, float lo, float hi, float edge_thr) -> (Tensor, Tensor, Tensor)");
@@ -1872,6 +1906,7 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("stereo_source", &stereo_source);
   m.impl("stereo_rows", &stereo_rows);
   m.impl("temporal_step_", &temporal_step_);
+  m.impl("temporal_motion_step_", &temporal_motion_step_);
   m.impl("bokeh_render", &bokeh_render);
   m.impl("bokeh_rows", &bokeh_rows);
   m.impl("view_source", &view_source);

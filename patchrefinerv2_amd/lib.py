@@ -212,6 +212,9 @@ SIGNATURES = {
     # temporal stabilisation (csrc/temporal.hip): n frames of a sequence aligned to and blended with the previous output
     "prv2_temporal_workspace_bytes": (_L, [_I, _I]),
     "prv2_temporal_step": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _D, _D, _P, _P, _P, _I, _P, _P, _P, _L, _P]),
+    # the same with the motion stage in front (csrc/motion.hip): block matching of the lumas, the state warped by the blocks' vectors
+    "prv2_temporal_motion_workspace_bytes": (_L, [_I, _I]),
+    "prv2_temporal_motion_step": (_I, [_P, _P, _I, _I, _I, _I, _I, _D, _I, _D, _D, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _L, _P]),
     # depth-of-field export (csrc/bokeh.hip): B frames re-rendered through a thin lens, as fp32 planes or as scanlines
     "prv2_bokeh_max_radius": (_I, []),
     "prv2_bokeh_tile_bound": (_I, [_I]),
@@ -226,6 +229,7 @@ SIGNATURES = {
 }
 SSI_VALUES = 41  # PRV2_SSI_VALUES: float64 values per frame of prv2_ssi_metrics
 TEMPORAL_STATS = 12  # PRV2_TEMPORAL_STATS: 8-byte words per frame of prv2_temporal_step's stats
+TEMPORAL_MOTION_STATS = 8  # PRV2_TEMPORAL_MOTION_STATS: 8-byte words per frame of prv2_temporal_motion_step's motion_stats
 SPARSIFY_MAX_LEVELS = 64  # PRV2_SPARSIFY_MAX_LEVELS
 BOUNDARY_MAX_THRESHOLDS = 16  # PRV2_BOUNDARY_MAX_THRESHOLDS
 

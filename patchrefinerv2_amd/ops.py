@@ -2078,6 +2078,31 @@ def view_rows(depth, image, intrinsics, poses, depth_range=(0.0, math.inf), edge
 TEMPORAL_STATS = L.TEMPORAL_STATS
 
 
+def _temporal_args(fn, depth, image, state_depth, luma_prev, luma_next):
+    """the tensor checks the temporal steps share -> (n, h, w)"""
+    from .temporal import MAX_PIXELS
+    tensors = dict(depth=depth, image=image, state_depth=state_depth, luma_prev=luma_prev, luma_next=luma_next)
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != depth.device:
+            raise ValueError(f"{fn}: {name} is a GPU tensor on the maps' device (temporal.temporal_step_host is the host's)")
+        want = torch.uint8 if name.startswith("luma") else torch.float32
+        if t.dtype != want or not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be a contiguous {want} tensor (got {t.dtype}, strides {t.stride()})")
+    if depth.dim() != 3 or depth.numel() == 0:
+        raise ValueError(f"{fn}: depth is [n, H, W] (got {tuple(depth.shape)})")
+    n, h, w = depth.shape
+    if h * w > MAX_PIXELS:
+        raise ValueError(f"{fn}: a frame of {h} x {w} exceeds 2^25 pixels (the bound of the exact int64 sums)")
+    if image.dim() != 4 or image.shape[0] != n or image.shape[1] != 3 or image.shape[2] < 1 or image.shape[3] < 1:
+        raise ValueError(f"{fn}: image is [n, 3, Hi, Wi] with the maps' n = {n} (got {tuple(image.shape)})")
+    for name in ("state_depth", "luma_prev", "luma_next"):
+        if tuple(tensors[name].shape) != (h, w):
+            raise ValueError(f"{fn}: {name} {tuple(tensors[name].shape)} is not the frames' [{h}, {w}]")
+    if luma_prev.data_ptr() == luma_next.data_ptr():
+        raise ValueError(f"{fn}: the two luma buffers must differ")
+    return n, h, w
+
+
 def temporal_step(depth, image, state_depth, luma_prev, luma_next, state_present, alpha=0.5, tau=6, rho=0.05, anchor=0.9):
     """n frames of a sequence, in order: ``depth`` fp32 [n, H, W] and ``image`` fp32 [n, 3, Hi, Wi] on the GPU -> (out fp32 [n, H, W],
     stats int64 [n, 12] on the device: the rows ``temporal.stats_dict`` names; include/prv2.h prv2_temporal_step).  The state is
@@ -2085,27 +2110,9 @@ def temporal_step(depth, image, state_depth, luma_prev, luma_next, state_present
     ``luma_next`` two distinct uint8 [H, W] buffers (frame f reads the previous luma from the first when f is even and writes its own
     into the other; the state leaves in ``luma_prev`` for an even n, in ``luma_next`` for an odd one).  Four launches per frame on the
     current stream, no host synchronisation; the same bits however a sequence is cut into calls."""
-    from .temporal import MAX_PIXELS, check_params
+    from .temporal import check_params
     alpha, tau, rho, anchor = check_params(alpha, tau, rho, anchor)
-    tensors = dict(depth=depth, image=image, state_depth=state_depth, luma_prev=luma_prev, luma_next=luma_next)
-    for name, t in tensors.items():
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != depth.device:
-            raise ValueError(f"temporal_step: {name} is a GPU tensor on the maps' device (temporal.temporal_step_host is the host's)")
-        want = torch.uint8 if name.startswith("luma") else torch.float32
-        if t.dtype != want or not t.is_contiguous():
-            raise ValueError(f"temporal_step: {name} must be a contiguous {want} tensor (got {t.dtype}, strides {t.stride()})")
-    if depth.dim() != 3 or depth.numel() == 0:
-        raise ValueError(f"temporal_step: depth is [n, H, W] (got {tuple(depth.shape)})")
-    n, h, w = depth.shape
-    if h * w > MAX_PIXELS:
-        raise ValueError(f"temporal_step: a frame of {h} x {w} exceeds 2^25 pixels (the bound of the exact int64 sums)")
-    if image.dim() != 4 or image.shape[0] != n or image.shape[1] != 3 or image.shape[2] < 1 or image.shape[3] < 1:
-        raise ValueError(f"temporal_step: image is [n, 3, Hi, Wi] with the maps' n = {n} (got {tuple(image.shape)})")
-    for name in ("state_depth", "luma_prev", "luma_next"):
-        if tuple(tensors[name].shape) != (h, w):
-            raise ValueError(f"temporal_step: {name} {tuple(tensors[name].shape)} is not the frames' [{h}, {w}]")
-    if luma_prev.data_ptr() == luma_next.data_ptr():
-        raise ValueError("temporal_step: the two luma buffers must differ")
+    n, h, w = _temporal_args("temporal_step", depth, image, state_depth, luma_prev, luma_next)
     box = []
     if DISPATCH == "torch":
         call = lambda: box.extend(_tops().temporal_step_(depth, image, alpha, tau, rho, anchor, state_depth, luma_prev, luma_next,  # noqa: E731
@@ -2124,6 +2131,38 @@ def temporal_step(depth, image, state_depth, luma_prev, luma_next, state_present
     # per pixel: the fit reads x, y, Lp and the image's three samples and writes L; the apply reads x, y, L, Lp and writes out
     PROFILER.launch_aux("temporal_step", n * h * w * 39.0, call, f"{n}x{h}x{w}")
     return box[0], box[1]
+
+
+def temporal_motion_step(depth, image, state_depth, luma_prev, luma_next, state_present, alpha=0.5, tau=6, rho=0.05, anchor=0.9,
+                         motion_range=8):
+    """``temporal_step`` with the motion stage in front (include/prv2.h prv2_temporal_motion_step; csrc/motion.hip): the same arguments
+    and state, ``motion_range`` = R in 1 .. 16 -> (out, stats, motion stats int64 [n, 8]: the rows ``temporal.motion_dict`` names,
+    vectors int16 [n, ceil(H / 16), ceil(W / 16), 2]: the blocks' (my, mx)), the last three on the device.  A frame with a state costs
+    six launches before the step's four; the bits equal ``temporal.temporal_step_host(motion_range=R)``'s."""
+    from .temporal import check_motion_range, check_params
+    alpha, tau, rho, anchor = check_params(alpha, tau, rho, anchor)
+    motion_range = check_motion_range(motion_range)
+    n, h, w = _temporal_args("temporal_motion_step", depth, image, state_depth, luma_prev, luma_next)
+    box = []
+    if DISPATCH == "torch":
+        call = lambda: box.extend(_tops().temporal_motion_step_(depth, image, alpha, tau, rho, anchor, motion_range, state_depth,  # noqa: E731
+                                                                luma_prev, luma_next, bool(state_present)))
+    else:
+        wsb = L.load().prv2_temporal_motion_workspace_bytes(h, w)
+        if wsb < 0:
+            raise ValueError(f"temporal_motion_step: bad frame shape {tuple(depth.shape)}")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=depth.device)
+        out = torch.empty_like(depth)
+        stats = torch.empty((n, TEMPORAL_STATS), dtype=torch.int64, device=depth.device)
+        mstats = torch.empty((n, L.TEMPORAL_MOTION_STATS), dtype=torch.int64, device=depth.device)
+        vectors = torch.empty((n, -(-h // 16), -(-w // 16), 2), dtype=torch.int16, device=depth.device)
+        box.extend((out, stats, mstats, vectors))
+        call = lambda: _c("temporal_motion_step", depth.data_ptr(), image.data_ptr(), n, h, w, image.shape[2], image.shape[3], alpha, tau,  # noqa: E731
+                          rho, anchor, motion_range, state_depth.data_ptr(), luma_prev.data_ptr(), luma_next.data_ptr(),
+                          int(bool(state_present)), out.data_ptr(), stats.data_ptr(), mstats.data_ptr(), vectors.data_ptr(), ws.data_ptr(), wsb)
+    # per pixel: the step's 39 bytes, the luma pass (12 read, 1 written), the warp (5 read, 5 written) and the refinement's windows (~3)
+    PROFILER.launch_aux("temporal_motion_step", n * h * w * 65.0, call, f"{n}x{h}x{w}")
+    return box[0], box[1], box[2], box[3]
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -15,7 +15,9 @@ binary point cloud of the result map, coloured from the image) and <name>_normal
 ``view_motion``, ``view_amplitude``, ``view_focus``) -- from the device map
 with the output stage, from output.py's host specification otherwise; the same files either way.
 ``runner_info.temporal_stabilize`` (--temporal-stabilize; ``temporal_alpha`` / ``_tau`` / ``_rho`` / ``_anchor``) treats the dataset as
-one video: every result map goes through temporal.TemporalStabilizer before it is saved, exported or scored.
+one video: every result map goes through temporal.TemporalStabilizer before it is saved, exported or scored;
+``runner_info.temporal_motion`` (--temporal-motion; ``temporal_motion_range`` = R in 1 .. 16) puts its block-motion stage in front, so
+that a moving camera does not gate the frames out.
 With ``--save``: <name>.png (colour map, tester.py:72-87), <name>_uint16.png (depth x 256, :89-91), <name>_coarse.png
 (coarse prediction resized to the raw shape, :93-96) and <name>_edge.png (Canny edges of the log depth, widened by one pixel,
 :98-106; metrics.depth_edges) -- colour maps and metrics in metrics.py, PNGs through a dependency-free encoder (output.py).
@@ -104,7 +106,7 @@ class Tester:
                 one = len(items) == 1
                 self._emit(results, item, result if one else result[f:f + 1], coarse if one or coarse is None else coarse[f:f + 1],
                            image_raw_shape, stage,
-                           **({} if temporal is None else dict(temporal={k: temporal[f][k] for k in self.TEMPORAL_KEYS})))
+                           **({} if temporal is None else dict(temporal=self._temporal_entry(temporal[f]))))
         if stage is not None:
             stage.close()  # every file is on disk (or its error raised) before run returns
         if not patches:
@@ -121,25 +123,39 @@ class Tester:
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
                 means = {"temporal_" + k: float(np.mean([t[k] for t in rows])) if rows else float("nan") for k in ("change_before", "change_after")}
+                if stab.motion_range:  # the share of moving blocks, over the frames whose motion stage ran
+                    moved = [r["temporal"]["motion"]["moving_fraction"] for r in results if r["temporal"]["motion"]["blocks"]]
+                    means["temporal_moving_fraction"] = float(np.mean(moved)) if moved else float("nan")
             scored = bool(results) and "metrics" in results[0]
             self.last_eval = {**(self.last_eval if scored else {}), **means}
         return results
 
     TEMPORAL_KEYS = ("reset", "static_fraction", "scale", "shift", "change_before", "change_after")  # of a result entry's ``temporal``
 
+    @classmethod
+    def _temporal_entry(cls, stats):
+        """a result entry's ``temporal`` from the frame's stats dict: ``TEMPORAL_KEYS``, and ``motion`` when the motion stage is on"""
+        entry = {k: stats[k] for k in cls.TEMPORAL_KEYS}
+        return entry if stats["motion"] is None else dict(entry, motion=stats["motion"])
+
     def _stabilizer(self):
         """the run's ``temporal.TemporalStabilizer`` when ``runner_info.temporal_stabilize`` is set (``temporal_alpha``, ``temporal_tau``,
-        ``temporal_rho``, ``temporal_anchor``: its parameters), else None.  The frames are one sequence in dataset order: a run over
-        several ranks is rejected (frame sharding breaks the order; the patch-sharded mode is not built)."""
+        ``temporal_rho``, ``temporal_anchor``: its parameters; ``temporal_motion`` and ``temporal_motion_range``: its motion stage), else
+        None.  The frames are one sequence in dataset order: a run over several ranks is rejected (frame sharding breaks the order; the
+        patch-sharded mode is not built)."""
         info = self.runner_info
+        motion = bool(getattr(info, "temporal_motion", False))
         if not getattr(info, "temporal_stabilize", False):
+            if motion:
+                raise ValueError("temporal_motion without temporal_stabilize: the motion stage is a part of the temporal stabiliser")
             return None
         if getattr(info, "world_size", 1) > 1:
             raise ValueError("temporal_stabilize: one process only -- the frames of a sequence are stabilised in dataset order, which a "
                              f"run over {info.world_size} ranks does not keep")
         from .temporal import DEFAULTS, TemporalStabilizer
+        mrange = getattr(info, "temporal_motion_range", None)
         return TemporalStabilizer(**{k: getattr(info, "temporal_" + k, None) if getattr(info, "temporal_" + k, None) is not None else v
-                                     for k, v in DEFAULTS.items()})
+                                     for k, v in DEFAULTS.items()}, motion=motion, motion_range=8 if mrange is None else mrange)
 
     def _frames(self, stage, cai_mode, process_num, image_raw_shape, patch_split_num, seed, frame_batch, device_scoring, patches=False,
                 want_device=False, **model_kw):

@@ -63,6 +63,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "stereo_rows", "stereo_source",
        # temporal stabilisation: frames of a sequence aligned to and blended with the previous output (state tensors updated in place)
        "temporal_step_",
+       # the same with the motion stage in front (also returns the motion stats rows and the blocks' vectors)
+       "temporal_motion_step_",
        # depth-of-field export: frames re-rendered through a thin lens, as fp32 planes or as scanlines (each with the focus used)
        "bokeh_render", "bokeh_rows",
        # novel-view export: frames seen from a list of camera poses, as source maps or as scanlines

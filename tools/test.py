@@ -227,6 +227,11 @@ def main():
     ap.add_argument("--temporal-rho", type=float, default=0.05, metavar="R", help="--temporal-stabilize: the relative depth change that halves the blend weight (> 0)")
     ap.add_argument("--temporal-anchor", type=float, default=0.9, metavar="K",
                     help="--temporal-stabilize: how much of the fitted scale and shift is applied, in [0, 1] (below 1 the sequence leaks back to the model's own scale)")
+    ap.add_argument("--temporal-motion", action="store_true",
+                    help="--temporal-stabilize: move the previous output by a field of block vectors first (integer block matching of the two "
+                         "frames' lumas, 16 x 16 blocks), so that a panning or hand-held camera does not gate the frame out")
+    ap.add_argument("--temporal-motion-range", type=int, default=8, metavar="R",
+                    help="--temporal-motion: the search range in quarter-resolution pixels, 1 .. 16 (vectors of up to 4R + 3 pixels a component)")
     ap.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("FX", "FY", "CX", "CY"),
                     help="--save-ply / --save-normals: the camera in pixels of the --image-raw-shape grid (scaled to the result's shape)")
     ap.add_argument("--fov", type=float, default=None, metavar="DEG",
@@ -272,6 +277,8 @@ def main():
         ap.error(f"--temporal-rho {args.temporal_rho}: positive and finite")
     if not 0.0 <= args.temporal_anchor <= 1.0:
         ap.error(f"--temporal-anchor {args.temporal_anchor}: in [0, 1]")
+    if not 1 <= args.temporal_motion_range <= 16:
+        ap.error(f"--temporal-motion-range {args.temporal_motion_range}: an integer in 1 .. 16")
     if args.temporal_stabilize and args.generate_pl:
         ap.error("--temporal-stabilize with --generate-pl: pseudo labels are per-image")
     if args.temporal_stabilize and int(os.environ.get("WORLD_SIZE", 1)) > 1:
@@ -317,7 +324,8 @@ def main():
                         intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
                         ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range),
                         temporal_stabilize=args.temporal_stabilize, temporal_alpha=args.temporal_alpha, temporal_tau=args.temporal_tau,
-                        temporal_rho=args.temporal_rho, temporal_anchor=args.temporal_anchor)
+                        temporal_rho=args.temporal_rho, temporal_anchor=args.temporal_anchor, temporal_motion=args.temporal_motion,
+                        temporal_motion_range=args.temporal_motion_range)
     tester = Tester(cfg, runner, dataset, model)
     if args.consistency:
         for r in tester.run_consistency(image_raw_shape=args.image_raw_shape, patch_split_num=args.patch_split_num, overlap=args.consistency):
@@ -357,6 +365,10 @@ def main():
                 t = r["temporal"]
                 print(f"[rank {rank}] {r['name']}: temporal " + ("reset" if t["reset"] else f"scale {t['scale']:.6f} shift {t['shift']:.6f} static "
                       f"{t['static_fraction']:.3f} change {t['change_before']:.6f} -> {t['change_after']:.6f}"))
+                if t.get("motion") and t["motion"]["blocks"]:
+                    m = t["motion"]
+                    print(f"[rank {rank}] {r['name']}: motion (dy, dx) mean ({m['mean_dy']:.2f}, {m['mean_dx']:.2f}), moving "
+                          f"{100.0 * m['moving_fraction']:.1f} %, max {m['max_abs']} px, SAD {m['sad_zero']} -> {m['sad']}")
             if args.test_type != "general" and "metrics" in r:  # a dataset evaluation: the frame's own row
                 print(f"[rank {rank}] {r['name']}: " + ", ".join(f"{k} {float(v):.6f}" for k, v in r["metrics"].items()))
         if getattr(tester, "last_eval", None):  # frames that came with ground truth (dataset gt_dir, or a dataset with its own)
