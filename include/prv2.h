@@ -1087,6 +1087,64 @@ int prv2_mesh_pack(const float* depth, int32_t n, int32_t h, int32_t w, float ed
                    int64_t workspace_bytes, uint8_t* faces, int64_t faces_fstride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Adaptive mesh export (csrc/mesh_adaptive.hip): a triangle mesh of the depth map with large triangles where the surface is flat and
+ * pixel-sized ones at its boundaries -- a right-triangulated irregular network, the longest-edge-bisection hierarchy of terrain
+ * renderers, with its own vertex list.  Not in the reference.  Fixed launch counts, no host synchronisation, no read-modify-write
+ * atomics: the same input gives the same bytes on every call.  Added without an ABI bump (additive).  The host specification is
+ * mesh_adaptive_host of patchrefinerv2_amd/output.py, which the kernels equal byte for byte.
+ *   parameters tolerance T (fp32, finite, >= 0), block B (a power of two in [2, 64], L = log2 B); depth range and edge_thr as in
+ *              "Geometry export"; there is no stride
+ *   grid       vertices are pixels, kept as in "Geometry export" at stride 1; the grid is padded to whole blocks of B x B cells,
+ *              Hp = B ceil((h - 1) / B) + 1, Wp likewise, with vertices that are neither kept nor smooth; h < 2 or w < 2: no face
+ *   smooth     v is kept, and every 8-neighbour inside the frame is kept and joined to v ("Mesh export"'s joined)
+ *   hierarchy  block (y0, x0) has the corners A = (y0, x0), B' = (y0, x0 + B), C = (y0 + B, x0), D = (y0 + B, x0 + B) and the root
+ *              triangles (D, A, C) then (A, D, B'); (a, b, c) has the hypotenuse a-b, the apex c, the midpoint m = (a + b) / 2 and
+ *              the children (c, a, m) then (b, c, m); after 2L bisections the legs are one pixel long (the finest triangles)
+ *   vertex     not a block corner, hh = 2^min(tz(y), tz(x)).  y / hh and x / hh odd: a centre; its hypotenuse is the diagonal of
+ *              the 2hh-square around it through the centre of the enclosing 4hh-aligned square (the block's A-D for 2hh = B), its
+ *              apexes are the square's other corners, its child vertices the axial neighbours at hh.  One of them odd: an edge
+ *              midpoint; hypotenuse ends at +-hh along the odd axis, apexes at +-hh along the other, child vertices the diagonal
+ *              neighbours at hh / 2.  What lies outside the padded grid does not exist.
+ *   required   of a vertex m that is not a block corner: m is not smooth, or a hypotenuse end or an existing apex is not kept, or an
+ *              existing child vertex is required, or s = Za + Zb, p = Zm s, q = (Za Zb) 2, |p - q| > T p (one fp32 operation each;
+ *              the depth at m against the harmonic mean of the ends, which is what a flat 3-D triangle has there)
+ *   faces      blocks row-major, roots and children in the order above; a triangle above the finest is a face iff its midpoint is
+ *              not required, else it splits; a finest one is a face iff its corners are kept and its edges joined.  Every face
+ *              looks at the camera as "Mesh export"'s do.  T bounds a vertex against its own hypotenuse, not a pixel against the
+ *              face finally emitted: no error bound is promised.
+ *   vertices   the kept pixels a face references, in row-major pixel order, as the 15-byte records of "Geometry export"
+ *   record     of a face: "Mesh export"'s 13 bytes, indices into the frame's vertex list
+ * ------------------------------------------------------------------------------------------ */
+
+/* bytes of workspace the two calls below need for n frames of h x w (-1 for bad arguments, among them n * Hp * Wp >= 2^29): per
+ * frame the vertex index map int32 [Hp, Wp], one int32 per run of 2048 finest slots (2 B^2 a block) and per run of 2048 padded
+ * vertices, and the kept and required maps uint8 [Hp, Wp]; 4 for a frame without a cell */
+int64_t prv2_mesh_adaptive_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t block);
+
+/* 15 * h * w and 26 * (h - 1) * (w - 1): the bytes of a frame's vertex and face records at most, those of the stride-1 cloud and
+ * mesh (-1 for bad arguments) */
+int64_t prv2_mesh_adaptive_vertex_bound(int32_t h, int32_t w);
+int64_t prv2_mesh_adaptive_face_bound(int32_t h, int32_t w);
+
+/* vertex_counts, face_counts: DEVICE int64 [n] = N and M of each frame.  Fills ``workspace`` (DEVICE, 4-byte aligned,
+ * prv2_mesh_adaptive_workspace_bytes(n, h, w, block)) with what prv2_mesh_adaptive_pack reads: the kept and required maps, a mark
+ * on every vertex a face uses (several lanes store the same value: no atomics), and the exclusive offsets of every run of slots and
+ * of vertices.  2 L + 5 launches for a frame with cells. */
+int prv2_mesh_adaptive_count(const float* depth, int32_t n, int32_t h, int32_t w, float lo, float hi, float edge_thr, float tolerance,
+                             int32_t block, int64_t* vertex_counts, int64_t* face_counts, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+
+/* the records: frame f's vertices at vertices[f * vertices_fstride + 15 * k], k < N, and its faces at faces[f * faces_fstride + 13 * k],
+ * k < M.  Same depth, range, edge_thr, tolerance and block as the prv2_mesh_adaptive_count call that filled ``workspace`` (which
+ * leaves with every used vertex's rank in place of its mark); image and intrinsics as in prv2_pointcloud_pack.  vertices, faces: DEVICE
+ * uint8, no alignment asked; vertices_fstride >= prv2_mesh_adaptive_vertex_bound(h, w), faces_fstride >=
+ * prv2_mesh_adaptive_face_bound(h, w).  Exactly the 15 * N and 13 * M bytes of a frame are written and nothing else is touched. */
+int prv2_mesh_adaptive_pack(const float* depth, const float* image, int32_t n, int32_t h, int32_t w, int32_t ih, int32_t iw, float fx,
+                            float fy, float cx, float cy, float lo, float hi, float edge_thr, float tolerance, int32_t block,
+                            void* workspace, int64_t workspace_bytes, uint8_t* vertices, int64_t vertices_fstride, uint8_t* faces,
+                            int64_t faces_fstride, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Stereo export (csrc/stereo.hip): the frame re-rendered from a second eye a baseline to the right of the camera, from its metric
  * depth map: B >= 1 dense frames [n, h, w] (h, w >= 1; n * h * w < 2^29; w <= prv2_stereo_max_width()).  Not in the reference.  One
  * workgroup per (frame, row) keeps the row in LDS; one launch, no host synchronisation; the depth test is an integer minimum, so the

@@ -10,40 +10,13 @@
 //     of the restatement); division and square root are the correctly rounded ones (sqrtf: HIP's __fsqrt_rn is the native,
 //     1-ulp instruction);
 //   - camera, valid, joined, the colour sample and its bytes, the faces of a cell: scene.h; Z = D[y, x];
+//   - the run a block owns, the keep predicate, the bytes of a vertex and of a face record, the scans: cloud.h (shared with mesh_adaptive.hip);
 //   - flying: a valid in-frame 4-neighbour Zn that is not joined to Z;
 //   - kept: valid, not flying, y % stride == 0 and x % stride == 0.
-#include "scene.h"
+#include "cloud.h"
 
 namespace prv2 {
 namespace {
-
-constexpr int kRun = 2048;     // pixels of a frame one block owns: kRounds steps of 256 lanes, lane t of step r has pixel r * 256 + t of the run
-constexpr int kRounds = kRun / 256;
-constexpr int kSegs = kRounds * 4;  // (step, wave) segments of 64 consecutive pixels
-constexpr int kRecord = 15;    // bytes of a vertex
-
-struct CloudArgs {
-  const float* depth;  // [n, h, w]
-  Camera cam;
-  float thr;           // flying-pixel threshold (<= 0: off)
-  int32_t h, w, stride;
-  int32_t nblk;        // blocks (runs) per frame
-};
-
-__device__ __forceinline__ bool flying(const Camera& c, float thr, float z, float zn) { return valid_z(c, zn) && !joined(thr, z, zn); }
-
-// the keep predicate of pixel (y, x) of frame ``d``; z = d[y * w + x]
-__device__ __forceinline__ bool keep_pixel(const CloudArgs& a, const float* __restrict__ d, int y, int x, float z) {
-  if (!valid_z(a.cam, z) || y % a.stride != 0 || x % a.stride != 0) return false;
-  if (!(a.thr > 0.0f)) return true;
-  const int64_t i = (int64_t)y * a.w + x;
-  bool fly = false;
-  if (x > 0) fly = fly || flying(a.cam, a.thr, z, d[i - 1]);
-  if (x + 1 < a.w) fly = fly || flying(a.cam, a.thr, z, d[i + 1]);
-  if (y > 0) fly = fly || flying(a.cam, a.thr, z, d[i - a.w]);
-  if (y + 1 < a.h) fly = fly || flying(a.cam, a.thr, z, d[i + a.w]);
-  return !fly;
-}
 
 // One step of a block over its run: lane t evaluates pixel p0 + t (p0 a multiple of 64 inside the frame's pixel range or behind it).
 // Returns the pixel's keep flag; ``below``: kept pixels of lower lanes of this wave, ``total``: of the whole wave.
@@ -85,35 +58,6 @@ __global__ void __launch_bounds__(256) cloud_count_kernel(CloudArgs a, int32_t* 
   }
 }
 
-// one block per frame: counts[f][0 .. nblk) -> their exclusive prefix sums in block order (in place), totals[f] = the frame's N
-__global__ void __launch_bounds__(256) cloud_scan_kernel(int32_t* __restrict__ counts, int32_t nblk, int64_t* __restrict__ totals) {
-  __shared__ int32_t part[256];
-  const int tid = threadIdx.x, f = blockIdx.x;
-  int32_t* c = counts + (int64_t)f * nblk;
-  const int per = (nblk + 255) / 256;  // a lane's contiguous chunk
-  const int i0 = tid * per < nblk ? tid * per : nblk, i1 = i0 + per < nblk ? i0 + per : nblk;
-  int32_t sum = 0;
-  for (int i = i0; i < i1; ++i) sum += c[i];
-  part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    int32_t run = 0;
-    for (int t = 0; t < 256; ++t) {
-      const int32_t v = part[t];
-      part[t] = run;
-      run += v;
-    }
-    totals[f] = (int64_t)run;
-  }
-  __syncthreads();
-  int32_t run = part[tid];
-  for (int i = i0; i < i1; ++i) {
-    const int32_t v = c[i];
-    c[i] = run;
-    run += v;
-  }
-}
-
 // The records of every run.  The block ranks its kept pixels in pixel order (ballot + popcount inside a wave, the (step, wave) segment
 // totals through LDS), builds the records in LDS and stores its byte range [15 off, 15 (off + cnt)) of the frame's vertex buffer.  That
 // range starts and ends at any byte alignment and the dwords at its two ends may belong to the neighbouring runs as well: the LDS image
@@ -136,17 +80,7 @@ __global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, ImageSrc s
     rank[r] = k ? below : -1;
     if ((tid & 63) == 0) seg[r * 4 + wave] = total;
   }
-  __syncthreads();
-  if (tid == 0) {  // exclusive prefix of the segment totals; seg[kSegs] = the run's count
-    int32_t run = 0;
-    for (int s = 0; s < kSegs; ++s) {
-      const int32_t v = seg[s];
-      seg[s] = run;
-      run += v;
-    }
-    seg[kSegs] = run;
-  }
-  __syncthreads();
+  scan_segments(seg, tid);  // exclusive prefix of the segment totals; seg[kSegs] = the run's count
   const int32_t cnt = seg[kSegs];
   if (cnt == 0) return;
   uint8_t* dst = out + (int64_t)f * out_fstride + (int64_t)kRecord * offsets[(int64_t)f * a.nblk + blockIdx.x];
@@ -158,18 +92,7 @@ __global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, ImageSrc s
     if (rank[r] < 0) continue;
     const int64_t p = p0 + r * 256 + tid;
     const int y = (int)(p / a.w), x = (int)(p - (int64_t)y * a.w);
-    const float* c = img + (int64_t)nearest(y, a.h, src.ih) * src.iw + nearest(x, a.w, src.iw);
-    const uint32_t w0 = __float_as_uint(cam_x(a.cam, x, z[r])), w1 = __float_as_uint(cam_y(a.cam, y, z[r])), w2 = __float_as_uint(z[r]);
-    uint8_t* rec = buf + shift + kRecord * (seg[r * 4 + wave] + rank[r]);
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      rec[b] = (uint8_t)(w0 >> (8 * b));
-      rec[4 + b] = (uint8_t)(w1 >> (8 * b));
-      rec[8 + b] = (uint8_t)(w2 >> (8 * b));
-    }
-    rec[12] = (uint8_t)color_byte(__fmul_rn(c[0], 255.0f));
-    rec[13] = (uint8_t)color_byte(__fmul_rn(c[plane], 255.0f));
-    rec[14] = (uint8_t)color_byte(__fmul_rn(c[2 * plane], 255.0f));
+    vertex_record(a.cam, src, img, plane, a.h, a.w, y, x, z[r], buf + shift + kRecord * (seg[r * 4 + wave] + rank[r]));
   }
   __syncthreads();
   store_ragged(dst, buf4, shift, kRecord * cnt, tid);
@@ -179,7 +102,6 @@ __global__ void __launch_bounds__(256) cloud_pack_kernel(CloudArgs a, ImageSrc s
 // The vertices are the cloud's.  Grid node (gy, gx) is pixel (gy * stride, gx * stride); cell (gy, gx), gy + 1 < gh, gx + 1 < gw, has the
 // corners a = (gy, gx), b = (gy, gx + 1), c = (gy + 1, gx), d = (gy + 1, gx + 1) and emits up to two faces.  Cells are ranked like pixels:
 // a block owns a run of kRun cells in row-major order, a lane has 0, 1 or 2 faces (two ballots).
-constexpr int kFace = 13;  // bytes of a face record: uchar 3 + three int32
 
 struct MeshArgs {
   const float* depth;    // [n, h, w]
@@ -193,7 +115,7 @@ struct MeshArgs {
 // index[f][gy][gx] of every node: the rank of its pixel among the frame's kept pixels (cloud_pack_kernel's order), -1 where not kept
 __global__ void __launch_bounds__(256) mesh_index_kernel(CloudArgs a, const int32_t* __restrict__ offsets, int32_t* __restrict__ index, int32_t gh,
                                                          int32_t gw) {
-  __shared__ int32_t seg[kSegs];
+  __shared__ int32_t seg[kSegs + 1];
   const int tid = threadIdx.x, wave = tid >> 6, f = blockIdx.y;
   const int64_t hw = (int64_t)a.h * a.w, p0 = (int64_t)blockIdx.x * kRun;
   const float* d = a.depth + (int64_t)f * hw;
@@ -206,16 +128,7 @@ __global__ void __launch_bounds__(256) mesh_index_kernel(CloudArgs a, const int3
     rank[r] = k ? below : -1;
     if ((tid & 63) == 0) seg[r * 4 + wave] = total;
   }
-  __syncthreads();
-  if (tid == 0) {  // exclusive prefix of the segment totals
-    int32_t run = 0;
-    for (int s = 0; s < kSegs; ++s) {
-      const int32_t v = seg[s];
-      seg[s] = run;
-      run += v;
-    }
-  }
-  __syncthreads();
+  scan_segments(seg, tid);  // exclusive prefix of the segment totals
   const int32_t base = offsets[(int64_t)f * a.nblk + blockIdx.x];
   int32_t* idx = index + (int64_t)f * gh * gw;
 #pragma unroll
@@ -300,17 +213,7 @@ __global__ void __launch_bounds__(256) mesh_pack_kernel(MeshArgs m, const int32_
     faces[r] = step_faces(m, d, idx, c0 + r * 256 + tid, tri[r], rank[r], total);
     if ((tid & 63) == 0) seg[r * 4 + wave] = total;
   }
-  __syncthreads();
-  if (tid == 0) {  // exclusive prefix of the segment totals; seg[kSegs] = the run's count
-    int32_t run = 0;
-    for (int s = 0; s < kSegs; ++s) {
-      const int32_t v = seg[s];
-      seg[s] = run;
-      run += v;
-    }
-    seg[kSegs] = run;
-  }
-  __syncthreads();
+  scan_segments(seg, tid);  // exclusive prefix of the segment totals; seg[kSegs] = the run's count
   const int32_t cnt = seg[kSegs];
   if (cnt == 0) return;
   uint8_t* dst = out + (int64_t)f * out_fstride + (int64_t)kFace * offsets[(int64_t)f * m.nrun + blockIdx.x];
@@ -320,14 +223,7 @@ __global__ void __launch_bounds__(256) mesh_pack_kernel(MeshArgs m, const int32_
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       if (j >= faces[r]) continue;
-      uint8_t* rec = buf + shift + kFace * (seg[r * 4 + wave] + rank[r] + j);
-      rec[0] = 3;
-#pragma unroll
-      for (int v = 0; v < 3; ++v) {
-        const uint32_t word = (uint32_t)tri[r][3 * j + v];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) rec[1 + 4 * v + b] = (uint8_t)(word >> (8 * b));
-      }
+      face_record(tri[r] + 3 * j, buf + shift + kFace * (seg[r * 4 + wave] + rank[r] + j));
     }
   }
   __syncthreads();

@@ -1466,6 +1466,35 @@ std::tuple<Tensor, Tensor> mesh_pack(const Tensor& depth, const Tensor& image, a
      "mesh_pack");
   return {nv, nf};
 }
+// adaptive mesh export (include/prv2.h "Adaptive mesh export"): the vertex and face records of a right-triangulated irregular network.
+// -> (N, M) int64 [n]; frame f's records are vertices[f, :15 * N[f]] and faces[f, :13 * M[f]] (the rest of both is left as it is)
+std::tuple<Tensor, Tensor> mesh_adaptive_pack(const Tensor& depth, const Tensor& image, at::ArrayRef<double> intrinsics, double lo, double hi,
+                                              double edge_thr, double tolerance, int64_t block, Tensor vertices, Tensor faces) {
+  scene_image(depth, image, "mesh_adaptive_pack");
+  const double* k = camera4(intrinsics, "mesh_adaptive_pack");
+  const int n = (int)depth.size(0), h = (int)depth.size(1), w = (int)depth.size(2);
+  TORCH_CHECK(block >= 2 && block <= 64 && (block & (block - 1)) == 0, "prv2::mesh_adaptive_pack: block ", block, ": a power of two in [2, 64]");
+  const int64_t bytes = prv2_mesh_adaptive_workspace_bytes(n, h, w, (int)block);
+  const int64_t vbound = prv2_mesh_adaptive_vertex_bound(h, w), fbound = prv2_mesh_adaptive_face_bound(h, w);
+  TORCH_CHECK(bytes > 0 && vbound > 0 && fbound >= 0, "prv2::mesh_adaptive_pack: bad frame shape ", depth.sizes());
+  TORCH_CHECK(vertices.is_cuda() && vertices.scalar_type() == at::kByte && vertices.dim() == 2 && vertices.is_contiguous() && vertices.size(0) == n &&
+                  vertices.size(1) >= vbound && vertices.device() == depth.device(),
+              "prv2::mesh_adaptive_pack: vertices must be a contiguous GPU uint8 [n, >= ", vbound, "] tensor");
+  TORCH_CHECK(faces.is_cuda() && faces.scalar_type() == at::kByte && faces.dim() == 2 && faces.is_contiguous() && faces.size(0) == n &&
+                  faces.size(1) >= fbound && faces.device() == depth.device(),
+              "prv2::mesh_adaptive_pack: faces must be a contiguous GPU uint8 [n, >= ", fbound, "] tensor");
+  Tensor ws = at::empty({bytes}, depth.options().dtype(at::kByte));
+  Tensor nv = at::empty({depth.size(0)}, depth.options().dtype(at::kLong)), nf = at::empty({depth.size(0)}, depth.options().dtype(at::kLong));
+  Launch L(depth);
+  const float* d = depth.data_ptr<float>();
+  ok(prv2_mesh_adaptive_count(d, n, h, w, (float)lo, (float)hi, (float)edge_thr, (float)tolerance, (int)block, nv.data_ptr<int64_t>(),
+                              nf.data_ptr<int64_t>(), ws.data_ptr(), ws.numel(), L.stream), "mesh_adaptive_count");
+  ok(prv2_mesh_adaptive_pack(d, image.data_ptr<float>(), n, h, w, (int)image.size(2), (int)image.size(3), (float)k[0], (float)k[1], (float)k[2],
+                             (float)k[3], (float)lo, (float)hi, (float)edge_thr, (float)tolerance, (int)block, ws.data_ptr(), ws.numel(),
+                             (uint8_t*)vertices.data_ptr(), vertices.size(1), (uint8_t*)faces.data_ptr(), faces.size(1), L.stream),
+     "mesh_adaptive_pack");
+  return {nv, nf};
+}
 Tensor normal_rows(const Tensor& depth, at::ArrayRef<double> intrinsics, double lo, double hi) {
   dev_frames(depth, "depth", at::kFloat);
   const double* k = camera4(intrinsics, "normal_rows");
@@ -1798,6 +1827,7 @@ TORCH_LIBRARY(prv2, m) {
   m.def("pointcloud_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices) -> Tensor");
   m.def("normal_rows(Tensor depth, float[] intrinsics, float lo, float hi) -> Tensor");
   m.def("mesh_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, int stride, Tensor(a!) vertices, Tensor(b!) faces) -> (Tensor, Tensor)");
+  m.def("mesh_adaptive_pack(Tensor depth, Tensor image, float[] intrinsics, float lo, float hi, float edge_thr, float tolerance, int block, Tensor(a!) vertices, Tensor(b!) faces) -> (Tensor, Tensor)");
   m.def("stereo_source(Tensor depth, float fx, float baseline, float convergence, float lo, float hi, float edge_thr) -> (Tensor, Tensor)");
   m.def("stereo_rows(Tensor depth, Tensor image, float fx, float baseline, float convergence, float lo, float hi, float edge_thr, int layout) -> Tensor");
   m.def("temporal_step_(Tensor depth, Tensor image, float alpha, int tau, float rho, float anchor, Tensor(a!) state_depth, Tensor(b!) luma0, Tensor(c!) luma1, bool state_present) -> (Tensor, Tensor)");
@@ -1903,6 +1933,7 @@ TORCH_LIBRARY_IMPL(prv2, CUDA, m) {
   m.impl("pointcloud_pack", &pointcloud_pack);
   m.impl("normal_rows", &normal_rows);
   m.impl("mesh_pack", &mesh_pack);
+  m.impl("mesh_adaptive_pack", &mesh_adaptive_pack);
   m.impl("stereo_source", &stereo_source);
   m.impl("stereo_rows", &stereo_rows);
   m.impl("temporal_step_", &temporal_step_);

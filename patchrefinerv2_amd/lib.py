@@ -205,6 +205,12 @@ SIGNATURES = {
     "prv2_mesh_index": (_I, [_P, _I, _I, _I, _F, _F, _F, _I, _P, _L, _P, _L, _P]),
     "prv2_mesh_count": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _L, _P]),
     "prv2_mesh_pack": (_I, [_P, _I, _I, _I, _F, _I, _P, _L, _P, _L, _P]),
+    # adaptive mesh export (csrc/mesh_adaptive.hip): the vertex and face records of a right-triangulated irregular network
+    "prv2_mesh_adaptive_workspace_bytes": (_L, [_I, _I, _I, _I]),
+    "prv2_mesh_adaptive_vertex_bound": (_L, [_I, _I]),
+    "prv2_mesh_adaptive_face_bound": (_L, [_I, _I]),
+    "prv2_mesh_adaptive_count": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _I, _P, _P, _P, _L, _P]),
+    "prv2_mesh_adaptive_pack": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _F, _I, _P, _L, _P, _L, _P, _L, _P]),
     # stereo export (csrc/stereo.hip): the right-eye view of B frames as scanlines, or its source-column maps
     "prv2_stereo_max_width": (_I, []),
     "prv2_stereo_source": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P]),

@@ -1874,6 +1874,37 @@ def mesh_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.
     return verts, n, faces, m
 
 
+def mesh_adaptive_pack(depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, tolerance=0.01, block=32, out_vertices=None,
+                       out_faces=None):
+    """the adaptive triangle mesh of fp32 depth frames [B, H, W] -> (vertex bytes uint8 [B, vbound], N int64 [B], face bytes uint8
+    [B, fbound], M int64 [B]), all on the device: a right-triangulated irregular network over the pixel grid, large triangles where
+    the depth at a hypotenuse midpoint is within ``tolerance`` (relative, along the ray) of a flat triangle's, pixel-sized ones at
+    depth edges and holes; ``block``: the side of the hierarchy's blocks in cells, a power of two in [2, 64].  The rule is
+    output.mesh_adaptive_host.  Frame f's vertices are the first 15 * N[f] bytes of row f (``pointcloud_pack``'s records of the
+    pixels a face uses, row-major) and its faces the first 13 * M[f] bytes (``mesh_pack``'s records, indices into that list);
+    vbound = 15 * H * W, fbound = 26 * (H - 1) * (W - 1); the bytes behind a frame's records are not written.  ``out_vertices`` /
+    ``out_faces``: uint8 [B, >= bound] buffers to write into (include/prv2.h "Adaptive mesh export")."""
+    from .output import mesh_adaptive_arguments
+    tol, block = mesh_adaptive_arguments(tolerance, block)
+    d, img, k, lo, hi, thr = _scene_inputs("mesh_adaptive_pack", depth, intrinsics, depth_range, image, edge_thr)
+    lib = L.load()
+    wsb = lib.prv2_mesh_adaptive_workspace_bytes(*d.shape, block)
+    if wsb < 0:
+        raise ValueError(f"mesh_adaptive_pack: bad frame shape {tuple(d.shape)}")
+    verts = _record_buffer("mesh_adaptive_pack: out_vertices", out_vertices, d, lib.prv2_mesh_adaptive_vertex_bound(d.shape[1], d.shape[2]))
+    faces = _record_buffer("mesh_adaptive_pack: out_faces", out_faces, d, lib.prv2_mesh_adaptive_face_bound(d.shape[1], d.shape[2]))
+    if DISPATCH == "torch":
+        n, m = _tops().mesh_adaptive_pack(d, img, k, lo, hi, thr, tol, block, verts, faces)
+        return verts, n, faces, m
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=d.device)
+    n = torch.empty((d.shape[0],), dtype=torch.int64, device=d.device)
+    m = torch.empty((d.shape[0],), dtype=torch.int64, device=d.device)
+    _c("mesh_adaptive_count", d.data_ptr(), *d.shape, lo, hi, thr, tol, block, n.data_ptr(), m.data_ptr(), ws.data_ptr(), wsb)
+    _c("mesh_adaptive_pack", d.data_ptr(), img.data_ptr(), *d.shape, img.shape[2], img.shape[3], *k, lo, hi, thr, tol, block, ws.data_ptr(), wsb,
+       verts.data_ptr(), verts.shape[1], faces.data_ptr(), faces.shape[1])
+    return verts, n, faces, m
+
+
 def normal_rows(depth, intrinsics, depth_range=(0.0, math.inf)):
     """the camera-facing surface normals of fp32 depth frames [B, H, W] as RGB scanlines (n * 0.5 + 0.5 in bytes; (0, 0, 0)
     where there is no normal) -> scanline buffer (include/prv2.h prv2_normal_rows)"""

@@ -22,6 +22,9 @@ pointcloud_host / normal_map_host / ply_bytes
                          the host specification of the geometry export (csrc/pointcloud.hip equals it bit for bit) and the PLY file
 mesh_faces_host / mesh_ply_bytes
                          the host specification of the mesh's faces (likewise) and the PLY file of vertices and faces
+mesh_adaptive_host / mesh_adaptive_vertices
+                         the host specification of the adaptive mesh (csrc/mesh_adaptive.hip equals it byte for byte): the used pixels
+                         and the faces of a right-triangulated irregular network, and the vertex records of those pixels
 stereo_source_host / stereo_view_host / stereo_image_host
                          the host specification of the right-eye view (csrc/stereo.hip equals it byte for byte)
 bokeh_render_host / bokeh_image_host
@@ -34,7 +37,8 @@ Geometry export (``runner_info.save_ply`` / ``save_normals``; tools/test.py --sa
 little-endian point cloud of the result map (float x, y, z + uchar red, green, blue per kept pixel, row-major pixel order), and
 <name>_normal.png, its camera-facing surface normals.  Pinhole camera, x right, y down, z forward.  ``runner_info.save_mesh``
 (--save-mesh) adds <name>_mesh.ply: the same vertices joined into camera-facing triangles along the pixel grid, two per cell of
-four kept neighbours at most, none across a depth discontinuity (``mesh_faces_host``).  ``runner_info.save_stereo`` (--save-stereo)
+four kept neighbours at most, none across a depth discontinuity (``mesh_faces_host``); with ``runner_info.mesh_tolerance``
+(--mesh-tolerance) the file holds the adaptive mesh instead, with its own vertex list (``mesh_adaptive_host``).  ``runner_info.save_stereo`` (--save-stereo)
 adds <name>_right.png (or _sbs / _anaglyph): the frame seen from a second eye ``stereo_baseline`` metres to the right
 (``stereo_source_host``: a per-row forward warp with a depth test, disocclusions filled from the farther side).
 ``runner_info.save_bokeh`` (--save-bokeh) adds <name>_bokeh.png: the frame seen through a thin lens of ``bokeh_aperture`` metres
@@ -372,6 +376,161 @@ def mesh_ply_bytes(n: int, vertex_bytes, m: int, face_bytes) -> bytes:
         raise ValueError(f"mesh_ply_bytes: {n} vertices and {m} faces need {PLY_VERTEX.itemsize * int(n)} + {PLY_FACE.itemsize * int(m)} bytes, "
                          f"got {len(verts)} + {len(faces)}")
     return mesh_ply_header(n, m) + bytes(verts) + bytes(faces)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# adaptive mesh export: the host specification of ``ops.mesh_adaptive_pack`` (csrc/mesh_adaptive.hip equals it byte for byte).
+# A right-triangulated irregular network over the pixel grid: the longest-edge-bisection hierarchy of blocks of ``block`` x
+# ``block`` cells, cut where one per-vertex map, ``required``, says so.  The map is closed under the hierarchy (a required child
+# vertex makes its parent required), which is what keeps the mesh free of T-junctions.
+#   grid       vertices are pixels; kept = keep_mask_host(stride 1); the grid is padded to whole blocks, Hp = B ceil((h - 1) / B) + 1,
+#              with vertices that are neither kept nor smooth
+#   smooth(v)  v is kept and every 8-neighbour inside the frame is kept and joined to v (mesh_faces_host's joined)
+#   hierarchy  block (y0, x0) has the corners A = (y0, x0), B' = (y0, x0 + B), C = (y0 + B, x0), D = (y0 + B, x0 + B) and the roots
+#              (D, A, C), (A, D, B'); a triangle (a, b, c) has the hypotenuse a-b, the apex c, the midpoint m = (a + b) / 2 and the
+#              children (c, a, m), (b, c, m); after 2 log2 B bisections the legs are one pixel long (the finest triangles)
+#   vertex     not a block corner, hh = 2^min(tz(y), tz(x)): y / hh and x / hh both odd: a centre, whose hypotenuse is the diagonal
+#              of its 2hh-square through the centre of the enclosing 4hh-square (the block's main diagonal for 2hh = B), whose
+#              apexes are the other two corners and whose child vertices are the axial neighbours at hh; one odd: an edge midpoint,
+#              hypotenuse ends at +-hh along the odd axis, apexes at +-hh along the other, child vertices the diagonal neighbours
+#              at hh / 2; what falls outside the padded grid does not exist
+#   required   m is not smooth, or a hypotenuse end or an existing apex is not kept, or an existing child vertex is required, or
+#              (m and both ends kept) s = Za + Zb, p = Zm s, q = (Za Zb) 2, |p - q| > T p in fp32: the depth at m differs from
+#              the harmonic mean of the ends -- a flat 3-D triangle's depth there -- by more than T, relative, along the ray
+#   faces      blocks row-major, roots and children in the order above; a triangle above the finest is a face iff its midpoint is
+#              not required, else it splits; a finest triangle is a face iff its corners are kept and its edges joined
+#   vertices   the kept pixels a face references, in row-major pixel order
+# ------------------------------------------------------------------------------------------------------------------
+def mesh_adaptive_arguments(tolerance, block):
+    """-> (T as a Python float holding a float32, B as an int), checked: T finite and >= 0, B a power of two in [2, 64]"""
+    try:
+        t, b = float(F32(tolerance)), int(block)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"mesh tolerance {tolerance!r} / block {block!r}: a finite number >= 0 and a power of two in [2, 64]") from None
+    if not (math.isfinite(t) and t >= 0.0):
+        raise ValueError(f"mesh tolerance {tolerance}: finite and >= 0")
+    if b != block or b < 2 or b > 64 or b & (b - 1):
+        raise ValueError(f"mesh block {block}: a power of two in [2, 64]")
+    return t, b
+
+
+def _adaptive_required(z, kept, smooth, T, B):
+    """the ``required`` map of the padded grid (z, kept, smooth: [Hp, Wp]); block corners are left False"""
+    Hp, Wp = kept.shape
+    R = ~smooth
+    R[::B, ::B] = False
+
+    def geo(zm, za, zb, k):
+        with np.errstate(all="ignore"):
+            p = zm * (za + zb)
+            q = (za * zb) * F32(2)
+            return k & (np.abs(p - q) > T * p)
+
+    def edges(R, kept, z, hh):
+        """the edge midpoints at hh whose odd axis is the second one (the others: the same on the transposed views)"""
+        n0 = R.shape[0]
+        m = (slice(0, n0, 2 * hh), slice(hh, None, 2 * hh))
+        a, b = (slice(0, n0, 2 * hh), slice(0, -1, 2 * hh)), (slice(0, n0, 2 * hh), slice(2 * hh, None, 2 * hh))
+        r = R[m] | ~kept[a] | ~kept[b] | geo(z[m], z[a], z[b], kept[m] & kept[a] & kept[b])
+        apex = ~kept[hh::2 * hh, hh::2 * hh]  # the rows between the edges' rows
+        r[1:] |= apex
+        r[:-1] |= apex
+        if hh >= 2:
+            c = R[hh // 2::hh, hh // 2::hh]
+            c = c[:, 0::2] | c[:, 1::2]
+            r[:-1] |= c[0::2]
+            r[1:] |= c[1::2]
+        R[m] = r
+
+    for lg in range(B.bit_length() - 1):
+        hh = 1 << lg
+        edges(R, kept, z, hh)
+        edges(R.T, kept.T, z.T, hh)
+        m = (slice(hh, None, 2 * hh), slice(hh, None, 2 * hh))
+        tl, tr = (slice(0, -1, 2 * hh), slice(0, -1, 2 * hh)), (slice(0, -1, 2 * hh), slice(2 * hh, None, 2 * hh))
+        bl, br = (slice(2 * hh, None, 2 * hh), slice(0, -1, 2 * hh)), (slice(2 * hh, None, 2 * hh), slice(2 * hh, None, 2 * hh))
+        i, j = np.ogrid[0:(Hp - 1) // (2 * hh), 0:(Wp - 1) // (2 * hh)]
+        main = ((i + j) % 2 == 0) | (2 * hh == B)
+        corners = kept[tl] & kept[tr] & kept[bl] & kept[br]
+        r = R[m] | ~corners | geo(z[m], np.where(main, z[tl], z[tr]), np.where(main, z[br], z[bl]), kept[m] & corners)
+        r |= R[0:-1:2 * hh, hh::2 * hh] | R[2 * hh::2 * hh, hh::2 * hh] | R[hh::2 * hh, 0:-1:2 * hh] | R[hh::2 * hh, 2 * hh::2 * hh]
+        R[m] = r
+    return R
+
+
+def mesh_adaptive_host(depth, depth_range=(0.0, math.inf), edge_thr=0.05, tolerance=0.01, block=32):
+    """The specification of ``ops.mesh_adaptive_pack`` for one frame (the rule is in the comment above) -> (the flat pixel indices
+    y * w + x of the used vertices, ascending, int64 [N]; faces '<i4' [M, 3], indices into that list).  The vertex records are
+    ``pointcloud_host``'s of those pixels."""
+    T, B = mesh_adaptive_arguments(tolerance, block)
+    T = F32(T)
+    d = np.ascontiguousarray(depth, dtype=F32)
+    h, w = d.shape
+    none = np.zeros((0,), dtype=np.int64), np.zeros((0, 3), dtype="<i4")
+    if h < 2 or w < 2:
+        return none
+    L = B.bit_length() - 1
+    Hp, Wp = B * (-(-(h - 1) // B)) + 1, B * (-(-(w - 1) // B)) + 1
+    z = np.zeros((Hp, Wp), dtype=F32)
+    kept = np.zeros((Hp, Wp), dtype=bool)
+    z[:h, :w], kept[:h, :w] = d, keep_mask_host(d, depth_range, edge_thr, 1)
+    thr = F32(edge_thr)
+
+    def joined(za, zb):
+        if not thr > 0:
+            return np.ones(np.broadcast(za, zb).shape, dtype=bool)
+        with np.errstate(all="ignore"):
+            return ~(np.abs(za - zb) > thr * np.minimum(za, zb))
+
+    smooth = kept.copy()
+    zr, kr, sr = z[:h, :w], kept[:h, :w], smooth[:h, :w]
+    for dy, dx in ((0, 1), (1, 0), (1, 1), (1, -1)):  # (joined is symmetric: each pair once, applied to both ends)
+        a = (slice(0, h - dy), slice(max(0, -dx), w - max(0, dx)))
+        b = (slice(dy, h), slice(max(0, dx), w - max(0, -dx)))
+        ok = kr[a] & kr[b] & joined(zr[a], zr[b])
+        sr[a] &= ok
+        sr[b] &= ok
+    R = _adaptive_required(z, kept, smooth, T, B)
+
+    # the triangles, level by level: slot = the first of the 2 B^2 finest slots of its block a triangle covers (+ 2 B^2 block)
+    by, bx = np.divmod(np.arange(((Hp - 1) // B) * ((Wp - 1) // B), dtype=np.int64), (Wp - 1) // B)
+    c16 = lambda v: v.astype(np.int16)  # noqa: E731
+    y0, x0, y1, x1 = c16(by * B), c16(bx * B), c16(by * B + B), c16(bx * B + B)
+    first = np.arange(by.size, dtype=np.int64) * (2 * B * B)
+    slot = np.concatenate([first, first + B * B])
+    ay, ax, by_, bx_ = np.concatenate([y1, y0]), np.concatenate([x1, x0]), np.concatenate([y0, y1]), np.concatenate([x0, x1])
+    cy, cx = np.concatenate([y1, y0]), np.concatenate([x0, x1])
+    out_slot, out_tri = [], []
+    for k in range(2 * L):
+        my, mx = (ay + by_) >> 1, (ax + bx_) >> 1
+        split = R[my, mx]
+        leaf = ~split
+        out_slot.append(slot[leaf])
+        out_tri.append(np.stack([ay[leaf], ax[leaf], by_[leaf], bx_[leaf], cy[leaf], cx[leaf]], axis=-1))
+        ay, ax, by_, bx_, cy, cx, my, mx, slot = (v[split] for v in (ay, ax, by_, bx_, cy, cx, my, mx, slot))
+        half = (B * B) >> (k + 1)
+        ay, ax, by_, bx_, cy, cx = (np.concatenate(p) for p in ((cy, by_), (cx, bx_), (ay, cy), (ax, cx), (my, my), (mx, mx)))
+        slot = np.concatenate([slot, slot + half])
+    face = kept[ay, ax] & kept[by_, bx_] & kept[cy, cx]
+    face &= joined(z[ay, ax], z[by_, bx_]) & joined(z[by_, bx_], z[cy, cx]) & joined(z[ay, ax], z[cy, cx])
+    out_slot.append(slot[face])
+    out_tri.append(np.stack([ay[face], ax[face], by_[face], bx_[face], cy[face], cx[face]], axis=-1))
+    slot, tri = np.concatenate(out_slot), np.concatenate(out_tri).astype(np.int64)
+    if not slot.size:
+        return none
+    tri = tri[np.argsort(slot, kind="stable")]
+    pix = tri[:, 0::2] * w + tri[:, 1::2]  # [M, 3]: every corner of a face is kept, so inside the frame
+    used = np.unique(pix)
+    return used, np.ascontiguousarray(np.searchsorted(used, pix), dtype="<i4")
+
+
+def mesh_adaptive_vertices(depth, image, intrinsics, used, depth_range=(0.0, math.inf), edge_thr=0.05) -> np.ndarray:
+    """the ``PLY_VERTEX`` records of the pixels ``used`` (``mesh_adaptive_host``): ``pointcloud_host``'s records of those pixels"""
+    d = np.ascontiguousarray(depth, dtype=F32)
+    keep = keep_mask_host(d, depth_range, edge_thr, 1).reshape(-1)
+    rank = np.cumsum(keep, dtype=np.int64) - 1
+    assert keep[used].all()
+    return pointcloud_host(d, image, intrinsics, depth_range, edge_thr, 1)[rank[used]]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -799,9 +958,15 @@ def _view_options(views):
     return opt
 
 
+def _no_stride_with_tolerance(stride):
+    if int(stride) != 1:
+        raise ValueError(f"the adaptive mesh (mesh_tolerance) has no stride: stride {stride} != 1")
+
+
 def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1, ply=True, normals=True,
-                        mesh=False, stereo=None, bokeh=None, views=None):
-    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png, <base>_mesh.ply, (``stereo``: a dict of
+                        mesh=False, stereo=None, bokeh=None, views=None, mesh_tolerance=None, mesh_block=32):
+    """the host route of ``OutputStage.submit_geometry``: <base>.ply, <base>_normal.png, <base>_mesh.ply (with ``mesh_tolerance``:
+    the adaptive mesh of ``mesh_adaptive_host`` with its own vertex list, which has no stride), (``stereo``: a dict of
     baseline, convergence, layout) <base>_right.png / _sbs.png / _anaglyph.png, (``bokeh``: a dict of aperture, focus, focus_point,
     max_radius) <base>_bokeh.png and (``views``: a dict of count, motion, amplitude, focus) <base>_view_000.png ... from the host
     specification"""
@@ -812,7 +977,13 @@ def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, m
             f.write(ply_bytes(v.size, v.tobytes()))
     if normals:
         write_png8(base + "_normal.png", normal_map_host(depth, intrinsics, depth_range))
-    if mesh:
+    if mesh and mesh_tolerance is not None:
+        _no_stride_with_tolerance(stride)
+        used, tri = mesh_adaptive_host(depth, depth_range, edge_thr, mesh_tolerance, mesh_block)
+        av, faces = mesh_adaptive_vertices(depth, image, intrinsics, used, depth_range, edge_thr), mesh_face_records(tri)
+        with open(base + "_mesh.ply", "wb") as f:
+            f.write(mesh_ply_bytes(av.size, av.tobytes(), faces.size, faces.tobytes()))
+    elif mesh:
         faces = mesh_face_records(mesh_faces_host(depth, depth_range, edge_thr, stride))
         with open(base + "_mesh.ply", "wb") as f:
             f.write(mesh_ply_bytes(v.size, v.tobytes(), faces.size, faces.tobytes()))
@@ -828,6 +999,9 @@ def write_geometry_host(base: str, depth, image, intrinsics, depth_range=(0.0, m
     if views is not None:
         for k, pose in enumerate(view_poses(**_view_options(views))):
             write_png8(f"{base}_view_{k:03d}.png", view_image_host(depth, image, intrinsics, pose, depth_range, edge_thr))
+
+
+save_geometry_host = write_geometry_host  # (the name the adaptive mesh's tests and tools use)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1121,7 +1295,7 @@ class OutputStage:
 
     @torch.no_grad()
     def submit_geometry(self, base: str, result: torch.Tensor, image_hr, intrinsics, depth_range=(0.0, math.inf), edge_thr=0.05, stride=1,
-                        ply=True, normals=True, mesh=False, stereo=None, bokeh=None, views=None):
+                        ply=True, normals=True, mesh=False, stereo=None, bokeh=None, views=None, mesh_tolerance=None, mesh_block=32):
         """the geometry of one frame, from the device map: <base>.ply (``ply``: the point cloud of ``pointcloud_host``, coloured
         from ``image_hr`` [3, Hi, Wi], a host or device tensor of any size), <base>_normal.png (``normals``: the map of
         ``normal_map_host``, through the PNG path of every other file, deflated on the device with ``device_deflate``) and
@@ -1136,8 +1310,14 @@ class OutputStage:
         back, for the warning of a frame whose focus pixel holds no valid depth.
         ``views`` (a dict of count, motion, amplitude, focus; default 8, 'circle', 0.05, inf) adds <base>_view_000.png ...: the frames
         of ``view_image_host`` along the camera path of ``view_poses``, rendered ``VIEW_CHUNK`` views per launch, each chunk in a
-        staging slot of its own, so the depth-test keys (8 bytes per view pixel) and the pinned scanlines stay bounded."""
+        staging slot of its own, so the depth-test keys (8 bytes per view pixel) and the pinned scanlines stay bounded.
+        ``mesh_tolerance`` (with ``mesh``; ``stride`` 1) makes <base>_mesh.ply the adaptive mesh of ``mesh_adaptive_host`` in blocks
+        of ``mesh_block`` cells, with its own vertex list: its records come from ``ops.mesh_adaptive_pack``, a <base>.ply of the same
+        call is the cloud's as before, and the copies are again the counts and exactly 15 N + 13 M bytes."""
         from . import ops
+        adaptive = mesh and mesh_tolerance is not None
+        if adaptive:
+            _no_stride_with_tolerance(stride)
         dev = result.device
         slot = self._begin(dev)
         if (ply or mesh) and self.copy_stream is None:
@@ -1176,9 +1356,9 @@ class OutputStage:
                     rows = ops.view_rows(d, img, intrinsics, poses[k0:k0 + VIEW_CHUNK], depth_range, edge_thr)
                     self._stage(self._begin(dev), [(f"{base}_view_{k0 + k:03d}.png", w, h, 3, rows[:, k]) for k in range(rows.shape[1])])
             if ply or mesh:
-                if mesh:
+                if mesh and not adaptive:
                     verts, counts, faces, n_faces = ops.mesh_pack(d, img, intrinsics, depth_range, edge_thr, stride)
-                else:
+                elif ply:
                     verts, counts = ops.pointcloud_pack(d, img, intrinsics, depth_range, edge_thr, stride)
             if ply:
                 if slot["ply"] is None or slot["ply"].numel() < verts.shape[1]:
@@ -1194,6 +1374,8 @@ class OutputStage:
                 slot["futures"].append(self.pool.submit(self._write_ply, base + ".ply", ply_header, [(verts[0], PLY_VERTEX.itemsize)], slot["ply_n"], ev,
                                                       slot["ply"]))
             if mesh:
+                if adaptive:  # (its own vertices: ``verts`` / ``counts`` stay the cloud's for the writer of <base>.ply)
+                    verts, counts, faces, n_faces = ops.mesh_adaptive_pack(d, img, intrinsics, depth_range, edge_thr, mesh_tolerance, mesh_block)
                 room = int(verts.shape[1]) + int(faces.shape[1])
                 if slot["mesh"] is None or slot["mesh"].numel() < room:
                     slot["mesh"] = torch.empty((room,), dtype=torch.uint8, pin_memory=True)

@@ -8,7 +8,9 @@ device_output) makes the zlib streams on the GPU as well: the files hold the dev
 stream differs from zlib's).
 ``runner_info.save_ply`` / ``save_normals`` (--save-ply / --save-normals, with ``save``) add the frame's geometry: <name>.ply (a
 binary point cloud of the result map, coloured from the image) and <name>_normal.png (its surface normals);
-``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles) and
+``runner_info.save_mesh`` (--save-mesh) adds <name>_mesh.ply (the cloud's vertices joined into triangles; with
+``runner_info.mesh_tolerance`` / ``mesh_block`` (--mesh-tolerance T, --mesh-block B) the adaptive mesh instead: large triangles
+where the surface is flat, pixel-sized ones at depth edges, its own vertex list) and
 ``runner_info.save_stereo`` (--save-stereo) <name>_right.png / _sbs.png / _anaglyph.png (the right-eye view),
 ``runner_info.save_bokeh`` (--save-bokeh) <name>_bokeh.png (the frame with a synthetic depth of field),
 ``runner_info.save_views`` = N (--save-views N; 0: off) <name>_view_000.png ... (the frame seen from N poses of a closed camera path:
@@ -225,7 +227,8 @@ class Tester:
     def _geometry(self, result, image_raw_shape):
         """the keyword arguments of ``submit_geometry`` / ``write_geometry_host`` for a result map, None without ``save_ply`` /
         ``save_normals`` / ``save_mesh`` / ``save_stereo``: the camera of ``runner_info.intrinsics`` (fx fy cx cy in pixels of the raw grid) or ``runner_info.fov``
-        (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``; with ``save_stereo`` the
+        (degrees, default 60) scaled to the result's grid, ``ply_depth_range``, ``ply_edge_thr``, ``ply_stride``; with ``mesh_tolerance``
+        that and ``mesh_block`` (32), checked; with ``save_stereo`` the
         ``stereo`` dict of ``stereo_baseline`` (default 0.065), ``stereo_convergence`` (inf) and ``stereo_layout`` ('right'); with
         ``save_bokeh`` the ``bokeh`` dict of ``bokeh_aperture`` (0.025), ``bokeh_focus`` (None: the depth under ``bokeh_focus_point``,
         default (0.5, 0.5)) and ``bokeh_max_radius`` (16); with ``save_views`` = N > 0 the ``views`` dict of N, ``view_motion`` ('circle'),
@@ -237,8 +240,15 @@ class Tester:
             return None
         from .output import camera_intrinsics
         k = camera_intrinsics(image_raw_shape, result.shape[-2:], getattr(info, "intrinsics", None), getattr(info, "fov", None) or 60.0)
+        tol = getattr(info, "mesh_tolerance", None)
+        if tol is not None:  # (the adaptive mesh: <name>_mesh.ply with its own vertex list; it has no stride)
+            from .output import mesh_adaptive_arguments
+            tol, block = mesh_adaptive_arguments(tol, getattr(info, "mesh_block", 32))
+            if not mesh or int(getattr(info, "ply_stride", 1)) != 1:
+                raise ValueError("runner_info.mesh_tolerance needs save_mesh and ply_stride 1")
         return dict(intrinsics=k, depth_range=tuple(getattr(info, "ply_depth_range", None) or (0.0, float("inf"))),
                     edge_thr=float(getattr(info, "ply_edge_thr", 0.05)), stride=int(getattr(info, "ply_stride", 1)), ply=ply, normals=normals, mesh=mesh,
+                    **(dict(mesh_tolerance=tol, mesh_block=block) if tol is not None else {}),
                     **(dict(stereo=dict(baseline=float(getattr(info, "stereo_baseline", 0.065)),
                                         convergence=float(getattr(info, "stereo_convergence", float("inf"))),
                                         layout=getattr(info, "stereo_layout", "right"))) if stereo else {}),

@@ -59,6 +59,8 @@ OPS = ("abi_version", "pack_conv_weight", "conv2d", "conv3x3_ups", "pack_gate_we
        "pointcloud_pack", "normal_rows",
        # mesh export: the cloud's vertex records and the face records over them
        "mesh_pack",
+       # adaptive mesh export: the vertex and face records of a right-triangulated irregular network over the depth map
+       "mesh_adaptive_pack",
        # stereo export: the right-eye view as scanlines, and its source-column maps
        "stereo_rows", "stereo_source",
        # temporal stabilisation: frames of a sequence aligned to and blended with the previous output (state tensors updated in place)

@@ -14,6 +14,9 @@ Extras: ``--synthetic-weights`` (the reference has not released checkpoints), ``
 and <name>_normal.png (surface normals); camera from ``--intrinsics FX FY CX CY`` (pixels of the --image-raw-shape grid) or ``--fov DEG``
 (horizontal, default 60); ``--ply-stride S``, ``--ply-edge-thr T`` (flying-pixel filter, <= 0 off), ``--ply-depth-range LO HI``.
 ``--save-mesh``: with ``--save``, <name>_mesh.ply: the same vertices plus a face element, triangles along the pixel grid (same camera and --ply-* options).
+``--mesh-tolerance T`` [``--mesh-block B``]: <name>_mesh.ply becomes the adaptive mesh (a right-triangulated irregular network in blocks of
+B x B cells, B a power of two in [2, 64], default 32): triangles up to B pixels wide where the surface is flat to within T, pixel-sized ones at
+depth edges; its own vertex list; --ply-stride must be 1.
 ``--save-bokeh``: with ``--save``, <name>_bokeh.png: the frame with a synthetic depth of field (``--bokeh-aperture M``, ``--bokeh-focus Z`` or
 ``--bokeh-focus-point U V``, ``--bokeh-max-radius PX``; same camera and --ply-depth-range).
 ``--save-views N``: with ``--save``, <name>_view_000.png ... <name>_view_{N-1:03d}.png: the frame seen from N poses of a closed camera path
@@ -42,6 +45,7 @@ Multi-GPU: ``sh tools/dist_test.sh CONFIG GPUS [arguments]`` (docs/user_infer.md
 """
 import argparse
 import ast
+import math
 import os
 import sys
 
@@ -188,6 +192,12 @@ def main():
     ap.add_argument("--save-mesh", action="store_true",
                     help="with --save: <name>_mesh.ply, the vertices of --save-ply joined into camera-facing triangles along the pixel grid (binary "
                          "little-endian PLY with a face element; no triangle across an edge --ply-edge-thr splits), made on the GPU with --device-output")
+    ap.add_argument("--mesh-tolerance", type=float, default=None, metavar="T",
+                    help="--save-mesh: write the adaptive mesh instead -- large triangles where the depth at a hypotenuse midpoint is within T "
+                         "(relative, along the ray; finite, >= 0) of a flat triangle's, pixel-sized ones at depth edges and holes; its own "
+                         "vertex list, no --ply-stride")
+    ap.add_argument("--mesh-block", type=int, default=32, metavar="B",
+                    help="--mesh-tolerance: the side of the hierarchy's blocks in cells, the largest triangle's legs (a power of two in [2, 64])")
     ap.add_argument("--save-stereo", action="store_true",
                     help="with --save: <name>_right.png (--stereo-layout: _sbs / _anaglyph), the frame seen from a second eye to the right: "
                          "a per-row forward warp of the image by the result map's disparity with a depth test, disocclusions filled from "
@@ -267,6 +277,15 @@ def main():
         ap.error(f"--stereo-convergence {args.stereo_convergence}: a depth other than 0")
     if args.ply_stride < 1:
         ap.error(f"--ply-stride {args.ply_stride}: at least 1")
+    if args.mesh_tolerance is not None:
+        if not args.save_mesh:
+            ap.error("--mesh-tolerance needs --save-mesh (it chooses the mesh that file holds)")
+        if args.ply_stride > 1:
+            ap.error(f"--mesh-tolerance with --ply-stride {args.ply_stride}: the adaptive mesh has no stride")
+        if not (math.isfinite(args.mesh_tolerance) and args.mesh_tolerance >= 0):
+            ap.error(f"--mesh-tolerance {args.mesh_tolerance}: finite and at least 0")
+        if args.mesh_block < 2 or args.mesh_block > 64 or args.mesh_block & (args.mesh_block - 1):
+            ap.error(f"--mesh-block {args.mesh_block}: a power of two in [2, 64]")
     if args.intrinsics is not None and args.fov is not None:
         ap.error("--intrinsics and --fov both given: the camera comes from one of them")
     if not 0.0 <= args.temporal_alpha < 1.0:
@@ -321,7 +340,7 @@ def main():
                         save_bokeh=args.save_bokeh, bokeh_aperture=args.bokeh_aperture, bokeh_focus=args.bokeh_focus,
                         bokeh_focus_point=tuple(args.bokeh_focus_point), bokeh_max_radius=args.bokeh_max_radius,
                         save_views=args.save_views, view_motion=args.view_motion, view_amplitude=args.view_amplitude, view_focus=args.view_focus,
-                        intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride,
+                        intrinsics=args.intrinsics, fov=args.fov, ply_stride=args.ply_stride, mesh_tolerance=args.mesh_tolerance, mesh_block=args.mesh_block,
                         ply_edge_thr=args.ply_edge_thr, ply_depth_range=tuple(args.ply_depth_range),
                         temporal_stabilize=args.temporal_stabilize, temporal_alpha=args.temporal_alpha, temporal_tau=args.temporal_tau,
                         temporal_rho=args.temporal_rho, temporal_anchor=args.temporal_anchor, temporal_motion=args.temporal_motion,
